@@ -5,7 +5,14 @@ A "step" is one pass of the hot path (HIP kernel k_profile behind bsig_plan_run)
 of ranges, with the read columns and the range work items already resident in HBM and the result
 left in HBM.  Default workload = the shape BASELINE.json's north star quotes its 1-GPU target on
 ("NS"): 100,000 x 2 kb ranges, 5e8 synthetic single-end reads on 10 x 250 Mbp (4.2 GB resident).
-At N = 1 the same run also reports
+
+A plain run sets up, warms up, times the K steps (--steps; `ms_per_step` = the wall time of the K steps / K) and
+prints the result line; `--dump-outputs DIR` also writes what its last step computed (dump_outputs).  Everything
+else runs with `--full`: the check of every timed range against the oracle (`parity_checked`), `cpu_baseline`,
+the blocks below, and at N > 1 `step_phases` (and the roofline figure quoted on it), `no_collective`, `strong`
+and `in_process`.  The same arguments give the same inputs in every run (seeded generators).
+
+With --full, at N = 1 the run also reports
 
   * "also"/"C2": the kernel-only step of BASELINE config 2 (10k x 2 kb, 5e7 reads) — the small launch;
   * "end_to_end": the file-level call bamProfile(bampath, GRanges) on the SAME workload written to
@@ -26,7 +33,7 @@ and the step is the launch alone.  The result assembled on rank 0 is compared wi
 every batch.  The reads are generated ONCE per node (local rank 0 -> .npy files in /dev/shm, the other ranks map
 them), so the N-rank run costs one generation and one copy of the columns in host memory, not N.
 
-A run with N > 1 also carries (informational, never `value`):
+A run with N > 1 and --full also carries (informational, never `value`):
   * "no_collective": every rank running the WHOLE range set by itself with nothing exchanged (N independent
     replicas: what rounds 1-4 reported as a weak-scaling `value`; linear by construction);
   * "strong": BASELINE config 5 at FIXED total size -- 1M x 1 kb ranges over 1e9 reads on 24
@@ -411,6 +418,97 @@ def end_to_end_realistic(seed, device, oracle_c):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def host_threads():
+    """Threads for the host-side setup: the CPUs this process may run on, at most 16 (and at most OMP_NUM_THREADS)."""
+    n = len(os.sched_getaffinity(0))
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    if env.isdigit() and int(env) > 0:
+        n = min(n, int(env))
+    return max(1, min(n, 16))
+
+
+def _sort_threaded(g, ex, threads):
+    """np.sort(g) on `threads` threads: the chunks are sorted, cut at common splitters, and every bucket of values
+    gathers its pieces and is sorted by itself.  A sort's result does not depend on how it was reached."""
+    cuts = np.linspace(0, len(g), threads + 1).astype(np.int64)
+    chunks = [g[cuts[i]:cuts[i + 1]] for i in range(threads)]
+    list(ex.map(np.ndarray.sort, chunks))
+    c0 = chunks[0]
+    split = c0[(len(c0) * np.arange(1, threads)) // threads] if len(c0) else np.zeros(threads - 1, np.int64)
+    idx = np.asarray([np.concatenate([[0], np.searchsorted(c, split), [len(c)]]) for c in chunks])
+    off = np.concatenate([[0], np.cumsum((idx[:, 1:] - idx[:, :-1]).sum(axis=0))])
+    out = np.empty_like(g)
+
+    def bucket(j):
+        dst = out[off[j]:off[j + 1]]
+        np.concatenate([c[idx[i, j]:idx[i, j + 1]] for i, c in enumerate(chunks)], out=dst)
+        dst.sort()
+    list(ex.map(bucket, range(threads)))
+    return out
+
+
+def synth_reads_threaded(n_reads, ref_len, seed, threads):
+    """bamsignals_amd.synth.synth_reads(n_reads, ref_len, seed=seed, paired=False, with_cigar=False), column for column:
+    the same draws from the same generator in the same order, made on one thread while `threads` others sort the
+    positions and derive the columns in slices (numpy releases the GIL in all of it)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from bamsignals_amd.synth import CIGAR_SPAN, synth_reads
+    rng = np.random.default_rng(seed)
+    ref_len = np.asarray(ref_len, dtype=np.int64)
+    gstart = np.concatenate([[0], np.cumsum(ref_len)])
+    g = rng.integers(0, int(gstart[-1]), n_reads, dtype=np.int64)
+
+    def later_draws():
+        # the draws that follow the positions, in synth_reads' order (none depends on the positions)
+        neg = rng.random(n_reads) < 0.5
+        menu0 = rng.random(n_reads) < 0.9
+        menu = rng.integers(1, 5, n_reads).astype(np.int8)
+        mapq = rng.integers(0, 61, n_reads).astype(np.uint8)
+        dup = rng.random(n_reads) < 0.02
+        return neg, menu0, menu, mapq, dup
+
+    cuts = np.linspace(0, n_reads, threads + 1).astype(np.int64)
+    parts = [slice(int(cuts[i]), int(cuts[i + 1])) for i in range(threads)]
+    rid = np.empty(n_reads, np.int32)
+    pos = np.empty(n_reads, np.int32)
+    with ThreadPoolExecutor(1) as drawer, ThreadPoolExecutor(threads) as ex:
+        draws = drawer.submit(later_draws)
+        g = _sort_threaded(g, ex, threads)
+
+        def place(s):
+            r = np.searchsorted(gstart, g[s], side="right") - 1
+            p = g[s] - gstart[r]
+            rid[s], pos[s] = r, p
+            return bool(np.any(p > ref_len[r] - 1))
+        # single-end positions lie inside their reference: nothing is clipped, so (rid, pos) keeps the sorted order
+        clipped = any(list(ex.map(place, parts)))
+        del g
+        neg, menu0, menu, mapq, dup = draws.result()
+        if clipped:
+            return synth_reads(n_reads, ref_len, seed=seed, paired=False, with_cigar=False)
+        flag = np.empty(n_reads, np.uint16)
+        which = np.empty(n_reads, np.int8)
+        end = np.empty(n_reads, np.int32)
+
+        def columns(s):
+            flag[s] = np.where(neg[s], 16, 0).astype(np.uint16) | np.where(dup[s], 0x400, 0).astype(np.uint16)
+            which[s] = np.where(menu0[s], 0, menu[s])
+            end[s] = pos[s] + CIGAR_SPAN[which[s]] - 1
+        list(ex.map(columns, parts))
+    ref_off = np.searchsorted(rid, np.arange(len(ref_len) + 1)).astype(np.int64)
+    return dict(ref_len=ref_len.astype(np.int32), ref_off=ref_off, rid=rid, pos=pos, flag=flag, mapq=mapq,
+                tlen=np.zeros(n_reads, dtype=np.int32), end=end, cigar_menu=which)
+
+
+def make_reads(n_reads, ref_len, seed, paired):
+    """The synthetic read columns of a configuration (single-end ones on host_threads() threads)."""
+    from bamsignals_amd.synth import synth_reads
+    if paired:
+        return synth_reads(n_reads, ref_len, seed=seed, paired=True, with_cigar=False)
+    return synth_reads_threaded(n_reads, ref_len, seed, host_threads())
+
+
 def host_ram_available():
     try:
         import psutil
@@ -422,22 +520,21 @@ def host_ram_available():
 class SharedReads:
     """The synthetic read columns of one configuration, generated once per node: local rank 0 runs the
     generator and writes the columns as .npy files (to /dev/shm when it has room, else TMPDIR), the other
-    ranks map them read-only after a barrier.  N ranks then cost one generation (26 s for 5e8 reads, 49 s for
-    1e9) and ONE copy of the columns in host memory (15 B per read) instead of N of each."""
+    ranks map them read-only after a barrier.  N ranks then cost one generation (11 s for 5e8 reads on 16 host threads)
+    and ONE copy of the columns in host memory (15 B per read) instead of N of each."""
 
     KEYS = ("ref_len", "ref_off", "pos", "flag", "mapq", "tlen", "end")
 
     def __init__(self, tag, n_reads, ref_len, seed, paired, rank, world, barrier):
         import shutil
 
-        from bamsignals_amd.synth import synth_reads
         self.dir = None
         self.leader = rank == 0
         t0 = time.time()
         need_gen = int(n_reads) * 48            # generator temporaries (int64 positions, sort buffers) + columns
         need_shm = int(n_reads) * 16
         if world == 1:
-            self.cols = synth_reads(n_reads, ref_len, seed=seed, paired=paired, with_cigar=False)
+            self.cols = make_reads(n_reads, ref_len, seed, paired)
             self.t_gen = time.time() - t0
             return
         root = None
@@ -456,7 +553,7 @@ class SharedReads:
                                  f"(available RAM {avail}, need about {need_gen + need_shm} bytes)")
             shutil.rmtree(self.dir, ignore_errors=True)
             os.makedirs(self.dir)
-            self.cols = synth_reads(n_reads, ref_len, seed=seed, paired=paired, with_cigar=False)
+            self.cols = make_reads(n_reads, ref_len, seed, paired)
             for k in self.KEYS:
                 np.save(os.path.join(self.dir, k + ".npy"), self.cols[k])
             log(f"{tag}: generated {n_reads} reads once for {world} ranks in {time.time() - t0:.1f} s -> {self.dir}")
@@ -490,7 +587,7 @@ class Workload:
 
         from bamsignals_amd import _lib
         from bamsignals_amd.device import Context, Plan, Reads, layout, make_params
-        from bamsignals_amd.synth import synth_ranges, synth_reads
+        from bamsignals_amd.synth import synth_ranges
         self.name, self.cfg = name, CONFIGS[name]
         cfg = self.cfg
         self.rank, self.world = rank, world
@@ -505,7 +602,7 @@ class Workload:
         # config 2; a batch of the larger configurations (>= 1 GB per step) exceeds it by itself
         nb = nb or (8 if self.n_reads <= 100_000_000 else 2)
         t0 = time.time()
-        self.cols = cols if cols is not None else synth_reads(self.n_reads, cfg["ref_len"], seed=a.seed, paired=cfg["paired"], with_cigar=False)
+        self.cols = cols if cols is not None else make_reads(self.n_reads, cfg["ref_len"], a.seed, cfg["paired"])
         self.full, self.batches = [], []
         for b in range(nb):
             all_rg = synth_ranges(self.n_ranges, self.width, cfg["ref_len"], seed=a.seed + 1 + 7919 * b)
@@ -766,6 +863,41 @@ def committed_traffic(a, name, cfg):
     return None, None
 
 
+DUMP_CELLS = 1 << 22            # cells sampled by --dump-outputs (32 MB as float64)
+DUMP_RANGES = 1 << 20           # ranges whose sum and width it writes (8 MB each as float64)
+
+
+def dump_pick(total, k, seed):
+    """The positions --dump-outputs writes out of `total`: all of them up to `k`, else a fixed, seeded, sorted sample."""
+    return np.arange(total, dtype=np.int64) if total <= k else np.unique(np.random.default_rng(seed).integers(0, total, k))
+
+
+def dump_outputs(w, steps, d):
+    """--dump-outputs: what the last timed step computed -- batch (steps - 1) % nb's result as its caller holds it (at
+    N > 1 assembled on rank 0) -- as float64 .npy files in `d`: cells_sample (the cells at DUMP_CELLS fixed, seeded
+    positions, all of them when there are fewer), range_sums and range_widths (every range's, or those of DUMP_RANGES
+    fixed, seeded ranges).  The positions depend only on the result's shape, so runs with the same arguments compare."""
+    import torch
+    b = (steps - 1) % w.nb
+    plan = w.full_plans[b]
+    cells = int(plan.cells)
+    res = w.final[b][:cells]
+    off = np.asarray(plan.offsets, dtype=np.int64)
+    ci, ri = dump_pick(cells, DUMP_CELLS, 0xD0C5), dump_pick(len(off) - 1, DUMP_RANGES, 0xD0C6)
+    # every range's sum from an int64 running sum on the device (the result is not copied to the host whole)
+    cs = torch.zeros(cells + 1, dtype=torch.int64, device=res.device)
+    cs[1:] = torch.cumsum(res, 0, dtype=torch.int64)
+    lo, hi = torch.from_numpy(off[ri]).to(res.device), torch.from_numpy(off[ri + 1]).to(res.device)
+    out = dict(cells_sample=res[torch.from_numpy(ci).to(res.device)].double().cpu().numpy(),
+               range_sums=(cs[hi] - cs[lo]).double().cpu().numpy(),
+               range_widths=(off[ri + 1] - off[ri]).astype(np.float64))
+    del cs
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    log(f"outputs of step {steps} (batch {b}) -> {d}: " + ", ".join(f"{k} {v.size}" for k, v in out.items()))
+
+
 def strong_block(a, rank, world, stream, ctx, reads, cols, use_dist, dist, cdev, barrier, backend, n_ranges_total, steps):
     """BASELINE config 5 at FIXED total size over `world` GPUs, the whole north-star step timed:
        kernel on this rank's shard of the (rid, loc)-sorted ranges (ref: src/bamsignals.cpp:222-226,246)
@@ -1016,17 +1148,36 @@ def main():
     ap.add_argument("--in-process-slots", type=int, default=0, help="run the in-process block with this many GPU slots even "
                     "with one rank (slots beyond the box's GPUs reuse them: testing)")
     ap.add_argument("--budget-s", type=float, default=420.0, help="optional blocks are skipped once the run is older than this")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the oracle parity check, cpu_baseline, end_to_end(_realistic), also.C2, "
+                         "and at N > 1 step_phases, no_collective, strong and in_process (a plain run sets up, warms up, "
+                         "times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; a fixed sample "
+                         "of the cells, every range's sum and width)")
     a = ap.parse_args()
     t_program = time.time()
-
-    import torch
-    import torch.distributed as dist
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full and (a.pipelined or a.strong or a.in_process_slots):
+        ap.error("--pipelined, --strong and --in-process-slots are measured with --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus}")
+    cfg = CONFIGS[a.config]
+    early = None
+    if world == 1:
+        # one rank: its reads are generated while torch and the HIP runtime start (numpy releases the GIL throughout)
+        from concurrent.futures import ThreadPoolExecutor
+        early = ThreadPoolExecutor(1)
+        early_reads = early.submit(SharedReads, a.config, a.reads or cfg["reads"], cfg["ref_len"], a.seed, cfg["paired"], 0, 1, None)
+
+    import torch
+    import torch.distributed as dist
+
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
     ngpu = torch.cuda.device_count()
@@ -1071,9 +1222,12 @@ def main():
         dist.broadcast(t, src=0, group=host_group) if host_group is not None else dist.broadcast(t, src=0)
         return bool(t.item())
 
-    cfg = CONFIGS[a.config]
     stream = torch.cuda.Stream()
-    shared = SharedReads(a.config, a.reads or cfg["reads"], cfg["ref_len"], a.seed, cfg["paired"], rank, world, host_barrier)
+    if early is not None:
+        shared = early_reads.result()
+        early.shutdown()
+    else:
+        shared = SharedReads(a.config, a.reads or cfg["reads"], cfg["ref_len"], a.seed, cfg["paired"], rank, world, host_barrier)
     gathered = world > 1 or a.force_dist
     w = Workload(a, a.config, rank, world, local, stream, a.reads, a.ranges, a.width, a.batches, cols=shared.cols, t_gen=shared.t_gen,
                  gathered=gathered)
@@ -1094,11 +1248,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(w, a.steps, a.dump_outputs)
 
     # ---- N > 1, informational: where a step's time goes (events between its parts, a second run of the same steps),
     # and every rank running the WHOLE range set alone with nothing exchanged (N replicas; rounds 1-4's `value`)
     phases = replicas = None
-    if gathered:
+    if gathered and a.full:
         ksteps = min(a.steps, 20)
         ph = w.phases(ksteps, stream, barrier)
         allph = [None] * world
@@ -1149,16 +1305,17 @@ def main():
             p2.close()
         ctx2.close()
 
-    # ---- correctness of what was just timed, then the CPU baseline (rank 0) ----------------------
-    got = w.outs[0][:plan.cells].cpu().numpy() if not gathered else None
+    # ---- correctness of what was just timed, then the CPU baseline (rank 0; --full) ----------------
+    got = w.outs[0][:plan.cells].cpu().numpy() if not gathered and a.full else None
     parity = cpu = e2e = None
     bases = w.step_bases[0]
-    # (the oracle is the checker and the CPU baseline: loaded on rank 0 only, after the timed region)
     if rank == 0:
-        from oracle import oracle_c
-        orc, parity = w.check_parity(oracle_c)
         if gathered and a.wire == "narrow" and any(m.narrow_overflowed() for ms in w.maps for m in ms):
             raise SystemExit("a narrow message had more exceptions than its list holds: refusing to report a number")
+    # (the oracle is the checker and the CPU baseline: loaded on rank 0 only, after the timed region)
+    if rank == 0 and a.full:
+        from oracle import oracle_c
+        orc, parity = w.check_parity(oracle_c)
         log(f"parity ok ({parity}); step {kernel_ms * 1e3:.1f} us")
         if not a.no_cpu_baseline and world == 1:          # (the contract: rank 0 at N = 1 only)
             # the oracle (C restatement of overlapAndPileup + Pileupper, single thread) on the
@@ -1216,7 +1373,8 @@ def main():
                                  "one bsig_plan_run per step from the host loop: k_resolve_tiles + the pileup launch in every step (BAMSIGNALS_CACHE_WINDOWS=0)",
                        "threads": w.params.threads or 64,
                        "tile_cells": w.params.tile_cells or "auto (widest range, at most 2048)"},
-            "roofline": w.roofline(kernel_ms, traffic, traffic_src),
+            # (at N > 1 the launch's own time comes from step_phases' run: --full)
+            "roofline": w.roofline(kernel_ms, traffic, traffic_src) if not gathered or a.full else None,
             "cpu_baseline": cpu,
             "end_to_end": None,
             "parity_checked": parity,
@@ -1235,8 +1393,8 @@ def main():
         }
 
     # ---- N > 1: config 5 at fixed total size with the collective in the timed region; the in-process route ------
-    want_strong = (world > 1 or a.strong) and not a.no_strong
-    want_inproc = (world > 1 and not a.no_in_process) or a.in_process_slots > 0
+    want_strong = a.full and (world > 1 or a.strong) and not a.no_strong
+    want_inproc = a.full and ((world > 1 and not a.no_in_process) or a.in_process_slots > 0)
     if want_strong or want_inproc:
         go = all_agree(time.time() - t_program < a.budget_s)
         if not go:
@@ -1303,8 +1461,8 @@ def main():
                 res["in_process"] = {"skipped": "time budget used up before the block"}
             del cols5
 
-    # ---- N = 1 extras: the same workload from a BAM file, and config 2's small launch ---------------
-    if rank == 0 and world == 1 and not use_dist and not (want_strong or want_inproc):
+    # ---- N = 1 extras (--full): the same workload from a BAM file, and config 2's small launch -------
+    if rank == 0 and world == 1 and not use_dist and a.full and not (want_strong or want_inproc):
         cols = w.cols
         want_flat = got[:plan.cells]
         # the cold calls run in child processes WHILE this process still holds its workload: round 3 freed 8 GB of

@@ -33,7 +33,7 @@ def test_two_ranks_emit_strong_and_in_process_blocks(wire):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", "C5",
-           "--reads", "3000000", "--ranges", "3000", "--strong-ranges", "6000", "--strong-steps", "3", "--steps", "6", "--warmup", "2", "--wire", wire]
+           "--reads", "3000000", "--ranges", "3000", "--strong-ranges", "6000", "--strong-steps", "3", "--steps", "6", "--warmup", "2", "--wire", wire, "--full"]
     if wire == "int32":
         cmd += ["--no-in-process"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=560, cwd=ROOT)

@@ -174,23 +174,57 @@ void R_init_bamsignals(DllInfo *info) { R_registerRoutines(info, NULL, m, NULL, 
     assert Rb.to_py(Rb.call("good", Rb.int([1]), Rb.int([2])))[0].tolist() == [0, 0]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference checkout is only present in the build container")
+# the five native routines the package's R code reaches by name (R/RcppExports.R) and their arities
+ROUTINES = {"bamsignals_checkList": 2, "bamsignals_fastWidth": 2, "bamsignals_pileup_core": 11,
+            "bamsignals_coverage_core": 8, "bamsignals_writeSamAsBamAndIndex": 2}
+
+
+def _standin_checkout(path):
+    """A small tree shaped like a bamsignals checkout -- the files and lines graft_into_reference.sh touches or must
+    leave alone, with placeholder contents -- so that the graft is tested without a checkout of the package."""
+    files = {
+        "DESCRIPTION": "Package: bamsignals\nType: Package\nImports:\n    methods,\n    Rcpp (>= 0.10.6),\n    IRanges\n"
+                       "LinkingTo: Rcpp, Rhtslib (>= 1.13.1)\nSystemRequirements: GNU make\nNeedsCompilation: yes\n",
+        "NAMESPACE": "export(bamProfile)\nimport(IRanges)\nimport(Rcpp)\nimport(methods)\nuseDynLib(bamsignals, .registration=TRUE)\n",
+        "R/RcppExports.R": "".join(
+            f"{n[len('bamsignals_'):]} <- function({', '.join(f'a{i}' for i in range(k))}) {{\n"
+            f"    .Call('{n}', PACKAGE = 'bamsignals', {', '.join(f'a{i}' for i in range(k))})\n}}\n\n" for n, k in ROUTINES.items()),
+        "R/wrappers.R": "# placeholder: the package's R front end\n",
+        "man/bamsignals.Rd": "% placeholder manual page\n",
+        "vignettes/bamsignals.Rmd": "placeholder vignette\n",
+        "inst/extdata/placeholder.txt": "placeholder data\n",
+        "src/bamsignals.cpp": "// placeholder\n", "src/CountSignals.cpp": "// placeholder\n",
+        "src/RcppExports.cpp": "// placeholder\n", "src/bamsignals_init.c": "/* placeholder */\n",
+        "src/Makevars": "PKG_LIBS = placeholder\n", "src/Makevars.win": "PKG_LIBS = placeholder\n",
+        "src/bamsignals.o": "", "src/bamsignals.so": "",
+        "tests/testthat.R": "library(testthat)\n",
+        "tests/testthat/test_methods.R": "# placeholder\n", "tests/testthat/test_CountSignals.R": "# placeholder\n",
+    }
+    for rel, text in files.items():
+        p = path / rel
+        p.parent.mkdir(parents=True, exist_ok=True)
+        p.write_text(text)
+    return path
+
+
 def test_graft_script_swaps_only_the_native_half(tmp_path):
-    """r_package/graft_into_reference.sh on a scratch copy of the reference: R/, man/, tests/ untouched,
+    """r_package/graft_into_reference.sh on a stand-in bamsignals checkout: R/, man/, tests/ untouched,
     src/ = shim.c + Makevars, Rcpp/Rhtslib gone from DESCRIPTION/NAMESPACE, and the grafted shim registers
     the names R/RcppExports.R calls."""
     import filecmp
     import re
     import shutil
+    pristine = _standin_checkout(tmp_path / "pristine")
     ref = tmp_path / "bamsignals"
-    shutil.copytree("/root/reference", ref)
+    shutil.copytree(pristine, ref)
     subprocess.check_call(["sh", os.path.join(ROOT, "bamsignals_amd", "r_package", "graft_into_reference.sh"), str(ref), ROOT])
     assert sorted(os.listdir(ref / "src")) == ["Makevars", "shim.c"]
     for sub in ("R", "man", "vignettes", "inst"):
-        cmp = filecmp.dircmp("/root/reference/" + sub, ref / sub)
+        cmp = filecmp.dircmp(pristine / sub, ref / sub)
         assert not cmp.diff_files and not cmp.left_only and not cmp.right_only, sub
     assert "Rcpp" not in (ref / "NAMESPACE").read_text() and "Rhtslib" not in (ref / "DESCRIPTION").read_text()
     called = set(re.findall(r"\.Call\('(bamsignals_\w+)'", (ref / "R" / "RcppExports.R").read_text()))
-    registered = set(re.findall(r'\{"(bamsignals_\w+)", \(DL_FUNC\)', (ref / "src" / "shim.c").read_text()))
-    assert called == registered and len(called) == 5
+    registered = dict((n, int(k)) for n, k in re.findall(r'\{"(bamsignals_\w+)", \(DL_FUNC\)[^,]*, (\d+)\}', (ref / "src" / "shim.c").read_text()))
+    assert called == set(registered) and len(called) == 5 and registered == ROUTINES
     assert {"test_methods.R", "test_CountSignals.R", "test_golden.R", "test_vignette_invariants.R"} <= set(os.listdir(ref / "tests" / "testthat"))
+    assert "gfx950" in (ref / "DESCRIPTION").read_text() and f"BAMSIGNALS_HIP_DIR ?= {ROOT}" in (ref / "src" / "Makevars").read_text()
