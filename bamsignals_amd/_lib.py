@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("BSIG_LIB_PATH") or os.path.join(_HERE, "libbamsignals_hip.so")
 
 BSIG_OK = 0
-MODE_PROFILE, MODE_COUNT, MODE_COVERAGE = 0, 1, 2
+MODE_PROFILE, MODE_COUNT, MODE_COVERAGE, MODE_COVERAGE_EX = 0, 1, 2, 3
 
 ERR_NAMES = {-1: "BSIG_ERR_ARG", -2: "BSIG_ERR_IO", -3: "BSIG_ERR_NOINDEX", -4: "BSIG_ERR_CHROM",
              -5: "BSIG_ERR_EXT", -6: "BSIG_ERR_DEVICE", -7: "BSIG_ERR_NOMEM", -8: "BSIG_ERR_FORMAT"}
@@ -104,6 +104,7 @@ def load():
     lib.bsig_plan_run.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_host_async.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_overflowed.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.bsig_plan_free.argtypes = [C.c_void_p]
     lib.bsig_plan_free.restype = None
     lib.bsig_pileup_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -135,6 +136,8 @@ def load():
     lib.bsig_coverage_core.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]
     lib.bsig_pileup_core_into.argtypes = core_head + [C.c_int32] * 9 + [C.c_void_p]
     lib.bsig_coverage_core_into.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
+    lib.bsig_coverage_core_ex.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]
+    lib.bsig_coverage_core_ex_into.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_write_sam_as_bam_and_index.argtypes = [C.c_char_p, C.c_char_p]
     lib.bsig_write_columns_as_bam.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(Columns),
                                               C.c_int32]

@@ -90,7 +90,7 @@ struct BsigKParams {
     int32_t midpoint;
     int32_t tspan;
     int32_t ss;
-    int32_t binsize;        // >= 1 (profile)
+    int32_t binsize;        // >= 1 (profile, binned coverage; 1 for per-base coverage)
     uint32_t div_magic;     // exact n / binsize for 0 <= n < 2^31:
     int32_t div_shift;      //   __umulhi(n, div_magic) >> div_shift        (binsize >= 2)
     uint32_t div_m15;       // ... and for 0 <= n < 2^15 (a range shorter than 32,768 bases) at the full rate of the
@@ -102,9 +102,11 @@ struct BsigKParams {
     int32_t resolved;       // 1: `windows` holds one BsigResolved per tile, written by k_resolve_tiles in
                             // front of this launch (large launches: the tile's item and its windows then
                             // arrive in ONE memory round trip instead of two dependent ones)
-    int32_t pad_;
+    int32_t cov_reps;       // binned coverage: copies of the tile image (set by the launch, see k_coverage_bins)
     const uint8_t *ptab;    // the packed class's filter table for THESE parameters (BSIG_PACK_CODES bytes on the
                             // device: bit 0 rejected, bit 1 reverse strand), made once per plan by k_make_ptab
+    int32_t *overflow;      // binned coverage: set to 1 by a heavy tile's slice whose atomic add took a bin past
+                            // INT32_MAX (the plan's device flag; NULL where no add can)
 };
 
 #endif

@@ -418,6 +418,8 @@ int run_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, c
         if (r) return r;
         r = bsig_plan_run(S.plan, X.d_shard);
         if (r) return r;
+        r = bsig::plan_check_overflow(S.plan);       // (binned coverage with heavy slices only: waits for the run)
+        if (r) return r;
         if (blocks) {
             // every contiguous slice of the caller's result this GPU owns leaves over this GPU's own PCIe link,
             // straight to its place: no gather on one GPU, no reassembly pass on the host
@@ -695,12 +697,16 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         if (width[i] < 0) return fail(BSIG_ERR_ARG, "range %lld has a negative width", (long long)i);
     }
     // same argument checks as bsig_plan_create, before any I/O
-    const bool mid = prm.mode != BSIG_MODE_COVERAGE && prm.pe_mid;
-    const bool tspan = prm.mode == BSIG_MODE_COVERAGE && prm.tspan;
+    const bool cov = prm.mode == BSIG_MODE_COVERAGE || prm.mode == BSIG_MODE_COVERAGE_EX;
+    const bool mid = !cov && prm.pe_mid;
+    const bool tspan = cov && prm.tspan;
     if ((mid || tspan) && prm.n_tlen_filter != 2)
         return fail(BSIG_ERR_ARG, "paired-end midpoint/extend needs a 2-element tlen_filter");
-    int64_t ext = prm.mode == BSIG_MODE_COVERAGE ? (tspan ? prm.tlen_filter[1] : 0)
-                                                 : std::llabs((long long)prm.shift) + (mid ? prm.tlen_filter[1] : 0);
+    if (prm.mode == BSIG_MODE_COVERAGE_EX && (prm.binsize < 1 || prm.binsize > bsig::kMaxCoverageBin))
+        return fail(BSIG_ERR_ARG, prm.binsize < 1 ? "provide a binsize greater or equal to 1"
+                                                  : "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
+    int64_t ext = cov ? (tspan ? prm.tlen_filter[1] : 0)
+                      : std::llabs((long long)prm.shift) + (mid ? prm.tlen_filter[1] : 0);
     if (ext < 0) return fail(BSIG_ERR_EXT, "negative 'ext' values don't make sense");             // ref: :243
 
     // the GPUs of this call: every device list seen keeps its own contexts, scratch and resident BAMs (a
@@ -1169,13 +1175,15 @@ static int coverage_core_impl(const char *bampath, int64_t n, const int32_t *seq
                               const char *const *levels, const int32_t *start, const int32_t *width,
                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
-                              int32_t maxgap, int32_t device, int32_t *out, const int64_t *off, int32_t *const *dst)
+                              int32_t maxgap, int32_t device, int32_t *out, const int64_t *off, int32_t *const *dst,
+                              bool ex = false, int32_t binsize = 1, int32_t ss = 0)
 {
     (void)maxgap;
     bsig_params p;
     memset(&p, 0, sizeof p);
-    p.mode = BSIG_MODE_COVERAGE;
-    p.mapqual = mapqual; p.binsize = 1; p.requiredF = requiredF; p.filteredF = filteredF; p.tspan = tspan;
+    p.mode = ex ? BSIG_MODE_COVERAGE_EX : BSIG_MODE_COVERAGE;
+    p.mapqual = mapqual; p.binsize = ex ? binsize : 1; p.requiredF = requiredF; p.filteredF = filteredF; p.tspan = tspan;
+    p.ss = ex && ss;
     if (n_tlen_filter != 0 && n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "tlen_filter must have 0 or 2 elements");
     p.n_tlen_filter = n_tlen_filter;
     for (int k = 0; k < n_tlen_filter; ++k) p.tlen_filter[k] = tlen_filter[k];
@@ -1183,8 +1191,9 @@ static int coverage_core_impl(const char *bampath, int64_t n, const int32_t *seq
     std::vector<int64_t> own_off;
     if (dst) {
         if (n < 0 || (n > 0 && !width)) return fail(BSIG_ERR_ARG, "range arrays missing");
+        // (a binsize outside 1 .. 65,536 fails in file_level before any I/O; the layout only needs it >= 1 here)
         own_off.resize((size_t)n + 1);
-        bsig_layout(n, width, 1, 0, own_off.data());
+        bsig_layout(n, width, std::max<int32_t>(p.binsize, 1), p.ss, own_off.data());
         D.off = own_off.data(); D.n = n; D.ptrs = dst;
     } else {
         D.flat = out; D.off = off; D.n = n;
@@ -1211,6 +1220,27 @@ int bsig_coverage_core_into(const char *bampath, int64_t n, const int32_t *seq_c
     if (!dst) return fail(BSIG_ERR_ARG, "destinations missing");
     return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
                               requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, dst);
+}
+
+int bsig_coverage_core_ex(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                          const char *const *levels, const int32_t *start, const int32_t *width,
+                          const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                          int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                          int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *out, const int64_t *off)
+{
+    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
+                              requiredF, filteredF, tspan, maxgap, device, out, off, nullptr, true, binsize, ss);
+}
+
+int bsig_coverage_core_ex_into(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                               const char *const *levels, const int32_t *start, const int32_t *width,
+                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *const *dst)
+{
+    if (!dst) return fail(BSIG_ERR_ARG, "destinations missing");
+    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
+                              requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, dst, true, binsize, ss);
 }
 
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath)

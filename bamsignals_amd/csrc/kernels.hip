@@ -8,6 +8,7 @@
 //   k_profile   Pileupper::setRead/pileup       src/bamsignals.cpp:326-363  (binsize >= 1)
 //   k_count     the same with binsize <= 0      src/bamsignals.cpp:148-169, 349-363
 //   k_coverage  Coverager::setRead/pileup+cumsum src/bamsignals.cpp:392-438, 464-470
+//   k_coverage_bins  the same summed over bins and / or split by strand (bamCoverage's binsize / ss)
 //   k_cigar_end bam_endpos - 1 from packed CIGAR (htslib; call site src/bamsignals.cpp:16-18)
 //   k_span_hist / k_scatter / k_build_idx       one-time layout of the reads in HBM (bsig_types.h)
 //   k_visits    counts read visits for the roofline figure
@@ -537,7 +538,7 @@ __device__ __forceinline__ void item_interval(const BsigWorkItem &w, const BsigK
 {
     const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
     if (mode == BSIG_MODE_COUNT) { tlo = (int64_t)w.loc + w.c0; thi = tlo + w.nc; }
-    else tile_interval(w, mode == BSIG_MODE_COVERAGE ? 1 : P.binsize, neg_range, tlo, thi);
+    else tile_interval(w, P.binsize, neg_range, tlo, thi);        // (1 for per-base coverage)
 }
 
 // Index lookup for every (tile, class): windows[BSIG_MAX_CLASSES*t + c] = [j_lo, j_hi) of class c's reads
@@ -1321,6 +1322,173 @@ __global__ __launch_bounds__(NT) void k_coverage(const BsigWorkItem *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// bamCoverage in bins of b bases and/or split by strand: the per-base coverage summed over each bin
+// ------------------------------------------------------------------------------------------
+// A read covers the bases [ra, rb] of the tile (range orientation, clipped to the tile), i.e. a tail h of
+// its first bin ja, every base of the bins between, and a head t of its last bin jb.  The tile keeps ONE
+// int32 difference image D whose prefix sum is the bin value: D[ja] += h, D[ja+1] += b - h, D[jb] += t - b,
+// D[jb+1] -= t (two adds if ja == jb, three if jb == ja + 1): at most four LDS atomics a read, whatever its
+// span.  Each read adds at most b to a cell in magnitude, and a tile that is not cut into slices has at most
+// 32,767 reads in its windows, so with b <= 65,536 neither a cell of D nor any prefix of it can leave int32.
+// With SS the image holds cell 2*bin + antisense -- the result's own order -- and the two rows are scanned
+// apart.
+// The reads of a pass are consecutive in position, so with wide bins most lanes of a wave add to the same one or two
+// cells, and LDS atomics to one address execute one after the other: the image is kept in P.cov_reps copies (lane l
+// adds to copy l % reps; copies lie an odd number of 16-B vectors apart, so one cell's copies sit in different banks),
+// summed when the scan reads them.
+template <bool SS>
+struct CoverBinsOne {
+    const BsigKParams &P;
+    int32_t *img;
+    int loc, c0, nc, sh;
+    bool neg_range;
+    int rend1;                              // last base of the range
+    int lo, hi;                             // the tile's bases in range orientation, [lo, hi]
+    __device__ __forceinline__ int bin_of(int x) const
+    {
+        return P.binsize == 1 ? x : (int)(__umulhi((uint32_t)x, P.div_magic) >> P.div_shift);
+    }
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        if (!valid || rej || tlen_rejected(P, tl)) return;            // ref: src/bamsignals.cpp:394-399
+        int start = p, end = e;
+        if (P.tspan) {                                                // :404-413 (the fragment keeps this read's strand)
+            if (neg && tl < 0) start = end + tl + 1;
+            else if (!neg && tl > 0) end = start + tl - 1;
+        }
+        int ra = neg_range ? rend1 - end : start - loc;
+        int rb = neg_range ? rend1 - start : end - loc;
+        ra = ra > lo ? ra : lo;
+        rb = rb < hi ? rb : hi;
+        if (ra > rb) return;
+        const int b = P.binsize;
+        const int ga = bin_of(ra), gb = bin_of(rb);
+        const int ja = ga - c0, jb = gb - c0;
+        constexpr int S = SS ? 2 : 1;
+        const int k = sh + (SS && neg != neg_range ? 1 : 0);         // antisense: the read's strand is not the range's
+        if (ja == jb) {
+            const int n = rb - ra + 1;
+            atomicAdd(&img[k + S * ja], n);
+            if (ja + 1 < nc) atomicAdd(&img[k + S * (ja + 1)], -n);
+            return;
+        }
+        const int h = b - (ra - ga * b), t = rb - gb * b + 1;
+        atomicAdd(&img[k + S * ja], h);
+        atomicAdd(&img[k + S * (ja + 1)], jb == ja + 1 ? t - h : b - h);
+        if (jb > ja + 1) atomicAdd(&img[k + S * jb], t - b);
+        if (jb + 1 < nc) atomicAdd(&img[k + S * (jb + 1)], -t);
+    }
+};
+
+// add_vec for binned coverage: every addend is >= 0, so an add that takes a cell past INT32_MAX is told by the
+// value it returns; it raises the plan's flag, and the host fails the call instead of returning a wrapped value
+__device__ __forceinline__ void add_vec_checked(int32_t *__restrict__ gbase, int v, int4 x, int sh, int nv,
+                                                int32_t *__restrict__ overflow)
+{
+    const int e0 = 4 * v, lo = sh, hi = sh + nv;
+    bool over = false;
+    auto one = [&](int e, int a) {
+        if (a && e >= lo && e < hi) over |= (int64_t)atomicAdd(gbase + e, a) + a > (int64_t)INT32_MAX;
+    };
+    one(e0 + 0, x.x);
+    one(e0 + 1, x.y);
+    one(e0 + 2, x.z);
+    one(e0 + 3, x.w);
+    if (over) atomicOr(overflow, 1);
+}
+
+// 16-B vectors of one copy of a k_coverage_bins image of `cells` cells (+ the shift), odd; and the copies a launch
+// keeps: as many as fit 8 KiB, at most 16 (env BAMSIGNALS_COVERAGE_REPLICAS: 1, 2, 4, 8 or 16 instead)
+__host__ __device__ __forceinline__ int cov_bins_vec(int cells) { return ((cells + 7) / 4) | 1; }
+static int cov_bins_reps(int cells)
+{
+    static const int forced = getenv("BAMSIGNALS_COVERAGE_REPLICAS") ? atoi(getenv("BAMSIGNALS_COVERAGE_REPLICAS")) : 0;
+    if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) return forced;
+    int r = 1;
+    while (r < 16 && 2 * r * cov_bins_vec(cells) * 16 <= 8192) r *= 2;
+    return r;
+}
+
+template <int NT, int PRE, bool RES, bool SS>
+__global__ __launch_bounds__(NT) void k_coverage_bins(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                      int32_t *__restrict__ out,
+                                                      const uint2 *__restrict__ windows,
+                                                      const BsigReadsDev R, const BsigKParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    constexpr int S = SS ? 2 : 1;
+    constexpr int NW = NT / kWave;
+    const int img_vec = cov_bins_vec(P.tile_cells * S);        // 16-B vectors of one copy (4 cells each, shift included)
+    const int reps = P.cov_reps;
+    int32_t *wtot = lds + 4 * img_vec * reps;                  // per-wave scan totals (S of them), behind the copies
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const uint32_t tile = tile_of_block(blockIdx.x, n_tiles);
+    const BsigWorkItem w = items[tile];
+    uint2 win[BSIG_MAX_CLASSES], clip;
+    PackedWin pk;
+    load_windows<RES>(R, P, BSIG_MODE_COVERAGE, w, items, windows, win, tile, pk, clip);
+    int4 *lds4 = reinterpret_cast<int4 *>(lds);
+    for (int v = tid; v < img_vec * reps; v += NT) lds4[v] = make_int4(0, 0, 0, 0);
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds4 + img_vec * reps + (S * NW + 3) / 4);
+    build_ptab<NT>(ptab, R, P, tid);
+    const int nv = w.nc * S;
+    const int sh = (int)(w.out_off & 3);                       // (even with SS: a range's cells come in pairs)
+    const int nvec = (sh + nv + 3) >> 2;
+    block_sync<NT>();
+
+    const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
+    const int lo = w.c0 * P.binsize;
+    const int64_t tile_end = ((int64_t)w.c0 + w.nc) * P.binsize;
+    const int hi = (int)(tile_end < w.len ? tile_end : (int64_t)w.len) - 1;
+    const CoverBinsOne<SS> one{P, lds + 4 * img_vec * (lane & (reps - 1)), w.loc, w.c0, w.nc, sh, neg_range, w.loc + w.len - 1, lo, hi};
+    for_each_read<NT, PRE>(R, P, win, pk.base, ptab, tid, one);
+    if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
+    block_sync<NT>();
+
+    // prefix sum of D (per row with SS): each lane owns 4 consecutive cells, wave scan of the lane totals, carry
+    // across waves and across passes
+    int32_t *gbase = out + (w.out_off - sh);
+    int carry0 = 0, carry1 = 0;
+    for (int base = 0; base < nvec; base += NT) {
+        const int v = base + tid;
+        int4 x = make_int4(0, 0, 0, 0);
+        if (v < nvec)
+            for (int r = 0; r < reps; ++r) {
+                const int4 y = lds4[r * img_vec + v];
+                x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+            }
+        int tot0, tot1 = 0;
+        if (SS) { x.z += x.x; x.w += x.y; tot0 = x.z; tot1 = x.w; }      // cells (bin, row): (j,0) (j,1) (j+1,0) (j+1,1)
+        else    { x.y += x.x; x.z += x.y; x.w += x.z; tot0 = x.w; }
+        const int incl0 = wave_inclusive_scan(tot0);
+        const int incl1 = SS ? wave_inclusive_scan(tot1) : 0;
+        int pre0 = carry0, pre1 = carry1;
+        int all0 = __builtin_amdgcn_readlane(incl0, kWave - 1);
+        int all1 = SS ? __builtin_amdgcn_readlane(incl1, kWave - 1) : 0;
+        if (NW > 1) {
+            if (lane == kWave - 1) { wtot[S * (tid / kWave)] = incl0; if (SS) wtot[S * (tid / kWave) + 1] = incl1; }
+            __syncthreads();
+            all0 = 0; all1 = 0;
+            for (int k = 0; k < NW; ++k) {
+                const int t0 = wtot[S * k], t1 = SS ? wtot[S * k + 1] : 0;
+                if (k < tid / kWave) { pre0 += t0; pre1 += t1; }
+                all0 += t0; all1 += t1;
+            }
+            __syncthreads();
+        }
+        const int add0 = pre0 + incl0 - tot0, add1 = pre1 + incl1 - tot1;
+        if (SS) { x.x += add0; x.z += add0; x.y += add1; x.w += add1; }
+        else    { x.x += add0; x.y += add0; x.z += add0; x.w += add0; }
+        if (v < nvec) {
+            if (P.accumulate) add_vec_checked(gbase, v, x, sh, nv, P.overflow);
+            else store_vec(gbase, v, x, sh, nv);
+        }
+        carry0 += all0; carry1 += all1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // one-time layout of the reads in HBM
 // ------------------------------------------------------------------------------------------
 
@@ -1809,6 +1977,16 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         if (ss) { if (pre <= 2) { if (w8) BSIG_KP(true, 2, 8); else BSIG_KP(true, 2, 1); } else if (pre == 3) BSIG_KP(true, 3, 1); else BSIG_KP(true, 4, 1); }
         else    { if (pre <= 2) { if (w8) BSIG_KP(false, 2, 8); else BSIG_KP(false, 2, 1); } else if (pre == 3) BSIG_KP(false, 3, 1); else BSIG_KP(false, 4, 1); }
 #undef BSIG_KP
+    } else if (mode == BSIG_MODE_COVERAGE && (P.binsize > 1 || ss)) {
+        // bins and / or strands (k_coverage_bins): int32 difference image, the scan totals, the packed class's table
+        const int S = ss ? 2 : 1;
+        BsigKParams Q = P;
+        Q.cov_reps = cov_bins_reps(tile_cells * S);
+        const size_t lds = (size_t)cov_bins_vec(tile_cells * S) * Q.cov_reps * 16 + (size_t)((S * NT / 64 + 3) / 4) * 16 + BSIG_PACK_CODES;
+#define BSIG_KB(RES_, SS_) hipLaunchKernelGGL((k_coverage_bins<NT, 2, RES_, SS_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, Q)
+        if (ss) { if (P.resolved) BSIG_KB(true, true); else BSIG_KB(false, true); }
+        else    { if (P.resolved) BSIG_KB(true, false); else BSIG_KB(false, false); }
+#undef BSIG_KB
     } else if (mode == BSIG_MODE_COVERAGE) {
         const size_t lds = (size_t)((tile_cells + 8 + 7) / 8) * 16 + (size_t)((NT / 64 + 3) / 4) * 16 + BSIG_PACK_CODES;   // signed 16-bit cells, scan totals, the packed class's table
         // (the packed class's passes hold 256 reads each: two in flight cover a 2-kb tile at 100-fold coverage; the form

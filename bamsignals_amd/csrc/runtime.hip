@@ -269,6 +269,7 @@ struct bsig_plan {
     bool have_stats = false;
     bsig_plan_stats stats{};
     uint8_t *ptab = nullptr;            // the packed class's filter table for kp (BsigKParams::ptab)
+    int32_t *overflow = nullptr;        // binned coverage with heavy slices: 1 if a run's atomic adds took a bin past INT32_MAX
     BsigResolved *resolved = nullptr;   // large launches: the windows of every tile, written by k_resolve_tiles
     uint64_t resolved_gen = 0;          // ... for this layout of the reads (0: not yet): a later run on the same layout reuses them
     uint64_t made_for_gen = 0;          // the layout the plan was made on: its tiles' heavy slices and the packed class's filter
@@ -1315,7 +1316,15 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
     if (n < 0 || (n > 0 && (!rid || !loc || !len || !strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
-    const int mode = prm->mode;
+    if (prm->mode == BSIG_MODE_COVERAGE_EX && (prm->binsize < 1 || prm->binsize > bsig::kMaxCoverageBin))
+        return fail(BSIG_ERR_ARG, prm->binsize < 1 ? "provide a binsize greater or equal to 1"
+                                                   : "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
+    // coverage with bins / strands IS coverage from here on (the result layout, ext, tspan, the heavy-tile ceiling);
+    // only cov_bin and cov_ss tell it apart (mode 2 ignores binsize and ss)
+    const bool cov_ex = prm->mode == BSIG_MODE_COVERAGE_EX;
+    const int mode = cov_ex ? BSIG_MODE_COVERAGE : prm->mode;
+    const int32_t cov_bin = cov_ex ? prm->binsize : 1;
+    const bool cov_ss = cov_ex && prm->ss != 0;
     if (mode != BSIG_MODE_PROFILE && mode != BSIG_MODE_COUNT && mode != BSIG_MODE_COVERAGE)
         return fail(BSIG_ERR_ARG, "unknown mode %d", mode);
     if (mode == BSIG_MODE_PROFILE && prm->binsize < 1)
@@ -1344,17 +1353,20 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     // default tile: the widest range if it fits 2048 cells (less LDS per workgroup = more
     // workgroups per CU), else 2048-cell tiles
     int64_t widest = 64;
+    // (binned profiles and binned / strand-split coverage size their tiles by one rule)
+    const bool binned = mode == BSIG_MODE_PROFILE || cov_ex;
+    const bool split_ss = binned && prm->ss;
     {
-        const int64_t bsz = mode == BSIG_MODE_PROFILE ? prm->binsize : 1;
+        const int64_t bsz = mode == BSIG_MODE_PROFILE ? prm->binsize : cov_bin;
         for (int64_t i = 0; i < n && mode != BSIG_MODE_COUNT; ++i)
             widest = std::max<int64_t>(widest, ((int64_t)len[i] + bsz - 1) / bsz);
     }
     // (strand-split images hold two values per cell: keep the image at 8 KiB there too, otherwise
     // only 10 workgroups fit a CU and the launch is occupancy-bound: 0.62 -> 0.55 ms on config 4)
-    const int64_t cap_cells = (mode == BSIG_MODE_PROFILE && prm->ss) ? 1024 : 2048;
+    const int64_t cap_cells = split_ss ? 1024 : 2048;
     P->tile_cells = prm->tile_cells > 0 ? prm->tile_cells : (int)std::min<int64_t>(widest, cap_cells);
     int min_cells = 64;
-    if (mode == BSIG_MODE_PROFILE && prm->binsize > 1 && prm->tile_cells <= 0) {
+    if (binned && prm->binsize > 1 && prm->tile_cells <= 0) {
         // wide bins: a tile of 2048 cells would span megabases and one wave would stream all of
         // its reads; keep a tile to about 16 kbp so that genome-wide binning still fills the chip
         const int64_t by_span = std::max<int64_t>(4, (16384 + prm->binsize - 1) / prm->binsize);
@@ -1362,7 +1374,7 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
         min_cells = 4;
     }
     // a tile image is at most 32 KiB of LDS
-    P->tile_cells = std::min(std::max(P->tile_cells, min_cells), prm->ss && mode == BSIG_MODE_PROFILE ? 4096 : 8192);
+    P->tile_cells = std::min(std::max(P->tile_cells, min_cells), split_ss ? 4096 : 8192);
     P->tile_cells = (P->tile_cells + 3) & ~3;
     P->threads = prm->threads > 0 ? prm->threads : 64;
     if (P->threads != 64 && P->threads != 128 && P->threads != 256) {
@@ -1378,8 +1390,8 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     K.shift = mode == BSIG_MODE_COVERAGE ? 0 : prm->shift;
     K.midpoint = mid; K.tspan = tspan;
     K.use_tlen = K.has_tlen_filter || mid || tspan;
-    K.ss = mode == BSIG_MODE_COVERAGE ? 0 : (prm->ss != 0);
-    K.binsize = mode == BSIG_MODE_PROFILE ? prm->binsize : 1;
+    K.ss = mode == BSIG_MODE_COVERAGE ? cov_ss : (prm->ss != 0);
+    K.binsize = mode == BSIG_MODE_PROFILE ? prm->binsize : mode == BSIG_MODE_COVERAGE ? cov_bin : 1;
     K.ext = (int32_t)ext;
     K.tile_cells = P->tile_cells;
     bsig::magic_u31(K.binsize, &K.div_magic, &K.div_shift);
@@ -1474,7 +1486,8 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     int64_t heavy_reads = 32768, slice_reads = 8192;
     // (k_profile's 16-bit tile image relies on the 32,768 ceiling: the environment may only lower it)
     if (const char *v = getenv("BAMSIGNALS_HEAVY_READS")) { heavy_reads = std::min<long long>(32768, std::max<long long>(4, atoll(v))); slice_reads = std::max<int64_t>(4, heavy_reads / 4); }
-    // (k_coverage's cells are SIGNED 16-bit: +32,768 starts on one cell would not fit)
+    // (k_coverage's cells are SIGNED 16-bit: +32,768 starts on one cell would not fit; k_coverage_bins' int32 cells
+    // need the same ceiling: 32,767 reads adding at most 65,536 each stay below 2^31)
     if (P->kernel_mode == BSIG_MODE_COVERAGE) heavy_reads = std::min<int64_t>(heavy_reads, 32767);
     if (e == hipSuccess && !items.empty()) {
         DevPool tmp;
@@ -1525,6 +1538,10 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
             if (e == hipSuccess) e = hipMemcpyAsync(hw, hwin.data(), hwin.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
             // the heavy flags of the main items
             if (e == hipSuccess) e = hipMemcpyAsync(P->items, items.data(), items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
+            // binned coverage: the slices' atomic adds are the only ones that can take a bin past INT32_MAX
+            if (e == hipSuccess && cov_ex) e = P->pool.alloc(&P->overflow, 1);
+            if (e == hipSuccess && P->overflow) e = hipMemsetAsync(P->overflow, 0, sizeof(int32_t), ctx->stream);
+            K.overflow = P->overflow;
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
     }
@@ -1578,6 +1595,7 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
     }
     if (p->n_heavy_slices) {
         // the first launch zero-filled the heavy tiles; their slices now add their partial images
+        if (p->overflow) HIP_TRY(hipMemsetAsync(p->overflow, 0, sizeof(int32_t), st));     // (the flag speaks of this run)
         BsigKParams acc = p->kp;
         acc.accumulate = 1;
         HIP_TRY(bsig::launch_pileup(p->kernel_mode, p->kp.ss, p->threads, p->reads->dev, acc, p->heavy_items,
@@ -1598,12 +1616,26 @@ int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
     int rc = bsig_plan_run(p, p->d_out);
     if (rc != BSIG_OK) return rc;
     const size_t bytes = (size_t)cells * sizeof(int32_t);
-    if (bytes >= (8u << 20) && !is_pinned_host(out_host))
-        return bsig::download_to_host(p->ctx, p->d_out, out_host, bytes);
+    if (bytes >= (8u << 20) && !is_pinned_host(out_host)) {
+        rc = bsig::download_to_host(p->ctx, p->d_out, out_host, bytes);
+        return rc == BSIG_OK ? bsig::plan_check_overflow(p) : rc;
+    }
     hipError_t e = hipMemcpyAsync(out_host, p->d_out, bytes, hipMemcpyDeviceToHost, p->ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->ctx->stream);
     if (e != hipSuccess) rc = fail(BSIG_ERR_DEVICE, "result download failed: %s", hipGetErrorString(e));
+    if (rc == BSIG_OK) rc = bsig::plan_check_overflow(p);
     return rc;
+}
+
+int bsig_plan_overflowed(bsig_plan *p, int32_t *flag)
+{
+    if (!p || !flag) return fail(BSIG_ERR_ARG, "NULL argument");
+    *flag = 0;
+    if (!p->overflow || !p->runs) return BSIG_OK;
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    HIP_TRY(hipMemcpyAsync(flag, p->overflow, sizeof(int32_t), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    return BSIG_OK;
 }
 
 }  // extern "C"
@@ -1624,7 +1656,16 @@ int bsig::plan_run_host_timed(bsig_plan *p, const HostDest &dst, double *t_kerne
     const auto t1 = std::chrono::steady_clock::now();
     rc = bsig::download_to_dest(p->ctx, p->d_out, dst, cells);
     *t_download = since(t1);
-    return rc;
+    return rc == BSIG_OK ? bsig::plan_check_overflow(p) : rc;
+}
+// a run whose slices took a bin past INT32_MAX fails (after the caller's synchronisation: no wait of its own)
+int bsig::plan_check_overflow(bsig_plan *p)
+{
+    int32_t f = 0;
+    const int rc = bsig_plan_overflowed(p, &f);
+    if (rc != BSIG_OK) return rc;
+    if (f) return fail(BSIG_ERR_ARG, "a coverage bin exceeds 2^31 - 1 reads x bases: choose a smaller binsize");
+    return BSIG_OK;
 }
 extern "C" {
 

@@ -285,6 +285,13 @@ class Plan:
         """Asynchronous launch on the context's stream; ``out_ptr`` is a device address."""
         _lib.check(self._lib.bsig_plan_run(self._h, C.c_void_p(out_ptr)))
 
+    def overflowed(self):
+        """Did the last run take a coverage bin past INT32_MAX (binned coverage, heavy tiles)?  For ``run_device``
+        callers; ``run_host`` raises by itself.  Synchronises where such a run is possible."""
+        f = C.c_int32(0)
+        _lib.check(self._lib.bsig_plan_overflowed(self._h, C.byref(f)))
+        return bool(f.value)
+
     def stats(self):
         s = _lib.PlanStats()
         _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))

@@ -106,20 +106,20 @@ def _sharded(kind, bampath, gr, dst, group, **kw):
         sig = fn(bampath, sub, verbose=False, **kw)
         parts = [(m.T.reshape(-1) if ss else m) for m in sig.as_list()]
         local = np.concatenate(parts).astype(np.int32, copy=False) if parts else np.zeros(0, np.int32)
-        binsize = int(kw.get("binsize", 1)) if kind == "profile" else 1
+        binsize = int(kw.get("binsize", 1))
     backend = dist.get_backend(group)
     t = torch.from_numpy(np.ascontiguousarray(local))
     if backend == "nccl":
         t = t.cuda()
-    out, off = gather_signals(t, ranges, binsize, ss and kind != "coverage", dst=dst, group=group)
+    out, off = gather_signals(t, ranges, binsize, ss, dst=dst, group=group)
     if rank != dst:
         return None
     if kind == "count":
         return out.reshape(-1, 2).T if ss else out
     sigs = [out[off[i]:off[i + 1]] for i in range(len(off) - 1)]
-    if ss and kind == "profile":
+    if ss:
         sigs = [v.reshape(-1, 2).T for v in sigs]
-    return CountSignals(sigs, ss and kind == "profile")
+    return CountSignals(sigs, ss)
 
 
 def bamProfile_sharded(bampath, gr, dst=0, group=None, **kw):  # noqa: N802
@@ -134,4 +134,5 @@ def bamCount_sharded(bampath, gr, dst=0, group=None, **kw):  # noqa: N802
 
 
 def bamCoverage_sharded(bampath, gr, dst=0, group=None, **kw):  # noqa: N802
+    """``bamCoverage`` over all ranks, as ``bamProfile_sharded`` (``binsize`` and ``ss`` included)."""
     return _sharded("coverage", bampath, gr, dst, group, **kw)

@@ -124,24 +124,33 @@ def pileup_core(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=Fals
     return _split(out, off, ss)
 
 
+def _is_ex(binsize, ss):
+    """bins or strands take bsig_coverage_core_ex[_into]; the defaults keep the reference's own entry point"""
+    return int(binsize) != 1 or bool(ss)
+
+
 def coverage_core(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                  maxgap=16385, device=None):
-    """The native entry point behind bamCoverage (ref: R/RcppExports.R:16-18)."""
+                  maxgap=16385, device=None, *, binsize=1, ss=False):
+    """The native entry point behind bamCoverage (ref: R/RcppExports.R:16-18).  ``binsize`` / ``ss``:
+    per-base coverage summed over bins / split into sense and antisense rows (bsig_coverage_core_ex)."""
     _check_gr(gr)
     lib = _lib.load()
     levels, codes, start, width, strand = gr.flatten()
     n = len(gr)
+    ex = _is_ex(binsize, ss)
     off = np.empty(n + 1, dtype=np.int64)
-    cells = lib.bsig_layout(n, width.ctypes.data, 1, 0, off.ctypes.data)
+    cells = lib.bsig_layout(n, width.ctypes.data, int(binsize) if ex else 1, int(bool(ss)) if ex else 0, off.ctypes.data)
     out = np.zeros(cells, dtype=np.int32)
     tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
     names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_coverage_core(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data,
-                                      len(levels), names, start.ctypes.data, width.ctypes.data,
-                                      strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual),
-                                      int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap),
-                                      _dev(device), out.ctypes.data, off.ctypes.data))
-    return _split(out, off, False)
+    head = (os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names, start.ctypes.data,
+            width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual), int(requiredF),
+            int(filteredF), int(bool(tspan)), int(maxgap), _dev(device))
+    if ex:
+        _lib.check(lib.bsig_coverage_core_ex(*head, int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
+    else:
+        _lib.check(lib.bsig_coverage_core(*head, out.ctypes.data, off.ctypes.data))
+    return _split(out, off, ex and bool(ss))
 
 
 def _alloc_signals(width, binsize, ss):
@@ -179,19 +188,22 @@ def pileup_core_into(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss
 
 
 def coverage_core_into(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                       maxgap=16385, device=None):
-    """coverage_core with the result delivered in place (bsig_coverage_core_into)."""
+                       maxgap=16385, device=None, *, binsize=1, ss=False):
+    """coverage_core with the result delivered in place (bsig_coverage_core_into / bsig_coverage_core_ex_into)."""
     _check_gr(gr)
     lib = _lib.load()
     levels, codes, start, width, strand = gr.flatten()
-    out, vs = _alloc_signals(width, 1, False)
+    ex = _is_ex(binsize, ss)
+    out, vs = _alloc_signals(width, max(int(binsize), 1) if ex else 1, ex and bool(ss))
     tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
     names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_coverage_core_into(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data,
-                                           len(levels), names, start.ctypes.data, width.ctypes.data,
-                                           strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual),
-                                           int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap),
-                                           _dev(device), _dest_pointers(vs)))
+    head = (os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+            start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual),
+            int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap), _dev(device))
+    if ex:
+        _lib.check(lib.bsig_coverage_core_ex_into(*head, int(binsize), int(bool(ss)), _dest_pointers(vs)))
+    else:
+        _lib.check(lib.bsig_coverage_core_into(*head, _dest_pointers(vs)))
     return out
 
 
@@ -242,12 +254,43 @@ def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N8
     return CountSignals(pu, bool(ss), _trusted=True)
 
 
+# widest coverage bin (include/bamsignals_abi.h, BSIG_MODE_COVERAGE_EX): a tile's sums cannot wrap below it
+MAX_COVERAGE_BINSIZE = 65536
+
+
+def _coverage_binsize(binsize):
+    if isinstance(binsize, (bool, np.bool_)) or not isinstance(binsize, (int, float, np.integer, np.floating)) \
+            or not float(binsize).is_integer():
+        raise ValueError("binsize must be a whole number of bases")
+    b = int(binsize)
+    if b < 1:
+        raise ValueError("provide a binsize greater or equal to 1")
+    if b > MAX_COVERAGE_BINSIZE:
+        raise ValueError(f"coverage bins are at most {MAX_COVERAGE_BINSIZE} bases wide; count at that scale with "
+                         "bamProfile or bamCount")
+    return b
+
+
 def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFilter=None,  # noqa: N802,N803
-                filteredFlag=-1, verbose=True):
-    """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173)."""
+                filteredFlag=-1, verbose=True, *, binsize=1, ss=False):
+    """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173).
+
+    ``binsize`` (1 .. 65,536): bin j of a range covers its bases [j*binsize, min((j+1)*binsize, width)) in range
+    orientation (a '-' range is mirrored first and binned second, as in bamProfile) and holds the sum of the per-base
+    coverage over them, so ``bamCoverage(binsize=b)[i] == np.add.reduceat(bamCoverage()[i], np.arange(0, w_i, b))``;
+    the last bin of a range may be shorter (warned about, as bamProfile does).
+    ``ss=True``: each signal is a 2 x n_bins matrix, row 0 (sense) the coverage by reads on the range's strand
+    ('*' counts as '+'), row 1 (antisense) by the others; with ``paired_end="extend"`` the whole fragment counts on
+    the strand of the read that passed the flag mask (the first mate).  sense + antisense is the unstranded result.
+    A bin whose sum would exceed 2^31 - 1 raises BsigError.  The defaults are the reference's call."""
     if verbose:
         _print_sentence(bampath)
+    b = _coverage_binsize(binsize)
+    _check_gr(gr)
+    if b > 1 and np.any(gr.width % b != 0):
+        warnings.warn("some ranges' widths are not a multiple of the selected\n"
+                      "             binsize, some bins will correspond to less than binsize basepairs")
     pe = _match_arg(paired_end, ("ignore", "extend"), "paired.end")
     pu = coverage_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                       flagMask(pe), filteredFlag, pe == "extend")
-    return CountSignals(pu, False, _trusted=True)
+                       flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
+    return CountSignals(pu, bool(ss), _trusted=True)

@@ -43,7 +43,12 @@ enum {
     BSIG_ERR_FORMAT = -8     /* malformed BAM / BAI / SAM                                     */
 };
 
-enum { BSIG_MODE_PROFILE = 0, BSIG_MODE_COUNT = 1, BSIG_MODE_COVERAGE = 2 };
+/* BSIG_MODE_COVERAGE_EX: bamCoverage with bsig_params.binsize (1 .. 65,536) and ss honoured -- bin j of a range
+ * holds the per-base coverage summed over its bases [j*binsize, min((j+1)*binsize, width)) in range orientation
+ * (a '-' range is mirrored first, binned second, as bamProfile does); with ss, cell 2*bin + antisense, where sense
+ * reads have the range's strand ('*' counts as '+') and paired.end = "extend" counts the fragment on the strand of
+ * the read that passed the flag mask.  BSIG_MODE_COVERAGE ignores binsize and ss, as it always has.           */
+enum { BSIG_MODE_PROFILE = 0, BSIG_MODE_COUNT = 1, BSIG_MODE_COVERAGE = 2, BSIG_MODE_COVERAGE_EX = 3 };
 
 int bsig_abi_version(void);
 /* CPUs the library sizes its host thread pools by: hardware threads, cut down by the affinity mask and
@@ -148,9 +153,9 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
 typedef struct {
     int32_t mode;              /* BSIG_MODE_*                                                   */
     int32_t mapqual;
-    int32_t binsize;           /* profile: >= 1; ignored otherwise                              */
+    int32_t binsize;           /* profile: >= 1; coverage_ex: 1 .. 65,536; ignored otherwise    */
     int32_t shift;
-    int32_t ss;
+    int32_t ss;                /* profile, count, coverage_ex                                   */
     int32_t requiredF;
     int32_t filteredF;
     int32_t pe_mid;            /* profile/count: paired.end == "midpoint"                       */
@@ -194,11 +199,16 @@ int bsig_plan_get_stats(bsig_plan *plan, bsig_plan_stats *stats);
 /* run on the context's stream; out_dev: device buffer of bsig_plan_cells() int32, 16-B aligned.
  * Asynchronous: call bsig_ctx_sync() (or synchronise the stream) before reading out_dev.       */
 int bsig_plan_run(bsig_plan *plan, int32_t *out_dev);
-/* run + copy to host memory + synchronise                                                      */
+/* run + copy to host memory + synchronise; fails (BSIG_ERR_ARG) if the run took a coverage bin past INT32_MAX */
 int bsig_plan_run_host(bsig_plan *plan, int32_t *out_host);
 /* the same without the final synchronisation (out_host should be page-locked, bsig_host_alloc):
  * lets one host thread keep several GPUs busy; finish with bsig_ctx_sync() on the plan's context */
 int bsig_plan_run_host_async(bsig_plan *plan, int32_t *out_host);
+/* Binned coverage (BSIG_MODE_COVERAGE_EX): a bin's true sum can exceed INT32_MAX only in a tile whose reads are cut
+ * into slices (heavy_tiles), whose atomic adds watch for it.  *flag = 1 if the plan's last run did so -- its result
+ * is then wrong --, else 0.  Synchronises the context's stream where such a run is possible; for callers of the
+ * asynchronous bsig_plan_run / bsig_plan_run_host_async (bsig_plan_run_host and the file-level calls check it).  */
+int bsig_plan_overflowed(bsig_plan *plan, int32_t *flag);
 void bsig_plan_free(bsig_plan *plan);
 
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
@@ -297,7 +307,17 @@ int bsig_coverage_core(const char *bampath, int64_t n_ranges, const int32_t *seq
                        const int32_t *tlen_filter, int32_t n_tlen_filter,
                        int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                        int32_t maxgap, int32_t device, int32_t *out, const int64_t *off);
-/* The same two calls with the result delivered IN PLACE, as the reference delivers it: allocateList (ref:
+/* bsig_coverage_core with bins and strands (BSIG_MODE_COVERAGE_EX): binsize 1 .. 65,536, ss 0 / 1; out/off as in
+ * bsig_layout(binsize, ss).  binsize = 1, ss = 0 is bsig_coverage_core, by the same kernel.
+ * A bin whose sum would exceed INT32_MAX fails the call (BSIG_ERR_ARG); it never returns a wrapped value. */
+int bsig_coverage_core_ex(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                          int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                          const int32_t *width, const int32_t *strand,
+                          const int32_t *tlen_filter, int32_t n_tlen_filter,
+                          int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                          int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+                          int32_t *out, const int64_t *off);
+/* The same calls with the result delivered IN PLACE, as the reference delivers it: allocateList (ref:
  * src/bamsignals.cpp:139-192) makes the R vectors first and the pileup counts straight into them (:361-362,
  * :423-436) -- ONE copy of the result in host memory.  dst[i] = where range i's cells go (the payload of its
  * vector / 2 x width matrix: (off[i+1] - off[i]) int32 of bsig_layout(); never touched for an empty range);
@@ -317,6 +337,12 @@ int bsig_coverage_core_into(const char *bampath, int64_t n_ranges, const int32_t
                             const int32_t *tlen_filter, int32_t n_tlen_filter,
                             int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                             int32_t maxgap, int32_t device, int32_t *const *dst);
+int bsig_coverage_core_ex_into(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                               int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                               const int32_t *width, const int32_t *strand,
+                               const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *const *dst);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);

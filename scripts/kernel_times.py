@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Kernel times and algorithmic-byte rates for the non-headline configurations (coverage tiling,
-paired-end strand-split profile, count).  Diagnostic companion of bench.py; prints JSON lines."""
+paired-end strand-split profile, count).  Diagnostic companion of bench.py; prints JSON lines.
+``--coverage-bins``: only the coverage of one whole chr1 range, per base and in bins (bamCoverage's binsize / ss)."""
 import json
 import os
 import sys
@@ -43,12 +44,19 @@ def main():
         cases.append(("count on the same tiling", reads, tiles, make_params(_lib.MODE_COUNT, binsize=-1)))
         one = dict(rid=np.zeros(1, np.int32), loc=np.zeros(1, np.int32), len=np.asarray([L], np.int32), strand=np.zeros(1, np.int32))
         cases.append(("coverage of ONE whole-chromosome range (tiled internally)", reads, one, make_params(_lib.MODE_COVERAGE)))
+        cases.append(("coverage, 50-bp bins: ONE chr1 range, binsize=50", reads, one, make_params(_lib.MODE_COVERAGE_EX, binsize=50)))
+        cases.append(("coverage, 1-kb bins: ONE chr1 range, binsize=1000", reads, one, make_params(_lib.MODE_COVERAGE_EX, binsize=1000)))
+        cases.append(("coverage, 50-bp bins, ss: ONE chr1 range, binsize=50", reads, one,
+                      make_params(_lib.MODE_COVERAGE_EX, binsize=50, ss=True)))
         cases.append(("genome-wide 8-bp bins: ONE chr1 range, binsize=8", reads, one, make_params(_lib.MODE_PROFILE, binsize=8)))
         cases.append(("genome-wide 32-bp bins: ONE chr1 range, binsize=32", reads, one, make_params(_lib.MODE_PROFILE, binsize=32)))
         cases.append(("genome-wide 64-bp bins: ONE chr1 range, binsize=64", reads, one, make_params(_lib.MODE_PROFILE, binsize=64)))
         cases.append(("genome-wide 200-bp bins, ss: ONE chr1 range, binsize=200", reads, one, make_params(_lib.MODE_PROFILE, binsize=200, ss=True)))
         cases.append(("genome-wide 1-kb bins: ONE chr1 range, binsize=1000", reads, one, make_params(_lib.MODE_PROFILE, binsize=1000)))
         cases.append(("genome-wide 100-kb bins: ONE chr1 range, binsize=100000", reads, one, make_params(_lib.MODE_PROFILE, binsize=100000)))
+        only_bins = "--coverage-bins" in sys.argv
+        if only_bins:
+            cases = [c for c in cases if c[0].startswith("coverage")]
         for name, rd, rg, prm in cases:
             plan = Plan(ctx, rd, rg["rid"], rg["loc"], rg["len"], rg["strand"], prm)
             out = torch.empty(max(plan.cells, 4), dtype=torch.int32, device="cuda")
@@ -59,6 +67,8 @@ def main():
             plan.close()
         reads.close()
         del cols
+        if only_bins:
+            return
         cols = synth_reads(100_000_000, [250_000_000], seed=9, paired=True, with_cigar=False)
         reads = Reads(ctx, cols["ref_len"], cols["ref_off"], cols["pos"], cols["flag"], cols["mapq"], cols["tlen"], end=cols["end"])
         rg = synth_ranges(100_000, 2000, [250_000_000], seed=10)
