@@ -207,6 +207,17 @@ struct SmallOne {
                                          const uint8_t *__restrict__ ptab) const
     {
         const uint32_t b0 = ptab[w.x >> 23], b1 = ptab[w.y >> 23], b2 = ptab[w.z >> 23], b3 = ptab[w.w >> 23];
+        if (!P.rel24) {                                                // (uniform: shifts or midpoints of megabases)
+            auto dec = [&](uint32_t x, uint32_t b, int tl, bool valid) {
+                const int pos = base + (int)((x - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u));
+                (*this)(pos, pos + (int)((x >> BSIG_PACK_POS_BITS) & 0xFFu), (b & 2u) != 0u, (b & 1u) != 0u, tl, valid);
+            };
+            dec(w.x, b0, t.x, dj < nj);
+            dec(w.y, b1, t.y, dj + 1u < nj);
+            dec(w.z, b2, t.z, dj + 2u < nj);
+            dec(w.w, b3, t.w, dj + 3u < nj);
+            return;
+        }
         // (uniform, like everything these branches ask.  Three forms only -- the orientation of the range is a sign and
         // a strand mask, not a fourth template argument: the kernel inlines this at four places, and 32 copies of the
         // read body were 35 KB of code that ran a third SLOWER than round 4's 16)
@@ -240,7 +251,7 @@ struct SmallOne {
                 if (P.has_tlen_filter) rj |= ((a < P.tf0) | (a > P.tf1)) ? -1 : 0;
                 if (P.midpoint) { h = a >> 1; spcd -= 2 * h; }
             }
-            // (|spcd| and fwd < 2^23: a window that takes this path is narrower than 32,768 bases, and so are shift and h)
+            // (|fwd| <= d + span - 1 + 2 |shift| + h < 2^23 under P.rel24, which quad() asked: see bsig_plan_create)
             const int fwd = (rev & spcd) + d + h;
             const uint32_t rel = (uint32_t)(__mul24(fwd, sgn) + Kv) | (uint32_t)rj;     // from the tile's first base, range orientation
             const uint32_t cell = NARROW ? __umul24(rel, P.div_m15) >> P.div_s15 : __umulhi(rel, P.div_magic) >> P.div_shift;
@@ -362,7 +373,7 @@ struct CountOne {
                                          const uint32_t *__restrict__ ctab, bool inner) const
     {
         const uint32_t b0 = ctab[w.x >> 23], b1 = ctab[w.y >> 23], b2 = ctab[w.z >> 23], b3 = ctab[w.w >> 23];
-        if (P.has_tlen_filter | P.midpoint) {                  // (uniform)
+        if (P.has_tlen_filter | P.midpoint | !P.rel24) {      // (uniform; !rel24: shifts of megabases)
             auto dec = [&](uint32_t x, uint32_t b, int tl, bool valid) {
                 const int pos = base + (int)((x - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u));
                 count_one(P, glo, gn, pos, pos + (int)((x >> BSIG_PACK_POS_BITS) & 0xFFu), (b & 1u) != 0u, (b >> 31) != 0u, tl, valid, acc);
@@ -377,7 +388,7 @@ struct CountOne {
         auto rel_of = [&](uint32_t x, uint32_t b) {
             const int d = (int)((x - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u));
             const int spcd = (int)((x >> BSIG_PACK_POS_BITS) & 0xFFu) + cd;
-            // (|spcd| < 2^23: a window that takes this path is narrower than 32,768 bases, and so is the shift)
+            // (|spcd| <= span - 1 + 2 |shift| < 2^23 under P.rel24, asked above: see bsig_plan_create)
             return ((uint32_t)(__mul24((int)b, spcd) + d + cp)) | (b & 0x80000000u);
         };
         if (inner) {

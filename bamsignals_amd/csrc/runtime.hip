@@ -1394,6 +1394,15 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     K.binsize = mode == BSIG_MODE_PROFILE ? prm->binsize : mode == BSIG_MODE_COVERAGE ? cov_bin : 1;
     K.ext = (int32_t)ext;
     K.tile_cells = P->tile_cells;
+    // The packed class's read bodies (SmallOne::four, CountOne::quad) take a read's offset from its chunk in signed
+    // 24-bit multiplies (v_mad_i32_i24: the low 24 bits of each operand, sign-extended), exact for operands in
+    // [-2^23, 2^23).  The operand is at most d + span - 1 + 2 |shift| + h in magnitude: d < 2^15 the position in the
+    // chunk, span - 1 < 256, h = |tlen| >> 1 <= tlen_filter[1] / 2 under the midpoint rule (a read outside the filter is
+    // forced out of every tile whatever its offset).  Wider shifts or template lengths take the full-width body.
+    {
+        const int64_t h_max = mid ? std::max<int64_t>(0, prm->tlen_filter[1]) / 2 : 0;
+        K.rel24 = 2 * std::llabs((long long)K.shift) + h_max + (1 << BSIG_PACK_POS_BITS) + 256 < (1ll << 23);
+    }
     bsig::magic_u31(K.binsize, &K.div_magic, &K.div_shift);
     K.div_m15 = 0; K.div_s15 = 0;
     if (K.binsize >= 2 && K.binsize <= 8192) {
