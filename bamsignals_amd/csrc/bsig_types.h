@@ -20,6 +20,10 @@
 //               class 1 (span <= 4096, flag < 4096): flag | mapq << 12 | (span - 1) << 20
 //               classes 2..3: flag | mapq << 16
 //        tlen : template length                                   (core.isize)
+//     The packed class has one more column, derived from fm and fmtab when the reads are made and never saved:
+//        p5h  : (5' end & 0x7FFF) | reverse << 15, 16 bits  (5' end = pos, or pos + span - 1 on the reverse strand)
+//     -- all a per-base profile without a template-length rule reads of a packed read when the plan's flag/mapq
+//     filter rejects none of the file's codes (bsig_plan_create: BsigKParams::packed_half).
 //     and a bucket index  idx[b] = first read of the class whose global coordinate
 //     g = (ref_unit0[rid] << 16) + pos  falls in bucket >= b, bucket = g >> kshift.
 //     References are laid out back to back in units of 64 kbp, so one flat index
@@ -43,6 +47,7 @@ struct BsigClassCols {
     const int32_t *end;
     const uint32_t *fm;
     const int32_t *tlen;
+    const uint16_t *p5h;     // packed class only (NULL elsewhere, or with BAMSIGNALS_PACKED_HALF=0): see above
     const uint32_t *idx;     // n_buckets + 1 entries
     int64_t n;               // reads in the class
     int32_t maxspan;         // max(end - pos + 1) over the class
@@ -98,6 +103,8 @@ struct BsigKParams {
     int32_t rel24;          // 1: the packed class's read bodies may take a read's offset from its chunk in 24-bit
                             //   multiplies (|2 shift| + tlen_filter[1] / 2 small enough: see bsig_plan_create); 0: they
                             //   take the full-width per-read body instead
+    int32_t packed_half;    // 1: the packed class is read from its 16-bit 5'-end column p5h (bamProfile, binsize 1, no
+                            //   template-length rule, no code rejected, every packed window one chunk: bsig_plan_create)
     int32_t ext;            // window extension on both sides (src/bamsignals.cpp:457,487)
     int32_t tile_cells;     // output cells per tile (sizes the dynamic LDS image)
     int32_t accumulate;     // 1: add the tile image into the result with integer atomics (slices of

@@ -23,6 +23,9 @@ hipError_t launch_pileup(int mode, int ss, int threads, const BsigReadsDev &R, c
                          void *windows /* n_items * BSIG_MAX_CLASSES * 8 bytes (fixed read ranges: slices of heavy tiles), or NULL */,
                          bool resolve_first /* fill `windows` with k_resolve before the pileup launch */,
                          int32_t *out, hipStream_t st);
+// the packed class's 16-bit 5'-end column (bsig_types.h: p5h) from its n words fm and the pair table fmtab: cap
+// (a multiple of 8, >= n + 8) entries at `out`, those from n on zero
+hipError_t launch_make_p5h(const uint32_t *fm, const uint32_t *fmtab, int64_t n, int64_t cap, uint16_t *out, hipStream_t st);
 // the packed class's filter table for P (BSIG_PACK_CODES bytes at `out`): once per plan
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st);
 hipError_t launch_resolve(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,

@@ -171,6 +171,34 @@ struct ProfileOne {
         rd(w.z, b2, t.z, 2u);
         rd(w.w, b3, t.w, 3u);
     }
+    // Eight reads of the packed class from its 16-bit column p5h (BsigKParams::packed_half: bins of one base, no
+    // template-length rule, no code rejected, the window one chunk).  A half-word h holds the low 15 bits of the
+    // 5' end and the strand in bit 15: d = (h - base) & 0x7FFF is the 5' end's distance from base, exact because
+    // bsig_plan_create keeps every window 256 bases short of a chunk.  No filter table, no span.
+    __device__ __forceinline__ void oct(const uint4 &w, uint32_t dj, uint32_t nj, int base) const
+    {
+        if (neg_range) eight<true>(w, dj, nj, base, len - 1 - c0 - (base - loc + P.shift));
+        else eight<false>(w, dj, nj, base, base - loc + P.shift - c0);
+    }
+    template <bool REV>
+    __device__ __forceinline__ void eight(const uint4 &w, uint32_t dj, uint32_t nj, int base, int K) const
+    {
+        const uint32_t cd = (uint32_t)(-2 * P.shift);
+        auto rd = [&](uint32_t h, uint32_t k) {                       // h: the half-word in the low 16 bits
+            const uint32_t d = (h - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u);
+            const uint32_t nm = (uint32_t)((int32_t)(h << 16) >> 31);
+            // 5' end from base + shift: d on the forward strand, d - 2 shift on the reverse one (d counts from pos + span - 1)
+            const uint32_t fwd = d + (nm & cd);
+            const uint32_t lc = REV ? (uint32_t)K - fwd : (uint32_t)K + fwd;
+            const bool ok = (dj + k < nj) & (lc < (uint32_t)nc);
+            const uint32_t cell = SS ? (uint32_t)sh + 2u * lc + ((REV ? ~nm : nm) & 1u) : (uint32_t)sh + lc;
+            if (ok) atomicAdd(&cnt[cell >> 1], 1u << ((cell << 4) & 31u));     // (masked: see four)
+        };
+        rd(w.x & 0xFFFFu, 0u); rd(w.x >> 16, 1u);
+        rd(w.y & 0xFFFFu, 2u); rd(w.y >> 16, 3u);
+        rd(w.z & 0xFFFFu, 4u); rd(w.z >> 16, 5u);
+        rd(w.w & 0xFFFFu, 6u); rd(w.w >> 16, 7u);
+    }
 };
 
 // bamProfile's per-read work on the wide-bin image of k_profile_small: 32-bit cells in the lane's own replica.
@@ -448,6 +476,23 @@ __global__ __launch_bounds__(128) void k_make_ptab(const BsigReadsDev R, const B
 }
 static_assert(BSIG_PACK_CODES == 4 * 128, "k_make_ptab: four codes per thread of one 128-thread workgroup");
 
+// The packed class's 16-bit column (bsig_types.h: p5h): the 5' end's low 15 bits and the strand, from a word
+// (pos & 0x7FFF | (span - 1) << 15 | code << 23) and its code's pair; entries n .. cap - 1 are zero (16-B loads read them)
+__global__ void k_make_p5h(const uint32_t *__restrict__ fm, const uint32_t *__restrict__ fmtab, int64_t n, int64_t cap,
+                           uint16_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    uint32_t h = 0;
+    if (i < n) {
+        const uint32_t w = fm[i];
+        const uint32_t rev = (fmtab[w >> 23] >> 4) & 1u;                      // 0x10: reverse strand (code < 512)
+        const uint32_t p5 = (w & kPackPosMask) + (rev ? (w >> BSIG_PACK_POS_BITS) & 0xFFu : 0u);
+        h = (p5 & kPackPosMask) | rev << 15;
+    }
+    out[i] = (uint16_t)h;
+}
+
 // The packed class's window of a tile: the reads whose pos lies in the bucket-rounded window [rlo, rhi) of the
 // reference, walked in chunks of kPackChunk bases (nearly always one): inside a chunk that starts at `base`,
 // pos = base + ((word - base) & kPackPosMask).
@@ -627,23 +672,30 @@ __device__ __forceinline__ void four_packed(const uint4 &w, const int4 &t, uint3
 // (kPre * 4 * NT reads) of the packed class, where nearly all reads live, and the first pass of classes 0
 // and 1.  Longer windows and the two long-span classes continue in plain loops.
 // (The packed class's later chunks -- windows wider than kPackChunk bases -- are walked by packed_later_chunks.)
-template <int NT, int kPre = 2, typename Tab, typename F>
+// HALF (BsigKParams::packed_half, the functor has `oct`): the packed class comes from its 16-bit column p5h, eight
+// reads per lane and 16-B load (passes of 8 * NT reads, no tlen column).
+template <int NT, int kPre = 2, bool HALF = false, typename Tab, typename F>
 __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigKParams &P,
                                               const uint2 (&win)[BSIG_MAX_CLASSES], int pbase,
                                               const Tab *__restrict__ ptab, int tid, F &&one)
 {
+    constexpr uint32_t kPer = HALF ? 8u : 4u;                        // packed reads per lane and 16-B load
     uint4 w0[kPre];
     int4 t0[kPre];
     const BsigClassCols &CP = R.cls[BSIG_CLASS_PACKED];
-    const uint32_t jbp = (win[BSIG_CLASS_PACKED].x & ~3u) + 4u * tid;
+    const uint32_t jbp = (win[BSIG_CLASS_PACKED].x & ~(kPer - 1u)) + kPer * tid;
 #pragma unroll
     for (int k = 0; k < kPre; ++k) {
-        const uint32_t j = jbp + 4u * NT * k;
+        const uint32_t j = jbp + kPer * NT * k;
         // (t0[k] is read under P.use_tlen only, which is when it is loaded: setting it to zero otherwise was four vector
         // instructions a pass in launches that are bound by exactly those)
         if (j < win[BSIG_CLASS_PACKED].y) {
-            w0[k] = *reinterpret_cast<const uint4 *>(CP.fm + j);
-            if (P.use_tlen) t0[k] = *reinterpret_cast<const int4 *>(CP.tlen + j);
+            if constexpr (HALF) {
+                w0[k] = *reinterpret_cast<const uint4 *>(CP.p5h + j);
+            } else {
+                w0[k] = *reinterpret_cast<const uint4 *>(CP.fm + j);
+                if (P.use_tlen) t0[k] = *reinterpret_cast<const int4 *>(CP.tlen + j);
+            }
         }
     }
     // The rare classes' windows are short -- the north star's tiles see some 20 reads of class 1 (the 5 % of reads
@@ -668,7 +720,24 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
     }
     // The 16-B aligned loads may start before j_lo (possibly on the previous reference) and end
     // after j_hi: only reads in [j_lo, j_hi) count -> `dj < nj` with unsigned wrap-around.
-    {   // ---- packed class (span <= 256, a frequent flag/mapq pair): one word per read -------------------
+    if constexpr (HALF) {   // ---- packed class from p5h: one half-word per read ----------------------------
+        (void)t0;
+        const uint32_t j_lo = win[BSIG_CLASS_PACKED].x, j_hi = win[BSIG_CLASS_PACKED].y, nj = j_hi - j_lo;
+#pragma unroll
+        for (int k = 0; k < kPre; ++k) {
+            const uint32_t j = jbp + 8u * NT * k;
+            if (j < j_hi) one.oct(w0[k], j - j_lo, nj, pbase);
+        }
+        // deeper windows: two passes per trip, both requested before either is consumed
+        for (uint32_t j = jbp + 8u * NT * kPre; j < j_hi; j += 16u * NT) {
+            const uint32_t j2 = j + 8u * NT;
+            const uint4 wa = *reinterpret_cast<const uint4 *>(CP.p5h + j);
+            uint4 wb = make_uint4(0, 0, 0, 0);
+            if (j2 < j_hi) wb = *reinterpret_cast<const uint4 *>(CP.p5h + j2);
+            one.oct(wa, j - j_lo, nj, pbase);
+            if (j2 < j_hi) one.oct(wb, j2 - j_lo, nj, pbase);
+        }
+    } else {   // ---- packed class (span <= 256, a frequent flag/mapq pair): one word per read -------------------
         const uint32_t j_lo = win[BSIG_CLASS_PACKED].x, j_hi = win[BSIG_CLASS_PACKED].y, nj = j_hi - j_lo;
         // a pass whose 4 * NT reads all belong to the window (uniform): nobody has to ask read by read
         const uint32_t jp0 = j_lo & ~3u;
@@ -918,11 +987,10 @@ __device__ __forceinline__ void add_vec(int32_t *__restrict__ gbase, int v, int4
 // half never sees a carry from the lower one.  Half the LDS per workgroup: 24 instead of 18
 // single-wave workgroups per CU (LDS is allocated in 1,280-byte granules on gfx950), which puts
 // config 2's 10,000 tiles into two rounds of resident workgroups instead of two and a sparse third.
-template <int NT, bool SS, int PRE, int WAVES, bool RES>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
-                                                int32_t *__restrict__ out,
-                                                const uint2 *__restrict__ windows,
-                                                const BsigReadsDev R, const BsigKParams P)
+// HALF: the packed class from its 16-bit column (BsigKParams::packed_half) -- k_profile_half; the same body otherwise.
+template <int NT, bool SS, int PRE, bool RES, bool HALF>
+__device__ __forceinline__ void profile_tile(const BsigWorkItem *__restrict__ items, uint32_t n_tiles, int32_t *__restrict__ out,
+                                             const uint2 *__restrict__ windows, const BsigReadsDev &R, const BsigKParams &P)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t lds[];
     constexpr int S = SS ? 2 : 1;
@@ -939,7 +1007,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
     for (int v = tid; v < img_vec; v += NT) lds4[v] = make_int4(0, 0, 0, 0);
     // ... and so does the packed class's filter table, which lives behind the image
     uint8_t *ptab = reinterpret_cast<uint8_t *>(lds4 + img_vec);
-    build_ptab<NT>(ptab, R, P, tid);
+    if (!HALF) build_ptab<NT>(ptab, R, P, tid);          // (the half form reads no table)
     const int nv = w.nc * S;
     const int sh = (int)(w.out_off & 3);
     const int nvec = (sh + nv + 3) >> 2;
@@ -951,8 +1019,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
 
     const ProfileOne<SS> one{P, cnt, w.loc, w.len, w.c0, w.nc, sh, neg_range};
     if (!BSIG_ABLATE(1)) {
-        for_each_read<NT, PRE>(R, P, win, pk.base, ptab, tid, one);
-        if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+        for_each_read<NT, PRE, HALF>(R, P, win, pk.base, ptab, tid, one);
+        // (the half form's windows are one chunk: bsig_plan_create)
+        if (!HALF && pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
     }
     block_sync<NT>();
     BSIG_STAMP(2);
@@ -980,15 +1049,31 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
     }
 #endif
 }
+template <int NT, bool SS, int PRE, int WAVES, bool RES>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                int32_t *__restrict__ out,
+                                                const uint2 *__restrict__ windows,
+                                                const BsigReadsDev R, const BsigKParams P)
+{
+    profile_tile<NT, SS, PRE, RES, false>(items, n_tiles, out, windows, R, P);
+}
+// k_profile reading the packed class's 16-bit column: a kernel of its own, so that the 4-byte form keeps its code
+template <int NT, bool SS, int PRE, int WAVES, bool RES>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile_half(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                int32_t *__restrict__ out,
+                                                const uint2 *__restrict__ windows,
+                                                const BsigReadsDev R, const BsigKParams P)
+{
+    profile_tile<NT, SS, PRE, RES, true>(items, n_tiles, out, windows, R, P);
+}
 
 // k_profile for T consecutive tiles per wave (large launches, windows from k_resolve_tiles): lane t fetches the work
 // item and the windows of tile t of its group -- ONE round trip for the T tiles -- and parks them in LDS; the wave then
 // works the tiles off one after the other through one image, which the store loop of a tile clears for the next.  From
 // its second tile on a wave pays neither a workgroup launch, nor the item / windows trip, nor the filter table.
-template <bool SS, int PRE, int WAVES, int T>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile_multi(
-    const BsigWorkItem *__restrict__ items, uint32_t n_tiles, int32_t *__restrict__ out, const uint2 *__restrict__ windows,
-    const BsigReadsDev R, const BsigKParams P)
+template <bool SS, int PRE, int T, bool HALF>
+__device__ __forceinline__ void profile_multi_tiles(const BsigWorkItem *__restrict__ items, uint32_t n_tiles, int32_t *__restrict__ out,
+                                                    const uint2 *__restrict__ windows, const BsigReadsDev &R, const BsigKParams &P)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t lds[];
     constexpr int S = SS ? 2 : 1;
@@ -1009,7 +1094,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(WAVES, 8)
         sp[0] = a; sp[1] = b; sp[2] = c; sp[3] = d; sp[4] = e;
     }
     for (int v = tid; v < img_vec; v += kWave) lds4[v] = make_int4(0, 0, 0, 0);
-    build_ptab<kWave>(ptab, R, P, tid);
+    if (!HALF) build_ptab<kWave>(ptab, R, P, tid);
     block_sync<kWave>();
     uint32_t *cnt = reinterpret_cast<uint32_t *>(lds);
     uint2 *lds2 = reinterpret_cast<uint2 *>(lds);
@@ -1030,8 +1115,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(WAVES, 8)
         const int nvec = (sh + nv + 3) >> 2;
         const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
         const ProfileOne<SS> one{P, cnt, w.loc, w.len, w.c0, w.nc, sh, neg_range};
-        for_each_read<kWave, PRE>(R, P, win, pbase, ptab, tid, one);
-        if (pchunks > 1) packed_later_chunks<kWave>(R, P, BSIG_MODE_PROFILE, w, pchunks, make_uint2(0u, 0xFFFFFFFFu), ptab, tid, one);
+        for_each_read<kWave, PRE, HALF>(R, P, win, pbase, ptab, tid, one);
+        if (!HALF && pchunks > 1) packed_later_chunks<kWave>(R, P, BSIG_MODE_PROFILE, w, pchunks, make_uint2(0u, 0xFFFFFFFFu), ptab, tid, one);
         block_sync<kWave>();
         int32_t *gbase = out + (w.out_off - sh);
         for (int v = tid; v < nvec; v += kWave) {
@@ -1041,6 +1126,20 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(WAVES, 8)
         }
         block_sync<kWave>();
     }
+}
+template <bool SS, int PRE, int WAVES, int T>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile_multi(
+    const BsigWorkItem *__restrict__ items, uint32_t n_tiles, int32_t *__restrict__ out, const uint2 *__restrict__ windows,
+    const BsigReadsDev R, const BsigKParams P)
+{
+    profile_multi_tiles<SS, PRE, T, false>(items, n_tiles, out, windows, R, P);
+}
+template <bool SS, int PRE, int WAVES, int T>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile_multi_half(
+    const BsigWorkItem *__restrict__ items, uint32_t n_tiles, int32_t *__restrict__ out, const uint2 *__restrict__ windows,
+    const BsigReadsDev R, const BsigKParams P)
+{
+    profile_multi_tiles<SS, PRE, T, true>(items, n_tiles, out, windows, R, P);
 }
 
 // Wide bins (binsize >~ 8): a tile has few cells and thousands of reads, and the position-sorted
@@ -1913,13 +2012,14 @@ namespace bsig {
 
 // Tuning knobs (defaults from the environment once, changeable at run time through bsig_debug_set_knob for
 // the sweep scripts): 0 = k_profile class-0 passes in flight (BAMSIGNALS_PROFILE_PRE), 1 = count tiles per
-// wave (BAMSIGNALS_COUNT_TILES), 2 = count passes in flight (BAMSIGNALS_COUNT_PRE).
-static int g_knobs[6] = {-1, -1, -1, -1, -1, -1};
+// wave (BAMSIGNALS_COUNT_TILES), 2 = count passes in flight (BAMSIGNALS_COUNT_PRE), 6 = k_profile_half's packed
+// passes in flight (BAMSIGNALS_PROFILE_HALF_PRE).
+static int g_knobs[7] = {-1, -1, -1, -1, -1, -1, -1};
 static int knob(int k)
 {
-    static const char *const names[6] = {"BAMSIGNALS_PROFILE_PRE", "BAMSIGNALS_COUNT_TILES", "BAMSIGNALS_COUNT_PRE", "BAMSIGNALS_KNOB3",
-                                         "BAMSIGNALS_KNOB4", "BAMSIGNALS_PROFILE_TILES"};
-    static const int dflt[6] = {2, 0, 0, 0, 0, 0};
+    static const char *const names[7] = {"BAMSIGNALS_PROFILE_PRE", "BAMSIGNALS_COUNT_TILES", "BAMSIGNALS_COUNT_PRE", "BAMSIGNALS_KNOB3",
+                                         "BAMSIGNALS_KNOB4", "BAMSIGNALS_PROFILE_TILES", "BAMSIGNALS_PROFILE_HALF_PRE"};
+    static const int dflt[7] = {2, 0, 0, 0, 0, 0, 2};
     if (g_knobs[k] < 0) {
         const char *e = getenv(names[k]);
         g_knobs[k] = e ? atoi(e) : dflt[k];
@@ -1959,11 +2059,16 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         // class-0 passes requested before anything is consumed (knob 0: 2, 3 or 4; fewer = fewer VGPRs = more
         // resident waves, more = one round trip for denser windows)
         const int pre = knob(0);
-#define BSIG_KP(SS_, PRE_, W_)                                                                                                          \
+        // the half form (P.packed_half: k_profile_half, k_profile_multi_half): one pass holds 8 * NT reads, a 2-kb tile's
+        // ~410 at the north star's depth; knob 6 (BAMSIGNALS_PROFILE_HALF_PRE): passes requested up front, 1 or 2
+        const bool half = P.packed_half != 0;
+        const int pre_h = knob(6) <= 1 ? 1 : 2;
+#define BSIG_KP(K_, SS_, PRE_, W_)                                                                                                      \
     do {                                                                                                                                \
-        if (P.resolved) hipLaunchKernelGGL((k_profile<NT, SS_, PRE_, W_, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); \
-        else hipLaunchKernelGGL((k_profile<NT, SS_, PRE_, W_, false>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); \
+        if (P.resolved) hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); \
+        else hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, false>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); \
     } while (0)
+#define BSIG_KPW(K_, SS_, PRE_) do { if (w8) BSIG_KP(K_, SS_, PRE_, 8); else BSIG_KP(K_, SS_, PRE_, 1); } while (0)
         // the build for 8 waves per SIMD (96 SGPRs, the rest kept in VGPR lanes; 57 VGPRs in the resolved form, which
         // alone has them to spare): narrow tiles -- many workgroups per byte moved -- gain from the eighth wave,
         // 2-kb tiles lose (same bases in 500 / 1,000 / 1,500 / 2,000-cell tiles, two launches, 7 -> 8 waves:
@@ -1979,14 +2084,29 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
             const int T = pt >= 4 ? 4 : 2;
             const dim3 g2((unsigned)((n_items + T - 1) / T));
             const size_t lds_m = lds + (size_t)T * 20 * sizeof(uint32_t);
-#define BSIG_KM(SS_, W_, T_) hipLaunchKernelGGL((k_profile_multi<SS_, 2, W_, T_>), g2, dim3(kWave), lds_m, st, items, (uint32_t)n_items, out, windows, R, P)
-            if (ss) { if (w8) { if (T == 4) BSIG_KM(true, 8, 4); else BSIG_KM(true, 8, 2); } else { if (T == 4) BSIG_KM(true, 1, 4); else BSIG_KM(true, 1, 2); } }
-            else    { if (w8) { if (T == 4) BSIG_KM(false, 8, 4); else BSIG_KM(false, 8, 2); } else { if (T == 4) BSIG_KM(false, 1, 4); else BSIG_KM(false, 1, 2); } }
+#define BSIG_KM(K_, SS_, PRE_, W_, T_) hipLaunchKernelGGL((K_<SS_, PRE_, W_, T_>), g2, dim3(kWave), lds_m, st, items, (uint32_t)n_items, out, windows, R, P)
+#define BSIG_KMT(K_, SS_, PRE_, W_) do { if (T == 4) BSIG_KM(K_, SS_, PRE_, W_, 4); else BSIG_KM(K_, SS_, PRE_, W_, 2); } while (0)
+#define BSIG_KMW(K_, SS_, PRE_) do { if (w8) BSIG_KMT(K_, SS_, PRE_, 8); else BSIG_KMT(K_, SS_, PRE_, 1); } while (0)
+            if (half) {
+                if (ss) { if (pre_h == 1) BSIG_KMW(k_profile_multi_half, true, 1); else BSIG_KMW(k_profile_multi_half, true, 2); }
+                else    { if (pre_h == 1) BSIG_KMW(k_profile_multi_half, false, 1); else BSIG_KMW(k_profile_multi_half, false, 2); }
+            } else {
+                if (ss) BSIG_KMW(k_profile_multi, true, 2);
+                else    BSIG_KMW(k_profile_multi, false, 2);
+            }
+#undef BSIG_KMW
+#undef BSIG_KMT
 #undef BSIG_KM
             return hipGetLastError();
         }
-        if (ss) { if (pre <= 2) { if (w8) BSIG_KP(true, 2, 8); else BSIG_KP(true, 2, 1); } else if (pre == 3) BSIG_KP(true, 3, 1); else BSIG_KP(true, 4, 1); }
-        else    { if (pre <= 2) { if (w8) BSIG_KP(false, 2, 8); else BSIG_KP(false, 2, 1); } else if (pre == 3) BSIG_KP(false, 3, 1); else BSIG_KP(false, 4, 1); }
+        if (half) {
+            if (ss) { if (pre_h == 1) BSIG_KPW(k_profile_half, true, 1); else BSIG_KPW(k_profile_half, true, 2); }
+            else    { if (pre_h == 1) BSIG_KPW(k_profile_half, false, 1); else BSIG_KPW(k_profile_half, false, 2); }
+            return hipGetLastError();
+        }
+        if (ss) { if (pre <= 2) BSIG_KPW(k_profile, true, 2); else if (pre == 3) BSIG_KP(k_profile, true, 3, 1); else BSIG_KP(k_profile, true, 4, 1); }
+        else    { if (pre <= 2) BSIG_KPW(k_profile, false, 2); else if (pre == 3) BSIG_KP(k_profile, false, 3, 1); else BSIG_KP(k_profile, false, 4, 1); }
+#undef BSIG_KPW
 #undef BSIG_KP
     } else if (mode == BSIG_MODE_COVERAGE && (P.binsize > 1 || ss)) {
         // bins and / or strands (k_coverage_bins): int32 difference image, the scan totals, the packed class's table
@@ -2035,6 +2155,13 @@ hipError_t launch_pileup(int mode, int ss, int threads, const BsigReadsDev &R, c
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL(k_make_ptab, dim3(1), dim3(128), 0, st, R, P, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_make_p5h(const uint32_t *fm, const uint32_t *fmtab, int64_t n, int64_t cap, uint16_t *out, hipStream_t st)
+{
+    if (cap <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_make_p5h, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, fm, fmtab, n, cap, out);
     return hipGetLastError();
 }
 
@@ -2164,7 +2291,7 @@ extern "C" int bsig_debug_set_resolve_min(long long n_tiles);     // runtime.hip
 extern "C" int bsig_debug_set_knob(int which, int value)
 {
     if (which == 4) return bsig_debug_set_resolve_min(value);
-    if (which < 0 || which >= 6 || value < 0) return -1;
+    if (which < 0 || which >= 7 || value < 0) return -1;
     bsig::g_knobs[which] = value;
     return 0;
 }
@@ -2172,7 +2299,8 @@ extern "C" int bsig_debug_set_knob(int which, int value)
 // (debug: what the compiler made of the pileup kernels the BASELINE configurations run -- registers per lane and
 // scratch bytes per lane (spills: there must be none); tests/test_gpu_parity.py.  which: 0 k_profile resolved,
 // 1 its 8-wave build, 2 k_profile fused, 3 k_profile_multi (8 waves, four tiles), 4 k_coverage resolved,
-// 5 k_count_multi<4, 2>, 6 k_profile resolved with strands)
+// 5 k_count_multi<4, 2>, 6 k_profile resolved with strands; the half form (k_profile_half): 7 resolved, 8 its build with
+// one pass in flight, 9 k_profile_multi_half (8 waves, four tiles), 10 resolved with strands)
 extern "C" int bsig_debug_pileup_attrs(int which, int *vgprs, int *scratch_bytes)
 {
     const void *f = nullptr;
@@ -2184,6 +2312,10 @@ extern "C" int bsig_debug_pileup_attrs(int which, int *vgprs, int *scratch_bytes
     case 4: f = reinterpret_cast<const void *>(&k_coverage<64, 2, true>); break;
     case 5: f = reinterpret_cast<const void *>(&k_count_multi<4, 2>); break;
     case 6: f = reinterpret_cast<const void *>(&k_profile<64, true, 2, 1, true>); break;
+    case 7: f = reinterpret_cast<const void *>(&k_profile_half<64, false, 2, 1, true>); break;
+    case 8: f = reinterpret_cast<const void *>(&k_profile_half<64, false, 1, 1, true>); break;
+    case 9: f = reinterpret_cast<const void *>(&k_profile_multi_half<false, 2, 8, 4>); break;
+    case 10: f = reinterpret_cast<const void *>(&k_profile_half<64, true, 2, 1, true>); break;
     default: return 1;
     }
     hipFuncAttributes a;

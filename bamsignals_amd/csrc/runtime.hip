@@ -439,6 +439,25 @@ uint64_t bsig::next_layout_gen()
     return ++g;
 }
 
+// The packed class's 16-bit 5'-end column (bsig_types.h: p5h), derived from its words and the pair table wherever a
+// bsig_reads is made (laid out, cloned, loaded) and never saved.  +2 bytes per packed read in HBM (R->info.hbm_bytes).
+// env BAMSIGNALS_PACKED_HALF=0, read here: no column, every plan reads the 4-byte words.
+static int make_packed_half(bsig_reads *R, hipStream_t st)
+{
+    BsigClassCols &C = R->dev.cls[BSIG_CLASS_PACKED];
+    C.p5h = nullptr;
+    const char *e = getenv("BAMSIGNALS_PACKED_HALF");
+    if (C.n == 0 || !R->dev.fmtab || (e && !strcmp(e, "0"))) return BSIG_OK;
+    const int64_t cap = (C.n + 7) / 8 * 8 + 8;           // the 16-B loads of the last reads stay inside, and read zeros
+    uint16_t *p = nullptr;
+    HIP_TRY(R->pool.alloc(&p, (size_t)cap));
+    HIP_TRY(bsig::launch_make_p5h(C.fm, R->dev.fmtab, C.n, cap, p, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    C.p5h = p;
+    R->info.hbm_bytes = R->pool.footprint();
+    return BSIG_OK;
+}
+
 int bsig::layout_from_device(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_ref, const int32_t *ref_len,
                              const int64_t *ref_off, const int32_t *d_pos, const int32_t *d_end,
                              const uint16_t *d_flag, const uint8_t *d_mapq, const int32_t *d_tlen)
@@ -614,7 +633,7 @@ int bsig::layout_from_device(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_
     HIP_TRY(hipStreamSynchronize(st));
     if (diag) fprintf(stderr, "  [layout] scatter + indexes %.1f ms\n", diag_ms());
     R->info.hbm_bytes = R->pool.footprint();
-    return BSIG_OK;
+    return make_packed_half(R, st);
 }
 
 extern "C" {
@@ -756,6 +775,11 @@ int bsig_reads_clone(const bsig_reads *src, bsig_ctx *dst_ctx, bsig_reads **out)
                     hipGetErrorString(e));
     }
     R->info.hbm_bytes = R->pool.footprint();
+    // (D = S above took the source's p5h: the clone makes its own, under this process's BAMSIGNALS_PACKED_HALF)
+    if (const int rc = make_packed_half(R, st)) {
+        delete R;
+        return rc;
+    }
     *out = R;
     return BSIG_OK;
 }
@@ -1302,6 +1326,7 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
         if (rc) return rc;
         if (sum != H.checksum) return fail(BSIG_ERR_FORMAT, "%s is damaged (checksum)", path);
     }
+    if (const int rc = make_packed_half(R.get(), ctx->stream)) return rc;
     *out = R.release();
     return BSIG_OK;
 }
@@ -1402,6 +1427,24 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     {
         const int64_t h_max = mid ? std::max<int64_t>(0, prm->tlen_filter[1]) / 2 : 0;
         K.rel24 = 2 * std::llabs((long long)K.shift) + h_max + (1 << BSIG_PACK_POS_BITS) + 256 < (1ll << 23);
+    }
+    // The packed class's 16-bit 5'-end column (kernels.hip: ProfileOne::oct) serves a plan that reads nothing else of
+    // a packed read: bins of one base, no template-length rule, and a flag/mapq filter that rejects none of the file's
+    // codes (fm_rejected, evaluated here on the pair table).  The half-word keeps 15 bits of the 5' end, so every
+    // tile's packed window must also lie in one chunk with room for a reverse read's span behind it: tile bases +
+    // 2 ext + maxspan + two buckets of rounding <= 2^15 - 256.  Then base + ((h - base) & 0x7FFF) is the 5' end, and
+    // no window has a second chunk (packed_later_chunks).  Anything else reads the 4-byte words.
+    {
+        const BsigClassCols &C = reads->dev.cls[BSIG_CLASS_PACKED];
+        bool half = mode == BSIG_MODE_PROFILE && K.binsize == 1 && !K.use_tlen && C.p5h != nullptr;
+        for (int c = 0; half && c < reads->dev.n_codes; ++c) {
+            const uint32_t fm = reads->fmtab[(size_t)c];
+            const uint32_t nf = ~(fm & 0xFFFFu);
+            const bool rej = (int)((fm >> 16) & 0xFFu) < K.mapqual || (K.requiredF & nf) != 0u || (K.filteredF & nf) == 0u;
+            half = !rej;
+        }
+        half = half && (int64_t)K.tile_cells + 2 * ext + C.maxspan + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
+        K.packed_half = half ? 1 : 0;
     }
     bsig::magic_u31(K.binsize, &K.div_magic, &K.div_shift);
     K.div_m15 = 0; K.div_s15 = 0;
@@ -1715,7 +1758,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
         t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
         t.streamed = (int64_t)acc[BSIG_MAX_CLASSES];
         t.heavy_tiles = (int32_t)std::min<int64_t>(p->n_heavy_tiles, INT32_MAX);
-        t.bytes_per_visit_packed = p->kp.use_tlen ? 8 : 4;     // the packed word [+ tlen]
+        t.bytes_per_visit_packed = p->kp.packed_half ? 2 : p->kp.use_tlen ? 8 : 4;     // the half-word, or the packed word [+ tlen]
         t.bytes_per_visit_short = p->kp.use_tlen ? 12 : 8;     // span <= 4096: pos + flag/mapq/span in one word [+ tlen]
         t.bytes_per_visit_long = p->kp.use_tlen ? 16 : 12;     // pos + end + flag/mapq [+ tlen]
         // reads + work items + index entries + result cells
