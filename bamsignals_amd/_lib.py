@@ -107,6 +107,11 @@ def load():
     lib.bsig_plan_overflowed.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.bsig_plan_free.argtypes = [C.c_void_p]
     lib.bsig_plan_free.restype = None
+    lib.bsig_plan_create_sum.argtypes = lib.bsig_plan_create.argtypes
+    lib.bsig_plan_sum_cells.argtypes = [C.c_void_p]
+    lib.bsig_plan_sum_cells.restype = C.c_int64
+    lib.bsig_plan_run_sum.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_run_sum_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_pileup_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
     lib.bsig_bam_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -138,6 +143,8 @@ def load():
     lib.bsig_coverage_core_into.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
     lib.bsig_coverage_core_ex.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]
     lib.bsig_coverage_core_ex_into.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
+    lib.bsig_pileup_sum.argtypes = core_head + [C.c_int32] * 9 + [C.c_void_p]
+    lib.bsig_coverage_sum.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_write_sam_as_bam_and_index.argtypes = [C.c_char_p, C.c_char_p]
     lib.bsig_write_columns_as_bam.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(Columns),
                                               C.c_int32]

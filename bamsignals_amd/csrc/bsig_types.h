@@ -119,4 +119,11 @@ struct BsigKParams {
                             // INT32_MAX (the plan's device flag; NULL where no add can)
 };
 
+// Sums over ranges (kernels.hip: k_sum_reduce): slabs [slot_lo, slot_hi) of runs of one tile position, added into the
+// per-base sums from value cell0 (= c0 * S) on, nvals (= nc * S) of them; at most kSumChunkSlots slabs a chunk
+struct BsigSumChunk {
+    uint32_t slot_lo, slot_hi;
+    int32_t cell0, nvals;
+};
+
 #endif

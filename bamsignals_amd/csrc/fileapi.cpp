@@ -633,15 +633,71 @@ bool regions_covered(const Resident &R, int64_t n, const int32_t *rid, const int
 }
 
 // the common body of pileup_core / coverage_core
+// A sum over ranges of one width (bsig_pileup_sum / bsig_coverage_sum): one GPU sums them all; with several, each sums
+// its block of the (rid, loc)-sorted ranges and the host adds the int64 vectors -- no per-range cell leaves a GPU
+int sum_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                 const int32_t *width, const int32_t *strand, const bsig_params &prm, int64_t cells, int64_t *sum, double *X,
+                 std::string &route)
+{
+    const size_t nd = reads.size();
+    if (nd == 1) {
+        const double t0 = now_s();
+        bsig_plan *plan = nullptr;
+        int rc = bsig_plan_create_sum(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, &plan);
+        X[3] = now_s() - t0;
+        if (rc == BSIG_OK) rc = bsig::plan_run_sum_host_timed(plan, sum, &X[4], &X[5]);
+        if (plan) bsig_plan_free(plan);
+        route = "sum";
+        return rc;
+    }
+    std::vector<int64_t> order;
+    bsig::sort_ranges(n, rid, loc, order);
+    std::vector<std::vector<int64_t>> part(nd, std::vector<int64_t>((size_t)cells, 0));
+    const int rc = for_each_slot(nd, [&](size_t k) -> int {
+        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
+        if (a >= b) return BSIG_OK;
+        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
+        for (int64_t i = a; i < b; ++i) {
+            const int64_t j = order[(size_t)i];
+            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
+        }
+        bsig_plan *plan = nullptr;
+        int rk = bsig_plan_create_sum(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &prm, &plan);
+        if (rk == BSIG_OK) rk = bsig_plan_run_sum_host(plan, part[k].data());
+        if (plan) bsig_plan_free(plan);
+        return rk;
+    });
+    if (rc != BSIG_OK) return rc;
+    for (int64_t c = 0; c < cells; ++c) {
+        int64_t t = 0;
+        for (size_t k = 0; k < nd; ++k) t += part[k][(size_t)c];
+        sum[c] = t;
+    }
+    route = "sum of " + std::to_string(nd) + " blocks of ranges, added on the host";
+    return BSIG_OK;
+}
+
 int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                const char *const *levels, const int32_t *start, const int32_t *width,
-               const int32_t *strand, const bsig_params &prm, int32_t device, const bsig::HostDest &dest)
+               const int32_t *strand, const bsig_params &prm, int32_t device, const bsig::HostDest &dest,
+               int64_t *sum = nullptr)
 {
     if (!bampath) return fail(BSIG_ERR_ARG, "bampath is NULL");
     if (n < 0 || (n > 0 && (!seq_code || !start || !width || !strand || !levels)))
         return fail(BSIG_ERR_ARG, "range arrays missing");
     const int64_t *off = dest.off;
-    if (!off) return fail(BSIG_ERR_ARG, "offsets missing");
+    if (!off && !sum) return fail(BSIG_ERR_ARG, "offsets missing");
+    int64_t sum_cells = 0;
+    if (sum) {
+        // the sum's own checks, before any I/O
+        if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
+        for (int64_t i = 1; i < n; ++i)
+            if (width[i] != width[0]) return fail(BSIG_ERR_ARG, "all signals must have the same length");
+        const int64_t b = prm.mode == BSIG_MODE_COVERAGE ? 1 : std::max<int32_t>(prm.binsize, 1);
+        const bool ss2 = prm.mode != BSIG_MODE_COVERAGE && prm.ss;
+        sum_cells = n > 0 && width[0] > 0 ? ((int64_t)width[0] + b - 1) / b * (ss2 ? 2 : 1) : 0;
+        for (int64_t c = 0; c < sum_cells; ++c) sum[c] = 0;
+    }
     double *T = g_call_timing, *X = g_call_timing_ex;
     for (int k = 0; k < 6; ++k) T[k] = 0;
     for (int k = 0; k < 10; ++k) X[k] = 0;
@@ -932,7 +988,9 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     std::string gather;
     for (int attempt = 0; attempt < 2; ++attempt) {
     if (attempt) drop_spare_device_memory(slots.get());        // (out of device memory: once more with the cache's spare memory given back)
-    if (!many) {
+    if (sum) {
+        rc = sum_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, sum_cells, sum, X, gather);
+    } else if (!many) {
         // plan (ranges -> tiles in HBM), kernels, download -- timed apart
         bsig_plan *plan = nullptr;
         rc = bsig_plan_create(slots->ctx[0], res->reads[0], n, rid.data(), loc.data(), width, strand, &prm, &plan);
@@ -956,7 +1014,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (rc == BSIG_OK) rc = bam_index_wait(bam);      // a damaged index fails the call, as it does in the reference's open
     T[4] = now_s() - t_begin;
     snprintf(g_call_route, sizeof g_call_route, "%zu GPU slot(s); reads: %s; result: %s", nd, how_decoded.c_str(),
-             many ? gather.c_str() : "download");
+             many || sum ? gather.c_str() : "download");
     return rc;
 }
 
@@ -1123,7 +1181,7 @@ static int pileup_core_impl(const char *bampath, int64_t n, const int32_t *seq_c
                             const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
                             int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss, int32_t requiredF,
                             int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int32_t *out,
-                            const int64_t *off, int32_t *const *dst)
+                            const int64_t *off, int32_t *const *dst, int64_t *sum = nullptr)
 {
     (void)maxgap;
     bsig_params p;
@@ -1136,6 +1194,10 @@ static int pileup_core_impl(const char *bampath, int64_t n, const int32_t *seq_c
     for (int k = 0; k < n_tlen_filter; ++k) p.tlen_filter[k] = tlen_filter[k];
     bsig::HostDest D;
     std::vector<int64_t> own_off;
+    if (sum) {
+        if (binsize <= 0) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
+        return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, D, sum);
+    }
     if (dst) {
         // in place: the layout is computed here (bsig_layout); bamCount's is one vector, dst[0]
         if (n < 0 || (n > 0 && !width)) return fail(BSIG_ERR_ARG, "range arrays missing");
@@ -1176,7 +1238,7 @@ static int coverage_core_impl(const char *bampath, int64_t n, const int32_t *seq
                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                               int32_t maxgap, int32_t device, int32_t *out, const int64_t *off, int32_t *const *dst,
-                              bool ex = false, int32_t binsize = 1, int32_t ss = 0)
+                              bool ex = false, int32_t binsize = 1, int32_t ss = 0, int64_t *sum = nullptr)
 {
     (void)maxgap;
     bsig_params p;
@@ -1189,6 +1251,7 @@ static int coverage_core_impl(const char *bampath, int64_t n, const int32_t *seq
     for (int k = 0; k < n_tlen_filter; ++k) p.tlen_filter[k] = tlen_filter[k];
     bsig::HostDest D;
     std::vector<int64_t> own_off;
+    if (sum) return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, D, sum);
     if (dst) {
         if (n < 0 || (n > 0 && !width)) return fail(BSIG_ERR_ARG, "range arrays missing");
         // (a binsize outside 1 .. 65,536 fails in file_level before any I/O; the layout only needs it >= 1 here)
@@ -1241,6 +1304,28 @@ int bsig_coverage_core_ex_into(const char *bampath, int64_t n, const int32_t *se
     if (!dst) return fail(BSIG_ERR_ARG, "destinations missing");
     return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
                               requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, dst, true, binsize, ss);
+}
+
+int bsig_pileup_sum(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                    const char *const *levels, const int32_t *start, const int32_t *width,
+                    const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                    int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss, int32_t requiredF,
+                    int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int64_t *sum)
+{
+    if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
+    return pileup_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual, binsize,
+                            shift, ss, requiredF, filteredF, pe_mid, maxgap, device, nullptr, nullptr, nullptr, sum);
+}
+
+int bsig_coverage_sum(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                      const char *const *levels, const int32_t *start, const int32_t *width,
+                      const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                      int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum)
+{
+    if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
+    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
+                              requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, nullptr, true, binsize, ss, sum);
 }
 
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath)

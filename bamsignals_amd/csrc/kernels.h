@@ -56,6 +56,22 @@ hipError_t launch_build_idx(int64_t n, const uint32_t *gb, uint64_t n_buckets, u
 hipError_t launch_checksum(const void *words, uint64_t n_words, uint64_t salt, unsigned long long *acc, hipStream_t st);
 // *bad (device) = 1 unless idx[0..n_buckets] is non-decreasing, <= n_reads, and ends at n_reads
 hipError_t launch_check_idx(const uint32_t *idx, uint64_t n_buckets, uint32_t n_reads, int *bad, hipStream_t st);
+// Sums over ranges of one width (bsig_plan_create_sum).  kind: 0 bamProfile, 1 coverage, 2 strand-split coverage.
+// k_sum_tiles: run r = tiles [runs[r].x, runs[r].y) of one c0 -> slab r (sum_tiles_lds / 4 int32 rounded: the caller
+// sizes it as tile_cells * S rounded up to 4); windows / resolve_first as in launch_pileup (P.resolved: BsigResolved
+// per tile), or the fixed windows of heavy slices
+size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells);
+int sum_blocks_per_cu(int kind, int ss, int nw, bool half, int tile_cells);
+hipError_t launch_sum_tiles(int kind, int ss, int nw, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
+                            int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int32_t *slab,
+                            hipStream_t st);
+// slabs -> per-base int64 sums (added: zero `base` first); signed for coverage differences
+hipError_t launch_sum_reduce(bool is_signed, const int32_t *slab, int32_t slab_vals, const BsigSumChunk *chunks, int64_t n_chunks,
+                             int32_t max_nvals, unsigned long long *base, hipStream_t st);
+// coverage: prefix sums of the per-base differences that restart at every tile boundary, in place
+hipError_t launch_sum_scan(long long *base, int32_t width, int32_t tile_cells, int32_t S, hipStream_t st);
+// per-base sums -> n_out = n_bins * S bins (2 * bin + s)
+hipError_t launch_sum_bins(const long long *base, int32_t width, int32_t binsize, int32_t S, int64_t n_out, long long *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

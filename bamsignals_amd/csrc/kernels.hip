@@ -1599,6 +1599,166 @@ __global__ __launch_bounds__(NT) void k_coverage_bins(const BsigWorkItem *__rest
 }
 
 // ------------------------------------------------------------------------------------------
+// Sums over ranges of one width (bsig_plan_create_sum): the metaprofile of alignSignals + rowMeans
+// ------------------------------------------------------------------------------------------
+// The plan tiles every range per base (bins come last: binning is linear) and orders its tiles by c0, so that all
+// tiles of one c0 -- one tile position in range orientation, the same nc for every range -- are consecutive.  A
+// workgroup owns a run of tiles of ONE c0 (bsig_plan_create_sum never lets a run cross a c0 or hold more than 65,536
+// tiles).  Its NW waves take the run's tiles in turn, each wave on its own tile and 16-bit image with the read bodies
+// of the per-range kernels (ProfileOne, CoverOne; CoverBinsOne at binsize 1 with strands), so that NW item -> windows
+// -> reads chains are in flight per workgroup.  A finished image is folded into the workgroup's 32-bit accumulator
+// with LDS atomics and cleared for the wave's next tile; at the end the accumulator is stored once, as the run's slab
+// (plain 16-B stores).  Exact: an unsliced tile adds at most 32,768 to a cell (a coverage difference at most 32,767 in
+// magnitude) and a slice of a heavy tile less, so 65,536 tiles stay below 2^32 unsigned (2^31 signed).
+enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 };
+
+template <int NW, int KIND, bool SS, bool HALF, bool RES>
+__global__ __launch_bounds__(NW * kWave) void k_sum_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                          int32_t *__restrict__ slab, const uint2 *__restrict__ windows,
+                                                          const BsigReadsDev R, const BsigKParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    constexpr int NT = NW * kWave;
+    constexpr int S = SS ? 2 : 1;
+    constexpr int mode = KIND == kSumProfile ? BSIG_MODE_PROFILE : BSIG_MODE_COVERAGE;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+    const int vals = P.tile_cells * S;
+    const int acc_v = (vals + 3) / 4;                                        // 16-B vectors of the accumulator
+    const int img_v = KIND == kSumCoverSS ? (vals + 3) / 4 : (vals + 7) / 8; // ... of one wave's image
+    int4 *lds4 = reinterpret_cast<int4 *>(lds);
+    uint32_t *acc = reinterpret_cast<uint32_t *>(lds);
+    int32_t *img = lds + 4 * (acc_v + img_v * wv);
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds4 + acc_v + img_v * NW);
+    for (int v = tid; v < acc_v + img_v * NW; v += NT) lds4[v] = make_int4(0, 0, 0, 0);
+    if (!HALF) build_ptab<NT>(ptab, R, P, tid);
+    const uint2 run = runs[blockIdx.x];
+    __syncthreads();
+
+#pragma unroll 1
+    for (uint32_t t = run.x + (uint32_t)wv; t < run.y; t += NW) {
+        const BsigWorkItem w = items[t];
+        uint2 win[BSIG_MAX_CLASSES], clip;
+        PackedWin pk;
+        load_windows<RES>(R, P, mode, w, items, windows, win, t, pk, clip);
+        const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
+        if constexpr (KIND == kSumProfile) {
+            const ProfileOne<SS> one{P, reinterpret_cast<uint32_t *>(img), w.loc, w.len, w.c0, w.nc, 0, neg_range};
+            for_each_read<kWave, 2, HALF>(R, P, win, pk.base, ptab, lane, one);
+            if (!HALF && pk.n_chunks > 1) packed_later_chunks<kWave>(R, P, mode, w, pk.n_chunks, clip, ptab, lane, one);
+        } else if constexpr (KIND == kSumCover) {
+            const CoverOne one{P, img, w.loc, w.c0, w.nc, 0, neg_range, w.loc + w.len - 1};
+            for_each_read<kWave, 2>(R, P, win, pk.base, ptab, lane, one);
+            if (pk.n_chunks > 1) packed_later_chunks<kWave>(R, P, mode, w, pk.n_chunks, clip, ptab, lane, one);
+        } else {
+            const int hi = (w.c0 + w.nc < w.len ? w.c0 + w.nc : w.len) - 1;
+            const CoverBinsOne<true> one{P, img, w.loc, w.c0, w.nc, 0, neg_range, w.loc + w.len - 1, w.c0, hi};
+            for_each_read<kWave, 2>(R, P, win, pk.base, ptab, lane, one);
+            if (pk.n_chunks > 1) packed_later_chunks<kWave>(R, P, mode, w, pk.n_chunks, clip, ptab, lane, one);
+        }
+        block_sync<kWave>();
+        // fold the image into the accumulator and clear it for this wave's next tile
+        const int nv = w.nc * S;
+        if constexpr (KIND == kSumCoverSS) {
+            for (int v = lane; v < nv; v += kWave) {
+                const int x = img[v];
+                img[v] = 0;
+                if (x) atomicAdd(&acc[v], (uint32_t)x);
+            }
+        } else {
+            uint32_t *im = reinterpret_cast<uint32_t *>(img);
+            for (int v = lane; 2 * v < nv; v += kWave) {
+                const uint32_t d = im[v];
+                im[v] = 0u;
+                // profile: two unsigned 16-bit counters; coverage: two signed 16-bit differences (see k_coverage)
+                const uint32_t a = KIND == kSumProfile ? d & 0xFFFFu : (uint32_t)(int)(int16_t)(uint16_t)d;
+                const uint32_t b = KIND == kSumProfile ? d >> 16 : (uint32_t)(int)(int16_t)(uint16_t)((d + 0x8000u) >> 16);
+                if (a) atomicAdd(&acc[2 * v], a);
+                if (b) atomicAdd(&acc[2 * v + 1], b);
+            }
+        }
+        block_sync<kWave>();
+    }
+    __syncthreads();
+    int4 *dst = reinterpret_cast<int4 *>(slab + (size_t)blockIdx.x * (size_t)(4 * acc_v));
+    for (int v = tid; v < acc_v; v += NT) dst[v] = lds4[v];
+}
+
+// The slabs of the runs of one c0, a chunk of at most kSumChunkSlots of them at a time, added into the per-base sums
+// (int64, cell x * S + s of the range-oriented width; zeroed in front): one thread per four cells, unsigned slabs for
+// profiles, signed ones for coverage differences
+template <bool SIGNED>
+__global__ __launch_bounds__(256) void k_sum_reduce(const int32_t *__restrict__ slab, int32_t slab_vals, const BsigSumChunk *__restrict__ chunks,
+                                                    unsigned long long *__restrict__ base)
+{
+    const BsigSumChunk c = chunks[blockIdx.y];
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (4 * v >= c.nvals) return;
+    int64_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    for (uint32_t k = c.slot_lo; k < c.slot_hi; ++k) {
+        const int4 x = reinterpret_cast<const int4 *>(slab + (size_t)k * (size_t)slab_vals)[v];
+        if (SIGNED) { s0 += x.x; s1 += x.y; s2 += x.z; s3 += x.w; }
+        else { s0 += (uint32_t)x.x; s1 += (uint32_t)x.y; s2 += (uint32_t)x.z; s3 += (uint32_t)x.w; }
+    }
+    unsigned long long *o = base + c.cell0 + 4 * v;
+    const int left = c.nvals - 4 * v;
+    if (s0) atomicAdd(o + 0, (unsigned long long)s0);
+    if (left > 1 && s1) atomicAdd(o + 1, (unsigned long long)s1);
+    if (left > 2 && s2) atomicAdd(o + 2, (unsigned long long)s2);
+    if (left > 3 && s3) atomicAdd(o + 3, (unsigned long long)s3);
+}
+
+// Coverage: the summed difference images become summed coverage by a prefix sum that RESTARTS at every tile boundary
+// c0 (each tile's image is self-contained: a read that crosses a boundary starts in both tiles).  One workgroup per
+// (tile position, row): each thread scans up to 32 consecutive cells, the workgroup scans the thread totals.
+__global__ __launch_bounds__(256) void k_sum_scan(long long *__restrict__ base, int32_t width, int32_t tile_cells, int32_t S)
+{
+    __shared__ long long tot[256];
+    const int q = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    const int c0 = q * tile_cells;
+    const int nc = width - c0 < tile_cells ? width - c0 : tile_cells;
+    const int per = (nc + 255) / 256;
+    const int a = tid * per, b = a + per < nc ? a + per : nc;
+    long long run = 0;
+    for (int i = a; i < b; ++i) run += base[(size_t)(c0 + i) * S + s];
+    tot[tid] = run;
+    __syncthreads();
+    for (int d = 1; d < 256; d *= 2) {           // inclusive Hillis-Steele scan of the thread totals
+        const long long y = tid >= d ? tot[tid - d] : 0;
+        __syncthreads();
+        tot[tid] += y;
+        __syncthreads();
+    }
+    long long acc = tot[tid] - run;
+    for (int i = a; i < b; ++i) {
+        long long *p = base + (size_t)(c0 + i) * S + s;
+        acc += *p;
+        *p = acc;
+    }
+}
+
+// Bins in range orientation: out[2 * bin + s] (out[bin] without strands) = the per-base sums of the bin's bases
+// [bin * binsize, min((bin + 1) * binsize, width)); one thread per cell for narrow bins, one wave per cell for wide ones
+template <bool WAVE>
+__global__ __launch_bounds__(256) void k_sum_bins(const long long *__restrict__ base, int32_t width, int32_t binsize, int32_t S,
+                                                  int64_t n_out, long long *__restrict__ out)
+{
+    const int64_t g = WAVE ? (int64_t)blockIdx.x * 4 + threadIdx.x / kWave : (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_out) return;
+    const int64_t j = g / S, s = g - j * S;
+    const int64_t x0 = j * binsize, x1 = x0 + binsize < width ? x0 + binsize : width;
+    long long sum = 0;
+    if (WAVE) {
+        for (int64_t x = x0 + (threadIdx.x & (kWave - 1)); x < x1; x += kWave) sum += base[x * S + s];
+        for (int m = kWave / 2; m >= 1; m /= 2) sum += __shfl_xor(sum, m);
+        if ((threadIdx.x & (kWave - 1)) == 0) out[g] = sum;
+    } else {
+        for (int64_t x = x0; x < x1; ++x) sum += base[x * S + s];
+        out[g] = sum;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // one-time layout of the reads in HBM
 // ------------------------------------------------------------------------------------------
 
@@ -2150,6 +2310,90 @@ hipError_t launch_pileup(int mode, int ss, int threads, const BsigReadsDev &R, c
     case 256: return launch_mode<256>(mode, ss, R, P, items, n_items, tile_cells, (uint2 *)windows, resolve_first, out, st);
     default:  return hipErrorInvalidValue;
     }
+}
+
+// ---- sums over ranges -------------------------------------------------------------------------------------------
+size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells)
+{
+    const int vals = tile_cells * (ss ? 2 : 1);
+    const int acc_v = (vals + 3) / 4, img_v = kind == kSumCoverSS ? (vals + 3) / 4 : (vals + 7) / 8;
+    return (size_t)(acc_v + img_v * nw) * 16 + BSIG_PACK_CODES;
+}
+
+// one k_sum_tiles instantiation by its run-time choices (f receives the kernel's address)
+template <typename Fn>
+static hipError_t with_sum_kernel(int kind, int ss, int nw, bool half, bool res, Fn &&f)
+{
+#define BSIG_SK(NW_, K_, SS_, H_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, H_, true>); else return f(k_sum_tiles<NW_, K_, SS_, H_, false>); } while (0)
+#define BSIG_SKN(K_, SS_, H_) do { if (nw == 1) BSIG_SK(1, K_, SS_, H_); else if (nw == 2) BSIG_SK(2, K_, SS_, H_); else BSIG_SK(4, K_, SS_, H_); } while (0)
+    if (nw != 1 && nw != 2 && nw != 4) return hipErrorInvalidValue;
+    if (kind == kSumProfile) {
+        if (ss) { if (half) BSIG_SKN(kSumProfile, true, true); else BSIG_SKN(kSumProfile, true, false); }
+        else    { if (half) BSIG_SKN(kSumProfile, false, true); else BSIG_SKN(kSumProfile, false, false); }
+    } else if (kind == kSumCover) {
+        BSIG_SKN(kSumCover, false, false);
+    } else if (kind == kSumCoverSS) {
+        BSIG_SKN(kSumCoverSS, true, false);
+    }
+#undef BSIG_SKN
+#undef BSIG_SK
+    return hipErrorInvalidValue;
+}
+
+int sum_blocks_per_cu(int kind, int ss, int nw, bool half, int tile_cells)
+{
+    int nb = 0;
+    const size_t lds = sum_tiles_lds(kind, ss, nw, tile_cells);
+    const hipError_t e = with_sum_kernel(kind, ss, nw, half, true, [&](auto k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, nw * kWave, lds);
+    });
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+hipError_t launch_sum_tiles(int kind, int ss, int nw, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
+                            int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int32_t *slab,
+                            hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, kind == kSumProfile ? BSIG_MODE_PROFILE : BSIG_MODE_COVERAGE, items,
+                           (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
+    }
+    const size_t lds = sum_tiles_lds(kind, ss, nw, P.tile_cells);
+    const hipError_t e = with_sum_kernel(kind, ss, nw, P.packed_half != 0, P.resolved != 0, [&](auto k) {
+        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(nw * kWave), lds, st, items, runs, slab, (const uint2 *)windows, R, P);
+        return hipGetLastError();
+    });
+    return e;
+}
+
+hipError_t launch_sum_reduce(bool is_signed, const int32_t *slab, int32_t slab_vals, const BsigSumChunk *chunks, int64_t n_chunks,
+                             int32_t max_nvals, unsigned long long *base, hipStream_t st)
+{
+    if (n_chunks <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((max_nvals + 1023) / 1024), (unsigned)n_chunks);
+    if (is_signed) hipLaunchKernelGGL(k_sum_reduce<true>, grid, dim3(256), 0, st, slab, slab_vals, chunks, base);
+    else hipLaunchKernelGGL(k_sum_reduce<false>, grid, dim3(256), 0, st, slab, slab_vals, chunks, base);
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_scan(long long *base, int32_t width, int32_t tile_cells, int32_t S, hipStream_t st)
+{
+    if (width <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sum_scan, dim3((unsigned)((width + tile_cells - 1) / tile_cells), (unsigned)S), dim3(256), 0, st,
+                       base, width, tile_cells, S);
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_bins(const long long *base, int32_t width, int32_t binsize, int32_t S, int64_t n_out, long long *out, hipStream_t st)
+{
+    if (n_out <= 0) return hipSuccess;
+    if (binsize > 64) hipLaunchKernelGGL(k_sum_bins<true>, dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, st, base, width, binsize, S, n_out, out);
+    else hipLaunchKernelGGL(k_sum_bins<false>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, base, width, binsize, S, n_out, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)

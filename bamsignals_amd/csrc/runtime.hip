@@ -275,6 +275,20 @@ struct bsig_plan {
     uint64_t made_for_gen = 0;          // the layout the plan was made on: its tiles' heavy slices and the packed class's filter
                                         // table are read off that layout, so a plan does not outlive it
     int64_t runs = 0;                   // runs so far (a plan that is run AGAIN is a resident one: plan_two_launches)
+    // a SUM plan (bsig_plan_create_sum): per-base tiles ordered by c0, summed over the ranges by k_sum_tiles
+    bool is_sum = false;
+    int sum_kind = 0, sum_nw = 4, sum_S = 1;
+    int32_t sum_width = 0, sum_binsize = 1;
+    int64_t sum_bins = 0;               // ceil(width / binsize)
+    uint2 *sum_runs = nullptr;          // runs of the main tiles, then those of the heavy slices: [t0, t1) of one c0
+    int64_t n_runs_main = 0, n_runs_heavy = 0;
+    BsigSumChunk *sum_chunks = nullptr;
+    int64_t n_sum_chunks = 0;
+    int32_t sum_max_nvals = 0;
+    int32_t slab_vals = 0;              // int32 per slab (tile_cells * S rounded up to 4)
+    int32_t *slab = nullptr;            // one slab per run
+    long long *sum_base = nullptr;      // per-base sums (binsize > 1; binsize 1 reduces straight into the result)
+    long long *d_sum = nullptr;         // device result of bsig_plan_run_sum_host
 };
 static int64_t g_resolve_min_override = -1;     // bsig_debug_set_knob(4, n): two launches from n tiles on (sweeps)
 // does a run of this plan look its windows up in a launch of its own?  (measured at the north star's read density,
@@ -1334,9 +1348,18 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
 // ---------------------------------------------------------------------------------------------
 // plans
 // ---------------------------------------------------------------------------------------------
-int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
-                     const int32_t *loc, const int32_t *len, const int32_t *strand,
-                     const bsig_params *prm, bsig_plan **out)
+}  // extern "C"
+// what bsig_plan_create_sum asks of a plan beyond the per-base one it is built on
+struct SumSpec {
+    int nw;              // waves per k_sum_tiles workgroup
+    int32_t width;       // every range's width
+    int32_t binsize;     // the caller's bins (the tiles are per base)
+};
+static int sum_setup(bsig_plan *P, const SumSpec &spec, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+// sum: a plan for bsig_plan_create_sum -- its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
+static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
+                            const int32_t *loc, const int32_t *len, const int32_t *strand,
+                            const bsig_params *prm, const SumSpec *sum, bsig_plan **out)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
@@ -1519,6 +1542,8 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
             }
         }
     }
+    // a sum plan adds up all tiles of one c0 (every range has the same width, so also the same nc): consecutive
+    if (sum) std::stable_sort(items.begin(), items.end(), [](const BsigWorkItem &a, const BsigWorkItem &b) { return a.c0 < b.c0; });
     P->n_items = (int64_t)items.size();
     if (P->n_items >= (1ll << 31)) { delete P; return fail(BSIG_ERR_ARG, "too many tiles for one launch"); }
     hipError_t e = hipSetDevice(ctx->device);
@@ -1541,6 +1566,7 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     // (k_coverage's cells are SIGNED 16-bit: +32,768 starts on one cell would not fit; k_coverage_bins' int32 cells
     // need the same ceiling: 32,767 reads adding at most 65,536 each stay below 2^31)
     if (P->kernel_mode == BSIG_MODE_COVERAGE) heavy_reads = std::min<int64_t>(heavy_reads, 32767);
+    std::vector<BsigWorkItem> hitems;
     if (e == hipSuccess && !items.empty()) {
         DevPool tmp;
         uint2 *d_win = nullptr;
@@ -1559,7 +1585,6 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
             e = hipMemcpyAsync(win.data(), d_win, win.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
-        std::vector<BsigWorkItem> hitems;
         std::vector<uint2> hwin;
         if (e == hipSuccess && n_heavy_dev) {
             for (size_t t = 0; t < items.size(); ++t) {
@@ -1601,8 +1626,78 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
         delete P;
         return fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "plan upload failed: %s", hipGetErrorString(e));
     }
+    if (sum) {
+        const int rc = sum_setup(P, *sum, items, hitems);
+        if (rc != BSIG_OK) { delete P; return rc; }
+    }
     *out = P;
     return BSIG_OK;
+}
+// The runs of a sum plan: tiles of one c0 cut into runs of at most `per` (a workgroup each, one slab each), the runs of
+// the heavy slices behind those of the main tiles; chunks of at most kSumChunkSlots slabs of one c0 for k_sum_reduce.
+// `per` fills the chip once (workgroups resident at a time, by occupancy) and never exceeds 65,536 tiles, which keeps
+// every slab exact in 32 bits (k_sum_tiles).
+static int sum_setup(bsig_plan *P, const SumSpec &spec, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems)
+{
+    constexpr int64_t kSumChunkSlots = 32, kMaxRunTiles = 65536;
+    P->is_sum = true;
+    P->sum_nw = spec.nw;
+    P->sum_width = spec.width;
+    P->sum_binsize = spec.binsize;
+    P->sum_S = P->kp.ss ? 2 : 1;
+    P->sum_bins = spec.width > 0 ? ((int64_t)spec.width + spec.binsize - 1) / spec.binsize : 0;
+    P->sum_kind = P->kernel_mode == BSIG_MODE_PROFILE ? 0 : P->kp.ss ? 2 : 1;
+    P->slab_vals = (P->tile_cells * P->sum_S + 3) & ~3;
+    int n_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
+    const int64_t resident = (int64_t)std::max(n_cu, 1) *
+                             bsig::sum_blocks_per_cu(P->sum_kind, P->sum_S == 2, P->sum_nw, P->kp.packed_half != 0, P->tile_cells);
+    const int64_t per = std::min<int64_t>(kMaxRunTiles, std::max<int64_t>(P->sum_nw, (P->n_items + resident - 1) / resident));
+    std::vector<uint2> runs;
+    std::vector<BsigSumChunk> chunks;
+    auto cut = [&](const std::vector<BsigWorkItem> &it) {
+        int64_t chunk_c0 = -1;
+        for (size_t a = 0; a < it.size();) {
+            size_t b = a;
+            while (b < it.size() && it[b].c0 == it[a].c0) ++b;             // the tiles of one c0: [a, b)
+            for (size_t r = a; r < b; r += (size_t)per) {
+                const uint32_t slot = (uint32_t)runs.size();
+                runs.push_back(make_uint2((uint32_t)r, (uint32_t)std::min<size_t>(b, r + (size_t)per)));
+                if (chunk_c0 != it[a].c0 || chunks.back().slot_hi - chunks.back().slot_lo >= kSumChunkSlots) {
+                    chunks.push_back(BsigSumChunk{slot, slot, it[a].c0 * P->sum_S, it[a].nc * P->sum_S});
+                    chunk_c0 = it[a].c0;
+                }
+                chunks.back().slot_hi = slot + 1;
+                P->sum_max_nvals = std::max(P->sum_max_nvals, it[a].nc * P->sum_S);
+            }
+            a = b;
+        }
+    };
+    cut(items);
+    P->n_runs_main = (int64_t)runs.size();
+    cut(hitems);
+    P->n_runs_heavy = (int64_t)runs.size() - P->n_runs_main;
+    P->n_sum_chunks = (int64_t)chunks.size();
+    hipStream_t st = P->ctx->stream;
+    if (!runs.empty()) {
+        HIP_TRY(P->pool.alloc(&P->sum_runs, runs.size()));
+        HIP_TRY(P->pool.alloc(&P->sum_chunks, chunks.size()));
+        HIP_TRY(P->pool.alloc(&P->slab, runs.size() * (size_t)P->slab_vals));
+        HIP_TRY(hipMemcpyAsync(P->sum_runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P->sum_chunks, chunks.data(), chunks.size() * sizeof(BsigSumChunk), hipMemcpyHostToDevice, st));
+    }
+    if (P->sum_binsize != 1 && P->sum_width > 0) HIP_TRY(P->pool.alloc(&P->sum_base, (size_t)P->sum_width * P->sum_S));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BSIG_OK;
+}
+
+extern "C" {
+
+int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
+                     const int32_t *loc, const int32_t *len, const int32_t *strand,
+                     const bsig_params *prm, bsig_plan **out)
+{
+    return plan_create_impl(ctx, reads, n, rid, loc, len, strand, prm, nullptr, out);
 }
 
 const int64_t *bsig_plan_offsets(const bsig_plan *p) { return p ? p->off.data() : nullptr; }
@@ -1612,6 +1707,7 @@ int64_t bsig_plan_cells(const bsig_plan *p) { return p ? p->off.back() : 0; }
 int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1660,6 +1756,7 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1696,6 +1793,7 @@ int bsig::plan_run_host_timed(bsig_plan *p, const HostDest &dst, double *t_kerne
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!dst.flat && !dst.ptrs) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1709,6 +1807,25 @@ int bsig::plan_run_host_timed(bsig_plan *p, const HostDest &dst, double *t_kerne
     rc = bsig::download_to_dest(p->ctx, p->d_out, dst, cells);
     *t_download = since(t1);
     return rc == BSIG_OK ? bsig::plan_check_overflow(p) : rc;
+}
+int bsig::plan_run_sum_host_timed(bsig_plan *p, int64_t *sum_host, double *t_kernels, double *t_download)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    const int64_t cells = bsig_plan_sum_cells(p);
+    if (cells == 0) return BSIG_OK;
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    if (!p->d_sum) HIP_TRY(p->pool.alloc(&p->d_sum, (size_t)cells));
+    const int rc = bsig_plan_run_sum(p, reinterpret_cast<int64_t *>(p->d_sum));
+    if (rc != BSIG_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    *t_kernels = since(t0);
+    const auto t1 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(sum_host, p->d_sum, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    *t_download = since(t1);
+    return BSIG_OK;
 }
 // a run whose slices took a bin past INT32_MAX fails (after the caller's synchronisation: no wait of its own)
 int bsig::plan_check_overflow(bsig_plan *p)
@@ -1724,6 +1841,7 @@ extern "C" {
 int bsig_plan_run_host_async(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1752,7 +1870,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
         bsig_plan_stats &t = p->stats;
         t.n_ranges = p->n_ranges;
         t.n_items = p->n_items;
-        t.cells = p->off.back();
+        t.cells = p->is_sum ? p->sum_bins * p->sum_S : p->off.back();
         t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
         t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
         t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
@@ -1761,10 +1879,11 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
         t.bytes_per_visit_packed = p->kp.packed_half ? 2 : p->kp.use_tlen ? 8 : 4;     // the half-word, or the packed word [+ tlen]
         t.bytes_per_visit_short = p->kp.use_tlen ? 12 : 8;     // span <= 4096: pos + flag/mapq/span in one word [+ tlen]
         t.bytes_per_visit_long = p->kp.use_tlen ? 16 : 12;     // pos + end + flag/mapq [+ tlen]
-        // reads + work items + index entries + result cells
+        // reads + work items + index entries + result cells (a sum plan: 8 B a cell of the sum, none per range)
         const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
         t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
-                              t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items + 4 * t.cells;
+                              t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
+                              (p->is_sum ? 8 : 4) * t.cells;
         if (plan_two_launches(p) && windows_kept()) {
             // a resident plan's step reads the windows kept from its first run: no index entry is touched
             t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
@@ -1780,6 +1899,95 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
 }
 
 void bsig_plan_free(bsig_plan *p) { delete p; }
+
+int bsig_plan_create_sum(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                         const int32_t *len, const int32_t *strand, const bsig_params *prm, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_sum");
+    *out = nullptr;
+    if (n < 0 || (n > 0 && !len)) return fail(BSIG_ERR_ARG, "range arrays missing");
+    if (prm->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
+    if (prm->mode != BSIG_MODE_PROFILE && prm->mode != BSIG_MODE_COVERAGE && prm->mode != BSIG_MODE_COVERAGE_EX)
+        return fail(BSIG_ERR_ARG, "unknown mode %d", prm->mode);
+    for (int64_t i = 1; i < n; ++i)
+        if (len[i] != len[0]) return fail(BSIG_ERR_ARG, "all signals must have the same length");     // alignSignals
+    if (prm->threads != 0 && prm->threads != 64 && prm->threads != 128 && prm->threads != 256)
+        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
+    if (prm->mode == BSIG_MODE_PROFILE && prm->binsize < 1) return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");
+    if (prm->mode == BSIG_MODE_COVERAGE_EX && (prm->binsize < 1 || prm->binsize > bsig::kMaxCoverageBin))
+        return fail(BSIG_ERR_ARG, prm->binsize < 1 ? "provide a binsize greater or equal to 1"
+                                                   : "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
+    // the tiles are per base (bins are summed at the end: binning is linear); mode 2 ignores binsize and ss
+    bsig_params q = *prm;
+    const int32_t binsize = prm->mode == BSIG_MODE_COVERAGE ? 1 : prm->binsize;
+    q.binsize = 1;
+    q.threads = 64;
+    const SumSpec spec{prm->threads > 0 ? prm->threads / 64 : 4, n > 0 ? len[0] : 0, binsize};
+    return plan_create_impl(ctx, reads, n, rid, loc, len, strand, &q, &spec, out);
+}
+
+int64_t bsig_plan_sum_cells(const bsig_plan *p) { return p && p->is_sum ? p->sum_bins * p->sum_S : 0; }
+
+int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->is_sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
+    const int64_t cells = p->sum_bins * p->sum_S;
+    if (cells == 0) return BSIG_OK;
+    if (!sum_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (((uintptr_t)sum_dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
+    if (p->reads->layout_gen != p->made_for_gen)
+        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    const int ss = p->sum_S == 2;
+    if (p->n_runs_main) {
+        // the windows as an ordinary plan looks them up: in the launch (fused), or in a launch of their own, kept
+        if (plan_two_launches(p)) {
+            const bool keep = windows_kept();
+            if (!p->resolved) HIP_TRY(p->pool.alloc(&p->resolved, (size_t)p->n_items));
+            const bool lookup = !keep || p->resolved_gen != p->reads->layout_gen;
+            BsigKParams res = p->kp;
+            res.resolved = 1;
+            HIP_TRY(bsig::launch_sum_tiles(p->sum_kind, ss, p->sum_nw, p->reads->dev, res, p->items, p->n_items, p->sum_runs,
+                                           p->n_runs_main, p->resolved, lookup, p->slab, st));
+            p->resolved_gen = p->reads->layout_gen;
+        } else {
+            HIP_TRY(bsig::launch_sum_tiles(p->sum_kind, ss, p->sum_nw, p->reads->dev, p->kp, p->items, p->n_items, p->sum_runs,
+                                           p->n_runs_main, nullptr, false, p->slab, st));
+        }
+    }
+    // the slices of heavy tiles: one more addend each, with their fixed windows, into slabs of their own
+    if (p->n_runs_heavy)
+        HIP_TRY(bsig::launch_sum_tiles(p->sum_kind, ss, p->sum_nw, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                       p->sum_runs + p->n_runs_main, p->n_runs_heavy, p->heavy_windows, false,
+                                       p->slab + (size_t)p->n_runs_main * (size_t)p->slab_vals, st));
+    long long *base = p->sum_binsize == 1 ? reinterpret_cast<long long *>(sum_dev) : p->sum_base;
+    HIP_TRY(hipMemsetAsync(base, 0, (size_t)p->sum_width * p->sum_S * sizeof(long long), st));
+    HIP_TRY(bsig::launch_sum_reduce(p->sum_kind != 0, p->slab, p->slab_vals, p->sum_chunks, p->n_sum_chunks, p->sum_max_nvals,
+                                    reinterpret_cast<unsigned long long *>(base), st));
+    if (p->sum_kind != 0) HIP_TRY(bsig::launch_sum_scan(base, p->sum_width, p->tile_cells, p->sum_S, st));
+    if (p->sum_binsize != 1)
+        HIP_TRY(bsig::launch_sum_bins(base, p->sum_width, p->sum_binsize, p->sum_S, cells, reinterpret_cast<long long *>(sum_dev), st));
+    ++p->runs;
+    return BSIG_OK;
+}
+
+int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->is_sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
+    const int64_t cells = p->sum_bins * p->sum_S;
+    if (cells == 0) return BSIG_OK;
+    if (!sum_host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    if (!p->d_sum) HIP_TRY(p->pool.alloc(&p->d_sum, (size_t)cells));
+    const int rc = bsig_plan_run_sum(p, reinterpret_cast<int64_t *>(p->d_sum));
+    if (rc != BSIG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(sum_host, p->d_sum, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    return BSIG_OK;
+}
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
 int bsig_debug_new_layout_gen(bsig_reads *reads)

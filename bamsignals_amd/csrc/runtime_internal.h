@@ -230,6 +230,8 @@ int download_slices_to_dest(bsig_ctx *ctx, const int32_t *src_dev, int64_t n_sli
                             const int64_t *cells, const HostDest &dst, int copy_threads);
 // bsig_plan_run_host with the kernels' and the download's seconds told apart (runtime.hip)
 int plan_run_host_timed(bsig_plan *p, const HostDest &dst, double *t_kernels, double *t_download);
+// bsig_plan_run_sum_host with the kernels' and the download's seconds told apart (runtime.hip)
+int plan_run_sum_host_timed(bsig_plan *p, int64_t *sum_host, double *t_kernels, double *t_download);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

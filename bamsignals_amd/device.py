@@ -306,6 +306,52 @@ class Plan:
         self.close()
 
 
+class SumPlan:
+    """Ranges of one width + call parameters resident in HBM, summed over the ranges (bsig_plan_create_sum): each run
+    gives the int64 sum of what ``Plan`` returns for the ranges, cell by cell -- ``n_bins`` cells, or ``2 x n_bins``
+    (cell ``2 * bin + antisense``) with strands.  ``params.threads`` 64 / 128 / 256: tiles in flight per workgroup."""
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params):
+        self._lib = _lib.load()
+        self.ctx, self.reads = ctx, reads
+        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_create_sum(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
+                                                  _ptr(strand), C.byref(params), C.byref(h)))
+        self._h = h
+        self.n_ranges = n
+        self.cells = int(self._lib.bsig_plan_sum_cells(h))
+
+    def run_host(self, out=None):
+        """Run and return the int64 sum in host memory (``out``: a reusable contiguous int64 array of ``cells``)."""
+        if out is None:
+            out = np.empty(self.cells, dtype=np.int64)
+        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
+        _lib.check(self._lib.bsig_plan_run_sum_host(self._h, _ptr(out)))
+        return out
+
+    def run_device(self, out_ptr):
+        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
+        _lib.check(self._lib.bsig_plan_run_sum(self._h, C.c_void_p(out_ptr)))
+
+    def stats(self):
+        s = _lib.PlanStats()
+        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class SegmentMap:
     """Device-side reassembly of sharded results: segment k of a source buffer goes to the destination at
     ``dst_off[which[k]]`` (bsig_segmap_*; the host-side twin is bsig_scatter_segments).  The tables are

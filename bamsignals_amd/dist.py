@@ -97,6 +97,20 @@ def _sharded(kind, bampath, gr, dst, group, **kw):
     mine = shard_indices(ranges["rid"], ranges["loc"], rank, world)
     sub = gr[mine]
     ss = bool(kw.get("ss", False))
+    if kw.get("aggregate", False):
+        # each rank sums its shard; one int64 reduce to dst replaces the gather
+        wrappers._check_equal_widths(gr)
+        fn = wrappers.bamProfile if kind == "profile" else wrappers.bamCoverage
+        w = int(width[0]) if len(width) else 0
+        b = int(kw.get("binsize", 1))
+        n_bins = (w + b - 1) // b if w > 0 else 0
+        shape = (2, n_bins) if ss else (n_bins,)
+        local = fn(bampath, sub, verbose=False, **kw) if len(sub) else np.zeros(shape, np.int64)
+        t = torch.from_numpy(np.ascontiguousarray(local, dtype=np.int64).reshape(-1).copy())
+        if dist.get_backend(group) == "nccl":
+            t = t.cuda()
+        dist.reduce(t, dst=dst, op=dist.ReduceOp.SUM, group=group)
+        return t.cpu().numpy().reshape(shape) if rank == dst else None
     if kind == "count":
         res = wrappers.bamCount(bampath, sub, verbose=False, **kw)
         local = (res.T.reshape(-1) if ss else res).astype(np.int32, copy=False)
@@ -125,11 +139,14 @@ def _sharded(kind, bampath, gr, dst, group, **kw):
 def bamProfile_sharded(bampath, gr, dst=0, group=None, **kw):  # noqa: N802
     """``bamProfile`` over all ranks of the process group (one process per GPU): ranges dealt
     round-robin, every rank reads the BAM, results gathered to ``dst`` (a CountSignals there,
-    ``None`` elsewhere).  Keyword arguments as ``bamProfile`` (without ``verbose``)."""
+    ``None`` elsewhere).  Keyword arguments as ``bamProfile`` (without ``verbose``); ``aggregate=True``: every
+    rank sums its shard and one int64 reduce (SUM) brings the sum to ``dst``."""
     return _sharded("profile", bampath, gr, dst, group, **kw)
 
 
 def bamCount_sharded(bampath, gr, dst=0, group=None, **kw):  # noqa: N802
+    if "aggregate" in kw:
+        raise TypeError("bamCount has no 'aggregate' argument")
     return _sharded("count", bampath, gr, dst, group, **kw)
 
 

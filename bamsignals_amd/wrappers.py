@@ -124,6 +124,57 @@ def pileup_core(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=Fals
     return _split(out, off, ss)
 
 
+def _check_equal_widths(gr):
+    """alignSignals' rule (R/zzzCountSignals.R:99-113): a sum over ranges needs ranges of one width."""
+    w = np.asarray(gr.width)
+    if w.size and np.any(w != w[0]):
+        raise ValueError("all signals must have the same length")
+    return int(w[0]) if w.size else 0
+
+
+def _sum_shape(sums, ss):
+    return sums.reshape(-1, 2).T.copy() if ss else sums
+
+
+def pileup_sum(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False, requiredF=0,
+               filteredF=-1, pe_mid=False, maxgap=16385, device=None):
+    """bamProfile's signals summed over the ranges (bsig_pileup_sum): int64, ``(n_bins,)`` or ``(2, n_bins)``."""
+    _check_gr(gr)
+    w = _check_equal_widths(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    n = len(gr)
+    n_bins = (w + int(binsize) - 1) // int(binsize) if n and w > 0 else 0
+    out = np.zeros(n_bins * (2 if ss else 1), dtype=np.int64)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_pileup_sum(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels),
+                                   names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
+                                   tf.ctypes.data, len(tf), int(mapqual), int(binsize), int(shift),
+                                   int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
+                                   int(maxgap), _dev(device), out.ctypes.data))
+    return _sum_shape(out, ss)
+
+
+def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
+                 maxgap=16385, device=None, *, binsize=1, ss=False):
+    """bamCoverage's signals summed over the ranges (bsig_coverage_sum): int64, ``(n_bins,)`` or ``(2, n_bins)``."""
+    _check_gr(gr)
+    w = _check_equal_widths(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    n = len(gr)
+    n_bins = (w + int(binsize) - 1) // int(binsize) if n and w > 0 else 0
+    out = np.zeros(n_bins * (2 if ss else 1), dtype=np.int64)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_coverage_sum(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names,
+                                     start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
+                                     int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap),
+                                     _dev(device), int(binsize), int(bool(ss)), out.ctypes.data))
+    return _sum_shape(out, ss)
+
+
 def _is_ex(binsize, ss):
     """bins or strands take bsig_coverage_core_ex[_into]; the defaults keep the reference's own entry point"""
     return int(binsize) != 1 or bool(ss)
@@ -237,18 +288,29 @@ def bamCount(bampath, gr, mapqual=0, shift=0, ss=False, paired_end=("ignore", "f
 
 
 def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N802
-               paired_end=("ignore", "filter", "midpoint"), tlenFilter=None, filteredFlag=-1, verbose=True):  # noqa: N803
+               paired_end=("ignore", "filter", "midpoint"), tlenFilter=None, filteredFlag=-1, verbose=True,  # noqa: N803
+               *, aggregate=False):
     """For each base pair (or bin) of the ranges, the number of reads whose 5' end maps there
-    (R/wrappers.R:124-151).  Returns a CountSignals."""
+    (R/wrappers.R:124-151).  Returns a CountSignals.
+
+    ``aggregate=True``: ranges of one width only; returns the int64 sum over the ranges of their signals, cell by
+    cell -- ``np.asarray(sig.alignSignals(), np.int64).sum(axis=-1)`` of the CountSignals above, shape ``(n_bins,)``
+    or ``(2, n_bins)`` with ``ss`` -- computed on the GPU without the per-range result.  The metaprofile (the
+    vignette's rowMeans of alignSignals) is this divided by ``len(gr)``."""
     if verbose:
         _print_sentence(bampath)
     if binsize < 1:
         raise ValueError("provide a binsize greater or equal to 1")
     _check_gr(gr)
+    if aggregate:
+        _check_equal_widths(gr)
     if binsize > 1 and np.any(gr.width % binsize != 0):
         warnings.warn("some ranges' widths are not a multiple of the selected\n"
                       "             binsize, some bins will correspond to less than binsize basepairs")
     pe = _match_arg(paired_end, ("ignore", "filter", "midpoint"), "paired.end")
+    if aggregate:
+        return pileup_sum(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
+                          int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
     pu = pileup_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                      int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
     return CountSignals(pu, bool(ss), _trusted=True)
@@ -272,7 +334,7 @@ def _coverage_binsize(binsize):
 
 
 def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFilter=None,  # noqa: N802,N803
-                filteredFlag=-1, verbose=True, *, binsize=1, ss=False):
+                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False):
     """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173).
 
     ``binsize`` (1 .. 65,536): bin j of a range covers its bases [j*binsize, min((j+1)*binsize, width)) in range
@@ -282,15 +344,21 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     ``ss=True``: each signal is a 2 x n_bins matrix, row 0 (sense) the coverage by reads on the range's strand
     ('*' counts as '+'), row 1 (antisense) by the others; with ``paired_end="extend"`` the whole fragment counts on
     the strand of the read that passed the flag mask (the first mate).  sense + antisense is the unstranded result.
-    A bin whose sum would exceed 2^31 - 1 raises BsigError.  The defaults are the reference's call."""
+    A bin whose sum would exceed 2^31 - 1 raises BsigError.  The defaults are the reference's call.
+    ``aggregate=True``: the int64 sum over ranges of one width, as in ``bamProfile``."""
     if verbose:
         _print_sentence(bampath)
     b = _coverage_binsize(binsize)
     _check_gr(gr)
+    if aggregate:
+        _check_equal_widths(gr)
     if b > 1 and np.any(gr.width % b != 0):
         warnings.warn("some ranges' widths are not a multiple of the selected\n"
                       "             binsize, some bins will correspond to less than binsize basepairs")
     pe = _match_arg(paired_end, ("ignore", "extend"), "paired.end")
+    if aggregate:
+        return coverage_sum(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
+                            flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
     pu = coverage_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                        flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
     return CountSignals(pu, bool(ss), _trusted=True)

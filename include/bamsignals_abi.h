@@ -211,6 +211,21 @@ int bsig_plan_run_host_async(bsig_plan *plan, int32_t *out_host);
 int bsig_plan_overflowed(bsig_plan *plan, int32_t *flag);
 void bsig_plan_free(bsig_plan *plan);
 
+/* Sums over ranges (the metaprofile: rowMeans(alignSignals(sigs)) without the per-range result, ref:
+ * R/zzzCountSignals.R:99-113).  Every range must have the same width w (else BSIG_ERR_ARG, "all signals must have
+ * the same length"); the result is n_bins = ceil(w / binsize) int64 cells, 2 * bin + antisense with ss -- cell by
+ * cell the sum over all ranges of what bsig_plan_create's plan returns for them, in range orientation.  mode:
+ * BSIG_MODE_PROFILE, BSIG_MODE_COVERAGE (binsize and ss ignored) or BSIG_MODE_COVERAGE_EX; BSIG_MODE_COUNT fails with
+ * BSIG_ERR_ARG.  threads 64 / 128 / 256 = 1 / 2 / 4 tiles in flight per workgroup (0: 4).  A sum plan runs with
+ * bsig_plan_run_sum* only, an ordinary plan never does (BSIG_ERR_ARG); bsig_plan_get_stats counts 8 B per sum cell
+ * and none per range.                                                                                              */
+int bsig_plan_create_sum(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                         const int32_t *len, const int32_t *strand, const bsig_params *params, bsig_plan **plan);
+int64_t bsig_plan_sum_cells(const bsig_plan *plan);              /* n_bins * (ss ? 2 : 1)                       */
+/* asynchronous, on the context's stream; sum_dev: bsig_plan_sum_cells() int64 on the device, 8-B aligned           */
+int bsig_plan_run_sum(bsig_plan *plan, int64_t *sum_dev);
+int bsig_plan_run_sum_host(bsig_plan *plan, int64_t *sum_host);
+
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
 int bsig_pileup_columns(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
                         const int32_t *rid, const int32_t *loc, const int32_t *len,
@@ -343,6 +358,22 @@ int bsig_coverage_core_ex_into(const char *bampath, int64_t n_ranges, const int3
                                const int32_t *tlen_filter, int32_t n_tlen_filter,
                                int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                                int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *const *dst);
+/* The file-level calls summed over ranges of one width (bsig_plan_create_sum): sum receives n_bins * (ss ? 2 : 1)
+ * int64 cells.  With several GPUs each sums its block of the (rid, loc)-sorted ranges and the host adds the
+ * vectors; no per-range cell is gathered (bsig_last_call_route() then says "sum").                              */
+int bsig_pileup_sum(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                    const int32_t *width, const int32_t *strand,
+                    const int32_t *tlen_filter, int32_t n_tlen_filter,
+                    int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss,
+                    int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t maxgap,
+                    int32_t device, int64_t *sum);
+int bsig_coverage_sum(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                      int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                      const int32_t *width, const int32_t *strand,
+                      const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                      int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
