@@ -632,7 +632,6 @@ bool regions_covered(const Resident &R, int64_t n, const int32_t *rid, const int
     return true;
 }
 
-// the common body of pileup_core / coverage_core
 // A sum over ranges of one width (bsig_pileup_sum / bsig_coverage_sum): one GPU sums them all; with several, each sums
 // its block of the (rid, loc)-sorted ranges and the host adds the int64 vectors -- no per-range cell leaves a GPU
 int sum_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
@@ -645,7 +644,7 @@ int sum_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, c
         bsig_plan *plan = nullptr;
         int rc = bsig_plan_create_sum(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, &plan);
         X[3] = now_s() - t0;
-        if (rc == BSIG_OK) rc = bsig::plan_run_sum_host_timed(plan, sum, &X[4], &X[5]);
+        if (rc == BSIG_OK) rc = bsig::plan_run_to_host(plan, nullptr, sum, false, &X[4], &X[5]);
         if (plan) bsig_plan_free(plan);
         route = "sum";
         return rc;
@@ -677,26 +676,30 @@ int sum_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, c
     return BSIG_OK;
 }
 
+// Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
+// layout is one vector, dst[0]), or the sum over the ranges
+struct FileDest {
+    int32_t *out = nullptr;
+    const int64_t *off = nullptr;
+    int32_t *const *dst = nullptr;
+    int64_t *sum = nullptr;
+};
+
 int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                const char *const *levels, const int32_t *start, const int32_t *width,
-               const int32_t *strand, const bsig_params &prm, int32_t device, const bsig::HostDest &dest,
-               int64_t *sum = nullptr)
+               const int32_t *strand, const bsig_params &prm, int32_t device, const FileDest &to)
 {
     if (!bampath) return fail(BSIG_ERR_ARG, "bampath is NULL");
     if (n < 0 || (n > 0 && (!seq_code || !start || !width || !strand || !levels)))
         return fail(BSIG_ERR_ARG, "range arrays missing");
-    const int64_t *off = dest.off;
-    if (!off && !sum) return fail(BSIG_ERR_ARG, "offsets missing");
-    int64_t sum_cells = 0;
+    if (!to.off && !to.dst && !to.sum) return fail(BSIG_ERR_ARG, "offsets missing");
+    int64_t *sum = to.sum;
+    bsig::SumShape shape{};
     if (sum) {
-        // the sum's own checks, before any I/O
-        if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
-        for (int64_t i = 1; i < n; ++i)
-            if (width[i] != width[0]) return fail(BSIG_ERR_ARG, "all signals must have the same length");
-        const int64_t b = prm.mode == BSIG_MODE_COVERAGE ? 1 : std::max<int32_t>(prm.binsize, 1);
-        const bool ss2 = prm.mode != BSIG_MODE_COVERAGE && prm.ss;
-        sum_cells = n > 0 && width[0] > 0 ? ((int64_t)width[0] + b - 1) / b * (ss2 ? 2 : 1) : 0;
-        for (int64_t c = 0; c < sum_cells; ++c) sum[c] = 0;
+        // the sum's own conditions, before any I/O
+        const int rc = bsig::sum_shape(prm, n, width, &shape);
+        if (rc) return rc;
+        std::fill(sum, sum + shape.cells, (int64_t)0);
     }
     double *T = g_call_timing, *X = g_call_timing_ex;
     for (int k = 0; k < 6; ++k) T[k] = 0;
@@ -750,20 +753,23 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
             return fail(BSIG_ERR_CHROM, "chromosome %s not present in the bam file", levels[c]);   // ref: :119
         rid[(size_t)i] = level_rid[(size_t)c];
         loc[(size_t)i] = start[i] - 1;                          // ref: :131
-        if (width[i] < 0) return fail(BSIG_ERR_ARG, "range %lld has a negative width", (long long)i);
     }
-    // same argument checks as bsig_plan_create, before any I/O
-    const bool cov = prm.mode == BSIG_MODE_COVERAGE || prm.mode == BSIG_MODE_COVERAGE_EX;
-    const bool mid = !cov && prm.pe_mid;
-    const bool tspan = cov && prm.tspan;
-    if ((mid || tspan) && prm.n_tlen_filter != 2)
-        return fail(BSIG_ERR_ARG, "paired-end midpoint/extend needs a 2-element tlen_filter");
-    if (prm.mode == BSIG_MODE_COVERAGE_EX && (prm.binsize < 1 || prm.binsize > bsig::kMaxCoverageBin))
-        return fail(BSIG_ERR_ARG, prm.binsize < 1 ? "provide a binsize greater or equal to 1"
-                                                  : "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
-    int64_t ext = cov ? (tspan ? prm.tlen_filter[1] : 0)
-                      : std::llabs((long long)prm.shift) + (mid ? prm.tlen_filter[1] : 0);
-    if (ext < 0) return fail(BSIG_ERR_EXT, "negative 'ext' values don't make sense");             // ref: :243
+    // bsig_plan_create's rule, before any decode
+    bsig::PlanRule rule;
+    rc = bsig::check_params(prm, n, width, &rule);
+    if (rc) return rc;
+    const int64_t ext = rule.ext;
+    bsig::HostDest dest;
+    std::vector<int64_t> own_off;
+    dest.flat = to.out; dest.off = to.off; dest.n = n;
+    if (to.dst) {
+        // in place: the layout is computed here
+        own_off.resize((size_t)n + 1);
+        bsig_layout(n, width, rule.lay_binsize, rule.ss, own_off.data());
+        dest.off = own_off.data();
+        if (rule.mode == BSIG_MODE_COUNT) dest.flat = to.dst[0]; else dest.ptrs = to.dst;
+    }
+    const int64_t *off = dest.off;
 
     // the GPUs of this call: every device list seen keeps its own contexts, scratch and resident BAMs (a
     // session that alternates between two device= arguments keeps both copies; the LRU budget bounds them)
@@ -989,7 +995,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     for (int attempt = 0; attempt < 2; ++attempt) {
     if (attempt) drop_spare_device_memory(slots.get());        // (out of device memory: once more with the cache's spare memory given back)
     if (sum) {
-        rc = sum_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, sum_cells, sum, X, gather);
+        rc = sum_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, shape.cells, sum, X, gather);
     } else if (!many) {
         // plan (ranges -> tiles in HBM), kernels, download -- timed apart
         bsig_plan *plan = nullptr;
@@ -997,7 +1003,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         X[3] = now_s() - t_run;
         if (rc == BSIG_OK && memcmp(off, bsig_plan_offsets(plan), (size_t)(n + 1) * sizeof(int64_t)) != 0)
             rc = fail(BSIG_ERR_ARG, "offsets do not match bsig_layout() for these parameters");
-        if (rc == BSIG_OK) rc = bsig::plan_run_host_timed(plan, dest, &X[4], &X[5]);
+        if (rc == BSIG_OK) rc = bsig::plan_run_to_host(plan, &dest, nullptr, false, &X[4], &X[5]);
         if (plan) bsig_plan_free(plan);
     } else {
         rc = run_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, dest, gather);
@@ -1176,40 +1182,36 @@ void bsig_bam_decode_timing(double *t6)
     for (int k = 0; k < 6; ++k) t6[k] = bsig::g_decode_timing[k];
 }
 
-static int pileup_core_impl(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
-                            const char *const *levels, const int32_t *start, const int32_t *width,
-                            const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
-                            int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss, int32_t requiredF,
-                            int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int32_t *out,
-                            const int64_t *off, int32_t *const *dst, int64_t *sum = nullptr)
+}  // extern "C"
+namespace {
+// The reference's two argument lists as bsig_params.  At most two filter values are copied: check_params judges their count.
+bsig_params with_filter(bsig_params p, const int32_t *tlen_filter, int32_t n_tlen_filter)
 {
-    (void)maxgap;
-    bsig_params p;
-    memset(&p, 0, sizeof p);
+    p.n_tlen_filter = n_tlen_filter;
+    for (int k = 0; k < std::min(n_tlen_filter, 2); ++k) p.tlen_filter[k] = tlen_filter[k];
+    return p;
+}
+bsig_params pileup_params(const int32_t *tlen_filter, int32_t n_tlen_filter, int32_t mapqual, int32_t binsize, int32_t shift,
+                          int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid)
+{
+    bsig_params p{};
     p.mode = binsize <= 0 ? BSIG_MODE_COUNT : BSIG_MODE_PROFILE;   // ref: allocateList :148
     p.mapqual = mapqual; p.binsize = binsize; p.shift = shift; p.ss = ss;
     p.requiredF = requiredF; p.filteredF = filteredF; p.pe_mid = pe_mid;
-    if (n_tlen_filter != 0 && n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "tlen_filter must have 0 or 2 elements");
-    p.n_tlen_filter = n_tlen_filter;
-    for (int k = 0; k < n_tlen_filter; ++k) p.tlen_filter[k] = tlen_filter[k];
-    bsig::HostDest D;
-    std::vector<int64_t> own_off;
-    if (sum) {
-        if (binsize <= 0) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
-        return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, D, sum);
-    }
-    if (dst) {
-        // in place: the layout is computed here (bsig_layout); bamCount's is one vector, dst[0]
-        if (n < 0 || (n > 0 && !width)) return fail(BSIG_ERR_ARG, "range arrays missing");
-        own_off.resize((size_t)n + 1);
-        bsig_layout(n, width, binsize, ss, own_off.data());
-        D.off = own_off.data(); D.n = n;
-        if (binsize <= 0) D.flat = dst[0]; else D.ptrs = dst;
-    } else {
-        D.flat = out; D.off = off; D.n = n;
-    }
-    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, D);
+    return with_filter(p, tlen_filter, n_tlen_filter);
 }
+// ex: bins and strands (BSIG_MODE_COVERAGE_EX); without, binsize and ss are not read
+bsig_params coverage_params(const int32_t *tlen_filter, int32_t n_tlen_filter, int32_t mapqual, int32_t requiredF,
+                            int32_t filteredF, int32_t tspan, bool ex = false, int32_t binsize = 1, int32_t ss = 0)
+{
+    bsig_params p{};
+    p.mode = ex ? BSIG_MODE_COVERAGE_EX : BSIG_MODE_COVERAGE;
+    p.mapqual = mapqual; p.binsize = ex ? binsize : 1; p.requiredF = requiredF; p.filteredF = filteredF; p.tspan = tspan;
+    p.ss = ex && ss;
+    return with_filter(p, tlen_filter, n_tlen_filter);
+}
+}  // namespace
+extern "C" {
 
 int bsig_pileup_core(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                      const char *const *levels, const int32_t *start, const int32_t *width,
@@ -1218,8 +1220,8 @@ int bsig_pileup_core(const char *bampath, int64_t n, const int32_t *seq_code, in
                      int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int32_t *out,
                      const int64_t *off)
 {
-    return pileup_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual, binsize,
-                            shift, ss, requiredF, filteredF, pe_mid, maxgap, device, out, off, nullptr);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device, {out, off});
 }
 
 int bsig_pileup_core_into(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1229,39 +1231,9 @@ int bsig_pileup_core_into(const char *bampath, int64_t n, const int32_t *seq_cod
                           int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int32_t *const *dst)
 {
     if (!dst) return fail(BSIG_ERR_ARG, "destinations missing");
-    return pileup_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual, binsize,
-                            shift, ss, requiredF, filteredF, pe_mid, maxgap, device, nullptr, nullptr, dst);
-}
-
-static int coverage_core_impl(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
-                              const char *const *levels, const int32_t *start, const int32_t *width,
-                              const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
-                              int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
-                              int32_t maxgap, int32_t device, int32_t *out, const int64_t *off, int32_t *const *dst,
-                              bool ex = false, int32_t binsize = 1, int32_t ss = 0, int64_t *sum = nullptr)
-{
-    (void)maxgap;
-    bsig_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = ex ? BSIG_MODE_COVERAGE_EX : BSIG_MODE_COVERAGE;
-    p.mapqual = mapqual; p.binsize = ex ? binsize : 1; p.requiredF = requiredF; p.filteredF = filteredF; p.tspan = tspan;
-    p.ss = ex && ss;
-    if (n_tlen_filter != 0 && n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "tlen_filter must have 0 or 2 elements");
-    p.n_tlen_filter = n_tlen_filter;
-    for (int k = 0; k < n_tlen_filter; ++k) p.tlen_filter[k] = tlen_filter[k];
-    bsig::HostDest D;
-    std::vector<int64_t> own_off;
-    if (sum) return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, D, sum);
-    if (dst) {
-        if (n < 0 || (n > 0 && !width)) return fail(BSIG_ERR_ARG, "range arrays missing");
-        // (a binsize outside 1 .. 65,536 fails in file_level before any I/O; the layout only needs it >= 1 here)
-        own_off.resize((size_t)n + 1);
-        bsig_layout(n, width, std::max<int32_t>(p.binsize, 1), p.ss, own_off.data());
-        D.off = own_off.data(); D.n = n; D.ptrs = dst;
-    } else {
-        D.flat = out; D.off = off; D.n = n;
-    }
-    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, D);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device,
+                      {nullptr, nullptr, dst});
 }
 
 int bsig_coverage_core(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1270,8 +1242,8 @@ int bsig_coverage_core(const char *bampath, int64_t n, const int32_t *seq_code, 
                        int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                        int32_t maxgap, int32_t device, int32_t *out, const int64_t *off)
 {
-    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
-                              requiredF, filteredF, tspan, maxgap, device, out, off, nullptr);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device, {out, off});
 }
 
 int bsig_coverage_core_into(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1281,8 +1253,8 @@ int bsig_coverage_core_into(const char *bampath, int64_t n, const int32_t *seq_c
                             int32_t maxgap, int32_t device, int32_t *const *dst)
 {
     if (!dst) return fail(BSIG_ERR_ARG, "destinations missing");
-    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
-                              requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, dst);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device, {nullptr, nullptr, dst});
 }
 
 int bsig_coverage_core_ex(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1291,8 +1263,9 @@ int bsig_coverage_core_ex(const char *bampath, int64_t n, const int32_t *seq_cod
                           int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                           int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *out, const int64_t *off)
 {
-    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
-                              requiredF, filteredF, tspan, maxgap, device, out, off, nullptr, true, binsize, ss);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device,
+                      {out, off});
 }
 
 int bsig_coverage_core_ex_into(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1302,8 +1275,9 @@ int bsig_coverage_core_ex_into(const char *bampath, int64_t n, const int32_t *se
                                int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *const *dst)
 {
     if (!dst) return fail(BSIG_ERR_ARG, "destinations missing");
-    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
-                              requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, dst, true, binsize, ss);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device,
+                      {nullptr, nullptr, dst});
 }
 
 int bsig_pileup_sum(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1313,8 +1287,9 @@ int bsig_pileup_sum(const char *bampath, int64_t n, const int32_t *seq_code, int
                     int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int64_t *sum)
 {
     if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
-    return pileup_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual, binsize,
-                            shift, ss, requiredF, filteredF, pe_mid, maxgap, device, nullptr, nullptr, nullptr, sum);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device,
+                      {nullptr, nullptr, nullptr, sum});
 }
 
 int bsig_coverage_sum(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1324,8 +1299,9 @@ int bsig_coverage_sum(const char *bampath, int64_t n, const int32_t *seq_code, i
                       int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum)
 {
     if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
-    return coverage_core_impl(bampath, n, seq_code, n_levels, levels, start, width, strand, tlen_filter, n_tlen_filter, mapqual,
-                              requiredF, filteredF, tspan, maxgap, device, nullptr, nullptr, nullptr, true, binsize, ss, sum);
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device,
+                      {nullptr, nullptr, nullptr, sum});
 }
 
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath)

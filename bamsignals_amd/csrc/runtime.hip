@@ -244,6 +244,22 @@ void block_cache_release()
 }
 }  // namespace bsig
 
+namespace { enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 }; }      // launch_sum_tiles' kinds (kernels.h)
+// a SUM plan's own (bsig_plan_create_sum): per-base tiles ordered by c0, summed over the ranges by k_sum_tiles
+struct SumState {
+    bsig::SumShape shape;
+    int kind = kSumProfile, S = 1;
+    uint2 *runs = nullptr;              // runs of the main tiles, then those of the heavy slices: [t0, t1) of one c0
+    int64_t n_runs_main = 0, n_runs_heavy = 0;
+    BsigSumChunk *chunks = nullptr;
+    int64_t n_chunks = 0;
+    int32_t max_nvals = 0;
+    int32_t slab_vals = 0;              // int32 per slab (tile_cells * S rounded up to 4)
+    int32_t *slab = nullptr;            // one slab per run
+    long long *base = nullptr;          // per-base sums (binsize > 1; binsize 1 reduces straight into the result)
+    int64_t *d_sum = nullptr;           // device result of bsig_plan_run_sum_host
+};
+
 struct bsig_plan {
     bsig_ctx *ctx = nullptr;
     const bsig_reads *reads = nullptr;
@@ -266,8 +282,8 @@ struct bsig_plan {
     // one workgroup's share, wide bins) or by no work item at all (zero-width ranges), so the result must
     // be zeroed in front of the launch.  Ranges of one tile store their counters themselves.
     bool needs_zero = false;
-    bool have_stats = false;
-    bsig_plan_stats stats{};
+    bool have_visits = false;
+    unsigned long long visits[BSIG_MAX_CLASSES + 1] = {};      // k_visits' counts (bsig_plan_get_stats), taken once
     uint8_t *ptab = nullptr;            // the packed class's filter table for kp (BsigKParams::ptab)
     int32_t *overflow = nullptr;        // binned coverage with heavy slices: 1 if a run's atomic adds took a bin past INT32_MAX
     BsigResolved *resolved = nullptr;   // large launches: the windows of every tile, written by k_resolve_tiles
@@ -275,20 +291,7 @@ struct bsig_plan {
     uint64_t made_for_gen = 0;          // the layout the plan was made on: its tiles' heavy slices and the packed class's filter
                                         // table are read off that layout, so a plan does not outlive it
     int64_t runs = 0;                   // runs so far (a plan that is run AGAIN is a resident one: plan_two_launches)
-    // a SUM plan (bsig_plan_create_sum): per-base tiles ordered by c0, summed over the ranges by k_sum_tiles
-    bool is_sum = false;
-    int sum_kind = 0, sum_nw = 4, sum_S = 1;
-    int32_t sum_width = 0, sum_binsize = 1;
-    int64_t sum_bins = 0;               // ceil(width / binsize)
-    uint2 *sum_runs = nullptr;          // runs of the main tiles, then those of the heavy slices: [t0, t1) of one c0
-    int64_t n_runs_main = 0, n_runs_heavy = 0;
-    BsigSumChunk *sum_chunks = nullptr;
-    int64_t n_sum_chunks = 0;
-    int32_t sum_max_nvals = 0;
-    int32_t slab_vals = 0;              // int32 per slab (tile_cells * S rounded up to 4)
-    int32_t *slab = nullptr;            // one slab per run
-    long long *sum_base = nullptr;      // per-base sums (binsize > 1; binsize 1 reduces straight into the result)
-    long long *d_sum = nullptr;         // device result of bsig_plan_run_sum_host
+    std::unique_ptr<SumState> sum;      // a sum plan's (bsig_plan_create_sum), else null
 };
 static int64_t g_resolve_min_override = -1;     // bsig_debug_set_knob(4, n): two launches from n tiles on (sweeps)
 // does a run of this plan look its windows up in a launch of its own?  (measured at the north star's read density,
@@ -1349,51 +1352,79 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
 // plans
 // ---------------------------------------------------------------------------------------------
 }  // extern "C"
-// what bsig_plan_create_sum asks of a plan beyond the per-base one it is built on
-struct SumSpec {
-    int nw;              // waves per k_sum_tiles workgroup
-    int32_t width;       // every range's width
-    int32_t binsize;     // the caller's bins (the tiles are per base)
-};
-static int sum_setup(bsig_plan *P, const SumSpec &spec, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+// The one rule for a plan's parameters: bsig_plan_create and bsig_plan_create_sum apply it, and the file-level calls
+// before any decode.  Of several faults the first in this order is reported: the mode; the binsize (profile >= 1,
+// coverage_ex 1 .. 65,536); the tlen filter's arity; midpoint / extend without a filter; ext < 0; ext > 2^30; threads;
+// a negative width.
+int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out)
+{
+    // coverage with bins / strands IS coverage from here on (the result layout, ext, tspan, the heavy-tile ceiling);
+    // only binsize, ss and cov_ex tell it apart (mode 2 ignores binsize and ss)
+    PlanRule r;
+    r.cov_ex = prm.mode == BSIG_MODE_COVERAGE_EX;
+    r.mode = r.cov_ex ? BSIG_MODE_COVERAGE : prm.mode;
+    if (r.mode != BSIG_MODE_PROFILE && r.mode != BSIG_MODE_COUNT && r.mode != BSIG_MODE_COVERAGE)
+        return fail(BSIG_ERR_ARG, "unknown mode %d", r.mode);
+    if ((r.mode == BSIG_MODE_PROFILE || r.cov_ex) && prm.binsize < 1)
+        return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");       // ref: R/wrappers.R:136-137
+    if (r.cov_ex && prm.binsize > kMaxCoverageBin)
+        return fail(BSIG_ERR_ARG, "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
+    if (prm.n_tlen_filter != 0 && prm.n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "tlen_filter must have 0 or 2 elements");
+    r.mid = r.mode != BSIG_MODE_COVERAGE && prm.pe_mid;
+    r.tspan = r.mode == BSIG_MODE_COVERAGE && prm.tspan;
+    if ((r.mid || r.tspan) && prm.n_tlen_filter != 2)
+        return fail(BSIG_ERR_ARG, "paired-end midpoint/extend needs a 2-element tlen_filter");
+    // ext: ref src/bamsignals.cpp:457 (pileup) and :487 (coverage); :243 rejects negatives
+    if (r.mode == BSIG_MODE_COVERAGE) r.ext = r.tspan ? prm.tlen_filter[1] : 0;
+    else r.ext = std::llabs((long long)prm.shift) + (r.mid ? (int64_t)prm.tlen_filter[1] : 0);
+    if (r.ext < 0) return fail(BSIG_ERR_EXT, "negative 'ext' values don't make sense");
+    if (r.ext > (1ll << 30)) return fail(BSIG_ERR_ARG, "shift / tlen filter too large");
+    r.threads = prm.threads != 0 ? prm.threads : 64;
+    if (r.threads != 64 && r.threads != 128 && r.threads != 256) return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
+    for (int64_t i = 0; i < n; ++i)
+        if (len[i] < 0) return fail(BSIG_ERR_ARG, "range %lld has a negative width", (long long)i);
+    r.binsize = r.mode == BSIG_MODE_PROFILE || r.cov_ex ? prm.binsize : 1;
+    r.ss = (r.mode != BSIG_MODE_COVERAGE || r.cov_ex) && prm.ss != 0;
+    r.lay_binsize = r.mode == BSIG_MODE_COUNT ? -1 : r.binsize;
+    *out = r;
+    return BSIG_OK;
+}
+
+// What only a sum over ranges asks, ahead of check_params: no bamCount, ranges of one width.  The sum is built on per-base
+// tiles; mode 2 ignores binsize and ss.
+int bsig::sum_shape(const bsig_params &prm, int64_t n, const int32_t *len, SumShape *out)
+{
+    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
+    for (int64_t i = 1; i < n; ++i)
+        if (len[i] != len[0]) return fail(BSIG_ERR_ARG, "all signals must have the same length");     // alignSignals
+    SumShape s;
+    s.tiles = prm;
+    s.tiles.binsize = 1;
+    s.tiles.threads = 64;
+    s.width = n > 0 ? len[0] : 0;
+    s.binsize = prm.mode == BSIG_MODE_COVERAGE ? 1 : prm.binsize;
+    s.nw = prm.threads > 0 ? prm.threads / 64 : 4;
+    const int64_t S = prm.mode != BSIG_MODE_COVERAGE && prm.ss ? 2 : 1;
+    // (a binsize below 1 fails check_params: no cells)
+    s.cells = s.width > 0 && s.binsize > 0 ? ((int64_t)s.width + s.binsize - 1) / s.binsize * S : 0;
+    *out = s;
+    return BSIG_OK;
+}
+
+static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
 // sum: a plan for bsig_plan_create_sum -- its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
 static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
                             const int32_t *loc, const int32_t *len, const int32_t *strand,
-                            const bsig_params *prm, const SumSpec *sum, bsig_plan **out)
+                            const bsig_params *prm, const bsig::SumShape *sum, bsig_plan **out)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
     if (n < 0 || (n > 0 && (!rid || !loc || !len || !strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
-    if (prm->mode == BSIG_MODE_COVERAGE_EX && (prm->binsize < 1 || prm->binsize > bsig::kMaxCoverageBin))
-        return fail(BSIG_ERR_ARG, prm->binsize < 1 ? "provide a binsize greater or equal to 1"
-                                                   : "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
-    // coverage with bins / strands IS coverage from here on (the result layout, ext, tspan, the heavy-tile ceiling);
-    // only cov_bin and cov_ss tell it apart (mode 2 ignores binsize and ss)
-    const bool cov_ex = prm->mode == BSIG_MODE_COVERAGE_EX;
-    const int mode = cov_ex ? BSIG_MODE_COVERAGE : prm->mode;
-    const int32_t cov_bin = cov_ex ? prm->binsize : 1;
-    const bool cov_ss = cov_ex && prm->ss != 0;
-    if (mode != BSIG_MODE_PROFILE && mode != BSIG_MODE_COUNT && mode != BSIG_MODE_COVERAGE)
-        return fail(BSIG_ERR_ARG, "unknown mode %d", mode);
-    if (mode == BSIG_MODE_PROFILE && prm->binsize < 1)
-        return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");       // ref: R/wrappers.R:136-137
-    if (prm->n_tlen_filter != 0 && prm->n_tlen_filter != 2)
-        return fail(BSIG_ERR_ARG, "tlen_filter must have 0 or 2 elements");
-    const bool mid = mode != BSIG_MODE_COVERAGE && prm->pe_mid;
-    const bool tspan = mode == BSIG_MODE_COVERAGE && prm->tspan;
-    if ((mid || tspan) && prm->n_tlen_filter != 2)
-        return fail(BSIG_ERR_ARG, "paired-end midpoint/extend needs a 2-element tlen_filter");
-    // ext: ref src/bamsignals.cpp:457 (pileup) and :487 (coverage); :243 rejects negatives
-    int64_t ext;
-    if (mode == BSIG_MODE_COVERAGE) ext = tspan ? prm->tlen_filter[1] : 0;
-    else ext = std::llabs((long long)prm->shift) + (mid ? (int64_t)prm->tlen_filter[1] : 0);
-    if (ext < 0) return fail(BSIG_ERR_EXT, "negative 'ext' values don't make sense");
-    if (ext > (1ll << 30)) return fail(BSIG_ERR_ARG, "shift / tlen filter too large");
-    for (int64_t i = 0; i < n; ++i) {
-        if (rid[i] < 0 || rid[i] >= reads->n_ref)
-            return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", rid[i]);
-        if (len[i] < 0) return fail(BSIG_ERR_ARG, "range %lld has a negative width", (long long)i);
-    }
+    bsig::PlanRule r;
+    if (const int rc = bsig::check_params(*prm, n, len, &r)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (rid[i] < 0 || rid[i] >= reads->n_ref) return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", rid[i]);
+    const int mode = r.mode;
 
     bsig_plan *P = new bsig_plan;
     P->ctx = ctx; P->reads = reads; P->mode = mode; P->n_ranges = n;
@@ -1402,33 +1433,26 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // workgroups per CU), else 2048-cell tiles
     int64_t widest = 64;
     // (binned profiles and binned / strand-split coverage size their tiles by one rule)
-    const bool binned = mode == BSIG_MODE_PROFILE || cov_ex;
-    const bool split_ss = binned && prm->ss;
-    {
-        const int64_t bsz = mode == BSIG_MODE_PROFILE ? prm->binsize : cov_bin;
-        for (int64_t i = 0; i < n && mode != BSIG_MODE_COUNT; ++i)
-            widest = std::max<int64_t>(widest, ((int64_t)len[i] + bsz - 1) / bsz);
-    }
+    const bool binned = mode == BSIG_MODE_PROFILE || r.cov_ex;
+    const bool split_ss = binned && r.ss;
+    for (int64_t i = 0; i < n && mode != BSIG_MODE_COUNT; ++i)
+        widest = std::max<int64_t>(widest, ((int64_t)len[i] + r.binsize - 1) / r.binsize);
     // (strand-split images hold two values per cell: keep the image at 8 KiB there too, otherwise
     // only 10 workgroups fit a CU and the launch is occupancy-bound: 0.62 -> 0.55 ms on config 4)
     const int64_t cap_cells = split_ss ? 1024 : 2048;
     P->tile_cells = prm->tile_cells > 0 ? prm->tile_cells : (int)std::min<int64_t>(widest, cap_cells);
     int min_cells = 64;
-    if (binned && prm->binsize > 1 && prm->tile_cells <= 0) {
+    if (binned && r.binsize > 1 && prm->tile_cells <= 0) {
         // wide bins: a tile of 2048 cells would span megabases and one wave would stream all of
         // its reads; keep a tile to about 16 kbp so that genome-wide binning still fills the chip
-        const int64_t by_span = std::max<int64_t>(4, (16384 + prm->binsize - 1) / prm->binsize);
+        const int64_t by_span = std::max<int64_t>(4, (16384 + r.binsize - 1) / r.binsize);
         P->tile_cells = (int)std::min<int64_t>(P->tile_cells, by_span);
         min_cells = 4;
     }
     // a tile image is at most 32 KiB of LDS
     P->tile_cells = std::min(std::max(P->tile_cells, min_cells), split_ss ? 4096 : 8192);
     P->tile_cells = (P->tile_cells + 3) & ~3;
-    P->threads = prm->threads > 0 ? prm->threads : 64;
-    if (P->threads != 64 && P->threads != 128 && P->threads != 256) {
-        delete P;
-        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
-    }
+    P->threads = r.threads;
     BsigKParams &K = P->kp;
     K.mapqual = prm->mapqual;
     K.requiredF = (uint32_t)prm->requiredF;
@@ -1436,11 +1460,11 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     K.has_tlen_filter = prm->n_tlen_filter == 2;
     K.tf0 = prm->tlen_filter[0]; K.tf1 = prm->tlen_filter[1];
     K.shift = mode == BSIG_MODE_COVERAGE ? 0 : prm->shift;
-    K.midpoint = mid; K.tspan = tspan;
-    K.use_tlen = K.has_tlen_filter || mid || tspan;
-    K.ss = mode == BSIG_MODE_COVERAGE ? cov_ss : (prm->ss != 0);
-    K.binsize = mode == BSIG_MODE_PROFILE ? prm->binsize : mode == BSIG_MODE_COVERAGE ? cov_bin : 1;
-    K.ext = (int32_t)ext;
+    K.midpoint = r.mid; K.tspan = r.tspan;
+    K.use_tlen = K.has_tlen_filter || r.mid || r.tspan;
+    K.ss = r.ss;
+    K.binsize = r.binsize;
+    K.ext = (int32_t)r.ext;
     K.tile_cells = P->tile_cells;
     // The packed class's read bodies (SmallOne::four, CountOne::quad) take a read's offset from its chunk in signed
     // 24-bit multiplies (v_mad_i32_i24: the low 24 bits of each operand, sign-extended), exact for operands in
@@ -1448,7 +1472,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // chunk, span - 1 < 256, h = |tlen| >> 1 <= tlen_filter[1] / 2 under the midpoint rule (a read outside the filter is
     // forced out of every tile whatever its offset).  Wider shifts or template lengths take the full-width body.
     {
-        const int64_t h_max = mid ? std::max<int64_t>(0, prm->tlen_filter[1]) / 2 : 0;
+        const int64_t h_max = r.mid ? std::max<int64_t>(0, prm->tlen_filter[1]) / 2 : 0;
         K.rel24 = 2 * std::llabs((long long)K.shift) + h_max + (1 << BSIG_PACK_POS_BITS) + 256 < (1ll << 23);
     }
     // The packed class's 16-bit 5'-end column (kernels.hip: ProfileOne::oct) serves a plan that reads nothing else of
@@ -1466,7 +1490,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             const bool rej = (int)((fm >> 16) & 0xFFu) < K.mapqual || (K.requiredF & nf) != 0u || (K.filteredF & nf) == 0u;
             half = !rej;
         }
-        half = half && (int64_t)K.tile_cells + 2 * ext + C.maxspan + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
+        half = half && (int64_t)K.tile_cells + 2 * r.ext + C.maxspan + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
         K.packed_half = half ? 1 : 0;
     }
     bsig::magic_u31(K.binsize, &K.div_magic, &K.div_shift);
@@ -1480,9 +1504,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         K.div_m15 = (uint32_t)((((uint64_t)1 << K.div_s15) + (uint64_t)K.binsize - 1) / (uint64_t)K.binsize);
     }
 
-    const int32_t lay_binsize = mode == BSIG_MODE_COUNT ? -1 : K.binsize;
     P->off.resize(n + 1);
-    bsig_layout(n, len, lay_binsize, K.ss, P->off.data());
+    bsig_layout(n, len, r.lay_binsize, K.ss, P->off.data());
 
     // tiles in genomic order (ref: std::sort by (rid, loc), src/bamsignals.cpp:222-226,246):
     // neighbouring workgroups then stream neighbouring reads
@@ -1616,7 +1639,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             // the heavy flags of the main items
             if (e == hipSuccess) e = hipMemcpyAsync(P->items, items.data(), items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
             // binned coverage: the slices' atomic adds are the only ones that can take a bin past INT32_MAX
-            if (e == hipSuccess && cov_ex) e = P->pool.alloc(&P->overflow, 1);
+            if (e == hipSuccess && r.cov_ex) e = P->pool.alloc(&P->overflow, 1);
             if (e == hipSuccess && P->overflow) e = hipMemsetAsync(P->overflow, 0, sizeof(int32_t), ctx->stream);
             K.overflow = P->overflow;
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1637,22 +1660,20 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
 // the heavy slices behind those of the main tiles; chunks of at most kSumChunkSlots slabs of one c0 for k_sum_reduce.
 // `per` fills the chip once (workgroups resident at a time, by occupancy) and never exceeds 65,536 tiles, which keeps
 // every slab exact in 32 bits (k_sum_tiles).
-static int sum_setup(bsig_plan *P, const SumSpec &spec, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems)
+static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems)
 {
     constexpr int64_t kSumChunkSlots = 32, kMaxRunTiles = 65536;
-    P->is_sum = true;
-    P->sum_nw = spec.nw;
-    P->sum_width = spec.width;
-    P->sum_binsize = spec.binsize;
-    P->sum_S = P->kp.ss ? 2 : 1;
-    P->sum_bins = spec.width > 0 ? ((int64_t)spec.width + spec.binsize - 1) / spec.binsize : 0;
-    P->sum_kind = P->kernel_mode == BSIG_MODE_PROFILE ? 0 : P->kp.ss ? 2 : 1;
-    P->slab_vals = (P->tile_cells * P->sum_S + 3) & ~3;
+    P->sum.reset(new SumState);
+    SumState &Q = *P->sum;
+    Q.shape = shape;
+    Q.S = P->kp.ss ? 2 : 1;
+    Q.kind = P->kernel_mode == BSIG_MODE_PROFILE ? kSumProfile : P->kp.ss ? kSumCoverSS : kSumCover;
+    Q.slab_vals = (P->tile_cells * Q.S + 3) & ~3;
     int n_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
     const int64_t resident = (int64_t)std::max(n_cu, 1) *
-                             bsig::sum_blocks_per_cu(P->sum_kind, P->sum_S == 2, P->sum_nw, P->kp.packed_half != 0, P->tile_cells);
-    const int64_t per = std::min<int64_t>(kMaxRunTiles, std::max<int64_t>(P->sum_nw, (P->n_items + resident - 1) / resident));
+                             bsig::sum_blocks_per_cu(Q.kind, Q.S == 2, shape.nw, P->kp.packed_half != 0, P->tile_cells);
+    const int64_t per = std::min<int64_t>(kMaxRunTiles, std::max<int64_t>(shape.nw, (P->n_items + resident - 1) / resident));
     std::vector<uint2> runs;
     std::vector<BsigSumChunk> chunks;
     auto cut = [&](const std::vector<BsigWorkItem> &it) {
@@ -1664,29 +1685,29 @@ static int sum_setup(bsig_plan *P, const SumSpec &spec, const std::vector<BsigWo
                 const uint32_t slot = (uint32_t)runs.size();
                 runs.push_back(make_uint2((uint32_t)r, (uint32_t)std::min<size_t>(b, r + (size_t)per)));
                 if (chunk_c0 != it[a].c0 || chunks.back().slot_hi - chunks.back().slot_lo >= kSumChunkSlots) {
-                    chunks.push_back(BsigSumChunk{slot, slot, it[a].c0 * P->sum_S, it[a].nc * P->sum_S});
+                    chunks.push_back(BsigSumChunk{slot, slot, it[a].c0 * Q.S, it[a].nc * Q.S});
                     chunk_c0 = it[a].c0;
                 }
                 chunks.back().slot_hi = slot + 1;
-                P->sum_max_nvals = std::max(P->sum_max_nvals, it[a].nc * P->sum_S);
+                Q.max_nvals = std::max(Q.max_nvals, it[a].nc * Q.S);
             }
             a = b;
         }
     };
     cut(items);
-    P->n_runs_main = (int64_t)runs.size();
+    Q.n_runs_main = (int64_t)runs.size();
     cut(hitems);
-    P->n_runs_heavy = (int64_t)runs.size() - P->n_runs_main;
-    P->n_sum_chunks = (int64_t)chunks.size();
+    Q.n_runs_heavy = (int64_t)runs.size() - Q.n_runs_main;
+    Q.n_chunks = (int64_t)chunks.size();
     hipStream_t st = P->ctx->stream;
     if (!runs.empty()) {
-        HIP_TRY(P->pool.alloc(&P->sum_runs, runs.size()));
-        HIP_TRY(P->pool.alloc(&P->sum_chunks, chunks.size()));
-        HIP_TRY(P->pool.alloc(&P->slab, runs.size() * (size_t)P->slab_vals));
-        HIP_TRY(hipMemcpyAsync(P->sum_runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(P->sum_chunks, chunks.data(), chunks.size() * sizeof(BsigSumChunk), hipMemcpyHostToDevice, st));
+        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
+        HIP_TRY(P->pool.alloc(&Q.chunks, chunks.size()));
+        HIP_TRY(P->pool.alloc(&Q.slab, runs.size() * (size_t)Q.slab_vals));
+        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(Q.chunks, chunks.data(), chunks.size() * sizeof(BsigSumChunk), hipMemcpyHostToDevice, st));
     }
-    if (P->sum_binsize != 1 && P->sum_width > 0) HIP_TRY(P->pool.alloc(&P->sum_base, (size_t)P->sum_width * P->sum_S));
+    if (shape.binsize != 1 && shape.width > 0) HIP_TRY(P->pool.alloc(&Q.base, (size_t)shape.width * Q.S));
     HIP_TRY(hipStreamSynchronize(st));
     return BSIG_OK;
 }
@@ -1704,10 +1725,37 @@ const int64_t *bsig_plan_offsets(const bsig_plan *p) { return p ? p->off.data() 
 
 int64_t bsig_plan_cells(const bsig_plan *p) { return p ? p->off.back() : 0; }
 
+}  // extern "C"
+// The main launch of a run, bsig_plan_run's or bsig_plan_run_sum's: launch(kp, resolved, lookup) enqueues it in the form
+// chosen here.  Large launches look their tiles' windows up in a launch of their own (k_resolve_tiles, one lane per
+// tile), so that a pileup workgroup -- which holds its LDS and registers from its first instruction on -- gets its work
+// item and its windows in ONE memory round trip instead of two dependent ones; small launches, where a second launch
+// costs more than it hides, look them up inside the pileup kernel (bam_itr_queryi's counterpart, ref: :267).  A plan and
+// a layout of the reads are both immutable, so the windows are a function of the two: the lookup launch runs in the
+// plan's FIRST run on a layout and its result is kept with the plan (round 5; 9-11 us of every later step of a resident
+// plan; env BAMSIGNALS_CACHE_WINDOWS=0: looked up in every run, as in round 4).  A file-level call makes its plan and
+// runs it once: it looks its windows up once either way.
+template <typename Launch>
+static int run_main(bsig_plan *p, Launch &&launch)
+{
+    if (!plan_two_launches(p)) {
+        HIP_TRY(launch(p->kp, nullptr, false));
+        return BSIG_OK;
+    }
+    const bool lookup = !windows_kept() || p->resolved_gen != p->reads->layout_gen;
+    if (!p->resolved) HIP_TRY(p->pool.alloc(&p->resolved, (size_t)p->n_items));
+    BsigKParams res = p->kp;
+    res.resolved = 1;
+    HIP_TRY(launch(res, p->resolved, lookup));
+    p->resolved_gen = p->reads->layout_gen;
+    return BSIG_OK;
+}
+extern "C" {
+
 int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
+    if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1719,28 +1767,11 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
     // (heavy tiles need no fill: their main item stores 0 and only the slices add)
     if (p->kernel_mode == BSIG_MODE_COUNT && p->needs_zero)
         HIP_TRY(hipMemsetAsync(out_dev, 0, cells * sizeof(int32_t), st));
-    // Large launches look their tiles' windows up in a launch of their own (k_resolve_tiles, one lane per tile), so
-    // that a pileup workgroup -- which holds its LDS and registers from its first instruction on -- gets its work
-    // item and its windows in ONE memory round trip instead of two dependent ones; small launches, where a second
-    // launch costs more than it hides, look them up inside the pileup kernel (bam_itr_queryi's counterpart, ref: :267).
-    // A plan and a layout of the reads are both immutable, so the windows are a function of the two: the lookup
-    // launch runs in the plan's FIRST run on a layout and its result is kept with the plan (round 5; 9-11 us of every
-    // later step of a resident plan; env BAMSIGNALS_CACHE_WINDOWS=0: looked up in every run, as in round 4).  A file-
-    // level call makes its plan and runs it once: it looks its windows up once either way.
-    const bool two_launches = plan_two_launches(p);
-    if (two_launches) {
-        const bool keep = windows_kept();
-        if (!p->resolved) HIP_TRY(p->pool.alloc(&p->resolved, (size_t)p->n_items));
-        const bool lookup = !keep || p->resolved_gen != p->reads->layout_gen;
-        BsigKParams res = p->kp;
-        res.resolved = 1;
-        HIP_TRY(bsig::launch_pileup(p->kernel_mode, p->kp.ss, p->threads, p->reads->dev, res, p->items, p->n_items,
-                                    p->tile_cells, p->resolved, lookup, out_dev, st));
-        p->resolved_gen = p->reads->layout_gen;
-    } else {
-        HIP_TRY(bsig::launch_pileup(p->kernel_mode, p->kp.ss, p->threads, p->reads->dev, p->kp, p->items, p->n_items,
-                                    p->tile_cells, nullptr, false, out_dev, st));
-    }
+    const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+        return bsig::launch_pileup(p->kernel_mode, p->kp.ss, p->threads, p->reads->dev, kp, p->items, p->n_items, p->tile_cells,
+                                   resolved, lookup, out_dev, st);
+    });
+    if (rc != BSIG_OK) return rc;
     if (p->n_heavy_slices) {
         // the first launch zero-filled the heavy tiles; their slices now add their partial images
         if (p->overflow) HIP_TRY(hipMemsetAsync(p->overflow, 0, sizeof(int32_t), st));     // (the flag speaks of this run)
@@ -1756,24 +1787,9 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
-    const int64_t cells = p->off.back();
-    if (cells == 0) return BSIG_OK;
-    if (!out_host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    if (!p->d_out) HIP_TRY(p->pool.alloc(&p->d_out, (size_t)cells));
-    int rc = bsig_plan_run(p, p->d_out);
-    if (rc != BSIG_OK) return rc;
-    const size_t bytes = (size_t)cells * sizeof(int32_t);
-    if (bytes >= (8u << 20) && !is_pinned_host(out_host)) {
-        rc = bsig::download_to_host(p->ctx, p->d_out, out_host, bytes);
-        return rc == BSIG_OK ? bsig::plan_check_overflow(p) : rc;
-    }
-    hipError_t e = hipMemcpyAsync(out_host, p->d_out, bytes, hipMemcpyDeviceToHost, p->ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->ctx->stream);
-    if (e != hipSuccess) rc = fail(BSIG_ERR_DEVICE, "result download failed: %s", hipGetErrorString(e));
-    if (rc == BSIG_OK) rc = bsig::plan_check_overflow(p);
-    return rc;
+    if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
+    const bsig::HostDest dst{out_host};
+    return bsig::plan_run_to_host(p, &dst, nullptr);
 }
 
 int bsig_plan_overflowed(bsig_plan *p, int32_t *flag)
@@ -1788,44 +1804,36 @@ int bsig_plan_overflowed(bsig_plan *p, int32_t *flag)
 }
 
 }  // extern "C"
-int bsig::plan_run_host_timed(bsig_plan *p, const HostDest &dst, double *t_kernels, double *t_download)
+int bsig::plan_run_to_host(bsig_plan *p, const HostDest *dst, int64_t *sum, bool async, double *t_kernels, double *t_download)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
-    const int64_t cells = p->off.back();
+    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    SumState *Q = p->sum.get();
+    const int64_t cells = Q ? Q->shape.cells : p->off.back();
     if (cells == 0) return BSIG_OK;
-    if (!dst.flat && !dst.ptrs) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (Q ? !sum : !dst || (!dst->flat && !dst->ptrs)) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     HIP_TRY(hipSetDevice(p->ctx->device));
-    if (!p->d_out) HIP_TRY(p->pool.alloc(&p->d_out, (size_t)cells));
-    int rc = bsig_plan_run(p, p->d_out);
+    hipStream_t st = p->ctx->stream;
+    if (Q && !Q->d_sum) HIP_TRY(p->pool.alloc(&Q->d_sum, (size_t)cells));
+    if (!Q && !p->d_out) HIP_TRY(p->pool.alloc(&p->d_out, (size_t)cells));
+    int rc = Q ? bsig_plan_run_sum(p, Q->d_sum) : bsig_plan_run(p, p->d_out);
     if (rc != BSIG_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    *t_kernels = since(t0);
+    if (t_kernels) {
+        HIP_TRY(hipStreamSynchronize(st));
+        *t_kernels = since(t0);
+    }
     const auto t1 = std::chrono::steady_clock::now();
-    rc = bsig::download_to_dest(p->ctx, p->d_out, dst, cells);
-    *t_download = since(t1);
-    return rc == BSIG_OK ? bsig::plan_check_overflow(p) : rc;
-}
-int bsig::plan_run_sum_host_timed(bsig_plan *p, int64_t *sum_host, double *t_kernels, double *t_download)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    const int64_t cells = bsig_plan_sum_cells(p);
-    if (cells == 0) return BSIG_OK;
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    if (!p->d_sum) HIP_TRY(p->pool.alloc(&p->d_sum, (size_t)cells));
-    const int rc = bsig_plan_run_sum(p, reinterpret_cast<int64_t *>(p->d_sum));
-    if (rc != BSIG_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    *t_kernels = since(t0);
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(sum_host, p->d_sum, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, p->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    *t_download = since(t1);
-    return BSIG_OK;
+    if (Q) {
+        HIP_TRY(hipMemcpyAsync(sum, Q->d_sum, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else if (async) {
+        HIP_TRY(hipMemcpyAsync(dst->flat, p->d_out, (size_t)cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        return BSIG_OK;
+    } else {
+        rc = download_to_dest(p->ctx, p->d_out, *dst, cells);
+    }
+    if (t_download) *t_download = since(t1);
+    return rc != BSIG_OK || Q ? rc : plan_check_overflow(p);
 }
 // a run whose slices took a bin past INT32_MAX fails (after the caller's synchronisation: no wait of its own)
 int bsig::plan_check_overflow(bsig_plan *p)
@@ -1841,60 +1849,56 @@ extern "C" {
 int bsig_plan_run_host_async(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->is_sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
-    const int64_t cells = p->off.back();
-    if (cells == 0) return BSIG_OK;
-    if (!out_host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    if (!p->d_out) HIP_TRY(p->pool.alloc(&p->d_out, (size_t)cells));
-    const int rc = bsig_plan_run(p, p->d_out);
-    if (rc != BSIG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, p->d_out, cells * sizeof(int32_t), hipMemcpyDeviceToHost, p->ctx->stream));
-    return BSIG_OK;
+    if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
+    const bsig::HostDest dst{out_host};
+    return bsig::plan_run_to_host(p, &dst, nullptr, true);
 }
 
+// The visit counts are taken once (a launch of k_visits); what follows from them is worked out at every call from the
+// plan's state, so that it describes the form the plan's next run takes.
 int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
 {
     if (!p || !s) return fail(BSIG_ERR_ARG, "NULL argument");
-    if (!p->have_stats) {
+    const unsigned long long *acc = p->visits;
+    if (!p->have_visits) {
         hipStream_t st = p->ctx->stream;
-        unsigned long long *d_acc = nullptr, acc[BSIG_MAX_CLASSES + 1] = {};
+        unsigned long long *d_acc = nullptr;
         HIP_TRY(hipSetDevice(p->ctx->device));
-        HIP_TRY(hipMalloc((void **)&d_acc, sizeof acc));
-        hipError_t e = hipMemsetAsync(d_acc, 0, sizeof acc, st);
+        HIP_TRY(hipMalloc((void **)&d_acc, sizeof p->visits));
+        hipError_t e = hipMemsetAsync(d_acc, 0, sizeof p->visits, st);
         if (e == hipSuccess) e = bsig::launch_visits(p->reads->dev, p->kp, p->kernel_mode, p->items, p->n_items, d_acc, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(p->visits, d_acc, sizeof p->visits, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         (void)hipFree(d_acc);
         if (e != hipSuccess) return fail(BSIG_ERR_DEVICE, "visit count failed: %s", hipGetErrorString(e));
-        bsig_plan_stats &t = p->stats;
-        t.n_ranges = p->n_ranges;
-        t.n_items = p->n_items;
-        t.cells = p->is_sum ? p->sum_bins * p->sum_S : p->off.back();
-        t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
-        t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
-        t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
-        t.streamed = (int64_t)acc[BSIG_MAX_CLASSES];
-        t.heavy_tiles = (int32_t)std::min<int64_t>(p->n_heavy_tiles, INT32_MAX);
-        t.bytes_per_visit_packed = p->kp.packed_half ? 2 : p->kp.use_tlen ? 8 : 4;     // the half-word, or the packed word [+ tlen]
-        t.bytes_per_visit_short = p->kp.use_tlen ? 12 : 8;     // span <= 4096: pos + flag/mapq/span in one word [+ tlen]
-        t.bytes_per_visit_long = p->kp.use_tlen ? 16 : 12;     // pos + end + flag/mapq [+ tlen]
-        // reads + work items + index entries + result cells (a sum plan: 8 B a cell of the sum, none per range)
-        const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
-        t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
-                              t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
-                              (p->is_sum ? 8 : 4) * t.cells;
-        if (plan_two_launches(p) && windows_kept()) {
-            // a resident plan's step reads the windows kept from its first run: no index entry is touched
-            t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
-        } else {
-            t.algorithmic_bytes += 8 * t.n_items * p->reads->info.n_classes;          // the index entries
-            // two launches: the work item is read twice and the tile's windows are written and read once
-            if (plan_two_launches(p)) t.algorithmic_bytes += (per_item + 2 * (int64_t)sizeof(BsigResolved)) * t.n_items;
-        }
-        p->have_stats = true;
+        p->have_visits = true;
     }
-    *s = p->stats;
+    bsig_plan_stats t{};
+    t.n_ranges = p->n_ranges;
+    t.n_items = p->n_items;
+    t.cells = p->sum ? p->sum->shape.cells : p->off.back();
+    t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
+    t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
+    t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
+    t.streamed = (int64_t)acc[BSIG_MAX_CLASSES];
+    t.heavy_tiles = (int32_t)std::min<int64_t>(p->n_heavy_tiles, INT32_MAX);
+    t.bytes_per_visit_packed = p->kp.packed_half ? 2 : p->kp.use_tlen ? 8 : 4;     // the half-word, or the packed word [+ tlen]
+    t.bytes_per_visit_short = p->kp.use_tlen ? 12 : 8;     // span <= 4096: pos + flag/mapq/span in one word [+ tlen]
+    t.bytes_per_visit_long = p->kp.use_tlen ? 16 : 12;     // pos + end + flag/mapq [+ tlen]
+    // reads + work items + index entries + result cells (a sum plan: 8 B a cell of the sum, none per range)
+    const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
+    t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
+                          t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
+                          (p->sum ? 8 : 4) * t.cells;
+    if (plan_two_launches(p) && windows_kept()) {
+        // a resident plan's step reads the windows kept from its first run: no index entry is touched
+        t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
+    } else {
+        t.algorithmic_bytes += 8 * t.n_items * p->reads->info.n_classes;          // the index entries
+        // two launches: the work item is read twice and the tile's windows are written and read once
+        if (plan_two_launches(p)) t.algorithmic_bytes += (per_item + 2 * (int64_t)sizeof(BsigResolved)) * t.n_items;
+    }
+    *s = t;
     return BSIG_OK;
 }
 
@@ -1906,33 +1910,21 @@ int bsig_plan_create_sum(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, cons
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_sum");
     *out = nullptr;
     if (n < 0 || (n > 0 && !len)) return fail(BSIG_ERR_ARG, "range arrays missing");
-    if (prm->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
-    if (prm->mode != BSIG_MODE_PROFILE && prm->mode != BSIG_MODE_COVERAGE && prm->mode != BSIG_MODE_COVERAGE_EX)
-        return fail(BSIG_ERR_ARG, "unknown mode %d", prm->mode);
-    for (int64_t i = 1; i < n; ++i)
-        if (len[i] != len[0]) return fail(BSIG_ERR_ARG, "all signals must have the same length");     // alignSignals
-    if (prm->threads != 0 && prm->threads != 64 && prm->threads != 128 && prm->threads != 256)
-        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
-    if (prm->mode == BSIG_MODE_PROFILE && prm->binsize < 1) return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");
-    if (prm->mode == BSIG_MODE_COVERAGE_EX && (prm->binsize < 1 || prm->binsize > bsig::kMaxCoverageBin))
-        return fail(BSIG_ERR_ARG, prm->binsize < 1 ? "provide a binsize greater or equal to 1"
-                                                   : "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
-    // the tiles are per base (bins are summed at the end: binning is linear); mode 2 ignores binsize and ss
-    bsig_params q = *prm;
-    const int32_t binsize = prm->mode == BSIG_MODE_COVERAGE ? 1 : prm->binsize;
-    q.binsize = 1;
-    q.threads = 64;
-    const SumSpec spec{prm->threads > 0 ? prm->threads / 64 : 4, n > 0 ? len[0] : 0, binsize};
-    return plan_create_impl(ctx, reads, n, rid, loc, len, strand, &q, &spec, out);
+    bsig::SumShape shape;
+    bsig::PlanRule caller;          // (the caller's binsize and threads; the per-base tiles' are the plan's)
+    int rc = bsig::sum_shape(*prm, n, len, &shape);
+    if (rc == BSIG_OK) rc = bsig::check_params(*prm, n, len, &caller);
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, &shape, out);
 }
 
-int64_t bsig_plan_sum_cells(const bsig_plan *p) { return p && p->is_sum ? p->sum_bins * p->sum_S : 0; }
+int64_t bsig_plan_sum_cells(const bsig_plan *p) { return p && p->sum ? p->sum->shape.cells : 0; }
 
 int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (!p->is_sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
-    const int64_t cells = p->sum_bins * p->sum_S;
+    if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
+    const SumState &Q = *p->sum;
+    const int64_t cells = Q.shape.cells;
     if (cells == 0) return BSIG_OK;
     if (!sum_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     if (((uintptr_t)sum_dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
@@ -1940,35 +1932,26 @@ int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
         return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
     HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
-    const int ss = p->sum_S == 2;
-    if (p->n_runs_main) {
-        // the windows as an ordinary plan looks them up: in the launch (fused), or in a launch of their own, kept
-        if (plan_two_launches(p)) {
-            const bool keep = windows_kept();
-            if (!p->resolved) HIP_TRY(p->pool.alloc(&p->resolved, (size_t)p->n_items));
-            const bool lookup = !keep || p->resolved_gen != p->reads->layout_gen;
-            BsigKParams res = p->kp;
-            res.resolved = 1;
-            HIP_TRY(bsig::launch_sum_tiles(p->sum_kind, ss, p->sum_nw, p->reads->dev, res, p->items, p->n_items, p->sum_runs,
-                                           p->n_runs_main, p->resolved, lookup, p->slab, st));
-            p->resolved_gen = p->reads->layout_gen;
-        } else {
-            HIP_TRY(bsig::launch_sum_tiles(p->sum_kind, ss, p->sum_nw, p->reads->dev, p->kp, p->items, p->n_items, p->sum_runs,
-                                           p->n_runs_main, nullptr, false, p->slab, st));
-        }
+    const int ss = Q.S == 2, nw = Q.shape.nw;
+    if (Q.n_runs_main) {
+        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+            return bsig::launch_sum_tiles(Q.kind, ss, nw, p->reads->dev, kp, p->items, p->n_items, Q.runs, Q.n_runs_main,
+                                          resolved, lookup, Q.slab, st);
+        });
+        if (rc != BSIG_OK) return rc;
     }
     // the slices of heavy tiles: one more addend each, with their fixed windows, into slabs of their own
-    if (p->n_runs_heavy)
-        HIP_TRY(bsig::launch_sum_tiles(p->sum_kind, ss, p->sum_nw, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                       p->sum_runs + p->n_runs_main, p->n_runs_heavy, p->heavy_windows, false,
-                                       p->slab + (size_t)p->n_runs_main * (size_t)p->slab_vals, st));
-    long long *base = p->sum_binsize == 1 ? reinterpret_cast<long long *>(sum_dev) : p->sum_base;
-    HIP_TRY(hipMemsetAsync(base, 0, (size_t)p->sum_width * p->sum_S * sizeof(long long), st));
-    HIP_TRY(bsig::launch_sum_reduce(p->sum_kind != 0, p->slab, p->slab_vals, p->sum_chunks, p->n_sum_chunks, p->sum_max_nvals,
+    if (Q.n_runs_heavy)
+        HIP_TRY(bsig::launch_sum_tiles(Q.kind, ss, nw, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                       Q.runs + Q.n_runs_main, Q.n_runs_heavy, p->heavy_windows, false,
+                                       Q.slab + (size_t)Q.n_runs_main * (size_t)Q.slab_vals, st));
+    const int32_t width = Q.shape.width, binsize = Q.shape.binsize;
+    long long *base = binsize == 1 ? reinterpret_cast<long long *>(sum_dev) : Q.base;
+    HIP_TRY(hipMemsetAsync(base, 0, (size_t)width * Q.S * sizeof(long long), st));
+    HIP_TRY(bsig::launch_sum_reduce(Q.kind != kSumProfile, Q.slab, Q.slab_vals, Q.chunks, Q.n_chunks, Q.max_nvals,
                                     reinterpret_cast<unsigned long long *>(base), st));
-    if (p->sum_kind != 0) HIP_TRY(bsig::launch_sum_scan(base, p->sum_width, p->tile_cells, p->sum_S, st));
-    if (p->sum_binsize != 1)
-        HIP_TRY(bsig::launch_sum_bins(base, p->sum_width, p->sum_binsize, p->sum_S, cells, reinterpret_cast<long long *>(sum_dev), st));
+    if (Q.kind != kSumProfile) HIP_TRY(bsig::launch_sum_scan(base, width, p->tile_cells, Q.S, st));
+    if (binsize != 1) HIP_TRY(bsig::launch_sum_bins(base, width, binsize, Q.S, cells, reinterpret_cast<long long *>(sum_dev), st));
     ++p->runs;
     return BSIG_OK;
 }
@@ -1976,17 +1959,8 @@ int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (!p->is_sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
-    const int64_t cells = p->sum_bins * p->sum_S;
-    if (cells == 0) return BSIG_OK;
-    if (!sum_host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    if (!p->d_sum) HIP_TRY(p->pool.alloc(&p->d_sum, (size_t)cells));
-    const int rc = bsig_plan_run_sum(p, reinterpret_cast<int64_t *>(p->d_sum));
-    if (rc != BSIG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(sum_host, p->d_sum, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, p->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    return BSIG_OK;
+    if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
+    return bsig::plan_run_to_host(p, nullptr, sum_host);
 }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)

@@ -228,10 +228,33 @@ int download_slice_to_dest(bsig_ctx *ctx, const int32_t *src_dev, const HostDest
 // ... several slices as ONE pipelined stream: slice k = cells[k] int32 at src_dev + src_c0[k], bound for cell dst_c0[k]
 int download_slices_to_dest(bsig_ctx *ctx, const int32_t *src_dev, int64_t n_slices, const int64_t *src_c0, const int64_t *dst_c0,
                             const int64_t *cells, const HostDest &dst, int copy_threads);
-// bsig_plan_run_host with the kernels' and the download's seconds told apart (runtime.hip)
-int plan_run_host_timed(bsig_plan *p, const HostDest &dst, double *t_kernels, double *t_download);
-// bsig_plan_run_sum_host with the kernels' and the download's seconds told apart (runtime.hip)
-int plan_run_sum_host_timed(bsig_plan *p, int64_t *sum_host, double *t_kernels, double *t_download);
+// bsig_plan_run (dst: an ordinary plan's int32 result) or bsig_plan_run_sum (sum: a sum plan's int64 cells) into the
+// plan's own device buffer, then the download to the host.  async: the copy is only enqueued.  With timers the kernels
+// are waited for first and the two stages timed apart; without them nothing waits between kernels and download.  The
+// caller has checked which kind of plan p is (runtime.hip)
+int plan_run_to_host(bsig_plan *p, const HostDest *dst, int64_t *sum, bool async = false, double *t_kernels = nullptr,
+                     double *t_download = nullptr);
+// bsig_params as every entry point reads them (runtime.hip: check_params)
+struct PlanRule {
+    int mode;               // the kernel family: BSIG_MODE_COVERAGE_EX is BSIG_MODE_COVERAGE with bins and / or strands
+    bool cov_ex;            // ... that coverage (binned tiles; heavy slices watch its bins for overflow)
+    int32_t binsize;        // the result's bins: profile's and coverage_ex's; 1 for coverage and count
+    bool ss;                // strand-split result (profile, count, coverage_ex)
+    bool mid, tspan;        // paired-end midpoint (profile, count) / extend (coverage)
+    int64_t ext;            // how far beyond a range a read can count: |shift| + midpoint's tlen_filter[1], or extend's
+    int32_t lay_binsize;    // bsig_layout's binsize (-1: count)
+    int threads;            // per workgroup
+};
+int check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out);
+// what only a sum over ranges asks (runtime.hip: sum_shape)
+struct SumShape {
+    bsig_params tiles;      // the per-base plan the sum is built on
+    int32_t width;          // every range's width
+    int32_t binsize;        // the caller's bins (the per-base sums are binned at the end: binning is linear)
+    int nw;                 // waves per k_sum_tiles workgroup
+    int64_t cells;          // ceil(width / binsize), twice that with strands
+};
+int sum_shape(const bsig_params &prm, int64_t n, const int32_t *len, SumShape *out);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

@@ -176,11 +176,14 @@ typedef struct {
     int64_t visits;            /* reads in the exact candidate windows of all tiles (V)         */
     int64_t visits_short;      /* ... of them in span classes 0-1 (span <= 4096: no end column) */
     int64_t streamed;          /* reads actually loaded (windows rounded to index buckets)      */
-    int64_t algorithmic_bytes; /* of one run of the resident plan: sum(bytes_per_visit*V) + 32*items + 4*cells
-                                * + 8*items*classes (the index entries; small launches look them up in the pileup kernel)
-                                * or + 48*items (large launches: the windows kept with the plan from its first run;
-                                * with BAMSIGNALS_CACHE_WINDOWS=0, looked up by a launch of their own in every run:
-                                * 8*items*classes + (32 + 2*48)*items) */
+    int64_t algorithmic_bytes; /* of one run in the form the plan's NEXT run takes (worked out at every call: a plan asked
+                                * before its first run and again after it gets two answers): sum(bytes_per_visit*V) +
+                                * 32*items + 4*cells
+                                * + 8*items*classes (the fused form, which a plan's first run below 32,768 tiles takes:
+                                * the index entries, looked up in the pileup kernel)
+                                * or + 48*items (the resolved form of large launches and of every later run: the windows
+                                * kept with the plan; with BAMSIGNALS_CACHE_WINDOWS=0, looked up by a launch of their own
+                                * in every run: 8*items*classes + (32 + 2*48)*items) */
     int32_t bytes_per_visit_short;   /* 8  (pos + flag|mapq|span - 1), 12 with the tlen column  */
     int32_t bytes_per_visit_long;    /* 12 (pos + end + flag|mapq), 16 with the tlen column     */
     int64_t visits_packed;     /* ... of V in the packed class (not part of visits_short)       */

@@ -365,8 +365,8 @@ def test_a_plan_that_is_run_again_takes_the_resolved_form(ctx, synth, monkeypatc
     """Below 32,768 tiles a plan's first run looks its windows up inside the pileup kernel (a file-level call runs its plan
     once and must not pay a launch for nothing); a plan that is run AGAIN is a resident one: its second run looks the
     windows up in a launch of their own and keeps them, the third reads them back (bamCount included).  Every run is
-    identical to the oracle; which form the next run takes shows in the plan's algorithmic bytes (the figure is
-    computed once, when it is first asked for: one plan per question)."""
+    identical to the oracle; which form the next run takes shows in the plan's algorithmic bytes (the figure is worked
+    out at every question: one plan asked before and after its first run answers as two plans asked once each)."""
     from bamsignals_amd import _lib
     from bamsignals_amd.device import Plan, make_params
     from bamsignals_amd.synth import synth_ranges
@@ -393,6 +393,11 @@ def test_a_plan_that_is_run_again_takes_the_resolved_form(ctx, synth, monkeypatc
             plan.close()
         # before any run: the fused form's bytes (the index entries); once it has run: the kept windows' (48 B a tile)
         assert asked[1] == asked[3] != asked[0], (mode, a, asked)
+        plan = Plan(ctx, gpu, rg["rid"], rg["loc"], rg["len"], rg["strand"], make_params(mode, **a))
+        before = per_tile(plan)
+        assert np.array_equal(plan.run_host(), want), (mode, a, "asked before")
+        assert (before, per_tile(plan)) == (asked[0], asked[1]), (mode, a)
+        plan.close()
     monkeypatch.setenv("BAMSIGNALS_CACHE_WINDOWS", "0")                  # nothing is kept: nothing to run again for
     plan = Plan(ctx, gpu, rg["rid"], rg["loc"], rg["len"], rg["strand"], make_params(_lib.MODE_PROFILE, binsize=1, ss=True))
     for run in range(2):
@@ -523,6 +528,16 @@ def test_error_paths(ctx, synth):
     ok.close()
     with pytest.raises(_lib.BsigError, match="sorted"):
         Reads(ctx, [100, 100], [0, 2, 4], [60, 50, 10, 20], [0] * 4, [9] * 4, [0] * 4, end=[65, 55, 15, 25])
+    # one rule for every entry point: a plan refuses each bad parameter with the file-level calls' code and message
+    from test_param_rule_cpu import CASES, args, params
+    from bamsignals_amd.device import SumPlan
+    for family, a, which, code, message in CASES:
+        w = np.asarray(args(a)["widths"], np.int32)
+        two = dict(rid=np.zeros(2, np.int32), loc=np.asarray([10, 500], np.int32), len=w, strand=np.asarray([1, -1], np.int32))
+        for kind in ((Plan, SumPlan) if which == "all" else (SumPlan,)):
+            with pytest.raises(_lib.BsigError) as e:
+                kind(ctx, gpu, two["rid"], two["loc"], two["len"], two["strand"], params(family, a))
+            assert (e.value.code, str(e.value)) == (code, message), (kind.__name__, family, a)
 
 
 def test_fuzz_small_inputs(ctx):
