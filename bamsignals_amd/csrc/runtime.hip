@@ -1669,11 +1669,26 @@ static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vecto
     Q.S = P->kp.ss ? 2 : 1;
     Q.kind = P->kernel_mode == BSIG_MODE_PROFILE ? kSumProfile : P->kp.ss ? kSumCoverSS : kSumCover;
     Q.slab_vals = (P->tile_cells * Q.S + 3) & ~3;
-    int n_cu = 0;
+    int n_cu = 0, lds_max = 0;
     HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
+    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    // The accumulator and one image per wave must fit a workgroup's LDS (a tile size of the caller's can ask for more:
+    // strand-split coverage, 4,096 cells, four waves = 160.5 KiB): fewer waves per workgroup, and if one is too many,
+    // no plan.  The library's own tile sizes (at most 2,048 cells, 1,024 with strands) need 40.5 KiB at most.
+    int &nw = Q.shape.nw;
+    while (nw > 1 && bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells) > (size_t)lds_max) nw /= 2;
+    if (bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells) > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "tile_cells %d needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells,
+                    bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells), lds_max);
     const int64_t resident = (int64_t)std::max(n_cu, 1) *
-                             bsig::sum_blocks_per_cu(Q.kind, Q.S == 2, shape.nw, P->kp.packed_half != 0, P->tile_cells);
-    const int64_t per = std::min<int64_t>(kMaxRunTiles, std::max<int64_t>(shape.nw, (P->n_items + resident - 1) / resident));
+                             bsig::sum_blocks_per_cu(Q.kind, Q.S == 2, nw, P->kp.packed_half != 0, P->tile_cells);
+    int64_t per = std::min<int64_t>(kMaxRunTiles, std::max<int64_t>(nw, (P->n_items + resident - 1) / resident));
+    // (tests: BAMSIGNALS_SUM_RUN_TILES = tiles per run instead of the occupancy's, read when a sum plan is made; shorter
+    // or longer runs, never past the cap that keeps a slab exact)
+    if (const char *v = getenv("BAMSIGNALS_SUM_RUN_TILES")) {
+        const long long forced = atoll(v);
+        if (forced > 0) per = std::min<long long>(kMaxRunTiles, std::max<long long>(1, forced));
+    }
     std::vector<uint2> runs;
     std::vector<BsigSumChunk> chunks;
     auto cut = [&](const std::vector<BsigWorkItem> &it) {
