@@ -72,6 +72,16 @@ hipError_t launch_sum_reduce(bool is_signed, const int32_t *slab, int32_t slab_v
 hipError_t launch_sum_scan(long long *base, int32_t width, int32_t tile_cells, int32_t S, hipStream_t st);
 // per-base sums -> n_out = n_bins * S bins (2 * bin + s)
 hipError_t launch_sum_bins(const long long *base, int32_t width, int32_t binsize, int32_t S, int64_t n_out, long long *out, hipStream_t st);
+// Strand cross-correlation over ranges (bsig_plan_create_xcorr).  k_xcorr_tiles: run r = tiles [runs[r].x, runs[r].y), a
+// tile = item.out_off body cells (<= body) + an antisense halo, item.nc <= P.tile_cells (>= body + max_lag) cells in all;
+// every workgroup ADDS its partial sums into out (max_lag + 1 lags, then the five moments; the first workgroup adds
+// n_cells, the plan's count of cells, to the first moment): zero `out` first.  wide: 32-bit image cells for tiles with
+// more reads than a 16-bit cell may see.  windows / resolve_first as in launch_sum_tiles (no fixed windows).
+size_t xcorr_tiles_lds(bool wide, int tile_cells, int body, int max_lag);
+int xcorr_blocks_per_cu(int threads, bool half, int tile_cells, int body, int max_lag);
+hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
+                              int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int body,
+                              int max_lag, unsigned long long n_cells, unsigned long long *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

@@ -1759,6 +1759,165 @@ __global__ __launch_bounds__(256) void k_sum_bins(const long long *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
+// Strand cross-correlation over ranges (bsig_plan_create_xcorr)
+// ------------------------------------------------------------------------------------------
+// A tile is a BODY of consecutive cells of one range (w.out_off of them: an xcorr tile writes no per-range cells) and an
+// antisense HALO behind it, w.nc = body + halo cells in all, halo = min(max_lag, cells left in the range).  A workgroup
+// owns a run of tiles.  Per tile it piles the 5' ends up per strand into an LDS image with the per-range read bodies
+// (ProfileOne<true>: dword x holds sense[x] in its low half and antisense[x] in its high half), compacts the body's
+// non-zero sense cells into a list, and then every lane takes lags d = tid, tid + NT, ... : for each it walks the list
+// and adds S[x] * A[x + d] -- consecutive lanes read consecutive LDS dwords, the list entry is a broadcast -- two lags
+// at a time, so that one list read serves two multiply-adds.  Cells of the image behind the tile's nc are zero (the
+// read bodies mask on nc), so a lag that runs past the range's end adds nothing and needs no test.
+// Exactness.  16-bit image: an unsliced tile has at most 32,768 reads in its windows and each counts in one cell, so
+// sum(S) + sum(A) <= 2^15 and a lag's sum over the tile is at most sum(S) * max(A) <= 2^28: a 32-bit register per lag
+// and tile, flushed after every tile into the lag's 64-bit LDS accumulator (owned by one lane: plain adds).  WIDE
+// (tiles with more reads, which the plan lists apart): 32-bit cells, read by read, 64-bit registers.  The plan proves
+// that no 64-bit sum reaches 2^63.  At the end of its run a workgroup adds its non-zero partial sums to the result with
+// one 64-bit atomic per lag, and its four moment sums with one per wave.
+
+// the read-by-read body of a WIDE tile: 32-bit cells, 2 * cell + antisense (shift 0, bins of one base)
+struct XcorrWideOne {
+    const BsigKParams &P;
+    uint32_t *cnt;
+    int loc, len, c0, nc;
+    bool neg_range;
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        if (!valid || rej || tlen_rejected(P, tl)) return;
+        int rel = (neg ? e : p) - loc;
+        if ((unsigned)rel >= (unsigned)len) return;
+        int anti = neg ? 1 : 0;
+        if (neg_range) { rel = len - rel - 1; anti ^= 1; }
+        const int lc = rel - c0;
+        if ((unsigned)lc < (unsigned)nc) atomicAdd(&cnt[2 * lc + anti], 1u);
+    }
+};
+
+// LDS of one k_xcorr_tiles workgroup, in dwords: image | list | 64-bit lag accumulators | counter (+ pad) | filter table
+struct XcorrLds {
+    int img, list, acc, misc, ptab, total;
+};
+__host__ __device__ inline XcorrLds xcorr_lds(bool wide, int tile_cells, int body, int max_lag)
+{
+    XcorrLds L;
+    L.img = 0;
+    L.list = ((wide ? 2 : 1) * tile_cells + 8 + 3) & ~3;
+    L.acc = (L.list + body + 3) & ~3;
+    L.misc = L.acc + 2 * (max_lag + 1);
+    L.ptab = L.misc + 4;
+    L.total = L.ptab + BSIG_PACK_CODES / 4;
+    return L;
+}
+
+template <int NT, bool HALF, bool WIDE>
+__global__ __launch_bounds__(NT) void k_xcorr_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                    unsigned long long *__restrict__ out, const uint2 *__restrict__ windows,
+                                                    const BsigReadsDev R, const BsigKParams P, int body, int max_lag,
+                                                    unsigned long long n_cells)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    typedef typename std::conditional<WIDE, unsigned long long, uint32_t>::type acc_t;
+    const int tid = threadIdx.x;
+    const XcorrLds L = xcorr_lds(WIDE, P.tile_cells, body, max_lag);
+    uint32_t *img = reinterpret_cast<uint32_t *>(lds) + L.img;
+    uint32_t *list = reinterpret_cast<uint32_t *>(lds) + L.list;
+    unsigned long long *lag = reinterpret_cast<unsigned long long *>(lds + L.acc);
+    uint32_t *nnz = reinterpret_cast<uint32_t *>(lds) + L.misc;
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds + L.ptab);
+    for (int v = tid; v < L.misc + 4; v += NT) lds[v] = 0;
+    if (!HALF) build_ptab<NT>(ptab, R, P, tid);
+    const uint2 run = runs[blockIdx.x];
+    unsigned long long m_s = 0, m_a = 0, m_ss = 0, m_aa = 0;
+    __syncthreads();
+
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        uint2 win[BSIG_MAX_CLASSES], clip;
+        PackedWin pk;
+        load_windows<false>(R, P, BSIG_MODE_PROFILE, w, items, windows, win, t, pk, clip);
+        const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
+        if constexpr (WIDE) {
+            const XcorrWideOne one{P, img, w.loc, w.len, w.c0, w.nc, neg_range};
+            for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+            if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+        } else {
+            const ProfileOne<true> one{P, img, w.loc, w.len, w.c0, w.nc, 0, neg_range};
+            for_each_read<NT, 2, HALF>(R, P, win, pk.base, ptab, tid, one);
+            if (!HALF && pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+        }
+        __syncthreads();
+        // the body's moments, and its non-zero sense cells into the list (in any order: a sum)
+        const int nb = (int)w.out_off;
+        for (int x = tid; x < nb; x += NT) {
+            const uint32_t s = WIDE ? img[2 * x] : img[x] & 0xFFFFu, a = WIDE ? img[2 * x + 1] : img[x] >> 16;
+            m_s += s; m_a += a;
+            m_ss += (unsigned long long)s * s; m_aa += (unsigned long long)a * a;
+            if (s) list[atomicAdd(nnz, 1u)] = WIDE ? (uint32_t)x : (uint32_t)x | s << 16;
+        }
+        __syncthreads();
+        const int n = (int)*nnz;
+        if (2 * (max_lag + 1) <= NT) {
+            // fewer lags than half the lanes: G groups of PW >= max_lag + 1 lanes share the list, entry i to group
+            // i mod G, and meet in the lag's accumulator with an LDS atomic
+            int PW = 1;
+            while (PW < max_lag + 1) PW <<= 1;
+            const int d = tid & (PW - 1), G = NT / PW;
+            if (d <= max_lag) {
+                acc_t a0 = 0;
+                for (int i = tid / PW; i < n; i += G) {
+                    const uint32_t e = list[i];
+                    if constexpr (WIDE) a0 += (unsigned long long)img[2 * e] * img[2 * (e + d) + 1];
+                    else a0 += (e >> 16) * (img[(e & 0xFFFFu) + d] >> 16);
+                }
+                if (a0) atomicAdd(&lag[d], (unsigned long long)a0);
+            }
+        } else
+        // lags tid + k NT, two per pass; a second lag beyond max_lag walks the first one's cells and is dropped
+        for (int d0 = tid; d0 <= max_lag; d0 += 2 * NT) {
+            const int d1 = d0 + NT;
+            const bool two = d1 <= max_lag;
+            const int e1 = two ? d1 : d0;
+            acc_t a0 = 0, a1 = 0;
+            for (int i = 0; i < n; ++i) {
+                const uint32_t e = list[i];
+                if constexpr (WIDE) {
+                    const unsigned long long s = img[2 * e];
+                    a0 += s * img[2 * (e + d0) + 1];
+                    a1 += s * img[2 * (e + e1) + 1];
+                } else {
+                    const uint32_t x = e & 0xFFFFu, s = e >> 16;
+                    a0 += s * (img[x + d0] >> 16);
+                    a1 += s * (img[x + e1] >> 16);
+                }
+            }
+            lag[d0] += a0;
+            if (two) lag[d1] += a1;
+        }
+        __syncthreads();
+        // the image and the list's counter, cleared for the run's next tile
+        for (int v = tid; v < (WIDE ? 2 : 1) * w.nc; v += NT) img[v] = 0u;
+        if (tid == 0) *nnz = 0u;
+        __syncthreads();
+    }
+    for (int d = tid; d <= max_lag; d += NT)
+        if (lag[d]) atomicAdd(out + d, lag[d]);
+    for (int m = kWave / 2; m >= 1; m /= 2) {
+        m_s += __shfl_xor(m_s, m); m_a += __shfl_xor(m_a, m);
+        m_ss += __shfl_xor(m_ss, m); m_aa += __shfl_xor(m_aa, m);
+    }
+    if ((tid & (kWave - 1)) == 0) {
+        unsigned long long *mo = out + max_lag + 1;          // moments: [cells (the plan's count), sum S, sum A, sum S^2, sum A^2]
+        if (blockIdx.x == 0 && tid == 0 && n_cells) atomicAdd(mo, n_cells);
+        if (m_s) atomicAdd(mo + 1, m_s);
+        if (m_a) atomicAdd(mo + 2, m_a);
+        if (m_ss) atomicAdd(mo + 3, m_ss);
+        if (m_aa) atomicAdd(mo + 4, m_aa);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // one-time layout of the reads in HBM
 // ------------------------------------------------------------------------------------------
 
@@ -2394,6 +2553,52 @@ hipError_t launch_sum_bins(const long long *base, int32_t width, int32_t binsize
     if (binsize > 64) hipLaunchKernelGGL(k_sum_bins<true>, dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, st, base, width, binsize, S, n_out, out);
     else hipLaunchKernelGGL(k_sum_bins<false>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, base, width, binsize, S, n_out, out);
     return hipGetLastError();
+}
+
+// ---- strand cross-correlation --------------------------------------------------------------------------------------
+size_t xcorr_tiles_lds(bool wide, int tile_cells, int body, int max_lag)
+{
+    return (size_t)xcorr_lds(wide, tile_cells, body, max_lag).total * 4;
+}
+
+// one k_xcorr_tiles instantiation by its run-time choices (f receives the kernel's address)
+template <typename Fn>
+static hipError_t with_xcorr_kernel(int threads, bool half, bool wide, Fn &&f)
+{
+#define BSIG_XK(NT_) do { if (wide) return f(k_xcorr_tiles<NT_, false, true>); else if (half) return f(k_xcorr_tiles<NT_, true, false>); else return f(k_xcorr_tiles<NT_, false, false>); } while (0)
+    if (threads == 64) BSIG_XK(64);
+    if (threads == 128) BSIG_XK(128);
+    if (threads == 256) BSIG_XK(256);
+#undef BSIG_XK
+    return hipErrorInvalidValue;
+}
+
+int xcorr_blocks_per_cu(int threads, bool half, int tile_cells, int body, int max_lag)
+{
+    int nb = 0;
+    const size_t lds = xcorr_tiles_lds(false, tile_cells, body, max_lag);
+    const hipError_t e = with_xcorr_kernel(threads, half, false, [&](auto k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
+    });
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
+                              int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int body,
+                              int max_lag, unsigned long long n_cells, unsigned long long *out, hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, BSIG_MODE_PROFILE, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
+    }
+    const size_t lds = xcorr_tiles_lds(wide, P.tile_cells, body, max_lag);
+    return with_xcorr_kernel(threads, !wide && P.packed_half != 0, wide, [&](auto k) {
+        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, body, max_lag, n_cells);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)

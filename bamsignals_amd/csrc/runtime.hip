@@ -260,6 +260,16 @@ struct SumState {
     int64_t *d_sum = nullptr;           // device result of bsig_plan_run_sum_host
 };
 
+// an XCORR plan's own (bsig_plan_create_xcorr): tiles of body + halo in genomic order, cut into one round of runs
+struct XcorrState {
+    bsig::XcorrShape shape;
+    int body = 0;                       // body cells of a tile (the image holds body + max_lag: the plan's tile_cells)
+    uint2 *runs = nullptr;              // runs of the main tiles, then those of the wide tiles (one tile each)
+    int64_t n_runs_main = 0, n_runs_wide = 0;
+    int64_t n_cells = 0;                // moments[0]: the sum of the ranges' widths
+    int64_t *d_out = nullptr;           // device result of bsig_plan_run_xcorr_host
+};
+
 struct bsig_plan {
     bsig_ctx *ctx = nullptr;
     const bsig_reads *reads = nullptr;
@@ -292,6 +302,7 @@ struct bsig_plan {
                                         // table are read off that layout, so a plan does not outlive it
     int64_t runs = 0;                   // runs so far (a plan that is run AGAIN is a resident one: plan_two_launches)
     std::unique_ptr<SumState> sum;      // a sum plan's (bsig_plan_create_sum), else null
+    std::unique_ptr<XcorrState> xcorr;  // an xcorr plan's (bsig_plan_create_xcorr), else null
 };
 static int64_t g_resolve_min_override = -1;     // bsig_debug_set_knob(4, n): two launches from n tiles on (sweeps)
 // does a run of this plan look its windows up in a launch of its own?  (measured at the north star's read density,
@@ -1411,11 +1422,36 @@ int bsig::sum_shape(const bsig_params &prm, int64_t n, const int32_t *len, SumSh
     return BSIG_OK;
 }
 
+// What only a strand cross-correlation asks, ahead of check_params: a lag range the kernel's LDS holds, and the one
+// profile the definition is stated in (per base, no shift, no midpoint; stranded by nature, so ss is not read).
+int bsig::xcorr_shape(const bsig_params &prm, int32_t max_lag, XcorrShape *out)
+{
+    if (max_lag < 0 || max_lag > BSIG_XCORR_MAX_LAG)
+        return fail(BSIG_ERR_ARG, "max_lag must be between 0 and %d", BSIG_XCORR_MAX_LAG);
+    if (prm.mode != BSIG_MODE_PROFILE) return fail(BSIG_ERR_ARG, "the strand cross-correlation is defined on bamProfile (mode %d given)", prm.mode);
+    if (prm.binsize != 1) return fail(BSIG_ERR_ARG, "the strand cross-correlation is per base: binsize must be 1");
+    if (prm.shift != 0) return fail(BSIG_ERR_ARG, "the strand cross-correlation measures the shift: shift must be 0");
+    if (prm.pe_mid) return fail(BSIG_ERR_ARG, "the strand cross-correlation has no paired-end midpoint rule");
+    XcorrShape s;
+    s.tiles = prm;
+    s.tiles.ss = 1;
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.max_lag = max_lag;
+    s.body = prm.tile_cells > 0 ? std::min(std::max(prm.tile_cells, 16), 2048) : 2048;
+    s.cells = (int64_t)max_lag + 1 + BSIG_XCORR_MOMENTS;
+    *out = s;
+    return BSIG_OK;
+}
+
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells);
 // sum: a plan for bsig_plan_create_sum -- its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
+// xc: a plan for bsig_plan_create_xcorr -- tiles of a body and an antisense halo, none of them cut into slices
+// (a plan is at most one of the two: never both)
 static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
                             const int32_t *loc, const int32_t *len, const int32_t *strand,
-                            const bsig_params *prm, const bsig::SumShape *sum, bsig_plan **out)
+                            const bsig_params *prm, const bsig::SumShape *sum, bsig_plan **out,
+                            const bsig::XcorrShape *xc = nullptr)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
@@ -1452,6 +1488,9 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // a tile image is at most 32 KiB of LDS
     P->tile_cells = std::min(std::max(P->tile_cells, min_cells), split_ss ? 4096 : 8192);
     P->tile_cells = (P->tile_cells + 3) & ~3;
+    // cross-correlation: a body no wider than the widest range, and an image of the body and a halo of max_lag cells
+    const int xbody = xc ? (int)std::min<int64_t>(xc->body, widest) : 0;
+    if (xc) P->tile_cells = (xbody + xc->max_lag + 3) & ~3;
     P->threads = r.threads;
     BsigKParams &K = P->kp;
     K.mapqual = prm->mapqual;
@@ -1555,6 +1594,16 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
                 if (split) { w.units_strand |= BSIG_ITEM_ATOMIC; P->needs_zero = true; }
                 items.push_back(w);
             }
+        } else if (xc) {
+            // a body of the range's cells and, behind it, as much of max_lag cells as the range still has: the tile is
+            // piled up over body + halo (nc) and correlated over the body, whose length rides in out_off
+            for (int64_t c0 = 0; c0 < len[i]; c0 += xbody) {
+                const int64_t nb = std::min<int64_t>(xbody, len[i] - c0);
+                w.c0 = (int32_t)c0;
+                w.nc = (int32_t)(nb + std::min<int64_t>(xc->max_lag, len[i] - c0 - nb));
+                w.out_off = nb;
+                items.push_back(w);
+            }
         } else {
             const int64_t cells = (P->off[i + 1] - P->off[i]) / mult;
             for (int64_t c0 = 0; c0 < cells; c0 += P->tile_cells) {
@@ -1609,12 +1658,21 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
         std::vector<uint2> hwin;
+        long double xc_heavy_sq = 0;
         if (e == hipSuccess && n_heavy_dev) {
             for (size_t t = 0; t < items.size(); ++t) {
                 int64_t total = 0;
                 for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
                 if (total <= heavy_reads) continue;
                 ++P->n_heavy_tiles;
+                if (xc) {
+                    // a product of two counts is not linear in slices of the reads: such a tile is walked whole, by one
+                    // workgroup of the second launch, into an image of 32-bit cells
+                    hitems.push_back(items[t]);
+                    xc_heavy_sq += (long double)total * (long double)total;
+                    items[t].units_strand |= BSIG_ITEM_HEAVY;
+                    continue;
+                }
                 BsigWorkItem sl = items[t];
                 if (P->kernel_mode == BSIG_MODE_COUNT) sl.units_strand |= BSIG_ITEM_ATOMIC;
                 for (int c = 0; c < BSIG_MAX_CLASSES; ++c) {
@@ -1632,10 +1690,10 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             P->n_heavy_slices = (int64_t)hitems.size();
             uint2 *hw = nullptr;
             e = P->pool.alloc(&P->heavy_items, hitems.size());
-            if (e == hipSuccess) e = P->pool.alloc(&hw, hwin.size());
+            if (e == hipSuccess && !hwin.empty()) e = P->pool.alloc(&hw, hwin.size());
             P->heavy_windows = hw;
             if (e == hipSuccess) e = hipMemcpyAsync(P->heavy_items, hitems.data(), hitems.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(hw, hwin.data(), hwin.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess && hw) e = hipMemcpyAsync(hw, hwin.data(), hwin.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
             // the heavy flags of the main items
             if (e == hipSuccess) e = hipMemcpyAsync(P->items, items.data(), items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
             // binned coverage: the slices' atomic adds are the only ones that can take a bin past INT32_MAX
@@ -1644,10 +1702,27 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             K.overflow = P->overflow;
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
+        // The cross-correlation's proof that no 64-bit sum wraps.  A tile with n reads in its windows counts each of
+        // them in at most one cell, so sum(S) + sum(A) <= n and every sum the tile adds to -- a lag's S[x] A[x + d], a
+        // strand's squares -- is at most n^2.  The tiles that are not heavy have n <= 2^15; the heavy ones' n is known.
+        if (e == hipSuccess && xc) {
+            const long double bound = (long double)(P->n_items - P->n_heavy_tiles) * 1073741824.0L + xc_heavy_sq;
+            if (bound >= 9223372036854775808.0L) {
+                delete P;
+                return fail(BSIG_ERR_ARG, "the cross-correlation of these ranges could exceed 2^63 - 1 (the squared read counts "
+                                          "of their tiles add up to %.3Lg): correlate fewer ranges per call", bound);
+            }
+        }
     }
     if (e != hipSuccess) {
         delete P;
         return fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "plan upload failed: %s", hipGetErrorString(e));
+    }
+    if (xc) {
+        int64_t n_cells = 0;
+        for (int64_t i = 0; i < n; ++i) n_cells += len[i];
+        const int rc = xcorr_setup(P, *xc, xbody, (int64_t)hitems.size(), n_cells);
+        if (rc != BSIG_OK) { delete P; return rc; }
     }
     if (sum) {
         const int rc = sum_setup(P, *sum, items, hitems);
@@ -1727,6 +1802,46 @@ static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vecto
     return BSIG_OK;
 }
 
+// The runs of an xcorr plan: the tiles, in genomic order, cut into as many runs as workgroups are resident at a time (by
+// occupancy), so that one round of workgroups walks the whole plan and each keeps its per-lag sums in LDS across its run
+// -- a whole-genome call then ends in one 64-bit atomic per lag and workgroup instead of one per lag and tile.  The wide
+// tiles (32-bit image) follow as runs of one tile each: they are few and long.
+static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells)
+{
+    P->xcorr.reset(new XcorrState);
+    XcorrState &Q = *P->xcorr;
+    Q.shape = shape;
+    Q.body = body;
+    Q.n_cells = n_cells;
+    int n_cu = 0, lds_max = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
+    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    const size_t lds = bsig::xcorr_tiles_lds(n_wide > 0, P->tile_cells, body, shape.max_lag);
+    if (lds > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "a tile of %d + %d cells needs %zu bytes of LDS per workgroup, the device has %d", body,
+                    shape.max_lag, lds, lds_max);
+    const int64_t resident = (int64_t)std::max(n_cu, 1) *
+                             bsig::xcorr_blocks_per_cu(P->threads, P->kp.packed_half != 0, P->tile_cells, body, shape.max_lag);
+    int64_t per = std::max<int64_t>(1, (P->n_items + resident - 1) / resident);
+    // (tests: BAMSIGNALS_XCORR_RUN_TILES = tiles per run instead of the occupancy's, read when the plan is made)
+    if (const char *v = getenv("BAMSIGNALS_XCORR_RUN_TILES")) {
+        const long long forced = atoll(v);
+        if (forced > 0) per = forced;
+    }
+    std::vector<uint2> runs;
+    for (int64_t a = 0; a < P->n_items; a += per) runs.push_back(make_uint2((uint32_t)a, (uint32_t)std::min<int64_t>(P->n_items, a + per)));
+    Q.n_runs_main = (int64_t)runs.size();
+    for (int64_t a = 0; a < n_wide; ++a) runs.push_back(make_uint2((uint32_t)a, (uint32_t)a + 1u));
+    Q.n_runs_wide = n_wide;
+    if (!runs.empty()) {
+        hipStream_t st = P->ctx->stream;
+        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
+        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return BSIG_OK;
+}
+
 extern "C" {
 
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
@@ -1771,6 +1886,7 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
+    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1803,6 +1919,7 @@ int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
+    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
     const bsig::HostDest dst{out_host};
     return bsig::plan_run_to_host(p, &dst, nullptr);
 }
@@ -1850,6 +1967,27 @@ int bsig::plan_run_to_host(bsig_plan *p, const HostDest *dst, int64_t *sum, bool
     if (t_download) *t_download = since(t1);
     return rc != BSIG_OK || Q ? rc : plan_check_overflow(p);
 }
+int bsig::plan_run_xcorr_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    XcorrState *Q = p->xcorr.get();
+    if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->shape.cells));
+    const int rc = bsig_plan_run_xcorr(p, Q->d_out);
+    if (rc != BSIG_OK) return rc;
+    if (t_kernels) {
+        HIP_TRY(hipStreamSynchronize(st));
+        *t_kernels = since(t0);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->shape.cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (t_download) *t_download = since(t1);
+    return BSIG_OK;
+}
 // a run whose slices took a bin past INT32_MAX fails (after the caller's synchronisation: no wait of its own)
 int bsig::plan_check_overflow(bsig_plan *p)
 {
@@ -1865,6 +2003,7 @@ int bsig_plan_run_host_async(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
+    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
     const bsig::HostDest dst{out_host};
     return bsig::plan_run_to_host(p, &dst, nullptr, true);
 }
@@ -1891,7 +2030,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     bsig_plan_stats t{};
     t.n_ranges = p->n_ranges;
     t.n_items = p->n_items;
-    t.cells = p->sum ? p->sum->shape.cells : p->off.back();
+    t.cells = p->sum ? p->sum->shape.cells : p->xcorr ? p->xcorr->shape.cells : p->off.back();
     t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
     t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
     t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
@@ -1904,7 +2043,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
     t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
                           t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
-                          (p->sum ? 8 : 4) * t.cells;
+                          (p->sum || p->xcorr ? 8 : 4) * t.cells;
     if (plan_two_launches(p) && windows_kept()) {
         // a resident plan's step reads the windows kept from its first run: no index entry is touched
         t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
@@ -1937,6 +2076,7 @@ int64_t bsig_plan_sum_cells(const bsig_plan *p) { return p && p->sum ? p->sum->s
 int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
     if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
     const SumState &Q = *p->sum;
     const int64_t cells = Q.shape.cells;
@@ -1974,8 +2114,58 @@ int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
     if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
     return bsig::plan_run_to_host(p, nullptr, sum_host);
+}
+
+int bsig_plan_create_xcorr(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                           const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t max_lag, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_xcorr");
+    *out = nullptr;
+    bsig::XcorrShape shape;
+    const int rc = bsig::xcorr_shape(*prm, max_lag, &shape);
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, nullptr, out, &shape);
+}
+
+int64_t bsig_plan_xcorr_cells(const bsig_plan *p) { return p && p->xcorr ? p->xcorr->shape.cells : 0; }
+
+int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum runs it" : "not an xcorr plan: bsig_plan_run runs it");
+    const XcorrState &Q = *p->xcorr;
+    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
+    if (p->reads->layout_gen != p->made_for_gen)
+        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    const int max_lag = Q.shape.max_lag;
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
+    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)Q.shape.cells * sizeof(int64_t), st));
+    if (Q.n_runs_main) {
+        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+            return bsig::launch_xcorr_tiles(p->threads, false, p->reads->dev, kp, p->items, p->n_items, Q.runs, Q.n_runs_main,
+                                            resolved, lookup, Q.body, max_lag, (unsigned long long)Q.n_cells, out, st);
+        });
+        if (rc != BSIG_OK) return rc;
+    }
+    // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
+    // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
+    if (Q.n_runs_wide)
+        HIP_TRY(bsig::launch_xcorr_tiles(p->threads, true, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                         Q.runs + Q.n_runs_main, Q.n_runs_wide, nullptr, false, Q.body, max_lag, 0ull, out, st));
+    ++p->runs;
+    return BSIG_OK;
+}
+
+int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum_host runs it" : "not an xcorr plan: bsig_plan_run_host runs it");
+    return bsig::plan_run_xcorr_to_host(p, host);
 }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)

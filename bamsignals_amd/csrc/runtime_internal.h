@@ -255,6 +255,17 @@ struct SumShape {
     int64_t cells;          // ceil(width / binsize), twice that with strands
 };
 int sum_shape(const bsig_params &prm, int64_t n, const int32_t *len, SumShape *out);
+// what only a strand cross-correlation asks, ahead of check_params (runtime.hip: xcorr_shape): max_lag in range, a
+// stranded per-base profile without shift or midpoint
+struct XcorrShape {
+    bsig_params tiles;      // the per-base, strand-split plan the tiles are piled up by
+    int32_t max_lag;
+    int32_t body;           // body cells of a tile at most (the caller's tile_cells, or the default)
+    int64_t cells;          // max_lag + 1 + BSIG_XCORR_MOMENTS
+};
+int xcorr_shape(const bsig_params &prm, int32_t max_lag, XcorrShape *out);
+// bsig_plan_run_xcorr into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
+int plan_run_xcorr_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

@@ -352,6 +352,55 @@ class SumPlan:
         self.close()
 
 
+class XcorrPlan:
+    """Ranges + call parameters resident in HBM for the strand cross-correlation (bsig_plan_create_xcorr): each run gives
+    ``max_lag + 1 + 5`` int64 -- ``cross[d]``, the sum over ranges and cells of sense[x] * antisense[x + d] of the ranges'
+    per-base, strand-split, unshifted ``Plan`` result, then the moments [cells, sum S, sum A, sum S^2, sum A^2].
+    ``params``: a per-base profile without shift or midpoint; ``tile_cells`` = body cells of a tile, ``threads`` per
+    workgroup.  ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit image."""
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, max_lag):
+        self._lib = _lib.load()
+        self.ctx, self.reads = ctx, reads
+        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_create_xcorr(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
+                                                    _ptr(strand), C.byref(params), int(max_lag), C.byref(h)))
+        self._h = h
+        self.n_ranges = n
+        self.max_lag = int(max_lag)
+        self.cells = int(self._lib.bsig_plan_xcorr_cells(h))
+
+    def run_host(self, out=None):
+        """Run and return the int64 result in host memory: ``out[:max_lag + 1]`` is cross, the rest the moments."""
+        if out is None:
+            out = np.empty(self.cells, dtype=np.int64)
+        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
+        _lib.check(self._lib.bsig_plan_run_xcorr_host(self._h, _ptr(out)))
+        return out
+
+    def run_device(self, out_ptr):
+        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
+        _lib.check(self._lib.bsig_plan_run_xcorr(self._h, C.c_void_p(out_ptr)))
+
+    def stats(self):
+        s = _lib.PlanStats()
+        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class SegmentMap:
     """Device-side reassembly of sharded results: segment k of a source buffer goes to the destination at
     ``dst_off[which[k]]`` (bsig_segmap_*; the host-side twin is bsig_scatter_segments).  The tables are

@@ -175,6 +175,21 @@ def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1,
     return _sum_shape(out, ss)
 
 
+def pileup_xcorr(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, max_lag=500, maxgap=16385, device=None):
+    """The strand cross-correlation over the ranges (bsig_pileup_xcorr): ``max_lag + 1 + 5`` int64, cross then moments."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    out = np.zeros(max(int(max_lag), 0) + 1 + _lib.XCORR_MOMENTS, dtype=np.int64)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_pileup_xcorr(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
+                                     names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
+                                     tf.ctypes.data, len(tf), int(mapqual), int(requiredF), int(filteredF),
+                                     int(max_lag), int(maxgap), _dev(device), out.ctypes.data))
+    return out
+
+
 def _is_ex(binsize, ss):
     """bins or strands take bsig_coverage_core_ex[_into]; the defaults keep the reference's own entry point"""
     return int(binsize) != 1 or bool(ss)

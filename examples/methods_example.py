@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from bamsignals_amd import GRanges, bamCount, bamCoverage, bamProfile  # noqa: E402
+from bamsignals_amd import GRanges, bamCount, bamCoverage, bamCrossCorr, bamProfile  # noqa: E402
 
 bampath = os.path.join(ROOT, "tests", "golden", "randomBam.bam")
 reg = json.load(open(os.path.join(ROOT, "tests", "golden", "regions.json")))
@@ -32,3 +32,8 @@ print(bamCount(bampath, genes, paired_end="midpoint", tlenFilter=(50, 300), verb
 # per-base coverage, fragments extended to the whole template
 cov = bamCoverage(bampath, genes, paired_end="extend", verbose=False)
 print(cov[0][:20])
+
+# the data's own value for `shift`: the lag at which forward and reverse 5' ends line up best over the genes
+cc = bamCrossCorr(bampath, genes, maxlag=300, verbose=False)
+print(cc.fragment_length(), cc.fragment_length() // 2)
+print(bamCount(bampath, genes, shift=cc.fragment_length() // 2, verbose=False))

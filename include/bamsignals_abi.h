@@ -229,6 +229,29 @@ int64_t bsig_plan_sum_cells(const bsig_plan *plan);              /* n_bins * (ss
 int bsig_plan_run_sum(bsig_plan *plan, int64_t *sum_dev);
 int bsig_plan_run_sum_host(bsig_plan *plan, int64_t *sum_host);
 
+/* Strand cross-correlation over ranges: the lag at which the 5' ends on a range's strand line up best with those on
+ * the other strand -- the fragment length read off the data, i.e. the value for `shift`.  With S_i, A_i the sense and
+ * antisense rows of bsig_plan_create's plan for range i (mode BSIG_MODE_PROFILE, binsize 1, shift 0, ss 1; width w_i):
+ *   cross[d] = sum_i sum_{x = 0 .. w_i - 1 - d} S_i[x] * A_i[x + d]     d = 0 .. max_lag   (nothing outside a range counts)
+ *   moments  = [ sum_i w_i, sum S_i[x], sum A_i[x], sum S_i[x]^2, sum A_i[x]^2 ]          (over all cells of all ranges)
+ * The result is bsig_plan_xcorr_cells() = max_lag + 1 + BSIG_XCORR_MOMENTS int64: cross, then moments.  Ranges may
+ * differ in width, overlap, repeat (a repeated range counts twice), overhang their reference or be empty.
+ * params: mode BSIG_MODE_PROFILE, binsize 1, shift 0, pe_mid 0 (anything else: BSIG_ERR_ARG); ss is ignored; tile_cells =
+ * body cells of a tile (16 .. 2,048; 0: 2,048), threads 64 / 128 / 256 per workgroup (0: 256).  max_lag outside
+ * 0 .. BSIG_XCORR_MAX_LAG: BSIG_ERR_ARG.  No sum ever wraps: the plan proves from the reads in its tiles' windows that
+ * every one stays below 2^63, or bsig_plan_create_xcorr fails with BSIG_ERR_ARG.  bsig_plan_get_stats' heavy_tiles counts
+ * the tiles that took the 32-bit image (more reads in their windows than a 16-bit cell may see).  An xcorr plan runs with
+ * bsig_plan_run_xcorr* only, and no other plan does (BSIG_ERR_ARG).                                                     */
+#define BSIG_XCORR_MAX_LAG 2047      /* the 64-bit accumulators of all lags + a 32-bit image of body + halo: 64 KiB of LDS */
+#define BSIG_XCORR_MOMENTS 5
+int bsig_plan_create_xcorr(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                           const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t max_lag,
+                           bsig_plan **plan);
+int64_t bsig_plan_xcorr_cells(const bsig_plan *plan);            /* max_lag + 1 + BSIG_XCORR_MOMENTS            */
+/* asynchronous, on the context's stream; dev: bsig_plan_xcorr_cells() int64 on the device, 8-B aligned               */
+int bsig_plan_run_xcorr(bsig_plan *plan, int64_t *dev);
+int bsig_plan_run_xcorr_host(bsig_plan *plan, int64_t *host);
+
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
 int bsig_pileup_columns(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
                         const int32_t *rid, const int32_t *loc, const int32_t *len,
@@ -377,6 +400,16 @@ int bsig_coverage_sum(const char *bampath, int64_t n_ranges, const int32_t *seq_
                       const int32_t *tlen_filter, int32_t n_tlen_filter,
                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                       int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum);
+/* The strand cross-correlation over the ranges (bsig_plan_create_xcorr): out receives max_lag + 1 + BSIG_XCORR_MOMENTS
+ * int64, cross then moments.  max_lag and the parameters are checked before the BAM is decoded.  With several GPUs each
+ * takes its block of the (rid, loc)-sorted ranges and the host adds the vectors (bsig_last_call_route(): "sum", as
+ * bsig_pileup_sum).                                                                                                 */
+int bsig_pileup_xcorr(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                      int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                      const int32_t *width, const int32_t *strand,
+                      const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t max_lag, int32_t maxgap,
+                      int32_t device, int64_t *out);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
