@@ -16,6 +16,8 @@ BSIG_OK = 0
 MODE_PROFILE, MODE_COUNT, MODE_COVERAGE, MODE_COVERAGE_EX = 0, 1, 2, 3
 # include/bamsignals_abi.h: BSIG_XCORR_MAX_LAG, BSIG_XCORR_MOMENTS
 XCORR_MAX_LAG, XCORR_MOMENTS = 2047, 5
+# include/bamsignals_abi.h: BSIG_FRAG_MAX_ROWS
+FRAG_MAX_ROWS = 16384
 
 ERR_NAMES = {-1: "BSIG_ERR_ARG", -2: "BSIG_ERR_IO", -3: "BSIG_ERR_NOINDEX", -4: "BSIG_ERR_CHROM",
              -5: "BSIG_ERR_EXT", -6: "BSIG_ERR_DEVICE", -7: "BSIG_ERR_NOMEM", -8: "BSIG_ERR_FORMAT"}
@@ -119,6 +121,13 @@ def load():
     lib.bsig_plan_xcorr_cells.restype = C.c_int64
     lib.bsig_plan_run_xcorr.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_xcorr_host.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_create_frag.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
+    lib.bsig_plan_frag_cells.argtypes = [C.c_void_p]
+    lib.bsig_plan_frag_cells.restype = C.c_int64
+    lib.bsig_plan_frag_runs.argtypes = [C.c_void_p]
+    lib.bsig_plan_frag_runs.restype = C.c_int64
+    lib.bsig_plan_run_frag.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_run_frag_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_pileup_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
     lib.bsig_bam_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -153,6 +162,7 @@ def load():
     lib.bsig_pileup_sum.argtypes = core_head + [C.c_int32] * 9 + [C.c_void_p]
     lib.bsig_coverage_sum.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_pileup_xcorr.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
+    lib.bsig_pileup_frag.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
     lib.bsig_write_sam_as_bam_and_index.argtypes = [C.c_char_p, C.c_char_p]
     lib.bsig_write_columns_as_bam.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(Columns),
                                               C.c_int32]

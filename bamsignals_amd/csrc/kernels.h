@@ -82,6 +82,15 @@ int xcorr_blocks_per_cu(int threads, bool half, int tile_cells, int body, int ma
 hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                               int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int body,
                               int max_lag, unsigned long long n_cells, unsigned long long *out, hipStream_t st);
+// Fragment-length histogram over ranges (bsig_plan_create_frag).  k_frag_tiles: run r = count tiles [runs[r].x, runs[r].y);
+// every workgroup ADDS its non-zero rows into out (n_rows int64): zero `out` first.  P.div_magic / P.div_shift divide by
+// lenbin (>= 2).  merge: equal rows of a wave are merged before the LDS atomic.  windows / resolve_first as in
+// launch_sum_tiles (no fixed windows).
+size_t frag_tiles_lds(int n_rows);
+int frag_blocks_per_cu(int threads, bool merge, int n_rows);
+hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
+                             int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int n_rows,
+                             int lenbin, unsigned long long *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

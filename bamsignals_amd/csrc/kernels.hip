@@ -1918,6 +1918,91 @@ __global__ __launch_bounds__(NT) void k_xcorr_tiles(const BsigWorkItem *__restri
 }
 
 // ------------------------------------------------------------------------------------------
+// Fragment-length histogram over ranges (bsig_plan_create_frag)
+// ------------------------------------------------------------------------------------------
+// A tile is a sub-interval [loc + c0, loc + c0 + nc) of a range, as a count tile is; it has no image.  A workgroup owns a
+// run of tiles and keeps ONE histogram of n_rows 32-bit counters in LDS for all of them: a read that is the first of a
+// proper pair (the plan's flag masks), whose |tlen| = a lies in the filter and whose position -- its 5' end, moved by
+// a / 2 under the midpoint rule -- lies in the tile adds 1 to row a / lenbin.  At the end of its run the workgroup adds
+// its non-zero rows to the int64 result with one 64-bit atomic each.
+// Exactness.  Every read in a tile's windows adds at most 1, and the plan cuts the runs so that the reads in a run's
+// windows stay below 2^32 (runtime.hip: frag_setup): no LDS counter wraps.  a < 2^31 is divided by lenbin with the
+// round-up multiplier of host_util.h (magic_u31), full width: a reaches 2^30, so no 24-bit multiply touches it or the
+// midpoint offset.
+// Contention.  All increments of a run land on n_rows LDS cells, and real lengths crowd onto a few hundred of them; a
+// pile of duplicates puts every lane of a wave on ONE cell, which the LDS serves one lane per cycle.  MERGE: the lanes
+// that hold the same row as the wave's first accepted lane are counted with a ballot and added by that lane alone; the
+// other rows take their own atomics.  A pile then costs one LDS cycle instead of 64; a wave of all-different rows pays
+// two scalar instructions and a lane read more than the plain form.
+template <bool MERGE>
+struct FragOne {
+    const BsigKParams &P;
+    uint32_t *hist;
+    int glo, gn, lenbin;
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        const int a = tl < 0 ? -tl : tl;
+        bool ok = valid & !rej & (a >= P.tf0) & (a <= P.tf1);
+        const int offset = P.midpoint ? a >> 1 : 0;
+        const int p5 = neg ? e - offset : p + offset;
+        ok = ok & ((unsigned)(p5 - glo) < (unsigned)gn);
+        // (P.div_magic / P.div_shift are lenbin's in a frag plan: its tiles are count tiles, whose binsize is not read)
+        const uint32_t row = lenbin == 1 ? (uint32_t)a : __umulhi((uint32_t)a, P.div_magic) >> P.div_shift;
+        if constexpr (MERGE) {
+            const unsigned long long m = __ballot(ok);
+            if (m == 0ull) return;                              // (uniform over the active lanes)
+            const int leader = __ffsll((long long)m) - 1;
+            const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)row, leader);
+            const bool same = ok & (row == r0);
+            const uint32_t n_same = (uint32_t)__popcll(__ballot(same));
+            const bool lead = (int)__lane_id() == leader;
+            if (ok & (!same | lead)) atomicAdd(&hist[row], same ? n_same : 1u);
+        } else {
+            if (ok) atomicAdd(&hist[row], 1u);
+        }
+    }
+};
+
+// LDS of one k_frag_tiles workgroup, in dwords: histogram | filter table (LTAB)
+__host__ __device__ inline int frag_hist_dwords(int n_rows) { return (n_rows + 3) & ~3; }
+
+// LTAB: the packed class's filter table is copied into LDS (as everywhere else); without, at the row cap, where the
+// histogram alone fills the 64 KiB a workgroup may ask for, its 512 bytes are read from global memory
+template <int NT, bool MERGE, bool LTAB>
+__global__ __launch_bounds__(NT) void k_frag_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                   unsigned long long *__restrict__ out, const uint2 *__restrict__ windows,
+                                                   const BsigReadsDev R, const BsigKParams P, int n_rows, int lenbin)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const int tid = threadIdx.x;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
+    for (int v = tid; v < n_rows; v += NT) hist[v] = 0u;
+    const uint8_t *ptab = P.ptab;
+    if constexpr (LTAB) {
+        uint8_t *lt = reinterpret_cast<uint8_t *>(lds + frag_hist_dwords(n_rows));
+        build_ptab<NT>(lt, R, P, tid);
+        ptab = lt;
+    }
+    const uint2 run = runs[blockIdx.x];
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        uint2 win[BSIG_MAX_CLASSES], clip;
+        PackedWin pk;
+        load_windows<false>(R, P, BSIG_MODE_COUNT, w, items, windows, win, t, pk, clip);
+        const FragOne<MERGE> one{P, hist, w.loc + w.c0, w.nc, lenbin};
+        for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+        if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COUNT, w, pk.n_chunks, clip, ptab, tid, one);
+    }
+    __syncthreads();
+    for (int v = tid; v < n_rows; v += NT) {
+        const uint32_t c = hist[v];
+        if (c) atomicAdd(out + v, (unsigned long long)c);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // one-time layout of the reads in HBM
 // ------------------------------------------------------------------------------------------
 
@@ -2597,6 +2682,54 @@ hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, con
     const size_t lds = xcorr_tiles_lds(wide, P.tile_cells, body, max_lag);
     return with_xcorr_kernel(threads, !wide && P.packed_half != 0, wide, [&](auto k) {
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, body, max_lag, n_cells);
+        return hipGetLastError();
+    });
+}
+
+// ---- fragment-length histogram --------------------------------------------------------------------------------------
+static bool frag_ltab(int n_rows) { return (size_t)frag_hist_dwords(n_rows) * 4 + BSIG_PACK_CODES <= 65536; }
+size_t frag_tiles_lds(int n_rows)
+{
+    return (size_t)frag_hist_dwords(n_rows) * 4 + (frag_ltab(n_rows) ? BSIG_PACK_CODES : 0);
+}
+
+// one k_frag_tiles instantiation by its run-time choices (f receives the kernel's address)
+template <typename Fn>
+static hipError_t with_frag_kernel(int threads, bool merge, bool ltab, Fn &&f)
+{
+#define BSIG_FK(NT_) do { if (merge) { if (ltab) return f(k_frag_tiles<NT_, true, true>); return f(k_frag_tiles<NT_, true, false>); } \
+                          if (ltab) return f(k_frag_tiles<NT_, false, true>); return f(k_frag_tiles<NT_, false, false>); } while (0)
+    if (threads == 64) BSIG_FK(64);
+    if (threads == 128) BSIG_FK(128);
+    if (threads == 256) BSIG_FK(256);
+#undef BSIG_FK
+    return hipErrorInvalidValue;
+}
+
+int frag_blocks_per_cu(int threads, bool merge, int n_rows)
+{
+    int nb = 0;
+    const size_t lds = frag_tiles_lds(n_rows);
+    const hipError_t e = with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
+    });
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
+                             int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int n_rows,
+                             int lenbin, unsigned long long *out, hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, BSIG_MODE_COUNT, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
+    }
+    const size_t lds = frag_tiles_lds(n_rows);
+    return with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k) {
+        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, lenbin);
         return hipGetLastError();
     });
 }

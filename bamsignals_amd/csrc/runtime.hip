@@ -270,6 +270,15 @@ struct XcorrState {
     int64_t *d_out = nullptr;           // device result of bsig_plan_run_xcorr_host
 };
 
+// a FRAG plan's own (bsig_plan_create_frag): count tiles in genomic order, cut into one round of runs
+struct FragState {
+    bsig::FragShape shape;
+    bool merge = false;                 // k_frag_tiles' form: equal rows of a wave merged before the LDS atomic (see frag_setup)
+    uint2 *runs = nullptr;
+    int64_t n_runs = 0;
+    int64_t *d_out = nullptr;           // device result of bsig_plan_run_frag_host
+};
+
 struct bsig_plan {
     bsig_ctx *ctx = nullptr;
     const bsig_reads *reads = nullptr;
@@ -303,6 +312,7 @@ struct bsig_plan {
     int64_t runs = 0;                   // runs so far (a plan that is run AGAIN is a resident one: plan_two_launches)
     std::unique_ptr<SumState> sum;      // a sum plan's (bsig_plan_create_sum), else null
     std::unique_ptr<XcorrState> xcorr;  // an xcorr plan's (bsig_plan_create_xcorr), else null
+    std::unique_ptr<FragState> frag;    // a frag plan's (bsig_plan_create_frag), else null
 };
 static int64_t g_resolve_min_override = -1;     // bsig_debug_set_knob(4, n): two launches from n tiles on (sweeps)
 // does a run of this plan look its windows up in a launch of its own?  (measured at the north star's read density,
@@ -1443,15 +1453,42 @@ int bsig::xcorr_shape(const bsig_params &prm, int32_t max_lag, XcorrShape *out)
     return BSIG_OK;
 }
 
+// What only a fragment-length histogram asks, ahead of check_params: bamCount's tiles without a shift, a length filter
+// (its upper end sizes the result) and as many rows as the kernel's LDS holds.  ss is not read: the range's strand does
+// not influence the result.
+int bsig::frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out)
+{
+    if (prm.mode != BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the fragment-length histogram is defined on bamCount (mode %d given)", prm.mode);
+    if (prm.shift != 0) return fail(BSIG_ERR_ARG, "the fragment-length histogram counts unshifted positions: shift must be 0");
+    if (prm.n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "the fragment-length histogram needs a 2-element tlen_filter");
+    if (len_bin < 1) return fail(BSIG_ERR_ARG, "len_bin must be greater or equal to 1");
+    if (prm.tlen_filter[1] < 0) return fail(BSIG_ERR_ARG, "tlen_filter[1] must not be negative");
+    const int64_t rows = (int64_t)prm.tlen_filter[1] / len_bin + 1;
+    if (rows > BSIG_FRAG_MAX_ROWS)
+        return fail(BSIG_ERR_ARG, "tlen_filter[1] / len_bin + 1 = %lld rows, at most %d fit: choose a wider len_bin", (long long)rows, BSIG_FRAG_MAX_ROWS);
+    FragShape s;
+    s.tiles = prm;
+    s.tiles.ss = 0;
+    s.tiles.pe_mid = prm.pe_mid != 0;
+    s.tiles.tlen_filter[0] = std::max(prm.tlen_filter[0], 0);      // (a length is never negative: rows start at 0)
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.len_bin = len_bin;
+    s.cells = rows;
+    *out = s;
+    return BSIG_OK;
+}
+
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &tile_reads);
 static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells);
 // sum: a plan for bsig_plan_create_sum -- its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
 // xc: a plan for bsig_plan_create_xcorr -- tiles of a body and an antisense halo, none of them cut into slices
-// (a plan is at most one of the two: never both)
+// fr: a plan for bsig_plan_create_frag -- count tiles, none of them cut into slices (they have no image)
+// (a plan is at most one of the three)
 static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
                             const int32_t *loc, const int32_t *len, const int32_t *strand,
                             const bsig_params *prm, const bsig::SumShape *sum, bsig_plan **out,
-                            const bsig::XcorrShape *xc = nullptr)
+                            const bsig::XcorrShape *xc = nullptr, const bsig::FragShape *fr = nullptr)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
@@ -1532,7 +1569,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         half = half && (int64_t)K.tile_cells + 2 * r.ext + C.maxspan + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
         K.packed_half = half ? 1 : 0;
     }
-    bsig::magic_u31(K.binsize, &K.div_magic, &K.div_shift);
+    // (a frag plan's tiles are count tiles, which divide by no binsize: the multiplier is its row width's)
+    bsig::magic_u31(fr ? fr->len_bin : K.binsize, &K.div_magic, &K.div_shift);
     K.div_m15 = 0; K.div_s15 = 0;
     if (K.binsize >= 2 && K.binsize <= 8192) {
         // s = 15 + ceil(log2 b), m = ceil(2^s / b): n * m / 2^s = n / b + n * e / (b * 2^s) with e < b, and the second
@@ -1555,7 +1593,9 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     const int64_t mult = K.ss ? 2 : 1;
     // count mode: bases per workgroup (with the window's reach on both sides still one chunk of the packed
     // class's position bits: one index lookup per tile)
-    const int count_split = 1 << (BSIG_PACK_POS_BITS - 1);
+    // (a frag plan's tile_cells: bases per tile, for tests of the tiles' seams)
+    const int count_split = fr && prm->tile_cells > 0 ? std::min(std::max(prm->tile_cells, 16), 1 << (BSIG_PACK_POS_BITS - 1))
+                                                      : 1 << (BSIG_PACK_POS_BITS - 1);
     // bins wider than a workgroup should stream on its own: every bin becomes bamCount-style
     // sub-intervals that add into the (zeroed) result with integer atomics
     const bool wide_bins = mode == BSIG_MODE_PROFILE && prm->tile_cells <= 0 && K.binsize > count_split / 2;
@@ -1639,6 +1679,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // need the same ceiling: 32,767 reads adding at most 65,536 each stay below 2^31)
     if (P->kernel_mode == BSIG_MODE_COVERAGE) heavy_reads = std::min<int64_t>(heavy_reads, 32767);
     std::vector<BsigWorkItem> hitems;
+    std::vector<int64_t> frag_reads;        // a frag plan: the reads in every tile's windows
     if (e == hipSuccess && !items.empty()) {
         DevPool tmp;
         uint2 *d_win = nullptr;
@@ -1651,15 +1692,24 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         if (e == hipSuccess) e = bsig::launch_count_heavy(d_win, P->n_items, heavy_reads, d_heavy, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        // the windows themselves are only fetched when there is something to slice
-        if (e == hipSuccess && n_heavy_dev) {
+        // the windows themselves are only fetched when there is something to slice (a frag plan cuts its runs by them)
+        if (e == hipSuccess && (n_heavy_dev || fr)) {
             win.resize(items.size() * BSIG_MAX_CLASSES);
             e = hipMemcpyAsync(win.data(), d_win, win.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
         std::vector<uint2> hwin;
         long double xc_heavy_sq = 0;
-        if (e == hipSuccess && n_heavy_dev) {
+        if (e == hipSuccess && fr) {
+            // a tile of a histogram has no image that its reads could overflow: none is heavy, none is sliced
+            frag_reads.resize(items.size());
+            for (size_t t = 0; t < items.size(); ++t) {
+                int64_t total = 0;
+                for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
+                frag_reads[t] = total;
+            }
+        }
+        if (e == hipSuccess && n_heavy_dev && !fr) {
             for (size_t t = 0; t < items.size(); ++t) {
                 int64_t total = 0;
                 for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
@@ -1726,6 +1776,10 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     }
     if (sum) {
         const int rc = sum_setup(P, *sum, items, hitems);
+        if (rc != BSIG_OK) { delete P; return rc; }
+    }
+    if (fr) {
+        const int rc = frag_setup(P, *fr, frag_reads);
         if (rc != BSIG_OK) { delete P; return rc; }
     }
     *out = P;
@@ -1842,6 +1896,63 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
     return BSIG_OK;
 }
 
+// The runs of a frag plan: the tiles, in genomic order, cut into as many runs as workgroups are resident at a time (by
+// occupancy), as an xcorr plan's are -- a workgroup keeps its histogram in LDS across its run and ends with one 64-bit
+// atomic per non-zero row.  The histogram's counters have 32 bits and every read in a tile's windows adds at most 1 to
+// one of them, so a run also ends where the reads in its tiles' windows would pass the ceiling of 2^32 - 1: no counter
+// wraps.  (A single tile cannot hold that many: its windows are index ranges of 32 bits in five classes, and the plan
+// refuses the one that would.)
+static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &tile_reads)
+{
+    constexpr int64_t kCounterMax = 4294967295ll;
+    P->frag.reset(new FragState);
+    FragState &Q = *P->frag;
+    Q.shape = shape;
+    // The form: one LDS atomic per accepted read ("plain", the default), or the rows equal to the wave's first accepted
+    // lane's merged before it ("merge").  The merging form becomes the default only where scripts/fragsizes_times.py
+    // shows it faster than the plain one by more than the runs' spread: BAMSIGNALS_FRAG_FORM chooses, read
+    // when the plan is made.
+    if (const char *v = getenv("BAMSIGNALS_FRAG_FORM")) Q.merge = strcmp(v, "merge") == 0;
+    int n_cu = 0, lds_max = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
+    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    const size_t lds = bsig::frag_tiles_lds((int)shape.cells);
+    if (lds > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "%lld rows need %zu bytes of LDS per workgroup, the device has %d", (long long)shape.cells, lds, lds_max);
+    const int64_t resident = (int64_t)std::max(n_cu, 1) * bsig::frag_blocks_per_cu(P->threads, Q.merge, (int)shape.cells);
+    int64_t per = std::max<int64_t>(1, (P->n_items + resident - 1) / resident);
+    // (tests: BAMSIGNALS_FRAG_RUN_TILES = tiles per run instead of the occupancy's, BAMSIGNALS_FRAG_FLUSH_READS = a lower
+    // ceiling for the reads of a run; both read when the plan is made)
+    if (const char *v = getenv("BAMSIGNALS_FRAG_RUN_TILES")) {
+        const long long forced = atoll(v);
+        if (forced > 0) per = forced;
+    }
+    int64_t ceiling = kCounterMax;
+    if (const char *v = getenv("BAMSIGNALS_FRAG_FLUSH_READS")) ceiling = std::min<long long>(kCounterMax, std::max<long long>(1, atoll(v)));
+    std::vector<uint2> runs;
+    int64_t a = 0, in_run = 0;
+    for (int64_t t = 0; t < P->n_items; ++t) {
+        const int64_t nr = tile_reads[(size_t)t];
+        if (nr > kCounterMax)
+            return fail(BSIG_ERR_ARG, "a tile of these ranges sees %lld reads, more than a 32-bit counter holds", (long long)nr);
+        // (a tile with more reads than a LOWERED ceiling makes a run of its own: it is the real ceiling that counters need)
+        if (t > a && (t - a >= per || in_run + nr > ceiling)) {
+            runs.push_back(make_uint2((uint32_t)a, (uint32_t)t));
+            a = t; in_run = 0;
+        }
+        in_run += nr;
+    }
+    if (a < P->n_items) runs.push_back(make_uint2((uint32_t)a, (uint32_t)P->n_items));
+    Q.n_runs = (int64_t)runs.size();
+    if (!runs.empty()) {
+        hipStream_t st = P->ctx->stream;
+        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
+        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return BSIG_OK;
+}
+
 extern "C" {
 
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
@@ -1887,6 +1998,7 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -1920,6 +2032,7 @@ int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
     const bsig::HostDest dst{out_host};
     return bsig::plan_run_to_host(p, &dst, nullptr);
 }
@@ -1988,6 +2101,27 @@ int bsig::plan_run_xcorr_to_host(bsig_plan *p, int64_t *host, double *t_kernels,
     if (t_download) *t_download = since(t1);
     return BSIG_OK;
 }
+int bsig::plan_run_frag_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    FragState *Q = p->frag.get();
+    if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->shape.cells));
+    const int rc = bsig_plan_run_frag(p, Q->d_out);
+    if (rc != BSIG_OK) return rc;
+    if (t_kernels) {
+        HIP_TRY(hipStreamSynchronize(st));
+        *t_kernels = since(t0);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->shape.cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (t_download) *t_download = since(t1);
+    return BSIG_OK;
+}
 // a run whose slices took a bin past INT32_MAX fails (after the caller's synchronisation: no wait of its own)
 int bsig::plan_check_overflow(bsig_plan *p)
 {
@@ -2004,6 +2138,7 @@ int bsig_plan_run_host_async(bsig_plan *p, int32_t *out_host)
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
     const bsig::HostDest dst{out_host};
     return bsig::plan_run_to_host(p, &dst, nullptr, true);
 }
@@ -2030,7 +2165,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     bsig_plan_stats t{};
     t.n_ranges = p->n_ranges;
     t.n_items = p->n_items;
-    t.cells = p->sum ? p->sum->shape.cells : p->xcorr ? p->xcorr->shape.cells : p->off.back();
+    t.cells = p->sum ? p->sum->shape.cells : p->xcorr ? p->xcorr->shape.cells : p->frag ? p->frag->shape.cells : p->off.back();
     t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
     t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
     t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
@@ -2043,7 +2178,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
     t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
                           t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
-                          (p->sum || p->xcorr ? 8 : 4) * t.cells;
+                          (p->sum || p->xcorr || p->frag ? 8 : 4) * t.cells;
     if (plan_two_launches(p) && windows_kept()) {
         // a resident plan's step reads the windows kept from its first run: no index entry is touched
         t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
@@ -2077,6 +2212,7 @@ int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
     if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
     const SumState &Q = *p->sum;
     const int64_t cells = Q.shape.cells;
@@ -2115,6 +2251,7 @@ int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
     if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
     return bsig::plan_run_to_host(p, nullptr, sum_host);
 }
@@ -2134,6 +2271,7 @@ int64_t bsig_plan_xcorr_cells(const bsig_plan *p) { return p && p->xcorr ? p->xc
 int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
     if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum runs it" : "not an xcorr plan: bsig_plan_run runs it");
     const XcorrState &Q = *p->xcorr;
     if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -2164,8 +2302,60 @@ int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
 int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
     if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum_host runs it" : "not an xcorr plan: bsig_plan_run_host runs it");
     return bsig::plan_run_xcorr_to_host(p, host);
+}
+
+int bsig_plan_create_frag(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                          const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t len_bin, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_frag");
+    *out = nullptr;
+    bsig::FragShape shape;
+    const int rc = bsig::frag_shape(*prm, len_bin, &shape);
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, nullptr, out, nullptr, &shape);
+}
+
+int64_t bsig_plan_frag_cells(const bsig_plan *p) { return p && p->frag ? p->frag->shape.cells : 0; }
+int64_t bsig_plan_frag_runs(const bsig_plan *p) { return p && p->frag ? p->frag->n_runs : 0; }
+
+// which run call a plan that is no frag plan takes (the refusals' wording)
+static const char *run_call_of(const bsig_plan *p, bool host)
+{
+    if (p->sum) return host ? "bsig_plan_run_sum_host" : "bsig_plan_run_sum";
+    if (p->xcorr) return host ? "bsig_plan_run_xcorr_host" : "bsig_plan_run_xcorr";
+    return host ? "bsig_plan_run_host" : "bsig_plan_run";
+}
+
+int bsig_plan_run_frag(bsig_plan *p, int64_t *dev)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->frag) return fail(BSIG_ERR_ARG, "not a frag plan: %s runs it", run_call_of(p, false));
+    const FragState &Q = *p->frag;
+    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
+    if (p->reads->layout_gen != p->made_for_gen)
+        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)Q.shape.cells * sizeof(int64_t), st));
+    if (Q.n_runs) {
+        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+            return bsig::launch_frag_tiles(p->threads, Q.merge, p->reads->dev, kp, p->items, p->n_items, Q.runs, Q.n_runs, resolved,
+                                           lookup, (int)Q.shape.cells, Q.shape.len_bin, reinterpret_cast<unsigned long long *>(dev), st);
+        });
+        if (rc != BSIG_OK) return rc;
+    }
+    ++p->runs;
+    return BSIG_OK;
+}
+
+int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->frag) return fail(BSIG_ERR_ARG, "not a frag plan: %s runs it", run_call_of(p, true));
+    return bsig::plan_run_frag_to_host(p, host);
 }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)

@@ -266,6 +266,16 @@ struct XcorrShape {
 int xcorr_shape(const bsig_params &prm, int32_t max_lag, XcorrShape *out);
 // bsig_plan_run_xcorr into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
 int plan_run_xcorr_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
+// what only a fragment-length histogram asks, ahead of check_params (runtime.hip: frag_shape): bamCount's tiles, no shift,
+// a length filter, a row width >= 1, at most BSIG_FRAG_MAX_ROWS rows
+struct FragShape {
+    bsig_params tiles;      // the unstranded count plan the tiles are walked by
+    int32_t len_bin;        // lengths per row
+    int64_t cells;          // rows: tlen_filter[1] / len_bin + 1
+};
+int frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out);
+// bsig_plan_run_frag into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
+int plan_run_frag_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

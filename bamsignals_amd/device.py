@@ -401,6 +401,56 @@ class XcorrPlan:
         self.close()
 
 
+class FragPlan:
+    """Ranges + call parameters resident in HBM for the fragment-length histogram (bsig_plan_create_frag): each run gives
+    ``tlen_filter[1] // len_bin + 1`` int64 -- row r counts the reads that ``Plan``'s bamCount (shift 0, unstranded) counts
+    over all ranges with ``|tlen| // len_bin == r``.  ``params``: mode COUNT without shift, with a 2-element
+    ``tlen_filter``; ``tile_cells`` = bases of a tile, ``threads`` per workgroup.  ``runs``: the runs of tiles (a
+    workgroup each) the plan was cut into."""
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, len_bin=1):
+        self._lib = _lib.load()
+        self.ctx, self.reads = ctx, reads
+        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_create_frag(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
+                                                   _ptr(strand), C.byref(params), int(len_bin), C.byref(h)))
+        self._h = h
+        self.n_ranges = n
+        self.len_bin = int(len_bin)
+        self.cells = int(self._lib.bsig_plan_frag_cells(h))
+        self.runs = int(self._lib.bsig_plan_frag_runs(h))
+
+    def run_host(self, out=None):
+        """Run and return the int64 histogram in host memory."""
+        if out is None:
+            out = np.empty(self.cells, dtype=np.int64)
+        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
+        _lib.check(self._lib.bsig_plan_run_frag_host(self._h, _ptr(out)))
+        return out
+
+    def run_device(self, out_ptr):
+        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
+        _lib.check(self._lib.bsig_plan_run_frag(self._h, C.c_void_p(out_ptr)))
+
+    def stats(self):
+        s = _lib.PlanStats()
+        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class SegmentMap:
     """Device-side reassembly of sharded results: segment k of a source buffer goes to the destination at
     ``dst_off[which[k]]`` (bsig_segmap_*; the host-side twin is bsig_scatter_segments).  The tables are

@@ -190,6 +190,23 @@ def pileup_xcorr(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1,
     return out
 
 
+def pileup_frag(bampath, gr, tlen_filter, mapqual=0, requiredF=66, filteredF=-1, pe_mid=False, len_bin=1, maxgap=16385,
+                device=None):
+    """The fragment-length histogram over the ranges (bsig_pileup_frag): ``tlen_filter[1] // len_bin + 1`` int64."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    rows = int(tf[1]) // int(len_bin) + 1 if len(tf) == 2 and int(len_bin) >= 1 and tf[1] >= 0 else 1
+    out = np.zeros(min(max(rows, 1), _lib.FRAG_MAX_ROWS), dtype=np.int64)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_pileup_frag(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
+                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
+                                    tf.ctypes.data, len(tf), int(mapqual), int(requiredF), int(filteredF),
+                                    int(bool(pe_mid)), int(len_bin), int(maxgap), _dev(device), out.ctypes.data))
+    return out
+
+
 def _is_ex(binsize, ss):
     """bins or strands take bsig_coverage_core_ex[_into]; the defaults keep the reference's own entry point"""
     return int(binsize) != 1 or bool(ss)

@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from bamsignals_amd import GRanges, bamCount, bamCoverage, bamCrossCorr, bamProfile  # noqa: E402
+from bamsignals_amd import GRanges, bamCount, bamCoverage, bamCrossCorr, bamFragSizes, bamProfile  # noqa: E402
 
 bampath = os.path.join(ROOT, "tests", "golden", "randomBam.bam")
 reg = json.load(open(os.path.join(ROOT, "tests", "golden", "regions.json")))
@@ -37,3 +37,8 @@ print(cov[0][:20])
 cc = bamCrossCorr(bampath, genes, maxlag=300, verbose=False)
 print(cc.fragment_length(), cc.fragment_length() // 2)
 print(bamCount(bampath, genes, shift=cc.fragment_length() // 2, verbose=False))
+
+# the data's own value for `tlenFilter`: the fragment lengths of the proper pairs over the genes
+fs = bamFragSizes(bampath, genes, verbose=False)
+print(fs.n, fs.mode(), fs.median(), fs.tlen_filter(0.99))
+print(bamCount(bampath, genes, paired_end="midpoint", tlenFilter=fs.tlen_filter(0.99), verbose=False))

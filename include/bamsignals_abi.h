@@ -252,6 +252,33 @@ int64_t bsig_plan_xcorr_cells(const bsig_plan *plan);            /* max_lag + 1 
 int bsig_plan_run_xcorr(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_xcorr_host(bsig_plan *plan, int64_t *host);
 
+/* Fragment-length histogram over ranges: how long the paired-end fragments are whose position lies in the ranges -- the
+ * nucleosome ladder, the insert sizes over peaks, the data's own tlen_filter.  With tf = params->tlen_filter:
+ *   n_rows  = tf[1] / len_bin + 1
+ *   hist[r] = sum over ranges i of bamCount(range i; shift 0, ss 0, the caller's pe_mid, flags and mapqual,
+ *                                           tlen_filter = (max(tf[0], r * len_bin), min(tf[1], (r + 1) * len_bin - 1)))
+ * i.e. a read that passes the flag / mapq filter (the caller sets requiredF: 66 for the first read of a proper pair),
+ * with a = |tlen| in [tf[0], tf[1]] and its position -- the 5' end, moved by a / 2 with pe_mid -- inside a range counts
+ * in row a / len_bin, once per range that holds it (a repeated range counts twice).  Ranges may differ in width, overlap,
+ * overhang their reference or be empty; their strand does not influence the result.  The result is
+ * bsig_plan_frag_cells() = n_rows int64; no count wraps (a workgroup's 32-bit counters see fewer than 2^32 reads: the
+ * plan cuts its runs of tiles by the reads in their windows).
+ * params: mode BSIG_MODE_COUNT, shift 0, n_tlen_filter 2 with tlen_filter[1] >= 0 (anything else: BSIG_ERR_ARG); ss is
+ * ignored; tile_cells = bases of a tile (16 .. 16,384; 0: 16,384), threads 64 / 128 / 256 per workgroup (0: 256).
+ * len_bin < 1 or more than BSIG_FRAG_MAX_ROWS rows: BSIG_ERR_ARG.  bsig_plan_get_stats: cells = n_rows, heavy_tiles = 0
+ * (a tile has no image, so none is cut into slices), visits as bamCount's with a length filter.  bsig_plan_frag_runs():
+ * the runs of tiles (a workgroup each) the plan was cut into.  A frag plan runs with bsig_plan_run_frag* only, and no
+ * other plan does (BSIG_ERR_ARG).                                                                                      */
+#define BSIG_FRAG_MAX_ROWS 16384     /* the 32-bit counters of all rows: 64 KiB of LDS */
+int bsig_plan_create_frag(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                          const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t len_bin,
+                          bsig_plan **plan);
+int64_t bsig_plan_frag_cells(const bsig_plan *plan);             /* n_rows, 0 for any other plan                */
+int64_t bsig_plan_frag_runs(const bsig_plan *plan);              /* runs of tiles, 0 for any other plan         */
+/* asynchronous, on the context's stream; dev: bsig_plan_frag_cells() int64 on the device, 8-B aligned                */
+int bsig_plan_run_frag(bsig_plan *plan, int64_t *dev);
+int bsig_plan_run_frag_host(bsig_plan *plan, int64_t *host);
+
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
 int bsig_pileup_columns(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
                         const int32_t *rid, const int32_t *loc, const int32_t *len,
@@ -410,6 +437,15 @@ int bsig_pileup_xcorr(const char *bampath, int64_t n_ranges, const int32_t *seq_
                       const int32_t *tlen_filter, int32_t n_tlen_filter,
                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t max_lag, int32_t maxgap,
                       int32_t device, int64_t *out);
+/* The fragment-length histogram over the ranges (bsig_plan_create_frag): out receives tlen_filter[1] / len_bin + 1 int64.
+ * len_bin and the parameters are checked before the BAM is opened or decoded.  With several GPUs each takes its block of
+ * the (rid, loc)-sorted ranges and the host adds the vectors (bsig_last_call_route(): "sum", as bsig_pileup_sum).      */
+int bsig_pileup_frag(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                     int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                     const int32_t *width, const int32_t *strand,
+                     const int32_t *tlen_filter, int32_t n_tlen_filter,
+                     int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t len_bin,
+                     int32_t maxgap, int32_t device, int64_t *out);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
