@@ -128,6 +128,18 @@ def load():
     lib.bsig_plan_frag_runs.restype = C.c_int64
     lib.bsig_plan_run_frag.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_frag_host.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_runs_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.bsig_runs_n_seg.argtypes = [C.c_void_p]
+    lib.bsig_runs_n_seg.restype = C.c_int64
+    lib.bsig_runs_cells.argtypes = [C.c_void_p]
+    lib.bsig_runs_cells.restype = C.c_int64
+    lib.bsig_runs_encode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.bsig_runs_device.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p)]
+    lib.bsig_runs_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bsig_runs_free.argtypes = [C.c_void_p]
+    lib.bsig_runs_free.restype = None
+    lib.bsig_plan_runs_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.bsig_pileup_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
     lib.bsig_bam_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -163,6 +175,15 @@ def load():
     lib.bsig_coverage_sum.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_pileup_xcorr.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
     lib.bsig_pileup_frag.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
+    lib.bsig_pileup_runs.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
+    lib.bsig_coverage_runs.argtypes = core_head + [C.c_int32] * 8 + [C.POINTER(C.c_void_p)]
+    lib.bsig_runs_result_n_seg.argtypes = [C.c_void_p]
+    lib.bsig_runs_result_n_seg.restype = C.c_int64
+    lib.bsig_runs_result_n_runs.argtypes = [C.c_void_p]
+    lib.bsig_runs_result_n_runs.restype = C.c_int64
+    lib.bsig_runs_result_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bsig_runs_result_free.argtypes = [C.c_void_p]
+    lib.bsig_runs_result_free.restype = None
     lib.bsig_write_sam_as_bam_and_index.argtypes = [C.c_char_p, C.c_char_p]
     lib.bsig_write_columns_as_bam.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(Columns),
                                               C.c_int32]

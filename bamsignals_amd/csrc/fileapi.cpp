@@ -765,6 +765,135 @@ int frag_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
     return BSIG_OK;
 }
 
+}  // namespace
+// the host-side result of bsig_pileup_runs / bsig_coverage_runs: the runs in the caller's range order
+struct bsig_runs_result {
+    int64_t n_seg = 0;
+    std::vector<int64_t> seg_off;
+    std::vector<int32_t> values, lengths;
+};
+namespace {
+
+// cells per block of ranges whose per-base result is in HBM at one time (bsig_pileup_runs / bsig_coverage_runs)
+int64_t runs_block_cells()
+{
+    if (const char *e = getenv("BAMSIGNALS_RUNS_BLOCK_CELLS")) {      // (read per call: tests force many blocks)
+        const long long v = atoll(e);
+        if (v >= 1) return (int64_t)v;
+    }
+    return (int64_t)1 << 31;
+}
+
+// The per-range result as runs (bsig_pileup_runs / bsig_coverage_runs).  Each GPU takes a contiguous share of the
+// (rid, loc)-sorted ranges, as sum_on_slots deals them, and cuts it into blocks of at most runs_block_cells() cells (a
+// single larger range is a block of its own): a block's plan runs into a device buffer, the overflow flag is checked,
+// the buffer is encoded (runs.hip) and only the runs are downloaded.  The host puts the segments in the caller's order.
+int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                  const int32_t *width, const int32_t *strand, const bsig_params &prm, const bsig::PlanRule &rule,
+                  bsig_runs_result &out, double *X, std::string &route)
+{
+    const size_t nd = reads.size();
+    const int64_t S = rule.ss ? 2 : 1;
+    const int64_t budget = runs_block_cells();
+    std::vector<int64_t> order;
+    bsig::sort_ranges(n, rid, loc, order);
+    auto cells_of = [&](int64_t i) -> int64_t {
+        const int32_t w = width[order[(size_t)i]];
+        return w > 0 ? S * (((int64_t)w + rule.binsize - 1) / rule.binsize) : 0;
+    };
+    struct Block {
+        int64_t a = 0, b = 0, cells = 0;      // ranges order[a .. b)
+        size_t slot = 0;
+        std::vector<int64_t> seg_off;
+        std::vector<int32_t> values, lengths;
+    };
+    std::vector<Block> blocks;
+    for (size_t k = 0; k < nd; ++k) {
+        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
+        for (int64_t i = a; i < b;) {
+            Block B;
+            B.a = i; B.slot = k;
+            B.cells = cells_of(i++);
+            while (i < b && B.cells + cells_of(i) <= budget) B.cells += cells_of(i++);
+            B.b = i;
+            blocks.push_back(std::move(B));
+        }
+    }
+    for (int k = 3; k < 6; ++k) X[k] = 0;
+    const int rc = for_each_slot(nd, [&](size_t k) -> int {
+        int64_t max_cells = 0;
+        for (const Block &B : blocks)
+            if (B.slot == k) max_cells = std::max(max_cells, B.cells);
+        if (hipSetDevice(sl.ctx[k]->device) != hipSuccess) return fail(BSIG_ERR_DEVICE, "cannot select GPU %d", sl.ctx[k]->device);
+        void *buf = nullptr;
+        size_t got = 0;
+        if (max_cells > 0) {
+            const hipError_t e = bsig::block_alloc(sl.ctx[k]->device, (size_t)max_cells * sizeof(int32_t), 1.125, &buf, &got);
+            if (e != hipSuccess)
+                return fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "no device memory for a block of %lld cells: %s",
+                            (long long)max_cells, hipGetErrorString(e));
+        }
+        int rk = BSIG_OK;
+        for (Block &B : blocks) {
+            if (B.slot != k || rk != BSIG_OK) continue;
+            const size_t m = (size_t)(B.b - B.a);
+            std::vector<int32_t> r(m), l(m), w(m), s(m);
+            for (size_t t = 0; t < m; ++t) {
+                const int64_t j = order[(size_t)B.a + t];
+                r[t] = rid[j]; l[t] = loc[j]; w[t] = width[j]; s[t] = strand[j];
+            }
+            const double t0 = now_s();
+            bsig_plan *plan = nullptr;
+            bsig_runs *enc = nullptr;
+            rk = bsig_plan_create(sl.ctx[k], reads[k], (int64_t)m, r.data(), l.data(), w.data(), s.data(), &prm, &plan);
+            if (rk == BSIG_OK && bsig_plan_cells(plan) != B.cells) rk = fail(BSIG_ERR_ARG, "a block's cells do not match its plan's");
+            const double t1 = now_s();
+            if (rk == BSIG_OK) rk = bsig_plan_run(plan, (int32_t *)buf);
+            if (rk == BSIG_OK) rk = bsig_ctx_sync(sl.ctx[k]);
+            // (a bin past INT32_MAX fails the call before anything is encoded)
+            if (rk == BSIG_OK) rk = bsig::plan_check_overflow(plan);
+            if (rk == BSIG_OK) rk = bsig_plan_runs_create(plan, &enc);
+            int64_t n_runs = 0;
+            if (rk == BSIG_OK) rk = bsig_runs_encode(enc, (const int32_t *)buf, &n_runs);
+            const double t2 = now_s();
+            if (rk == BSIG_OK) {
+                B.seg_off.resize(m * (size_t)S + 1);
+                B.values.resize((size_t)n_runs);
+                B.lengths.resize((size_t)n_runs);
+                rk = bsig_runs_fetch(enc, B.seg_off.data(), B.values.data(), B.lengths.data());
+            }
+            if (nd == 1) { X[3] += t1 - t0; X[4] += t2 - t1; X[5] += now_s() - t2; }
+            if (enc) bsig_runs_free(enc);
+            if (plan) bsig_plan_free(plan);
+        }
+        if (buf) bsig::block_free(sl.ctx[k]->device, buf, got);
+        return rk;
+    });
+    if (rc != BSIG_OK) return rc;
+    // the segments in the caller's order: count, scan, copy
+    out.n_seg = n * S;
+    out.seg_off.assign((size_t)(n * S) + 1, 0);
+    for (const Block &B : blocks)
+        for (int64_t t = 0; t < B.b - B.a; ++t)
+            for (int64_t a = 0; a < S; ++a)
+                out.seg_off[(size_t)(order[(size_t)(B.a + t)] * S + a) + 1] = B.seg_off[(size_t)(t * S + a) + 1] - B.seg_off[(size_t)(t * S + a)];
+    for (int64_t k = 0; k < n * S; ++k) out.seg_off[(size_t)k + 1] += out.seg_off[(size_t)k];
+    out.values.resize((size_t)out.seg_off.back());
+    out.lengths.resize((size_t)out.seg_off.back());
+    for (const Block &B : blocks)
+        for (int64_t t = 0; t < B.b - B.a; ++t) {
+            // (a range's segments are neighbours on both sides)
+            const int64_t from = B.seg_off[(size_t)(t * S)], cnt = B.seg_off[(size_t)((t + 1) * S)] - from;
+            const int64_t to = out.seg_off[(size_t)(order[(size_t)(B.a + t)] * S)];
+            if (cnt) {
+                memcpy(out.values.data() + to, B.values.data() + from, (size_t)cnt * sizeof(int32_t));
+                memcpy(out.lengths.data() + to, B.lengths.data() + from, (size_t)cnt * sizeof(int32_t));
+            }
+        }
+    route = "runs of " + std::to_string(blocks.size()) + " block(s) of ranges, put in order on the host";
+    return BSIG_OK;
+}
+
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
 // layout is one vector, dst[0]), or the sum over the ranges
 struct FileDest {
@@ -776,6 +905,7 @@ struct FileDest {
     int32_t max_lag = 0;
     int64_t *frag = nullptr;        // tlen_filter[1] / len_bin + 1 cells: the fragment-length histogram over the ranges
     int32_t len_bin = 0;
+    bsig_runs_result *runs = nullptr;   // the per-range result as runs, in the caller's range order
 };
 
 int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -785,7 +915,15 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (!bampath) return fail(BSIG_ERR_ARG, "bampath is NULL");
     if (n < 0 || (n > 0 && (!seq_code || !start || !width || !strand || !levels)))
         return fail(BSIG_ERR_ARG, "range arrays missing");
-    if (!to.off && !to.dst && !to.sum && !to.xcorr && !to.frag) return fail(BSIG_ERR_ARG, "offsets missing");
+    if (!to.off && !to.dst && !to.sum && !to.xcorr && !to.frag && !to.runs) return fail(BSIG_ERR_ARG, "offsets missing");
+    if (to.runs) {
+        // runs: bamCount has none; the plan's rule, before the BAM is opened
+        g_call_route[0] = 0;
+        if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
+        bsig::PlanRule early;
+        const int rc = bsig::check_params(prm, n, width, &early);
+        if (rc) return rc;
+    }
     int64_t *sum = to.sum;
     bsig::SumShape shape{};
     if (sum) {
@@ -1108,6 +1246,8 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         rc = xcorr_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.max_lag, xshape.cells, to.xcorr, X, gather);
     } else if (to.frag) {
         rc = frag_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.len_bin, fshape.cells, to.frag, X, gather);
+    } else if (to.runs) {
+        rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, rule, *to.runs, X, gather);
     } else if (!many) {
         // plan (ranges -> tiles in HBM), kernels, download -- timed apart
         bsig_plan *plan = nullptr;
@@ -1132,7 +1272,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (rc == BSIG_OK) rc = bam_index_wait(bam);      // a damaged index fails the call, as it does in the reference's open
     T[4] = now_s() - t_begin;
     snprintf(g_call_route, sizeof g_call_route, "%zu GPU slot(s); reads: %s; result: %s", nd, how_decoded.c_str(),
-             many || sum || to.xcorr || to.frag ? gather.c_str() : "download");
+             many || sum || to.xcorr || to.frag || to.runs ? gather.c_str() : "download");
     return rc;
 }
 
@@ -1431,6 +1571,59 @@ int bsig_pileup_frag(const char *bampath, int64_t n, const int32_t *seq_code, in
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
                       pileup_params(tlen_filter, n_tlen_filter, mapqual, -1, 0, 0, requiredF, filteredF, pe_mid != 0), device, to);
 }
+
+int bsig_pileup_runs(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                     const char *const *levels, const int32_t *start, const int32_t *width,
+                     const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                     int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss, int32_t requiredF,
+                     int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, bsig_runs_result **result)
+{
+    if (!result) return fail(BSIG_ERR_ARG, "result is NULL");
+    *result = nullptr;
+    std::unique_ptr<bsig_runs_result> res(new bsig_runs_result);
+    FileDest to;
+    to.runs = res.get();
+    const int rc = file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                              pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device, to);
+    if (rc == BSIG_OK) *result = res.release();
+    return rc;
+}
+
+int bsig_coverage_runs(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                       const char *const *levels, const int32_t *start, const int32_t *width,
+                       const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                       int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result)
+{
+    if (!result) return fail(BSIG_ERR_ARG, "result is NULL");
+    *result = nullptr;
+    std::unique_ptr<bsig_runs_result> res(new bsig_runs_result);
+    FileDest to;
+    to.runs = res.get();
+    const int rc = file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                              coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device, to);
+    if (rc == BSIG_OK) *result = res.release();
+    return rc;
+}
+
+int64_t bsig_runs_result_n_seg(const bsig_runs_result *r) { return r ? r->n_seg : 0; }
+
+int64_t bsig_runs_result_n_runs(const bsig_runs_result *r) { return r && !r->seg_off.empty() ? r->seg_off.back() : 0; }
+
+int bsig_runs_result_copy(const bsig_runs_result *r, int64_t *seg_off, int32_t *values, int32_t *lengths)
+{
+    if (!r || !seg_off) return fail(BSIG_ERR_ARG, "NULL argument");
+    const size_t n_runs = (size_t)bsig_runs_result_n_runs(r);
+    if (n_runs && (!values || !lengths)) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    memcpy(seg_off, r->seg_off.data(), r->seg_off.size() * sizeof(int64_t));
+    if (n_runs) {
+        memcpy(values, r->values.data(), n_runs * sizeof(int32_t));
+        memcpy(lengths, r->lengths.data(), n_runs * sizeof(int32_t));
+    }
+    return BSIG_OK;
+}
+
+void bsig_runs_result_free(bsig_runs_result *r) { delete r; }
 
 int bsig_coverage_sum(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                       const char *const *levels, const int32_t *start, const int32_t *width,

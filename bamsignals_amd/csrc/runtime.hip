@@ -2359,6 +2359,26 @@ int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host)
 }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
+// The run-length encoder (runs.hip) of a plan's own layout: range i's cells off[i] .. off[i + 1] are one segment, or with
+// strands the two rows of the 2 * bin + antisense cells (stride 2)
+int bsig_plan_runs_create(const bsig_plan *p, bsig_runs **out)
+{
+    if (!p || !out) return fail(BSIG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (p->sum || p->xcorr || p->frag)
+        return fail(BSIG_ERR_ARG, "a %s plan has no per-range result to encode", p->sum ? "sum" : p->xcorr ? "xcorr" : "frag");
+    if (p->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
+    const int S = p->kp.ss ? 2 : 1;
+    std::vector<int64_t> base((size_t)(p->n_ranges * S));
+    std::vector<int32_t> len((size_t)(p->n_ranges * S));
+    for (int64_t i = 0; i < p->n_ranges; ++i)
+        for (int a = 0; a < S; ++a) {
+            base[(size_t)(i * S + a)] = p->off[(size_t)i] + a;
+            len[(size_t)(i * S + a)] = (int32_t)((p->off[(size_t)i + 1] - p->off[(size_t)i]) / S);
+        }
+    return bsig_runs_create(p->ctx, p->n_ranges * S, base.data(), len.data(), S, out);
+}
+
 int bsig_debug_new_layout_gen(bsig_reads *reads)
 {
     if (!reads) return 1;

@@ -292,6 +292,14 @@ class Plan:
         _lib.check(self._lib.bsig_plan_overflowed(self._h, C.byref(f)))
         return bool(f.value)
 
+    def runs(self):
+        """The run-length encoder of this plan's result layout (bsig_plan_runs_create): ``n_ranges`` segments, or
+        ``2 * n_ranges`` (segment ``2 * i + antisense``) with strands; ``encode`` what ``run_device`` wrote.  Not for a
+        bamCount plan."""
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_runs_create(self._h, C.byref(h)))
+        return RunEncoder._adopt(self.ctx, h)
+
     def stats(self):
         s = _lib.PlanStats()
         _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
@@ -445,6 +453,68 @@ class FragPlan:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.bsig_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class RunEncoder:
+    """Run-length encoder of int32 device buffers (bsig_runs_*): segment k is the ``length[k]`` cells
+    ``src[base[k] + p * stride]``; ``stride`` 1, or 2 for one row of the interleaved ``2 * bin + antisense`` layout.
+    ``encode(src_ptr)`` counts, allocates and writes the runs on the device and returns their number; ``fetch()`` copies
+    them to the host, ``device_pointers()`` leaves them in HBM.  An object encodes any number of buffers."""
+
+    def __init__(self, ctx, base, length, stride=1):
+        self._lib = _lib.load()
+        base = np.ascontiguousarray(base, dtype=np.int64)
+        length = _i32(length)
+        if len(base) != len(length):
+            raise ValueError("base and length differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_runs_create(ctx._h, len(base), _ptr(base), _ptr(length), int(stride), C.byref(h)))
+        self.ctx, self._h = ctx, h
+        self.n_seg = len(base)
+        self.cells = int(self._lib.bsig_runs_cells(h))
+        self.n_runs = None
+
+    @classmethod
+    def _adopt(cls, ctx, h):
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        self.ctx, self._h = ctx, h
+        self.n_seg = int(self._lib.bsig_runs_n_seg(h))
+        self.cells = int(self._lib.bsig_runs_cells(h))
+        self.n_runs = None
+        return self
+
+    def encode(self, src_ptr):
+        """Encode the int32 device buffer at ``src_ptr`` (synchronises); returns the number of runs."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.bsig_runs_encode(self._h, C.c_void_p(src_ptr), C.byref(n)))
+        self.n_runs = int(n.value)
+        return self.n_runs
+
+    def device_pointers(self):
+        """(n_runs, seg_off, values, lengths): device addresses of the last encode's result (valid until the next)."""
+        n = C.c_int64(0)
+        so, va, le = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(self._lib.bsig_runs_device(self._h, C.byref(n), C.byref(so), C.byref(va), C.byref(le)))
+        return int(n.value), so.value, va.value, le.value
+
+    def fetch(self):
+        """(seg_off int64[n_seg + 1], values int32[n_runs], lengths int32[n_runs]) of the last encode, in host memory."""
+        if self.n_runs is None:
+            raise ValueError("nothing has been encoded yet")
+        seg_off = np.empty(self.n_seg + 1, dtype=np.int64)
+        values = np.empty(self.n_runs, dtype=np.int32)
+        lengths = np.empty(self.n_runs, dtype=np.int32)
+        _lib.check(self._lib.bsig_runs_fetch(self._h, _ptr(seg_off), _ptr(values), _ptr(lengths)))
+        return seg_off, values, lengths
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_runs_free(self._h)
             self._h = None
 
     def __del__(self):

@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from .countsignals import CountSignals
 from .granges import GRanges
+from .runsignals import RunSignals
 
 
 def _match_arg(value, choices, name):
@@ -207,6 +208,52 @@ def pileup_frag(bampath, gr, tlen_filter, mapqual=0, requiredF=66, filteredF=-1,
     return out
 
 
+def _take_runs(lib, handle, ss):
+    """a bsig_runs_result handle -> RunSignals (the arrays are allocated once the handle says how large they are)"""
+    try:
+        n_seg, n_runs = int(lib.bsig_runs_result_n_seg(handle)), int(lib.bsig_runs_result_n_runs(handle))
+        seg_off = np.empty(n_seg + 1, dtype=np.int64)
+        values = np.empty(n_runs, dtype=np.int32)
+        lengths = np.empty(n_runs, dtype=np.int32)
+        _lib.check(lib.bsig_runs_result_copy(handle, seg_off.ctypes.data, values.ctypes.data, lengths.ctypes.data))
+    finally:
+        lib.bsig_runs_result_free(handle)
+    return RunSignals(seg_off, values, lengths, bool(ss))
+
+
+def pileup_runs(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False, requiredF=0,
+                filteredF=-1, pe_mid=False, maxgap=16385, device=None):
+    """bamProfile's signals as runs (bsig_pileup_runs): a RunSignals; the per-base cells stay on the GPU."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    h = C.c_void_p()
+    _lib.check(lib.bsig_pileup_runs(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
+                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
+                                    tf.ctypes.data, len(tf), int(mapqual), int(binsize), int(shift),
+                                    int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
+                                    int(maxgap), _dev(device), C.byref(h)))
+    return _take_runs(lib, h, ss)
+
+
+def coverage_runs(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
+                  maxgap=16385, device=None, *, binsize=1, ss=False):
+    """bamCoverage's signals as runs (bsig_coverage_runs): a RunSignals; the per-base cells stay on the GPU."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    h = C.c_void_p()
+    _lib.check(lib.bsig_coverage_runs(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+                                      start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
+                                      int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap),
+                                      _dev(device), int(binsize), int(bool(ss)), C.byref(h)))
+    return _take_runs(lib, h, ss)
+
+
 def _is_ex(binsize, ss):
     """bins or strands take bsig_coverage_core_ex[_into]; the defaults keep the reference's own entry point"""
     return int(binsize) != 1 or bool(ss)
@@ -321,14 +368,19 @@ def bamCount(bampath, gr, mapqual=0, shift=0, ss=False, paired_end=("ignore", "f
 
 def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N802
                paired_end=("ignore", "filter", "midpoint"), tlenFilter=None, filteredFlag=-1, verbose=True,  # noqa: N803
-               *, aggregate=False):
+               *, aggregate=False, runs=False):
     """For each base pair (or bin) of the ranges, the number of reads whose 5' end maps there
     (R/wrappers.R:124-151).  Returns a CountSignals.
 
     ``aggregate=True``: ranges of one width only; returns the int64 sum over the ranges of their signals, cell by
     cell -- ``np.asarray(sig.alignSignals(), np.int64).sum(axis=-1)`` of the CountSignals above, shape ``(n_bins,)``
     or ``(2, n_bins)`` with ``ss`` -- computed on the GPU without the per-range result.  The metaprofile (the
-    vignette's rowMeans of alignSignals) is this divided by ``len(gr)``."""
+    vignette's rowMeans of alignSignals) is this divided by ``len(gr)``.
+
+    ``runs=True``: returns a RunSignals -- the same signals as runs (value, length), encoded on the GPU, so that the
+    per-base cells are never downloaded; ``sig.decode(i)`` is the CountSignals' element i.  Not with ``aggregate``."""
+    if runs and aggregate:
+        raise ValueError("runs=True and aggregate=True exclude each other: a sum over ranges has no per-range runs")
     if verbose:
         _print_sentence(bampath)
     if binsize < 1:
@@ -343,6 +395,9 @@ def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N8
     if aggregate:
         return pileup_sum(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                           int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
+    if runs:
+        return pileup_runs(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
+                           int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
     pu = pileup_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                      int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
     return CountSignals(pu, bool(ss), _trusted=True)
@@ -366,7 +421,7 @@ def _coverage_binsize(binsize):
 
 
 def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFilter=None,  # noqa: N802,N803
-                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False):
+                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False, runs=False):
     """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173).
 
     ``binsize`` (1 .. 65,536): bin j of a range covers its bases [j*binsize, min((j+1)*binsize, width)) in range
@@ -377,7 +432,11 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     ('*' counts as '+'), row 1 (antisense) by the others; with ``paired_end="extend"`` the whole fragment counts on
     the strand of the read that passed the flag mask (the first mate).  sense + antisense is the unstranded result.
     A bin whose sum would exceed 2^31 - 1 raises BsigError.  The defaults are the reference's call.
-    ``aggregate=True``: the int64 sum over ranges of one width, as in ``bamProfile``."""
+    ``aggregate=True``: the int64 sum over ranges of one width, as in ``bamProfile``.
+    ``runs=True``: a RunSignals instead of a CountSignals, as in ``bamProfile`` -- the form of an RleList or a bedGraph
+    (``sig.to_bedgraph``); a whole-genome track without its 4 bytes per base in host memory.  Not with ``aggregate``."""
+    if runs and aggregate:
+        raise ValueError("runs=True and aggregate=True exclude each other: a sum over ranges has no per-range runs")
     if verbose:
         _print_sentence(bampath)
     b = _coverage_binsize(binsize)
@@ -391,6 +450,9 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     if aggregate:
         return coverage_sum(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                             flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
+    if runs:
+        return coverage_runs(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
+                             flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
     pu = coverage_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                        flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
     return CountSignals(pu, bool(ss), _trusted=True)

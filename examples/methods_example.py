@@ -42,3 +42,8 @@ print(bamCount(bampath, genes, shift=cc.fragment_length() // 2, verbose=False))
 fs = bamFragSizes(bampath, genes, verbose=False)
 print(fs.n, fs.mode(), fs.median(), fs.tlen_filter(0.99))
 print(bamCount(bampath, genes, paired_end="midpoint", tlenFilter=fs.tlen_filter(0.99), verbose=False))
+
+# the coverage of the genes as runs (an RleList's form) and as a bedGraph: the per-base cells never leave the GPU
+runs = bamCoverage(bampath, genes, runs=True, verbose=False)
+print(runs, runs[0][0][:5], runs[0][1][:5])
+print(runs.to_bedgraph(os.path.join(os.environ.get("TMPDIR", "/tmp"), "genes.bedGraph"), genes), "bedGraph lines")

@@ -279,6 +279,34 @@ int64_t bsig_plan_frag_runs(const bsig_plan *plan);              /* runs of tile
 int bsig_plan_run_frag(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_frag_host(bsig_plan *plan, int64_t *host);
 
+/* Run-length encoding on the device: a per-range result as runs (value, length), the form of an Rle / a bedGraph.  The
+ * encoder works on ANY int32 device buffer plus a table of segments: segment k is the len[k] cells
+ * src[base[k] + p * stride], p = 0 .. len[k] - 1; stride 1, or 2 for one row of the 2 * bin + antisense layout (else
+ * BSIG_ERR_ARG, as for n_seg < 0, a negative len or base).  A segment holds fewer than 2^31 cells; all segments together
+ * may hold more.  The runs of a segment are its maximal stretches of equal consecutive cells, compared on all 32 bits; a
+ * segment boundary always starts a run, a zero-length segment has none.  The result is three device arrays:
+ *   seg_off  int64, n_seg + 1 : segment k owns runs seg_off[k] .. seg_off[k + 1]
+ *   values   int32, seg_off[n_seg]        lengths  int32, seg_off[n_seg] (each >= 1; a segment's sum to its len)
+ * bsig_runs_encode counts the runs, allocates values / lengths at their exact size (the worst case is one run per
+ * cell), writes them and synchronises; the object may encode any number of buffers, each encode replaces the result of
+ * the one before.  bsig_runs_device hands out the device pointers (valid until the next encode or bsig_runs_free; values
+ * and lengths are NULL when there is no run), bsig_runs_fetch copies to host memory (seg_off: n_seg + 1 int64; values,
+ * lengths: n_runs int32 each).  env BAMSIGNALS_RUNS_CHUNK_CELLS (read by bsig_runs_create; 64 .. 2^24, default 2,048):
+ * the cells of the flattened segments that one workgroup walks (testing).                                              */
+typedef struct bsig_runs bsig_runs;
+int bsig_runs_create(bsig_ctx *ctx, int64_t n_seg, const int64_t *base, const int32_t *len, int32_t stride, bsig_runs **runs);
+int64_t bsig_runs_n_seg(const bsig_runs *runs);
+int64_t bsig_runs_cells(const bsig_runs *runs);                  /* the sum of len                              */
+int bsig_runs_encode(bsig_runs *runs, const int32_t *src_dev, int64_t *n_runs);
+int bsig_runs_device(const bsig_runs *runs, int64_t *n_runs, const int64_t **seg_off, const int32_t **values,
+                     const int32_t **lengths);
+int bsig_runs_fetch(bsig_runs *runs, int64_t *seg_off, int32_t *values, int32_t *lengths);
+void bsig_runs_free(bsig_runs *runs);
+/* The encoder of a plan's own result layout (bsig_plan_offsets): n_seg = n_ranges * S segments, S = 2 with strands (segment
+ * S * i + antisense, stride 2), else 1; encode what bsig_plan_run wrote.  For ordinary plans of mode BSIG_MODE_PROFILE,
+ * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr or frag plan fail with BSIG_ERR_ARG. */
+int bsig_plan_runs_create(const bsig_plan *plan, bsig_runs **runs);
+
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
 int bsig_pileup_columns(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
                         const int32_t *rid, const int32_t *loc, const int32_t *len,
@@ -446,6 +474,33 @@ int bsig_pileup_frag(const char *bampath, int64_t n_ranges, const int32_t *seq_c
                      const int32_t *tlen_filter, int32_t n_tlen_filter,
                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t len_bin,
                      int32_t maxgap, int32_t device, int64_t *out);
+/* The file-level calls with the result as RUNS (bsig_runs_*): bsig_pileup_core's / bsig_coverage_core_ex's arguments
+ * without out / off; binsize <= 0 (bamCount) fails with BSIG_ERR_ARG, and all parameters are checked before the BAM is
+ * opened.  The per-base cells live only in HBM, and only for one block of the (rid, loc)-sorted ranges at a time: a block
+ * holds at most env BAMSIGNALS_RUNS_BLOCK_CELLS cells (read per call; default 2^31, 8 GiB of int32), a single larger range
+ * is a block of its own.  With several GPUs each takes a contiguous share of the sorted ranges and encodes it; no per-base
+ * cell is gathered.  The host puts the segments in the caller's range order: segment S * i + antisense of range i (S = 2
+ * with ss).  A coverage bin past INT32_MAX fails the call before anything is encoded.  The result is a host-side handle,
+ * because its size is known only afterwards: ask it for n_seg and n_runs, copy it out (seg_off: n_seg + 1 int64;
+ * values, lengths: n_runs int32 each) and free it.  bsig_last_call_route() says "runs".                              */
+typedef struct bsig_runs_result bsig_runs_result;
+int bsig_pileup_runs(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                     int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                     const int32_t *width, const int32_t *strand,
+                     const int32_t *tlen_filter, int32_t n_tlen_filter,
+                     int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss,
+                     int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t maxgap,
+                     int32_t device, bsig_runs_result **result);
+int bsig_coverage_runs(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                       int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                       const int32_t *width, const int32_t *strand,
+                       const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                       int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result);
+int64_t bsig_runs_result_n_seg(const bsig_runs_result *result);
+int64_t bsig_runs_result_n_runs(const bsig_runs_result *result);
+int bsig_runs_result_copy(const bsig_runs_result *result, int64_t *seg_off, int32_t *values, int32_t *lengths);
+void bsig_runs_result_free(bsig_runs_result *result);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
