@@ -549,7 +549,10 @@ __device__ __forceinline__ int wave_inclusive_scan(int v)
 
 // Pileup kernels take (items, n_tiles, out, windows) first: with -amdgpu-kernarg-preload-count=8
 // (Makefile) those arrive in SGPRs, so the work-item load is issued with the first instruction
-// instead of behind a kernarg fetch (config 2: 24.9 -> 24.6 us).
+// instead of behind a kernarg fetch (config 2: 24.9 -> 24.6 us).  k_profile and k_profile_half take
+// (items, n_tiles, img_vec, out, windows): items 2 dwords + n_tiles 1 + img_vec 1 + out 2 + windows 2 are exactly
+// the eight preloaded ones -- img_vec fills the padding that stood between n_tiles and the 8-byte aligned `out`.
+// Any further argument in front of `windows` pushes it out of the preload.
 // Workgroups are dealt round-robin to the 8 XCDs (blocks b and b+8 share an L2), tiles are sorted
 // by position: give every XCD one contiguous run of the tile list, so that neighbouring tiles,
 // whose read windows overlap, meet in the same L2.  A bijection of [0, n); any mapping would be
@@ -585,6 +588,61 @@ __device__ __forceinline__ void store_vec(int32_t *__restrict__ gbase, int v, in
         if (e0 + 1 >= lo && e0 + 1 < hi) gbase[e0 + 1] = x.y;
         if (e0 + 2 >= lo && e0 + 2 < hi) gbase[e0 + 2] = x.z;
         if (e0 + 3 >= lo && e0 + 3 < hi) gbase[e0 + 3] = x.w;
+    }
+}
+
+// a dword pair of a 16-bit tile image (two counters per LDS dword) as the four int32 cells it holds
+__device__ __forceinline__ int4 widen16(uint2 d)
+{
+    return make_int4((int)(d.x & 0xFFFFu), (int)(d.x >> 16), (int)(d.y & 0xFFFFu), (int)(d.y >> 16));
+}
+
+// KB rows of NT interior vectors from row r0 on: all LDS reads issued before the first is consumed, then the 16-B
+// non-temporal stores back to back, each under nothing but "this lane has a vector in this row"
+template <int NT, int KB>
+__device__ __forceinline__ void store_rows16(int4 *__restrict__ g4, const uint2 *__restrict__ l2, int tid, int r0, int n_int)
+{
+    typedef int v4i_t __attribute__((ext_vector_type(4)));
+    uint2 d[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+        const int i = r0 + k * NT + tid;
+        d[k] = l2[i < n_int ? i : n_int - 1];                        // (clamped, not masked: a read inside the image)
+    }
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+        const int i = r0 + k * NT + tid;
+        const int4 x = widen16(d[k]);
+        const v4i_t xv = {x.x, x.y, x.z, x.w};
+        if (i < n_int) __builtin_nontemporal_store(xv, reinterpret_cast<v4i_t *>(g4 + i));
+    }
+}
+
+// The whole image of a tile whose cells are 16-bit counters (two per LDS dword), stored as store_vec would store its
+// nvec vectors one by one -- but the interior vectors, those that lie in [sh, sh + nv) with all four values, go in
+// batches (store_rows16): one LDS round trip for a batch instead of one per vector and lane.  sh and nv are uniform,
+// so the interior is a run [v_lo, v_hi) with at most one edge vector on either side; those two keep store_vec's
+// form, on two lanes.  The batch is sized to what is left of the run -- eight rows of NT vectors, four or two -- so
+// that a 500- or 1,000-cell tile does not issue reads and store slots for rows it does not have.
+template <int NT>
+__device__ __forceinline__ void store_image16(int32_t *__restrict__ gbase, const uint2 *__restrict__ lds2, int tid, int sh, int nv)
+{
+    const int nvec = (sh + nv + 3) >> 2;
+    const int v_lo = (sh + 3) >> 2, v_hi = (sh + nv) >> 2;          // interior: 4 v >= sh and 4 v + 4 <= sh + nv
+    const int n_int = v_hi - v_lo;                                   // (<= 0: a tile inside one or two edge vectors)
+    int4 *const g4 = reinterpret_cast<int4 *>(gbase) + v_lo;
+    const uint2 *const l2 = lds2 + v_lo;
+    for (int r0 = 0; r0 < n_int;) {                                  // (uniform)
+        const int left = n_int - r0;
+        if (left > 4 * NT)      { store_rows16<NT, 8>(g4, l2, tid, r0, n_int); r0 += 8 * NT; }
+        else if (left > 2 * NT) { store_rows16<NT, 4>(g4, l2, tid, r0, n_int); r0 += 4 * NT; }
+        else                    { store_rows16<NT, 2>(g4, l2, tid, r0, n_int); r0 += 2 * NT; }
+    }
+    // the edge vectors: vector 0 if the image starts inside it, the last one if the image ends inside it
+    if (tid < 2 && nvec > 0) {
+        const int v = tid ? nvec - 1 : 0;
+        const bool edge = (v < v_lo || v >= v_hi) && (tid == 0 || nvec > 1);
+        if (edge) store_vec(gbase, v, widen16(lds2[v]), sh, nv);
     }
 }
 
@@ -990,7 +1048,8 @@ __device__ __forceinline__ void add_vec(int32_t *__restrict__ gbase, int v, int4
 // HALF: the packed class from its 16-bit column (BsigKParams::packed_half) -- k_profile_half; the same body otherwise.
 template <int NT, bool SS, int PRE, bool RES, bool HALF>
 __device__ __forceinline__ void profile_tile(const BsigWorkItem *__restrict__ items, uint32_t n_tiles, int32_t *__restrict__ out,
-                                             const uint2 *__restrict__ windows, const BsigReadsDev &R, const BsigKParams &P)
+                                             const uint2 *__restrict__ windows, const BsigReadsDev &R, const BsigKParams &P,
+                                             uint32_t img_vec_launch)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t lds[];
     constexpr int S = SS ? 2 : 1;
@@ -1002,8 +1061,11 @@ __device__ __forceinline__ void profile_tile(const BsigWorkItem *__restrict__ it
     PackedWin pk;
     load_windows<RES>(R, P, BSIG_MODE_PROFILE, w, items, windows, win, tile, pk, clip);
     int4 *lds4 = reinterpret_cast<int4 *>(lds);
-    // clear the whole tile image: this needs nothing from the work item, so it overlaps its load
-    const int img_vec = (P.tile_cells * S + 8 + 7) / 8;
+    // clear the whole tile image: this needs nothing from the work item, so it overlaps its load -- and nothing from
+    // the parameter block either, whose scalar loads return with the item's (scalar loads are waited for all at
+    // once): the image's size in 16-B vectors is an argument of its own, the one that sized the launch's LDS, and
+    // sits among the preloaded ones (= (P.tile_cells * S + 8 + 7) / 8)
+    const int img_vec = (int)img_vec_launch;
     for (int v = tid; v < img_vec; v += NT) lds4[v] = make_int4(0, 0, 0, 0);
     // ... and so does the packed class's filter table, which lives behind the image
     uint8_t *ptab = reinterpret_cast<uint8_t *>(lds4 + img_vec);
@@ -1028,13 +1090,10 @@ __device__ __forceinline__ void profile_tile(const BsigWorkItem *__restrict__ it
 
     int32_t *gbase = out + (w.out_off - sh);
     const uint2 *lds2 = reinterpret_cast<const uint2 *>(lds);
-    auto widen = [](uint2 d) {
-        return make_int4((int)(d.x & 0xFFFFu), (int)(d.x >> 16), (int)(d.y & 0xFFFFu), (int)(d.y >> 16));
-    };
     if (P.accumulate) {
-        for (int v = tid; v < nvec; v += NT) add_vec(gbase, v, widen(lds2[v]), sh, nv);
+        for (int v = tid; v < nvec; v += NT) add_vec(gbase, v, widen16(lds2[v]), sh, nv);
     } else if (!BSIG_ABLATE(2)) {
-        for (int v = tid; v < nvec; v += NT) store_vec(gbase, v, widen(lds2[v]), sh, nv);
+        store_image16<NT>(gbase, lds2, tid, sh, nv);
     }
     BSIG_STAMP(3);
 #ifdef BSIG_STAMPS
@@ -1051,20 +1110,20 @@ __device__ __forceinline__ void profile_tile(const BsigWorkItem *__restrict__ it
 }
 template <int NT, bool SS, int PRE, int WAVES, bool RES>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
-                                                int32_t *__restrict__ out,
+                                                uint32_t img_vec, int32_t *__restrict__ out,
                                                 const uint2 *__restrict__ windows,
                                                 const BsigReadsDev R, const BsigKParams P)
 {
-    profile_tile<NT, SS, PRE, RES, false>(items, n_tiles, out, windows, R, P);
+    profile_tile<NT, SS, PRE, RES, false>(items, n_tiles, out, windows, R, P, img_vec);
 }
 // k_profile reading the packed class's 16-bit column: a kernel of its own, so that the 4-byte form keeps its code
 template <int NT, bool SS, int PRE, int WAVES, bool RES>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile_half(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
-                                                int32_t *__restrict__ out,
+                                                uint32_t img_vec, int32_t *__restrict__ out,
                                                 const uint2 *__restrict__ windows,
                                                 const BsigReadsDev R, const BsigKParams P)
 {
-    profile_tile<NT, SS, PRE, RES, true>(items, n_tiles, out, windows, R, P);
+    profile_tile<NT, SS, PRE, RES, true>(items, n_tiles, out, windows, R, P, img_vec);
 }
 
 // k_profile for T consecutive tiles per wave (large launches, windows from k_resolve_tiles): lane t fetches the work
@@ -2459,7 +2518,11 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         else    { if (P.resolved) BSIG_KS(false, true); else BSIG_KS(false, false); }
 #undef BSIG_KS
     } else if (mode == BSIG_MODE_PROFILE) {
-        const size_t lds = (size_t)((tile_cells * (ss ? 2 : 1) + 8 + 7) / 8) * 16 + BSIG_PACK_CODES;     // 16-bit counters + the packed class's table
+        // 16-bit counters + the packed class's table.  img_vec is ONE number in three places: it sizes the LDS here, and
+        // k_profile / k_profile_half clear that many vectors and put the table right behind them (profile_tile takes it as
+        // an argument; profile_multi_tiles computes the same from P.tile_cells, which is this tile_cells, and SS, which is ss)
+        const uint32_t img_vec = (uint32_t)((tile_cells * (ss ? 2 : 1) + 8 + 7) / 8);
+        const size_t lds = (size_t)img_vec * 16 + BSIG_PACK_CODES;
         // class-0 passes requested before anything is consumed (knob 0: 2, 3 or 4; fewer = fewer VGPRs = more
         // resident waves, more = one round trip for denser windows)
         const int pre = knob(0);
@@ -2469,8 +2532,8 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         const int pre_h = knob(6) <= 1 ? 1 : 2;
 #define BSIG_KP(K_, SS_, PRE_, W_)                                                                                                      \
     do {                                                                                                                                \
-        if (P.resolved) hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); \
-        else hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, false>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); \
+        if (P.resolved) hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, true>), grid, block, lds, st, items, (uint32_t)n_items, img_vec, out, windows, R, P); \
+        else hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, false>), grid, block, lds, st, items, (uint32_t)n_items, img_vec, out, windows, R, P); \
     } while (0)
 #define BSIG_KPW(K_, SS_, PRE_) do { if (w8) BSIG_KP(K_, SS_, PRE_, 8); else BSIG_KP(K_, SS_, PRE_, 1); } while (0)
         // the build for 8 waves per SIMD (96 SGPRs, the rest kept in VGPR lanes; 57 VGPRs in the resolved form, which
