@@ -16,8 +16,14 @@
 #include <type_traits>
 #include <stdint.h>
 #include <stdlib.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
+#include <atomic>
+#include <mutex>
+#include <string>
 
 #include "bsig_types.h"
 #include "kernels.h"
@@ -2474,7 +2480,7 @@ __global__ void k_visits(const BsigReadsDev R, const BsigKParams P, int mode,
 namespace bsig {
 
 // Tuning knobs (defaults from the environment once, changeable at run time through bsig_debug_set_knob for
-// the sweep scripts): 0 = k_profile class-0 passes in flight (BAMSIGNALS_PROFILE_PRE), 1 = count tiles per
+// the sweep scripts): 0 = k_profile packed-class passes in flight (BAMSIGNALS_PROFILE_PRE), 1 = count tiles per
 // wave (BAMSIGNALS_COUNT_TILES), 2 = count passes in flight (BAMSIGNALS_COUNT_PRE), 6 = k_profile_half's packed
 // passes in flight (BAMSIGNALS_PROFILE_HALF_PRE).
 static int g_knobs[7] = {-1, -1, -1, -1, -1, -1, -1};
@@ -2489,6 +2495,30 @@ static int knob(int k)
     }
     return g_knobs[k];
 }
+
+// The launch log (bsig_debug_launch_log, for the tests): the name of every pileup and sum-tiles kernel form launched while
+// it is on -- the kernel template, its arguments and the run-time choices that change the code path.  The names are
+// made in the dispatch macros below from the macros' own arguments, so a new branch reports itself.  Host code only; off,
+// a launch pays one load and one branch.  Multi-slot calls launch from several threads: a mutex guards the text, which
+// stops growing at 64 KB.
+static std::atomic<int> g_log_on{0};
+static std::mutex g_log_mu;
+static std::string g_log_text;
+static int g_log_names = 0;
+static void log_launch(const char *fmt, ...)
+{
+    char name[160];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof name, fmt, ap);
+    va_end(ap);
+    std::lock_guard<std::mutex> lock(g_log_mu);
+    if (g_log_text.size() + strlen(name) + 1 > (size_t)65536) return;
+    g_log_text += name;
+    g_log_text += '\n';
+    ++g_log_names;
+}
+#define BSIG_LOG(...) do { if (__builtin_expect(g_log_on.load(std::memory_order_relaxed) != 0, 0)) log_launch(__VA_ARGS__); } while (0)
 
 template <int NT>
 static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const BsigKParams &P,
@@ -2513,7 +2543,8 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         const int stride = (tile_cells * (ss ? 2 : 1)) | 1;
         const size_t lds = (size_t)((small_image_dwords(stride) + 3) & ~3) * sizeof(int32_t) + BSIG_PACK_CODES;   // + the packed class's table
         // (the form for resolved windows has no lookup code in it, as k_profile's)
-#define BSIG_KS(SS_, RES_) hipLaunchKernelGGL((k_profile_small<NT, SS_, RES_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P)
+#define BSIG_KS(SS_, RES_) do { BSIG_LOG("k_profile_small<%d,ss=%d,res=%d> acc=%d", NT, (int)SS_, (int)RES_, (int)P.accumulate); \
+        hipLaunchKernelGGL((k_profile_small<NT, SS_, RES_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P); } while (0)
         if (ss) { if (P.resolved) BSIG_KS(true, true); else BSIG_KS(true, false); }
         else    { if (P.resolved) BSIG_KS(false, true); else BSIG_KS(false, false); }
 #undef BSIG_KS
@@ -2523,7 +2554,7 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         // an argument; profile_multi_tiles computes the same from P.tile_cells, which is this tile_cells, and SS, which is ss)
         const uint32_t img_vec = (uint32_t)((tile_cells * (ss ? 2 : 1) + 8 + 7) / 8);
         const size_t lds = (size_t)img_vec * 16 + BSIG_PACK_CODES;
-        // class-0 passes requested before anything is consumed (knob 0: 2, 3 or 4; fewer = fewer VGPRs = more
+        // the packed class's passes requested before anything is consumed (knob 0: 2, 3 or 4; fewer = fewer VGPRs = more
         // resident waves, more = one round trip for denser windows)
         const int pre = knob(0);
         // the half form (P.packed_half: k_profile_half, k_profile_multi_half): one pass holds 8 * NT reads, a 2-kb tile's
@@ -2532,6 +2563,7 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         const int pre_h = knob(6) <= 1 ? 1 : 2;
 #define BSIG_KP(K_, SS_, PRE_, W_)                                                                                                      \
     do {                                                                                                                                \
+        BSIG_LOG(#K_ "<%d,ss=%d,pre=%d,w=%d,res=%d> acc=%d", NT, (int)SS_, PRE_, W_, P.resolved ? 1 : 0, (int)P.accumulate);           \
         if (P.resolved) hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, true>), grid, block, lds, st, items, (uint32_t)n_items, img_vec, out, windows, R, P); \
         else hipLaunchKernelGGL((K_<NT, SS_, PRE_, W_, false>), grid, block, lds, st, items, (uint32_t)n_items, img_vec, out, windows, R, P); \
     } while (0)
@@ -2551,7 +2583,8 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
             const int T = pt >= 4 ? 4 : 2;
             const dim3 g2((unsigned)((n_items + T - 1) / T));
             const size_t lds_m = lds + (size_t)T * 20 * sizeof(uint32_t);
-#define BSIG_KM(K_, SS_, PRE_, W_, T_) hipLaunchKernelGGL((K_<SS_, PRE_, W_, T_>), g2, dim3(kWave), lds_m, st, items, (uint32_t)n_items, out, windows, R, P)
+#define BSIG_KM(K_, SS_, PRE_, W_, T_) do { BSIG_LOG(#K_ "<ss=%d,pre=%d,w=%d,T=%d> acc=%d", (int)SS_, PRE_, W_, T_, (int)P.accumulate); \
+        hipLaunchKernelGGL((K_<SS_, PRE_, W_, T_>), g2, dim3(kWave), lds_m, st, items, (uint32_t)n_items, out, windows, R, P); } while (0)
 #define BSIG_KMT(K_, SS_, PRE_, W_) do { if (T == 4) BSIG_KM(K_, SS_, PRE_, W_, 4); else BSIG_KM(K_, SS_, PRE_, W_, 2); } while (0)
 #define BSIG_KMW(K_, SS_, PRE_) do { if (w8) BSIG_KMT(K_, SS_, PRE_, 8); else BSIG_KMT(K_, SS_, PRE_, 1); } while (0)
             if (half) {
@@ -2581,7 +2614,8 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         BsigKParams Q = P;
         Q.cov_reps = cov_bins_reps(tile_cells * S);
         const size_t lds = (size_t)cov_bins_vec(tile_cells * S) * Q.cov_reps * 16 + (size_t)((S * NT / 64 + 3) / 4) * 16 + BSIG_PACK_CODES;
-#define BSIG_KB(RES_, SS_) hipLaunchKernelGGL((k_coverage_bins<NT, 2, RES_, SS_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, Q)
+#define BSIG_KB(RES_, SS_) do { BSIG_LOG("k_coverage_bins<%d,pre=2,res=%d,ss=%d> acc=%d cov_reps=%d", NT, (int)RES_, (int)SS_, (int)Q.accumulate, (int)Q.cov_reps); \
+        hipLaunchKernelGGL((k_coverage_bins<NT, 2, RES_, SS_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, Q); } while (0)
         if (ss) { if (P.resolved) BSIG_KB(true, true); else BSIG_KB(false, true); }
         else    { if (P.resolved) BSIG_KB(true, false); else BSIG_KB(false, false); }
 #undef BSIG_KB
@@ -2589,6 +2623,7 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         const size_t lds = (size_t)((tile_cells + 8 + 7) / 8) * 16 + (size_t)((NT / 64 + 3) / 4) * 16 + BSIG_PACK_CODES;   // signed 16-bit cells, scan totals, the packed class's table
         // (the packed class's passes hold 256 reads each: two in flight cover a 2-kb tile at 100-fold coverage; the form
         // for resolved windows has no lookup code in it)
+        BSIG_LOG("k_coverage<%d,pre=2,res=%d> acc=%d", NT, P.resolved ? 1 : 0, (int)P.accumulate);
         if (P.resolved) hipLaunchKernelGGL((k_coverage<NT, 2, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
         else hipLaunchKernelGGL((k_coverage<NT, 2, false>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
     } else if (NT == kWave && (!windows || P.resolved) && count_tiles > 1) {
@@ -2596,12 +2631,14 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         // the wider workgroups keep the one-tile kernel)
         const int T = count_tiles >= 8 ? 8 : count_tiles >= 4 ? 4 : 2;
         const dim3 g2((unsigned)((n_items + T - 1) / T));
-#define BSIG_CM(T_, PRE_) hipLaunchKernelGGL((k_count_multi<T_, PRE_>), g2, dim3(kWave), 0, st, items, (uint32_t)n_items, out, windows, R, P)
+#define BSIG_CM(T_, PRE_) do { BSIG_LOG("k_count_multi<T=%d,pre=%d> acc=%d", T_, PRE_, (int)P.accumulate); \
+        hipLaunchKernelGGL((k_count_multi<T_, PRE_>), g2, dim3(kWave), 0, st, items, (uint32_t)n_items, out, windows, R, P); } while (0)
         if (count_pre <= 2)      { if (T == 8) BSIG_CM(8, 2); else if (T == 4) BSIG_CM(4, 2); else BSIG_CM(2, 2); }
         else if (count_pre == 3) { if (T == 8) BSIG_CM(8, 3); else if (T == 4) BSIG_CM(4, 3); else BSIG_CM(2, 3); }
         else                     { if (T == 8) BSIG_CM(8, 4); else if (T == 4) BSIG_CM(4, 4); else BSIG_CM(2, 4); }
 #undef BSIG_CM
     } else {
+        BSIG_LOG("k_count<%d> acc=%d", NT, (int)P.accumulate);
         hipLaunchKernelGGL((k_count<NT>), grid, block, 0, st, items, (uint32_t)n_items, out, windows, R, P);
     }
     return hipGetLastError();
@@ -2627,11 +2664,13 @@ size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells)
     return (size_t)(acc_v + img_v * nw) * 16 + BSIG_PACK_CODES;
 }
 
-// one k_sum_tiles instantiation by its run-time choices (f receives the kernel's address)
+// one k_sum_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
+// form's name as a format of its two flags)
 template <typename Fn>
 static hipError_t with_sum_kernel(int kind, int ss, int nw, bool half, bool res, Fn &&f)
 {
-#define BSIG_SK(NW_, K_, SS_, H_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, H_, true>); else return f(k_sum_tiles<NW_, K_, SS_, H_, false>); } while (0)
+#define BSIG_SK(NW_, K_, SS_, H_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, H_, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=1>", (int)SS_, (int)H_); \
+                                        else return f(k_sum_tiles<NW_, K_, SS_, H_, false>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=0>", (int)SS_, (int)H_); } while (0)
 #define BSIG_SKN(K_, SS_, H_) do { if (nw == 1) BSIG_SK(1, K_, SS_, H_); else if (nw == 2) BSIG_SK(2, K_, SS_, H_); else BSIG_SK(4, K_, SS_, H_); } while (0)
     if (nw != 1 && nw != 2 && nw != 4) return hipErrorInvalidValue;
     if (kind == kSumProfile) {
@@ -2651,7 +2690,7 @@ int sum_blocks_per_cu(int kind, int ss, int nw, bool half, int tile_cells)
 {
     int nb = 0;
     const size_t lds = sum_tiles_lds(kind, ss, nw, tile_cells);
-    const hipError_t e = with_sum_kernel(kind, ss, nw, half, true, [&](auto k) {
+    const hipError_t e = with_sum_kernel(kind, ss, nw, half, true, [&](auto k, const char *, int, int) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, nw * kWave, lds);
     });
     return e == hipSuccess && nb > 0 ? nb : 1;
@@ -2670,7 +2709,8 @@ hipError_t launch_sum_tiles(int kind, int ss, int nw, const BsigReadsDev &R, con
                            (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
     }
     const size_t lds = sum_tiles_lds(kind, ss, nw, P.tile_cells);
-    const hipError_t e = with_sum_kernel(kind, ss, nw, P.packed_half != 0, P.resolved != 0, [&](auto k) {
+    const hipError_t e = with_sum_kernel(kind, ss, nw, P.packed_half != 0, P.resolved != 0, [&](auto k, const char *name, int s_, int h_) {
+        BSIG_LOG(name, s_, h_);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(nw * kWave), lds, st, items, runs, slab, (const uint2 *)windows, R, P);
         return hipGetLastError();
     });
@@ -2939,6 +2979,28 @@ extern "C" int bsig_debug_set_knob(int which, int value)
     if (which < 0 || which >= 7 || value < 0) return -1;
     bsig::g_knobs[which] = value;
     return 0;
+}
+
+// (debug, tests: the launch log.  buf == NULL: cap 1 turns it on, cap 0 off, either way empty.  With a buffer: the names
+// of the pileup and sum-tiles kernel forms launched since the last call, one a line, as many whole lines as fit cap
+// bytes with their final 0; the log is emptied.  Returns the number of names the log held.)
+extern "C" int bsig_debug_launch_log(char *buf, int cap)
+{
+    std::lock_guard<std::mutex> lock(bsig::g_log_mu);
+    const int n = bsig::g_log_names;
+    if (!buf) {
+        if (cap != 0 && cap != 1) return -1;
+        bsig::g_log_on.store(cap, std::memory_order_relaxed);
+    } else {
+        if (cap < 1) return -1;
+        size_t len = std::min(bsig::g_log_text.size(), (size_t)cap - 1);
+        while (len > 0 && bsig::g_log_text[len - 1] != '\n') --len;
+        memcpy(buf, bsig::g_log_text.data(), len);
+        buf[len] = 0;
+    }
+    bsig::g_log_text.clear();
+    bsig::g_log_names = 0;
+    return n;
 }
 
 // (debug: what the compiler made of the pileup kernels the BASELINE configurations run -- registers per lane and

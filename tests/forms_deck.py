@@ -1,0 +1,323 @@
+"""The input of tests/test_kernel_forms_gpu.py, and what the C oracle says about it (tests/test_forms_deck_cpu.py checks
+the deck's own claims without a GPU).  Everything is exact int32 / int64.
+
+Reads (coordinate-sorted columns, seeded):
+  * three bulk references of 70,000, 65,536 and 65,537 bp with 20,000 reads each: spans 1 .. 70,000 with the class
+    borders 1, 255, 256, 257, 4,095, 4,096, 4,097, 65,535, 65,536 and 65,537 among them, mapq 0 .. 255, the flags 0x4
+    and 0x400, paired flags with a template length, and a share of rare (flag, mapq) pairs that the packed class's table
+    has no room for;
+  * 48 "short" island references of 4,096 bp that hold exactly m reads each, all of them starting in [1024, 3072), of
+    span 1 .. 256, flag 0 or 16 and one mapq -- packed in the default layout, class 0 with BAMSIGNALS_PACK=0 -- for m in
+    ISLAND_COUNTS: a reference is its own run of 64-kbp units, so the window of a range over [1024, 3072) holds exactly
+    its m reads (for_each_read's nj), and the window starts at the number of reads of that class in front of it;
+  * 24 "long" islands with the counts up to 769: m reads of span 257 .. 4,096 (class 1) and m of span 4,097 .. 9,000
+    (class 2) each.
+
+Ranges: every width of WIDTHS 16 times on the bulk references in a seeded order (all strands, one at base 0, one that
+ends on a last base, some hanging over both ends, duplicates, every width at all four values of out_off & 3), then one
+range [1024, 3072) per island.  `cut` drops the last few bulk ranges so that the tiles number a chosen residue modulo 8.  SUM_RANGES
+are ranges of one width for the sums over ranges."""
+import functools
+
+import numpy as np
+
+ISLAND_KS = (64, 128, 256, 512, 768, 1024, 1536, 2048, 3072, 4096, 6144, 8192, 10240)
+ISLAND_COUNTS = tuple(sorted({0, 1, 2, 3, 4, 5, 7, 8, 9} | {k + d for k in ISLAND_KS for d in (-1, 0, 1)}))
+LONG_COUNTS = tuple(m for m in ISLAND_COUNTS if m <= 769)
+BULK_REFS = (70_000, 65_536, 65_537)
+BULK_READS = 20_000                      # per bulk reference
+ISLAND_LEN, ISLAND_LO, ISLAND_HI = 4096, 1024, 3072
+ISLAND_MAPQ = 30
+TILES = (64, 256, 2048)                  # the tile sizes (cells) the matrix runs the per-base forms at
+WIDTHS = tuple(sorted(set(range(10)) | {63, 64, 65, 255, 256, 257} | {w for t in TILES for w in (t - 1, t, t + 1, 2 * t + 3)}))
+COPIES = 16
+SPAN_EDGES = (1, 255, 256, 257, 4095, 4096, 4097, 65_535, 65_536, 65_537)
+SUM_WIDTH = 2048
+
+# name -> (oracle entry, its arguments): every set of call parameters the matrix compares
+PARAM_SETS = {
+    "half_ss0": ("pileup", dict(binsize=1, shift=0, ss=False)),
+    "half_ss1": ("pileup", dict(binsize=1, shift=0, ss=True)),
+    "word_ss0": ("pileup", dict(binsize=1, shift=75, mapqual=10, ss=False)),
+    "word_ss1": ("pileup", dict(binsize=1, shift=75, mapqual=10, ss=True)),
+    "small_ss0": ("pileup", dict(binsize=7, shift=0, ss=False)),
+    "small_ss1": ("pileup", dict(binsize=7, shift=0, ss=True)),
+    "count": ("pileup", dict(binsize=-1, shift=0, ss=True)),
+    "cover": ("coverage", dict(binsize=1, ss=False)),
+    "bins2_ss0": ("coverage", dict(binsize=2, ss=False)),
+    "bins2_ss1": ("coverage", dict(binsize=2, ss=True)),
+    "bins274_ss1": ("coverage", dict(binsize=274, ss=True)),
+}
+SUM_SETS = {
+    "sum_half_ss0": ("pileup", dict(binsize=1, shift=0, ss=False)),
+    "sum_half_ss1": ("pileup", dict(binsize=1, shift=0, ss=True)),
+    "sum_word_ss0": ("pileup", dict(binsize=1, shift=75, mapqual=10, ss=False)),
+    "sum_word_ss1": ("pileup", dict(binsize=1, shift=75, mapqual=10, ss=True)),
+    "sum_cover": ("coverage", dict(binsize=1, ss=False)),
+    "sum_cover_ss": ("coverage", dict(binsize=1, ss=True)),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# reads
+# ---------------------------------------------------------------------------------------------------------------
+def _bulk(rng, ref_len):
+    n = BULK_READS
+    pos = rng.integers(0, ref_len, n)
+    u = rng.random(n)
+    span = rng.integers(1, 257, n)
+    c1, c2, c3 = (u >= 0.90) & (u < 0.97), (u >= 0.97) & (u < 0.995), u >= 0.995
+    span[c1] = rng.integers(257, 4097, int(c1.sum()))
+    span[c2] = rng.integers(4097, 65_537, int(c2.sum()))
+    span[c3] = rng.integers(65_537, 70_001, int(c3.sum()))
+    edge = rng.random(n) < 0.05                                  # the borders of the span classes, many times each
+    span[edge] = np.asarray(SPAN_EDGES)[rng.integers(0, len(SPAN_EDGES), int(edge.sum()))]
+    flags = np.asarray([0, 16, 0, 16, 4, 20, 0x400, 0x410, 99, 147, 83, 163])
+    flag = flags[rng.integers(0, len(flags), n)]
+    mapq = np.asarray([0, 10, 30, 60, 255])[rng.integers(0, 5, n)]
+    rare = rng.random(n) < 0.03                                  # pairs the 512-entry table has no room for
+    flag[rare] = rng.integers(0, 4096, int(rare.sum()))
+    mapq[rare] = rng.integers(1, 255, int(rare.sum()))
+    paired = (flag & 1) != 0
+    tlen = np.where(paired, rng.integers(50, 601, n) * np.where((flag & 16) != 0, -1, 1), 0)
+    return pos, span, flag, mapq, tlen
+
+
+def _island(rng, m, lo_span, hi_span):
+    pos = rng.integers(ISLAND_LO, ISLAND_HI, m)
+    span = rng.integers(lo_span, hi_span + 1, m)
+    if m >= 3 and lo_span == 1:
+        span[:3] = (1, 255, 256)
+    flag = np.where(rng.random(m) < 0.5, 16, 0)
+    return pos, span, flag, np.full(m, ISLAND_MAPQ), np.zeros(m, np.int64)
+
+
+def _permuted(rng, counts):
+    """a seeded order of the islands' counts in which the reads in front of an island -- its window's start, up to the
+    bulk references' share -- take every residue modulo 8"""
+    for _ in range(100):
+        m = rng.permutation(np.asarray(counts))
+        start = np.concatenate([[0], np.cumsum(m[:-1])])
+        if set((start[m > 0] % 8).tolist()) == set(range(8)):
+            return m
+    raise AssertionError("no order of the islands with every window start modulo 8")
+
+
+@functools.lru_cache(maxsize=None)
+def reads():
+    """dict(ref_len, ref_off, pos, end, flag, mapq, tlen, short_refs, long_refs, short_m, long_m): the columns, and the
+    islands' reference ids with their read counts (in reference order, a seeded permutation of the counts)."""
+    rng = np.random.default_rng(20_250)
+    parts, ref_len = [], list(BULK_REFS)
+    for L in BULK_REFS:
+        parts.append(_bulk(rng, L))
+    short_m, long_m = _permuted(rng, ISLAND_COUNTS), _permuted(rng, LONG_COUNTS)
+    for m in short_m:
+        parts.append(_island(rng, int(m), 1, 256))
+        ref_len.append(ISLAND_LEN)
+    for m in long_m:
+        a, b = _island(rng, int(m), 257, 4096), _island(rng, int(m), 4097, 9000)
+        parts.append(tuple(np.concatenate([x, y]) for x, y in zip(a, b)))
+        ref_len.append(ISLAND_LEN)
+    cols = {k: [] for k in ("pos", "span", "flag", "mapq", "tlen")}
+    counts = []
+    for pos, span, flag, mapq, tlen in parts:
+        order = np.argsort(pos, kind="stable")
+        for k, v in zip(("pos", "span", "flag", "mapq", "tlen"), (pos, span, flag, mapq, tlen)):
+            cols[k].append(np.asarray(v, np.int64)[order])
+        counts.append(len(pos))
+    pos, span = np.concatenate(cols["pos"]), np.concatenate(cols["span"])
+    nb = len(BULK_REFS)
+    return dict(ref_len=np.asarray(ref_len, np.int32), ref_off=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64),
+                pos=pos.astype(np.int32), end=(pos + span - 1).astype(np.int32),
+                flag=np.concatenate(cols["flag"]).astype(np.uint16), mapq=np.concatenate(cols["mapq"]).astype(np.uint8),
+                tlen=np.concatenate(cols["tlen"]).astype(np.int32),
+                short_refs=np.arange(nb, nb + len(short_m)), long_refs=np.arange(nb + len(short_m), nb + len(short_m) + len(long_m)),
+                short_m=short_m, long_m=long_m)
+
+
+def read_classes(packed):
+    """The class the resident layout gives every read (csrc/bsig_types.h): 0 .. 3 by span (<= 256, <= 4,096, <= 65,536,
+    longer), 4 = packed (the default layout; none with BAMSIGNALS_PACK=0)."""
+    from conftest import expected_packed
+    c = reads()
+    span = c["end"].astype(np.int64) - c["pos"] + 1
+    cls = np.where(span <= 256, 0, np.where(span <= 4096, 1, np.where(span <= 65_536, 2, 3)))
+    if packed:
+        cls[expected_packed(c["pos"], c["end"], c["flag"], c["mapq"], c["ref_off"], c["ref_len"])[0]] = 4
+    return cls
+
+
+def island_windows(packed, cls_id, refs):
+    """(start, count) of class `cls_id`'s window over each of the island references `refs`: the reads of the class in
+    front of the reference, and on it."""
+    c = reads()
+    is_c = read_classes(packed) == cls_id
+    before = np.concatenate([[0], np.cumsum(is_c)])
+    lo, hi = c["ref_off"][refs], c["ref_off"][np.asarray(refs) + 1]
+    return before[lo], before[hi] - before[lo]
+
+
+def oracle_reads(mask=None):
+    from oracle import oracle_c
+    c = reads()
+    if mask is None:
+        return oracle_c.OracleReads(c["ref_off"], c["pos"], c["end"], c["flag"], c["mapq"], c["tlen"])
+    rid = np.repeat(np.arange(len(c["ref_len"])), np.diff(c["ref_off"]))
+    off = np.concatenate([[0], np.cumsum(np.bincount(rid[mask], minlength=len(c["ref_len"])))]).astype(np.int64)
+    return oracle_c.OracleReads(off, c["pos"][mask], c["end"][mask], c["flag"][mask], c["mapq"][mask], c["tlen"][mask])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ranges
+# ---------------------------------------------------------------------------------------------------------------
+def _island_ranges(refs):
+    n = len(refs)
+    return dict(rid=np.asarray(refs, np.int32), loc=np.full(n, ISLAND_LO, np.int32), len=np.full(n, ISLAND_HI - ISLAND_LO, np.int32),
+                strand=np.asarray([(1, -1, 0)[i % 3] for i in range(n)], np.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def ranges():
+    """The deck: len(WIDTHS) * COPIES ranges on the bulk references, then the islands' (short, then long)."""
+    c = reads()
+    for seed in range(5, 200):
+        rng = np.random.default_rng(seed)
+        width = rng.permutation(np.repeat(np.asarray(WIDTHS, np.int64), COPIES))
+        off = np.concatenate([[0], np.cumsum(width[:-1])])
+        if all(set((off[width == w] & 3).tolist()) == {0, 1, 2, 3} for w in WIDTHS):
+            break
+    else:
+        raise AssertionError("no order in which every width meets all four values of out_off & 3")
+    n = len(width)
+    rid = rng.integers(0, len(BULK_REFS), n)
+    L = np.asarray(BULK_REFS, np.int64)[rid]
+    loc = (rng.random(n) * (L - width)).astype(np.int64)
+    strand = rng.choice(np.asarray([1, -1, 0]), n)
+    loc[0] = 0                                                   # at a reference's first base
+    loc[1] = L[1] - width[1]                                     # ends on a reference's last base
+    wide = np.flatnonzero(width >= 63)
+    loc[wide[2:5]] = -3                                          # hang over a reference's first base ...
+    loc[wide[5:8]] = L[wide[5:8]] - width[wide[5:8]] + 5         # ... and over its last
+    for w in (1, 64, 257, 2048):                                 # duplicates
+        k = np.flatnonzero(width == w)[-3:]
+        rid[k[1:]], loc[k[1:]] = rid[k[0]], loc[k[0]]
+    bulk = dict(rid=rid.astype(np.int32), loc=loc.astype(np.int32), len=width.astype(np.int32), strand=strand.astype(np.int32))
+    isl = _island_ranges(np.concatenate([c["short_refs"], c["long_refs"]]))
+    return {k: np.concatenate([bulk[k], isl[k]]) for k in bulk}
+
+
+N_BULK_RANGES = len(WIDTHS) * COPIES
+
+
+def tiles_of(rg, tile_cells, binsize=1):
+    """work items per range of a plan with `tile_cells` cells a tile (bamCount, tile_cells None: one per range)"""
+    w = np.asarray(rg["len"], np.int64)
+    if tile_cells is None:
+        return (w > 0).astype(np.int64)
+    cells = (w + binsize - 1) // binsize
+    return (cells + tile_cells - 1) // tile_cells
+
+
+def cut(tile_cells, residue, binsize=1):
+    """The deck without the last k of its bulk ranges, k the smallest that leaves tiles numbering `residue` modulo 8 (all
+    islands stay in: their ranges are whole multiples of most tile sizes); returns (ranges, k)."""
+    rg = ranges()
+    per = tiles_of(rg, tile_cells, binsize)
+    total = int(per.sum())
+    dropped = np.concatenate([[0], np.cumsum(per[:N_BULK_RANGES][::-1])])
+    k = int(np.flatnonzero((total - dropped) % 8 == residue)[0])
+    assert k < 64, (tile_cells, residue, k)
+    keep = np.r_[0:N_BULK_RANGES - k, N_BULK_RANGES:len(per)]
+    return {key: v[keep] for key, v in rg.items()}, k
+
+
+def cut_expected(name, k):
+    """expected(name) for a cut that dropped the last k bulk ranges"""
+    want, off = expected(name)
+    return np.concatenate([want[:off[N_BULK_RANGES - k]], want[off[N_BULK_RANGES]:]])
+
+
+@functools.lru_cache(maxsize=None)
+def sum_ranges():
+    """Ranges of one width for the sums: the islands' and 60 on the bulk references, strands mixed."""
+    c = reads()
+    rng = np.random.default_rng(77)
+    n = 60
+    rid = rng.integers(0, len(BULK_REFS), n)
+    loc = (rng.random(n) * (np.asarray(BULK_REFS)[rid] - SUM_WIDTH)).astype(np.int64)
+    loc[:2] = (-5, 0)
+    isl = _island_ranges(np.concatenate([c["short_refs"], c["long_refs"]]))
+    bulk = dict(rid=rid.astype(np.int32), loc=loc.astype(np.int32), len=np.full(n, SUM_WIDTH, np.int32),
+                strand=rng.choice(np.asarray([1, -1, 0], np.int32), n))
+    return {k: np.concatenate([bulk[k], isl[k]]) for k in bulk}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# expected values (computed once per parameter set, shared and never written to)
+# ---------------------------------------------------------------------------------------------------------------
+def _binned(v, b):
+    return np.add.reduceat(v, np.arange(0, len(v), b)) if len(v) else np.zeros(0, np.int64)
+
+
+def _coverage(rg, binsize, ss):
+    """per-base oracle coverage (all reads, or forward and reverse reads apart: the sense row counts the reads on the
+    range's strand, '*' = '+'), summed over bins, in the plan's flat layout; returns (flat int64, offsets)"""
+    from oracle import oracle_c
+    c = reads()
+
+    def per_base(mask):
+        out, off = oracle_c.coverage_core(oracle_reads(mask), rg)
+        return [out[off[i]:off[i + 1]].astype(np.int64) for i in range(len(off) - 1)]
+    if not ss:
+        parts = [_binned(v, binsize) for v in per_base(None)]
+    else:
+        fwd = (c["flag"] & 16) == 0
+        parts = []
+        for i, (f, r) in enumerate(zip(per_base(fwd), per_base(~fwd))):
+            sense, anti = (r, f) if rg["strand"][i] < 0 else (f, r)
+            parts.append(np.stack([_binned(sense, binsize), _binned(anti, binsize)]).T.reshape(-1))
+    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
+    return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), off
+
+
+def _expected(entry, args, rg):
+    from oracle import oracle_c
+    if entry == "pileup":
+        out, off = oracle_c.pileup_core(oracle_reads(), rg, **args)
+    else:
+        out, off = _coverage(rg, args["binsize"], args["ss"])
+        assert out.max(initial=0) < 2 ** 31
+        out = out.astype(np.int32)
+    out.setflags(write=False)
+    return out, off
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name):
+    """(flat int32 result, offsets per range) of PARAM_SETS[name] on the whole deck; a cut's is its prefix"""
+    return _expected(*PARAM_SETS[name], ranges())
+
+
+@functools.lru_cache(maxsize=None)
+def expected_sum(name):
+    """the int64 sum over SUM_RANGES of what the oracle gives per range (cell 2 * bin + antisense with strands)"""
+    entry, args = SUM_SETS[name]
+    rg = sum_ranges()
+    out, _ = _expected(entry, args, rg)
+    s = out.astype(np.int64).reshape(len(rg["len"]), -1).sum(axis=0)
+    s.setflags(write=False)
+    return s
+
+
+def gpu_args(name):
+    """make_params' arguments for a parameter set (mode, keywords)"""
+    from bamsignals_amd import _lib
+    entry, args = {**PARAM_SETS, **SUM_SETS}[name]
+    a = dict(args)
+    if entry == "pileup":
+        mode = _lib.MODE_COUNT if a["binsize"] < 0 else _lib.MODE_PROFILE
+        return mode, a
+    if a["binsize"] == 1 and not a["ss"]:
+        return _lib.MODE_COVERAGE, {}
+    return _lib.MODE_COVERAGE_EX, a
