@@ -18,6 +18,8 @@ MODE_PROFILE, MODE_COUNT, MODE_COVERAGE, MODE_COVERAGE_EX = 0, 1, 2, 3
 XCORR_MAX_LAG, XCORR_MOMENTS = 2047, 5
 # include/bamsignals_abi.h: BSIG_FRAG_MAX_ROWS
 FRAG_MAX_ROWS = 16384
+# include/bamsignals_abi.h: BSIG_HIST_MAX_ROWS, BSIG_HIST_MOMENTS
+HIST_MAX_ROWS, HIST_MOMENTS = 8192, 2
 
 ERR_NAMES = {-1: "BSIG_ERR_ARG", -2: "BSIG_ERR_IO", -3: "BSIG_ERR_NOINDEX", -4: "BSIG_ERR_CHROM",
              -5: "BSIG_ERR_EXT", -6: "BSIG_ERR_DEVICE", -7: "BSIG_ERR_NOMEM", -8: "BSIG_ERR_FORMAT"}
@@ -128,6 +130,13 @@ def load():
     lib.bsig_plan_frag_runs.restype = C.c_int64
     lib.bsig_plan_run_frag.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_frag_host.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_create_hist.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
+    lib.bsig_plan_hist_cells.argtypes = [C.c_void_p]
+    lib.bsig_plan_hist_cells.restype = C.c_int64
+    lib.bsig_plan_hist_runs.argtypes = [C.c_void_p]
+    lib.bsig_plan_hist_runs.restype = C.c_int64
+    lib.bsig_plan_run_hist.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_run_hist_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_runs_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.bsig_runs_n_seg.argtypes = [C.c_void_p]
     lib.bsig_runs_n_seg.restype = C.c_int64
@@ -175,6 +184,8 @@ def load():
     lib.bsig_coverage_sum.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_pileup_xcorr.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
     lib.bsig_pileup_frag.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
+    lib.bsig_pileup_hist.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
+    lib.bsig_coverage_hist.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
     lib.bsig_pileup_runs.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
     lib.bsig_coverage_runs.argtypes = core_head + [C.c_int32] * 8 + [C.POINTER(C.c_void_p)]
     lib.bsig_runs_result_n_seg.argtypes = [C.c_void_p]

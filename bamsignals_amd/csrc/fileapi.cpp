@@ -765,6 +765,51 @@ int frag_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
     return BSIG_OK;
 }
 
+// The depth histogram over the ranges (bsig_pileup_hist / bsig_coverage_hist): as frag_on_slots -- one GPU takes all ranges;
+// several take a block of the (rid, loc)-sorted ranges each and the host adds the int64 vectors (every row and both moments
+// are sums over ranges)
+int hist_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                  const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t max_value, int64_t cells,
+                  int64_t *out, double *X, std::string &route)
+{
+    const size_t nd = reads.size();
+    if (nd == 1) {
+        const double t0 = now_s();
+        bsig_plan *plan = nullptr;
+        int rc = bsig_plan_create_hist(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, max_value, &plan);
+        X[3] = now_s() - t0;
+        if (rc == BSIG_OK) rc = bsig::plan_run_hist_to_host(plan, out, &X[4], &X[5]);
+        if (plan) bsig_plan_free(plan);
+        route = "sum";
+        return rc;
+    }
+    std::vector<int64_t> order;
+    bsig::sort_ranges(n, rid, loc, order);
+    std::vector<std::vector<int64_t>> part(nd, std::vector<int64_t>((size_t)cells, 0));
+    const int rc = for_each_slot(nd, [&](size_t k) -> int {
+        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
+        if (a >= b) return BSIG_OK;
+        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
+        for (int64_t i = a; i < b; ++i) {
+            const int64_t j = order[(size_t)i];
+            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
+        }
+        bsig_plan *plan = nullptr;
+        int rk = bsig_plan_create_hist(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &prm, max_value, &plan);
+        if (rk == BSIG_OK) rk = bsig_plan_run_hist_host(plan, part[k].data());
+        if (plan) bsig_plan_free(plan);
+        return rk;
+    });
+    if (rc != BSIG_OK) return rc;
+    for (int64_t c = 0; c < cells; ++c) {
+        int64_t t = 0;
+        for (size_t k = 0; k < nd; ++k) t += part[k][(size_t)c];
+        out[c] = t;
+    }
+    route = "sum of " + std::to_string(nd) + " blocks of ranges, added on the host";
+    return BSIG_OK;
+}
+
 }  // namespace
 // the host-side result of bsig_pileup_runs / bsig_coverage_runs: the runs in the caller's range order
 struct bsig_runs_result {
@@ -905,6 +950,8 @@ struct FileDest {
     int32_t max_lag = 0;
     int64_t *frag = nullptr;        // tlen_filter[1] / len_bin + 1 cells: the fragment-length histogram over the ranges
     int32_t len_bin = 0;
+    int64_t *hist = nullptr;        // max_value + 1 + BSIG_HIST_MOMENTS cells: the depth histogram over the ranges
+    int32_t max_value = 0;
     bsig_runs_result *runs = nullptr;   // the per-range result as runs, in the caller's range order
 };
 
@@ -915,7 +962,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (!bampath) return fail(BSIG_ERR_ARG, "bampath is NULL");
     if (n < 0 || (n > 0 && (!seq_code || !start || !width || !strand || !levels)))
         return fail(BSIG_ERR_ARG, "range arrays missing");
-    if (!to.off && !to.dst && !to.sum && !to.xcorr && !to.frag && !to.runs) return fail(BSIG_ERR_ARG, "offsets missing");
+    if (!to.off && !to.dst && !to.sum && !to.xcorr && !to.frag && !to.hist && !to.runs) return fail(BSIG_ERR_ARG, "offsets missing");
     if (to.runs) {
         // runs: bamCount has none; the plan's rule, before the BAM is opened
         g_call_route[0] = 0;
@@ -946,6 +993,17 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         const int rc = bsig::frag_shape(prm, to.len_bin, &fshape);
         if (rc) return rc;
         std::fill(to.frag, to.frag + fshape.cells, (int64_t)0);
+    }
+    bsig::HistShape hshape{};
+    if (to.hist) {
+        // ... and the depth histogram's
+        g_call_route[0] = 0;
+        int rc = bsig::hist_shape(prm, to.max_value, &hshape);
+        // (the plan's rule as well, before the BAM is opened)
+        bsig::PlanRule early;
+        if (rc == BSIG_OK) rc = bsig::check_params(hshape.tiles, n, width, &early);
+        if (rc) return rc;
+        std::fill(to.hist, to.hist + hshape.cells, (int64_t)0);
     }
     double *T = g_call_timing, *X = g_call_timing_ex;
     for (int k = 0; k < 6; ++k) T[k] = 0;
@@ -1246,6 +1304,8 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         rc = xcorr_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.max_lag, xshape.cells, to.xcorr, X, gather);
     } else if (to.frag) {
         rc = frag_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.len_bin, fshape.cells, to.frag, X, gather);
+    } else if (to.hist) {
+        rc = hist_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.max_value, hshape.cells, to.hist, X, gather);
     } else if (to.runs) {
         rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, rule, *to.runs, X, gather);
     } else if (!many) {
@@ -1272,7 +1332,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (rc == BSIG_OK) rc = bam_index_wait(bam);      // a damaged index fails the call, as it does in the reference's open
     T[4] = now_s() - t_begin;
     snprintf(g_call_route, sizeof g_call_route, "%zu GPU slot(s); reads: %s; result: %s", nd, how_decoded.c_str(),
-             many || sum || to.xcorr || to.frag || to.runs ? gather.c_str() : "download");
+             many || sum || to.xcorr || to.frag || to.hist || to.runs ? gather.c_str() : "download");
     return rc;
 }
 
@@ -1570,6 +1630,34 @@ int bsig_pileup_frag(const char *bampath, int64_t n, const int32_t *seq_code, in
     to.len_bin = len_bin;
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
                       pileup_params(tlen_filter, n_tlen_filter, mapqual, -1, 0, 0, requiredF, filteredF, pe_mid != 0), device, to);
+}
+
+int bsig_pileup_hist(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                     const char *const *levels, const int32_t *start, const int32_t *width,
+                     const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                     int32_t mapqual, int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t max_value,
+                     int32_t maxgap, int32_t device, int64_t *out)
+{
+    if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
+    FileDest to;
+    to.hist = out;
+    to.max_value = max_value;
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, ss != 0, requiredF, filteredF, pe_mid != 0), device, to);
+}
+
+int bsig_coverage_hist(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                       const char *const *levels, const int32_t *start, const int32_t *width,
+                       const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t max_value,
+                       int32_t maxgap, int32_t device, int64_t *out)
+{
+    if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
+    FileDest to;
+    to.hist = out;
+    to.max_value = max_value;
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device, to);
 }
 
 int bsig_pileup_runs(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,

@@ -91,6 +91,18 @@ int frag_blocks_per_cu(int threads, bool merge, int n_rows);
 hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                              int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int n_rows,
                              int lenbin, unsigned long long *out, hipStream_t st);
+// Depth histogram over ranges (bsig_plan_create_hist).  k_hist_tiles: run r = per-base tiles [runs[r].x, runs[r].y) of 5' ends
+// (P.ss: every (base, strand) a cell; else the strands' sum) or of coverage; every workgroup ADDS its non-zero rows into out
+// (n_rows int64: row min(value, n_rows - 1)), then the sum of the values into out[n_rows + 1]; the first workgroup adds
+// n_cells, the plan's count of cells, to out[n_rows]: zero `out` first.  wide: 32-bit image cells for the tiles with more
+// reads than a 16-bit cell may see (tiles flagged BSIG_ITEM_HEAVY are skipped by the launch that is not wide).  merge:
+// zero cells counted by ballot, equal rows of a wave merged before the LDS atomic.  half: the form for P.packed_half.
+// windows / resolve_first as in launch_sum_tiles (no fixed windows).
+size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows);
+int hist_blocks_per_cu(int threads, bool coverage, bool half, bool merge, int tile_cells, int n_rows);
+hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, const BsigReadsDev &R, const BsigKParams &P,
+                             const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                             bool resolve_first, int n_rows, unsigned long long n_cells, unsigned long long *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

@@ -2068,6 +2068,252 @@ __global__ __launch_bounds__(NT) void k_frag_tiles(const BsigWorkItem *__restric
 }
 
 // ------------------------------------------------------------------------------------------
+// Depth histogram over ranges (bsig_plan_create_hist)
+// ------------------------------------------------------------------------------------------
+// A tile is up to P.tile_cells consecutive cells of one range, as an ordinary per-base tile is, and writes no per-range
+// cell.  A workgroup owns a run of tiles and keeps ONE histogram of n_rows = V + 1 32-bit counters in LDS for all of
+// them.  Per tile it builds the image the ordinary kernels build -- 5' ends per strand (ProfileOne<true>: dword x holds
+// sense[x] in its low half and antisense[x] in its high half; with P.ss every half is a cell, without the cell is their
+// sum), or coverage's signed 16-bit difference image (CoverOne) followed by k_coverage's workgroup prefix scan -- and
+// then counts the tile's cells by value: row min(value, V) += 1, and the true value into the lane's 64-bit sum.  A lane
+// clears the image cells it has just read, so the tile ends with one barrier.  Cells of the image behind the tile's nc
+// are never counted.
+// WIDE (tiles with more reads in their windows than a 16-bit cell may see, which the plan lists apart; they cannot be
+// cut into slices, because a cell's value must be complete before it is counted): 32-bit image cells, read by read.
+// Exactness.  Every cell adds 1 to one counter and the plan ends a run before its cells pass 2^32 - 1 (runtime.hip:
+// hist_setup); the plan bounds the sum moment below 2^63.  At the end of its run a workgroup adds its non-zero rows to
+// the int64 result with one 64-bit atomic each and its sum with one per wave.
+// Contention.  EVERY cell of a tile goes to the histogram, and on sparse data nearly all of them to row 0 -- one LDS
+// address, which the LDS serves one lane per cycle.  FORM 0 (plain): one LDS atomic per cell.  FORM 1 (merge): the zero
+// cells of a wave are counted by ballot into a scalar that the wave adds to row 0 once per tile; of the others, the lanes
+// that hold the row of the wave's first such lane are counted with a second ballot and added by that lane alone
+// (FragOne<true>'s scheme), the rest add for themselves.
+enum { kHistEnds = 0, kHistEndsHalf = 1, kHistCover = 2 };
+
+// the read-by-read body of a WIDE coverage tile: an int32 difference image
+struct CoverWideOne {
+    const BsigKParams &P;
+    int32_t *img;
+    int loc, c0, nc;
+    bool neg_range;
+    int rend1;
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        if (!valid || rej || tlen_rejected(P, tl)) return;
+        int start = p, end = e;
+        if (P.tspan) {
+            if (neg && tl < 0) start = end + tl + 1;
+            else if (!neg && tl > 0) end = start + tl - 1;
+        }
+        const int ra = neg_range ? rend1 - end : start - loc;
+        const int rb = neg_range ? rend1 - start : end - loc;
+        const int la = ra - c0, lb = rb - c0;
+        if (la >= nc || lb < 0) return;
+        atomicAdd(&img[la > 0 ? la : 0], 1);
+        if (lb + 1 < nc) atomicAdd(&img[lb + 1], -1);
+    }
+};
+
+// LDS of one k_hist_tiles workgroup, in dwords: image | scan totals | filter table | histogram
+struct HistLds {
+    int img, wtot, ptab, hist, total;
+};
+__host__ __device__ inline int hist_img_dwords(int kind, bool wide, int tile_cells)
+{
+    // coverage: whole 16-B vectors of four cells a lane (16-bit: 8-B pairs of dwords, four cells); ends: a dword per cell,
+    // two with 32-bit cells
+    if (kind == kHistCover) return wide ? (tile_cells + 3) & ~3 : ((tile_cells + 3) / 4 * 2 + 3) & ~3;
+    return ((wide ? 2 : 1) * tile_cells + 3) & ~3;
+}
+__host__ __device__ inline HistLds hist_lds(int kind, bool wide, int tile_cells, int n_rows)
+{
+    HistLds L;
+    L.img = 0;
+    L.wtot = hist_img_dwords(kind, wide, tile_cells);
+    L.ptab = L.wtot + 4;
+    L.hist = L.ptab + BSIG_PACK_CODES / 4;
+    L.total = L.hist + ((n_rows + 3) & ~3);
+    return L;
+}
+
+template <int FORM>
+struct HistCounter {
+    uint32_t *hist;
+    uint32_t top;                       // V: the overflow row
+    uint32_t zeros = 0;                 // FORM 1: the wave's zero cells of this tile (uniform over the wave)
+    unsigned long long sum = 0;
+    // (called by all lanes of a wave together: the loops around it are uniform)
+    __device__ __forceinline__ void operator()(uint32_t v, bool ok)
+    {
+        sum += ok ? v : 0u;
+        const uint32_t row = v < top ? v : top;
+        if constexpr (FORM == 1) {
+            const bool z = ok & (v == 0u);
+            zeros += (uint32_t)__popcll(__ballot(z));
+            const bool rest = ok & !z;
+            const unsigned long long m = __ballot(rest);
+            if (m == 0ull) return;                              // (uniform)
+            const int leader = __ffsll((long long)m) - 1;
+            const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)row, leader);
+            const bool same = rest & (row == r0);
+            const uint32_t n_same = (uint32_t)__popcll(__ballot(same));
+            const bool lead = (int)__lane_id() == leader;
+            if (rest & (!same | lead)) atomicAdd(&hist[row], same ? n_same : 1u);
+        } else {
+            if (ok) atomicAdd(&hist[row], 1u);
+        }
+    }
+    // once per tile
+    __device__ __forceinline__ void flush_zeros()
+    {
+        if constexpr (FORM == 1) {
+            if (zeros && __lane_id() == 0) atomicAdd(&hist[0], zeros);
+            zeros = 0;
+        }
+    }
+};
+
+template <int NT, int KIND, bool WIDE, int FORM>
+__global__ __launch_bounds__(NT) void k_hist_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                   unsigned long long *__restrict__ out, const uint2 *__restrict__ windows,
+                                                   const BsigReadsDev R, const BsigKParams P, int n_rows,
+                                                   unsigned long long n_cells)
+{
+    static_assert(!(WIDE && KIND == kHistEndsHalf), "a wide tile reads the packed words");
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const HistLds L = hist_lds(KIND, WIDE, P.tile_cells, n_rows);
+    uint32_t *img = reinterpret_cast<uint32_t *>(lds) + L.img;
+    int32_t *wtot = lds + L.wtot;
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds + L.ptab);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds) + L.hist;
+    for (int v = tid; v < L.ptab; v += NT) lds[v] = 0;
+    for (int v = tid; v < n_rows; v += NT) hist[v] = 0u;
+    if (KIND != kHistEndsHalf) build_ptab<NT>(ptab, R, P, tid);
+    const uint2 run = runs[blockIdx.x];
+    HistCounter<FORM> cnt{hist, (uint32_t)(n_rows - 1)};
+    __syncthreads();
+
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        // (a tile listed apart for the wide launch: its cells are counted there, none here)
+        if (!WIDE && (w.units_strand & BSIG_ITEM_HEAVY)) continue;
+        uint2 win[BSIG_MAX_CLASSES], clip;
+        PackedWin pk;
+        const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
+        const int nc = w.nc;
+        if constexpr (KIND == kHistCover) {
+            load_windows<false>(R, P, BSIG_MODE_COVERAGE, w, items, windows, win, t, pk, clip);
+            const int rend1 = w.loc + w.len - 1;
+            if constexpr (WIDE) {
+                const CoverWideOne one{P, reinterpret_cast<int32_t *>(img), w.loc, w.c0, nc, neg_range, rend1};
+                for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+                if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
+            } else {
+                const CoverOne one{P, reinterpret_cast<int32_t *>(img), w.loc, w.c0, nc, 0, neg_range, rend1};
+                for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+                if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
+            }
+            __syncthreads();
+            // k_coverage's scan: each lane owns 4 consecutive cells, wave scan of the lane totals, carry across waves
+            // and passes; the cells are counted instead of stored
+            const int nvec = (nc + 3) >> 2;
+            auto lo16 = [](uint32_t d) { return (int)(int16_t)(uint16_t)d; };
+            auto hi16 = [](uint32_t d) { return (int)(int16_t)(uint16_t)((d + 0x8000u) >> 16); };
+            int carry = 0;
+            for (int base = 0; base < nvec; base += NT) {
+                const int v = base + tid;
+                int4 x = make_int4(0, 0, 0, 0);
+                if (v < nvec) {
+                    if constexpr (WIDE) {
+                        int4 *p4 = reinterpret_cast<int4 *>(img) + v;
+                        x = *p4;
+                        *p4 = make_int4(0, 0, 0, 0);
+                    } else {
+                        uint2 *p2 = reinterpret_cast<uint2 *>(img) + v;
+                        const uint2 d = *p2;
+                        *p2 = make_uint2(0u, 0u);
+                        x = make_int4(lo16(d.x), hi16(d.x), lo16(d.y), hi16(d.y));
+                    }
+                }
+                x.y += x.x; x.z += x.y; x.w += x.z;
+                const int tot = x.w;
+                const int incl = wave_inclusive_scan(tot);
+                int pre = carry;
+                int all = __builtin_amdgcn_readlane(incl, kWave - 1);
+                if (NT > kWave) {
+                    if (lane == kWave - 1) wtot[tid / kWave] = incl;
+                    __syncthreads();
+                    all = 0;
+                    for (int k = 0; k < NT / kWave; ++k) {
+                        const int s = wtot[k];
+                        if (k < tid / kWave) pre += s;
+                        all += s;
+                    }
+                    __syncthreads();
+                }
+                const int add = pre + incl - tot;
+                const int c = 4 * v;
+                cnt((uint32_t)(x.x + add), c < nc);
+                cnt((uint32_t)(x.y + add), c + 1 < nc);
+                cnt((uint32_t)(x.z + add), c + 2 < nc);
+                cnt((uint32_t)(x.w + add), c + 3 < nc);
+                carry += all;
+            }
+        } else {
+            load_windows<false>(R, P, BSIG_MODE_PROFILE, w, items, windows, win, t, pk, clip);
+            if constexpr (WIDE) {
+                const XcorrWideOne one{P, img, w.loc, w.len, w.c0, nc, neg_range};
+                for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+                if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+            } else {
+                constexpr bool HALF = KIND == kHistEndsHalf;
+                const ProfileOne<true> one{P, img, w.loc, w.len, w.c0, nc, 0, neg_range};
+                for_each_read<NT, 2, HALF>(R, P, win, pk.base, ptab, tid, one);
+                if (!HALF && pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+            }
+            __syncthreads();
+            const bool ss = P.ss != 0;                                  // (uniform)
+            for (int base = 0; base < nc; base += NT) {
+                const int x = base + tid;
+                const bool ok = x < nc;
+                uint32_t s = 0, a = 0;
+                if (ok) {
+                    if constexpr (WIDE) {
+                        uint2 *p2 = reinterpret_cast<uint2 *>(img) + x;
+                        const uint2 d = *p2;
+                        *p2 = make_uint2(0u, 0u);
+                        s = d.x; a = d.y;
+                    } else {
+                        const uint32_t d = img[x];
+                        img[x] = 0u;
+                        s = d & 0xFFFFu; a = d >> 16;
+                    }
+                }
+                if (ss) { cnt(s, ok); cnt(a, ok); }
+                else cnt(s + a, ok);
+            }
+        }
+        cnt.flush_zeros();
+        __syncthreads();
+    }
+    __syncthreads();
+    for (int v = tid; v < n_rows; v += NT) {
+        const uint32_t c = hist[v];
+        if (c) atomicAdd(out + v, (unsigned long long)c);
+    }
+    unsigned long long m_sum = cnt.sum;
+    for (int m = kWave / 2; m >= 1; m /= 2) m_sum += __shfl_xor(m_sum, m);
+    if (lane == 0) {
+        unsigned long long *mo = out + n_rows;                  // moments: [cells (the plan's count), sum of the values]
+        if (blockIdx.x == 0 && tid == 0 && n_cells) atomicAdd(mo, n_cells);
+        if (m_sum) atomicAdd(mo + 1, m_sum);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // one-time layout of the reads in HBM
 // ------------------------------------------------------------------------------------------
 
@@ -2833,6 +3079,58 @@ hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, con
     const size_t lds = frag_tiles_lds(n_rows);
     return with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k) {
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, lenbin);
+        return hipGetLastError();
+    });
+}
+
+// ---- depth histogram -----------------------------------------------------------------------------------------------
+size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows)
+{
+    return (size_t)hist_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells, n_rows).total * 4;
+}
+
+// one k_hist_tiles instantiation by its run-time choices (f receives the kernel's address)
+template <typename Fn>
+static hipError_t with_hist_kernel(int threads, bool coverage, bool half, bool wide, bool merge, Fn &&f)
+{
+#define BSIG_HF(NT_, F_) do { if (coverage) { if (wide) return f(k_hist_tiles<NT_, kHistCover, true, F_>); return f(k_hist_tiles<NT_, kHistCover, false, F_>); } \
+                              if (wide) return f(k_hist_tiles<NT_, kHistEnds, true, F_>); \
+                              if (half) return f(k_hist_tiles<NT_, kHistEndsHalf, false, F_>); \
+                              return f(k_hist_tiles<NT_, kHistEnds, false, F_>); } while (0)
+#define BSIG_HK(NT_) do { if (merge) BSIG_HF(NT_, 1); BSIG_HF(NT_, 0); } while (0)
+    if (threads == 64) BSIG_HK(64);
+    if (threads == 128) BSIG_HK(128);
+    if (threads == 256) BSIG_HK(256);
+#undef BSIG_HK
+#undef BSIG_HF
+    return hipErrorInvalidValue;
+}
+
+int hist_blocks_per_cu(int threads, bool coverage, bool half, bool merge, int tile_cells, int n_rows)
+{
+    int nb = 0;
+    const size_t lds = hist_tiles_lds(coverage, false, tile_cells, n_rows);
+    const hipError_t e = with_hist_kernel(threads, coverage, half, false, merge, [&](auto k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
+    });
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, const BsigReadsDev &R, const BsigKParams &P,
+                             const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                             bool resolve_first, int n_rows, unsigned long long n_cells, unsigned long long *out, hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE, items, (uint32_t)n_items,
+                           reinterpret_cast<BsigResolved *>(windows));
+    }
+    const size_t lds = hist_tiles_lds(coverage, wide, P.tile_cells, n_rows);
+    return with_hist_kernel(threads, coverage, !wide && P.packed_half != 0, wide, merge, [&](auto k) {
+        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, n_cells);
         return hipGetLastError();
     });
 }

@@ -279,6 +279,17 @@ struct FragState {
     int64_t *d_out = nullptr;           // device result of bsig_plan_run_frag_host
 };
 
+// a HIST plan's own (bsig_plan_create_hist): per-base tiles in genomic order, cut into one round of runs
+struct HistState {
+    bsig::HistShape shape;
+    bool coverage = false;              // the signal: coverage, else 5' ends
+    bool merge = false;                 // k_hist_tiles' form: zero cells by ballot, equal rows of a wave merged (see hist_setup)
+    uint2 *runs = nullptr;              // runs of the main tiles, then those of the wide tiles (one tile each)
+    int64_t n_runs_main = 0, n_runs_wide = 0;
+    int64_t n_cells = 0;                // moments[0]: the cells of all ranges
+    int64_t *d_out = nullptr;           // device result of bsig_plan_run_hist_host
+};
+
 struct bsig_plan {
     bsig_ctx *ctx = nullptr;
     const bsig_reads *reads = nullptr;
@@ -313,6 +324,7 @@ struct bsig_plan {
     std::unique_ptr<SumState> sum;      // a sum plan's (bsig_plan_create_sum), else null
     std::unique_ptr<XcorrState> xcorr;  // an xcorr plan's (bsig_plan_create_xcorr), else null
     std::unique_ptr<FragState> frag;    // a frag plan's (bsig_plan_create_frag), else null
+    std::unique_ptr<HistState> hist;    // a hist plan's (bsig_plan_create_hist), else null
 };
 static int64_t g_resolve_min_override = -1;     // bsig_debug_set_knob(4, n): two launches from n tiles on (sweeps)
 // does a run of this plan look its windows up in a launch of its own?  (measured at the north star's read density,
@@ -1478,17 +1490,48 @@ int bsig::frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out)
     return BSIG_OK;
 }
 
+// What only a depth histogram asks, ahead of check_params: one of the two per-base signals the definition is stated in
+// (5' ends per base without a shift; plain coverage, which has no strands), as many rows as the kernel's LDS holds beside
+// its widest image, and a workgroup and tile the kernel is built for.
+int bsig::hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out)
+{
+    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the depth histogram counts per-base cells: bamCount has one cell per range");
+    if (prm.mode == BSIG_MODE_COVERAGE_EX)
+        return fail(BSIG_ERR_ARG, "the depth histogram of coverage is per base and unstranded: mode BSIG_MODE_COVERAGE");
+    if (prm.mode == BSIG_MODE_PROFILE && prm.binsize != 1) return fail(BSIG_ERR_ARG, "the depth histogram is per base: binsize must be 1");
+    if (prm.shift != 0) return fail(BSIG_ERR_ARG, "the depth histogram counts unshifted positions: shift must be 0");
+    if (prm.mode == BSIG_MODE_COVERAGE && prm.ss != 0) return fail(BSIG_ERR_ARG, "the depth histogram of coverage has no strands: ss must be 0");
+    if (max_value < 1 || max_value > BSIG_HIST_MAX_ROWS - 1)
+        return fail(BSIG_ERR_ARG, "max_value must be between 1 and %d", BSIG_HIST_MAX_ROWS - 1);
+    if (prm.threads != 0 && prm.threads != 64 && prm.threads != 128 && prm.threads != 256)
+        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
+    if (prm.tile_cells != 0 && (prm.tile_cells < 16 || prm.tile_cells > 2048))
+        return fail(BSIG_ERR_ARG, "tile_cells must be between 16 and 2048");
+    HistShape s;
+    s.tiles = prm;
+    s.tiles.ss = prm.mode == BSIG_MODE_PROFILE && prm.ss != 0;
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.tiles.tile_cells = prm.tile_cells != 0 ? prm.tile_cells : 2048;
+    s.max_value = max_value;
+    s.cells = (int64_t)max_value + 1 + BSIG_HIST_MOMENTS;
+    *out = s;
+    return BSIG_OK;
+}
+
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells);
 static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &tile_reads);
 static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells);
 // sum: a plan for bsig_plan_create_sum -- its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
 // xc: a plan for bsig_plan_create_xcorr -- tiles of a body and an antisense halo, none of them cut into slices
 // fr: a plan for bsig_plan_create_frag -- count tiles, none of them cut into slices (they have no image)
-// (a plan is at most one of the three)
+// hs: a plan for bsig_plan_create_hist -- the mode's per-base tiles, none of them cut into slices
+// (a plan is at most one of the four)
 static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
                             const int32_t *loc, const int32_t *len, const int32_t *strand,
                             const bsig_params *prm, const bsig::SumShape *sum, bsig_plan **out,
-                            const bsig::XcorrShape *xc = nullptr, const bsig::FragShape *fr = nullptr)
+                            const bsig::XcorrShape *xc = nullptr, const bsig::FragShape *fr = nullptr,
+                            const bsig::HistShape *hs = nullptr)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
@@ -1528,6 +1571,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // cross-correlation: a body no wider than the widest range, and an image of the body and a halo of max_lag cells
     const int xbody = xc ? (int)std::min<int64_t>(xc->body, widest) : 0;
     if (xc) P->tile_cells = (xbody + xc->max_lag + 3) & ~3;
+    // depth histogram: the caller's tile (16 .. 2,048 cells, checked by hist_shape), whatever the widest range
+    if (hs) P->tile_cells = (hs->tiles.tile_cells + 3) & ~3;
     P->threads = r.threads;
     BsigKParams &K = P->kp;
     K.mapqual = prm->mapqual;
@@ -1693,7 +1738,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         if (e == hipSuccess) e = hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         // the windows themselves are only fetched when there is something to slice (a frag plan cuts its runs by them)
-        if (e == hipSuccess && (n_heavy_dev || fr)) {
+        if (e == hipSuccess && (n_heavy_dev || fr || hs)) {
             win.resize(items.size() * BSIG_MAX_CLASSES);
             e = hipMemcpyAsync(win.data(), d_win, win.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1709,12 +1754,34 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
                 frag_reads[t] = total;
             }
         }
+        if (e == hipSuccess && hs) {
+            // The depth histogram's proof that its sum moment stays below 2^63: a read in a tile's windows adds at most 1 to
+            // one cell of the tile (5' ends) or to each of its cells (coverage)
+            long double bound = 0;
+            for (size_t t = 0; t < items.size(); ++t) {
+                int64_t total = 0;
+                for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
+                bound += mode == BSIG_MODE_COVERAGE ? (long double)total * (long double)items[t].nc : (long double)total;
+            }
+            if (bound >= 9223372036854775808.0L) {
+                delete P;
+                return fail(BSIG_ERR_ARG, "the summed depth of these ranges could exceed 2^63 - 1 (the reads of their tiles add up "
+                                          "to %.3Lg): take fewer ranges per call", bound);
+            }
+        }
         if (e == hipSuccess && n_heavy_dev && !fr) {
             for (size_t t = 0; t < items.size(); ++t) {
                 int64_t total = 0;
                 for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
                 if (total <= heavy_reads) continue;
                 ++P->n_heavy_tiles;
+                if (hs) {
+                    // a cell's value must be complete before it is counted: such a tile is walked whole, by one workgroup
+                    // of the second launch, into an image of 32-bit cells
+                    hitems.push_back(items[t]);
+                    items[t].units_strand |= BSIG_ITEM_HEAVY;
+                    continue;
+                }
                 if (xc) {
                     // a product of two counts is not linear in slices of the reads: such a tile is walked whole, by one
                     // workgroup of the second launch, into an image of 32-bit cells
@@ -1780,6 +1847,12 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     }
     if (fr) {
         const int rc = frag_setup(P, *fr, frag_reads);
+        if (rc != BSIG_OK) { delete P; return rc; }
+    }
+    if (hs) {
+        int64_t n_cells = 0;
+        for (int64_t i = 0; i < n; ++i) n_cells += (int64_t)len[i] * mult;
+        const int rc = hist_setup(P, *hs, items, (int64_t)hitems.size(), n_cells);
         if (rc != BSIG_OK) { delete P; return rc; }
     }
     *out = P;
@@ -1953,6 +2026,69 @@ static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vec
     return BSIG_OK;
 }
 
+// The runs of a hist plan: the tiles, in genomic order, cut into as many runs as workgroups are resident at a time (by
+// occupancy), as a frag plan's are -- a workgroup keeps its histogram in LDS across its run and ends with one 64-bit atomic
+// per non-zero row.  The histogram's counters have 32 bits and every cell of a tile adds 1 to one of them, so a run also
+// ends where the cells of its tiles would pass the ceiling of 2^32 - 1: no counter wraps.  The wide tiles (32-bit image)
+// follow as runs of one tile each: they are few and long.
+static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells)
+{
+    constexpr int64_t kCounterMax = 4294967295ll;
+    P->hist.reset(new HistState);
+    HistState &Q = *P->hist;
+    Q.shape = shape;
+    Q.coverage = P->mode == BSIG_MODE_COVERAGE;
+    Q.n_cells = n_cells;
+    // The form: one LDS atomic per cell ("plain", the default), or the zero cells of a wave counted by ballot and the rows
+    // equal to the wave's first non-zero lane's merged before the atomic ("merge").  The merging form becomes the default
+    // only where scripts/depthhist_times.py shows it faster than the plain one by more than the runs' spread:
+    // BAMSIGNALS_HIST_FORM chooses, read when the plan is made.
+    if (const char *v = getenv("BAMSIGNALS_HIST_FORM")) Q.merge = strcmp(v, "merge") == 0;
+    const int n_rows = shape.max_value + 1;
+    int n_cu = 0, lds_max = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
+    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    const size_t lds = bsig::hist_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells, n_rows);
+    if (lds > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "%d rows and a tile of %d cells need %zu bytes of LDS per workgroup, the device has %d", n_rows,
+                    P->tile_cells, lds, lds_max);
+    const int64_t resident = (int64_t)std::max(n_cu, 1) *
+                             bsig::hist_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, Q.merge, P->tile_cells, n_rows);
+    int64_t per = std::max<int64_t>(1, (P->n_items + resident - 1) / resident);
+    // (tests: BAMSIGNALS_HIST_RUN_TILES = tiles per run instead of the occupancy's, BAMSIGNALS_HIST_FLUSH_CELLS = a lower
+    // ceiling for the cells of a run; both read when the plan is made)
+    if (const char *v = getenv("BAMSIGNALS_HIST_RUN_TILES")) {
+        const long long forced = atoll(v);
+        if (forced > 0) per = forced;
+    }
+    int64_t ceiling = kCounterMax;
+    if (const char *v = getenv("BAMSIGNALS_HIST_FLUSH_CELLS")) ceiling = std::min<long long>(kCounterMax, std::max<long long>(1, atoll(v)));
+    const int64_t S = P->kp.ss ? 2 : 1;
+    std::vector<uint2> runs;
+    int64_t a = 0, in_run = 0;
+    for (int64_t t = 0; t < P->n_items; ++t) {
+        // (a tile holds at most 2 x 2,048 cells: it is the real ceiling that counters need, a lowered one may be passed
+        // by a run of one tile)
+        const int64_t nc = (int64_t)items[(size_t)t].nc * S;
+        if (t > a && (t - a >= per || in_run + nc > ceiling)) {
+            runs.push_back(make_uint2((uint32_t)a, (uint32_t)t));
+            a = t; in_run = 0;
+        }
+        in_run += nc;
+    }
+    if (a < P->n_items) runs.push_back(make_uint2((uint32_t)a, (uint32_t)P->n_items));
+    Q.n_runs_main = (int64_t)runs.size();
+    for (int64_t k = 0; k < n_wide; ++k) runs.push_back(make_uint2((uint32_t)k, (uint32_t)k + 1u));
+    Q.n_runs_wide = n_wide;
+    if (!runs.empty()) {
+        hipStream_t st = P->ctx->stream;
+        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
+        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return BSIG_OK;
+}
+
 extern "C" {
 
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
@@ -1999,6 +2135,7 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -2033,6 +2170,7 @@ int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
     const bsig::HostDest dst{out_host};
     return bsig::plan_run_to_host(p, &dst, nullptr);
 }
@@ -2122,6 +2260,27 @@ int bsig::plan_run_frag_to_host(bsig_plan *p, int64_t *host, double *t_kernels, 
     if (t_download) *t_download = since(t1);
     return BSIG_OK;
 }
+int bsig::plan_run_hist_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    HistState *Q = p->hist.get();
+    if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->shape.cells));
+    const int rc = bsig_plan_run_hist(p, Q->d_out);
+    if (rc != BSIG_OK) return rc;
+    if (t_kernels) {
+        HIP_TRY(hipStreamSynchronize(st));
+        *t_kernels = since(t0);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->shape.cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (t_download) *t_download = since(t1);
+    return BSIG_OK;
+}
 // a run whose slices took a bin past INT32_MAX fails (after the caller's synchronisation: no wait of its own)
 int bsig::plan_check_overflow(bsig_plan *p)
 {
@@ -2139,6 +2298,7 @@ int bsig_plan_run_host_async(bsig_plan *p, int32_t *out_host)
     if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
     const bsig::HostDest dst{out_host};
     return bsig::plan_run_to_host(p, &dst, nullptr, true);
 }
@@ -2165,7 +2325,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     bsig_plan_stats t{};
     t.n_ranges = p->n_ranges;
     t.n_items = p->n_items;
-    t.cells = p->sum ? p->sum->shape.cells : p->xcorr ? p->xcorr->shape.cells : p->frag ? p->frag->shape.cells : p->off.back();
+    t.cells = p->sum ? p->sum->shape.cells : p->xcorr ? p->xcorr->shape.cells : p->frag ? p->frag->shape.cells : p->hist ? p->hist->shape.cells : p->off.back();
     t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
     t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
     t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
@@ -2178,7 +2338,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
     t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
                           t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
-                          (p->sum || p->xcorr || p->frag ? 8 : 4) * t.cells;
+                          (p->sum || p->xcorr || p->frag || p->hist ? 8 : 4) * t.cells;
     if (plan_two_launches(p) && windows_kept()) {
         // a resident plan's step reads the windows kept from its first run: no index entry is touched
         t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
@@ -2213,6 +2373,7 @@ int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
     if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
     const SumState &Q = *p->sum;
     const int64_t cells = Q.shape.cells;
@@ -2252,6 +2413,7 @@ int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host)
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
     if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
     return bsig::plan_run_to_host(p, nullptr, sum_host);
 }
@@ -2272,6 +2434,7 @@ int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
     if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum runs it" : "not an xcorr plan: bsig_plan_run runs it");
     const XcorrState &Q = *p->xcorr;
     if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -2303,6 +2466,7 @@ int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
     if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum_host runs it" : "not an xcorr plan: bsig_plan_run_host runs it");
     return bsig::plan_run_xcorr_to_host(p, host);
 }
@@ -2320,17 +2484,20 @@ int bsig_plan_create_frag(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, con
 int64_t bsig_plan_frag_cells(const bsig_plan *p) { return p && p->frag ? p->frag->shape.cells : 0; }
 int64_t bsig_plan_frag_runs(const bsig_plan *p) { return p && p->frag ? p->frag->n_runs : 0; }
 
-// which run call a plan that is no frag plan takes (the refusals' wording)
+// which run call a plan takes (the refusals' wording)
 static const char *run_call_of(const bsig_plan *p, bool host)
 {
     if (p->sum) return host ? "bsig_plan_run_sum_host" : "bsig_plan_run_sum";
     if (p->xcorr) return host ? "bsig_plan_run_xcorr_host" : "bsig_plan_run_xcorr";
+    if (p->frag) return host ? "bsig_plan_run_frag_host" : "bsig_plan_run_frag";
+    if (p->hist) return host ? "bsig_plan_run_hist_host" : "bsig_plan_run_hist";
     return host ? "bsig_plan_run_host" : "bsig_plan_run";
 }
 
 int bsig_plan_run_frag(bsig_plan *p, int64_t *dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
     if (!p->frag) return fail(BSIG_ERR_ARG, "not a frag plan: %s runs it", run_call_of(p, false));
     const FragState &Q = *p->frag;
     if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -2354,8 +2521,59 @@ int bsig_plan_run_frag(bsig_plan *p, int64_t *dev)
 int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
     if (!p->frag) return fail(BSIG_ERR_ARG, "not a frag plan: %s runs it", run_call_of(p, true));
     return bsig::plan_run_frag_to_host(p, host);
+}
+
+int bsig_plan_create_hist(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                          const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t max_value, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_hist");
+    *out = nullptr;
+    bsig::HistShape shape;
+    const int rc = bsig::hist_shape(*prm, max_value, &shape);
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, nullptr, out, nullptr, nullptr, &shape);
+}
+
+int64_t bsig_plan_hist_cells(const bsig_plan *p) { return p && p->hist ? p->hist->shape.cells : 0; }
+int64_t bsig_plan_hist_runs(const bsig_plan *p) { return p && p->hist ? p->hist->n_runs_main + p->hist->n_runs_wide : 0; }
+
+int bsig_plan_run_hist(bsig_plan *p, int64_t *dev)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->hist) return fail(BSIG_ERR_ARG, "not a hist plan: %s runs it", run_call_of(p, false));
+    const HistState &Q = *p->hist;
+    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
+    if (p->reads->layout_gen != p->made_for_gen)
+        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    const int n_rows = Q.shape.max_value + 1;
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
+    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)Q.shape.cells * sizeof(int64_t), st));
+    if (Q.n_runs_main) {
+        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+            return bsig::launch_hist_tiles(p->threads, Q.coverage, false, Q.merge, p->reads->dev, kp, p->items, p->n_items, Q.runs,
+                                           Q.n_runs_main, resolved, lookup, n_rows, (unsigned long long)Q.n_cells, out, st);
+        });
+        if (rc != BSIG_OK) return rc;
+    }
+    // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
+    // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
+    if (Q.n_runs_wide)
+        HIP_TRY(bsig::launch_hist_tiles(p->threads, Q.coverage, true, Q.merge, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                        Q.runs + Q.n_runs_main, Q.n_runs_wide, nullptr, false, n_rows, 0ull, out, st));
+    ++p->runs;
+    return BSIG_OK;
+}
+
+int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (!p->hist) return fail(BSIG_ERR_ARG, "not a hist plan: %s runs it", run_call_of(p, true));
+    return bsig::plan_run_hist_to_host(p, host);
 }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
@@ -2365,8 +2583,8 @@ int bsig_plan_runs_create(const bsig_plan *p, bsig_runs **out)
 {
     if (!p || !out) return fail(BSIG_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (p->sum || p->xcorr || p->frag)
-        return fail(BSIG_ERR_ARG, "a %s plan has no per-range result to encode", p->sum ? "sum" : p->xcorr ? "xcorr" : "frag");
+    if (p->sum || p->xcorr || p->frag || p->hist)
+        return fail(BSIG_ERR_ARG, "a %s plan has no per-range result to encode", p->sum ? "sum" : p->xcorr ? "xcorr" : p->frag ? "frag" : "hist");
     if (p->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
     const int S = p->kp.ss ? 2 : 1;
     std::vector<int64_t> base((size_t)(p->n_ranges * S));

@@ -276,6 +276,16 @@ struct FragShape {
 int frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out);
 // bsig_plan_run_frag into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
 int plan_run_frag_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
+// what only a depth histogram asks, ahead of check_params (runtime.hip: hist_shape): per-base 5' ends or plain coverage, no
+// shift, 1 <= max_value < BSIG_HIST_MAX_ROWS, threads and tile_cells the kernel's LDS holds
+struct HistShape {
+    bsig_params tiles;      // the per-base plan the tiles are piled up by (threads and tile_cells resolved)
+    int32_t max_value;      // V: the overflow row
+    int64_t cells;          // V + 1 + BSIG_HIST_MOMENTS
+};
+int hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out);
+// bsig_plan_run_hist into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
+int plan_run_hist_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

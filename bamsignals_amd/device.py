@@ -459,6 +459,57 @@ class FragPlan:
         self.close()
 
 
+class HistPlan:
+    """Ranges + call parameters resident in HBM for the depth histogram (bsig_plan_create_hist): each run gives
+    ``max_value + 1 + 2`` int64 -- row r counts the cells of value r that ``Plan`` returns for the ranges under the same
+    parameters, the last row those of value >= ``max_value``; then the moments [cells, sum of the cell values].
+    ``params``: mode COVERAGE (ss 0), or mode PROFILE with binsize 1 and shift 0 (ss: every (base, strand) a cell);
+    ``tile_cells`` = cells of a tile (16 .. 2,048), ``threads`` per workgroup.  ``runs``: the runs of tiles (a workgroup
+    each) the plan was cut into.  ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit image."""
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, max_value):
+        self._lib = _lib.load()
+        self.ctx, self.reads = ctx, reads
+        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_create_hist(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
+                                                   _ptr(strand), C.byref(params), int(max_value), C.byref(h)))
+        self._h = h
+        self.n_ranges = n
+        self.max_value = int(max_value)
+        self.cells = int(self._lib.bsig_plan_hist_cells(h))
+        self.runs = int(self._lib.bsig_plan_hist_runs(h))
+
+    def run_host(self, out=None):
+        """Run and return the int64 result in host memory: ``out[:max_value + 1]`` is the histogram, the rest the moments."""
+        if out is None:
+            out = np.empty(self.cells, dtype=np.int64)
+        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
+        _lib.check(self._lib.bsig_plan_run_hist_host(self._h, _ptr(out)))
+        return out
+
+    def run_device(self, out_ptr):
+        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
+        _lib.check(self._lib.bsig_plan_run_hist(self._h, C.c_void_p(out_ptr)))
+
+    def stats(self):
+        s = _lib.PlanStats()
+        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class RunEncoder:
     """Run-length encoder of int32 device buffers (bsig_runs_*): segment k is the ``length[k]`` cells
     ``src[base[k] + p * stride]``; ``stride`` 1, or 2 for one row of the interleaved ``2 * bin + antisense`` layout.

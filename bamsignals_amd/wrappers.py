@@ -208,6 +208,44 @@ def pileup_frag(bampath, gr, tlen_filter, mapqual=0, requiredF=66, filteredF=-1,
     return out
 
 
+def _hist_out(max_value):
+    rows = min(max(int(max_value), 0), _lib.HIST_MAX_ROWS - 1) + 1
+    return np.zeros(rows + _lib.HIST_MOMENTS, dtype=np.int64)
+
+
+def pileup_hist(bampath, gr, tlen_filter, mapqual=0, ss=False, requiredF=0, filteredF=-1, pe_mid=False, max_value=1000,
+                maxgap=16385, device=None):
+    """The depth histogram of the 5' ends over the ranges (bsig_pileup_hist): ``max_value + 1 + 2`` int64, the histogram
+    (last row: values >= ``max_value``) then the moments [cells, sum of the values]."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    out = _hist_out(max_value)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_pileup_hist(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
+                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
+                                    tf.ctypes.data, len(tf), int(mapqual), int(bool(ss)), int(requiredF), int(filteredF),
+                                    int(bool(pe_mid)), int(max_value), int(maxgap), _dev(device), out.ctypes.data))
+    return out
+
+
+def coverage_hist(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False, max_value=1000,
+                  maxgap=16385, device=None):
+    """The depth histogram of the per-base coverage over the ranges (bsig_coverage_hist): as ``pileup_hist``."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    out = _hist_out(max_value)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_coverage_hist(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+                                      start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
+                                      int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(max_value),
+                                      int(maxgap), _dev(device), out.ctypes.data))
+    return out
+
+
 def _take_runs(lib, handle, ss):
     """a bsig_runs_result handle -> RunSignals (the arrays are allocated once the handle says how large they are)"""
     try:

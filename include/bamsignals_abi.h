@@ -279,6 +279,40 @@ int64_t bsig_plan_frag_runs(const bsig_plan *plan);              /* runs of tile
 int bsig_plan_run_frag(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_frag_host(bsig_plan *plan, int64_t *host);
 
+/* Depth histogram over ranges: how the depth is distributed over the targets -- the share of bases covered at >= 20x, the
+ * mean and median depth of a panel, the duplication histogram of the 5' ends -- without the per-base result.  Two signals:
+ * mode BSIG_MODE_COVERAGE (per-base coverage with the caller's tspan / tlen filter / flags / mapqual; ss must be 0) and mode
+ * BSIG_MODE_PROFILE (5'-end counts, binsize 1, shift 0, the caller's pe_mid / filters; with ss = 1 every (base, strand) is a
+ * cell of its own, so a range has 2 w cells; with ss = 0 a cell is a base and its value the sum of both strands).  With
+ * V = max_value and cells_i the cells that bsig_plan_create's plan returns for range i under the same parameters:
+ *   n_rows  = V + 1
+ *   hist[r] = #{cells c of all ranges : c == r}   r < V          hist[V] = #{cells c of all ranges : c >= V}  (overflow row)
+ *   moments = [ number of cells, sum of all cell values ]         (the sum is of the true values, not the clipped ones)
+ * The result is bsig_plan_hist_cells() = n_rows + BSIG_HIST_MOMENTS int64: the histogram, then the moments.  Ranges may
+ * differ in width, overlap, repeat (a repeated range counts twice), overhang their reference (cells of an overhang are
+ * cells of value 0) or be empty; their strand does not influence the result.
+ * params: mode as above (BSIG_MODE_COUNT, BSIG_MODE_COVERAGE_EX: BSIG_ERR_ARG), binsize 1 for BSIG_MODE_PROFILE, shift 0, ss 0
+ * for coverage; tile_cells = cells of a tile (16 .. 2,048; 0: 2,048), threads 64 / 128 / 256 per workgroup (0: 256);
+ * 1 <= max_value <= BSIG_HIST_MAX_ROWS - 1; anything else: BSIG_ERR_ARG.  No count wraps (a workgroup's 32-bit counters see
+ * fewer than 2^32 cells: the plan cuts its runs of tiles by their cells; bsig_plan_hist_runs() shows the cut), and the plan
+ * proves from the reads in its tiles' windows that the sum moment stays below 2^63, or bsig_plan_create_hist fails with
+ * BSIG_ERR_ARG.  bsig_plan_get_stats: cells = n_rows + BSIG_HIST_MOMENTS, visits as the ordinary plan's of the same mode,
+ * parameters and tile_cells, heavy_tiles = the tiles that took the 32-bit image (more reads in their windows than a 16-bit
+ * cell may see; they are not cut into slices: a cell's value must be complete before it is counted).  A hist plan runs with
+ * bsig_plan_run_hist* only, and no other plan does (BSIG_ERR_ARG).
+ * BSIG_HIST_MAX_ROWS: 8,192 32-bit counters are 32 KiB of LDS; the widest image, 32-bit cells of a 2,048-cell tile with
+ * strands, is 16 KiB; the scan totals 16 B and the filter table 512 B: 49,680 of the 65,536 bytes a workgroup may ask for. */
+#define BSIG_HIST_MAX_ROWS 8192
+#define BSIG_HIST_MOMENTS 2
+int bsig_plan_create_hist(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                          const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t max_value,
+                          bsig_plan **plan);
+int64_t bsig_plan_hist_cells(const bsig_plan *plan);             /* max_value + 1 + BSIG_HIST_MOMENTS, 0 for any other plan */
+int64_t bsig_plan_hist_runs(const bsig_plan *plan);              /* runs of tiles, 0 for any other plan         */
+/* asynchronous, on the context's stream; dev: bsig_plan_hist_cells() int64 on the device, 8-B aligned (zeroed by the call) */
+int bsig_plan_run_hist(bsig_plan *plan, int64_t *dev);
+int bsig_plan_run_hist_host(bsig_plan *plan, int64_t *host);
+
 /* Run-length encoding on the device: a per-range result as runs (value, length), the form of an Rle / a bedGraph.  The
  * encoder works on ANY int32 device buffer plus a table of segments: segment k is the len[k] cells
  * src[base[k] + p * stride], p = 0 .. len[k] - 1; stride 1, or 2 for one row of the 2 * bin + antisense layout (else
@@ -304,7 +338,7 @@ int bsig_runs_fetch(bsig_runs *runs, int64_t *seg_off, int32_t *values, int32_t 
 void bsig_runs_free(bsig_runs *runs);
 /* The encoder of a plan's own result layout (bsig_plan_offsets): n_seg = n_ranges * S segments, S = 2 with strands (segment
  * S * i + antisense, stride 2), else 1; encode what bsig_plan_run wrote.  For ordinary plans of mode BSIG_MODE_PROFILE,
- * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr or frag plan fail with BSIG_ERR_ARG. */
+ * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr, frag or hist plan fail with BSIG_ERR_ARG. */
 int bsig_plan_runs_create(const bsig_plan *plan, bsig_runs **runs);
 
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
@@ -474,6 +508,22 @@ int bsig_pileup_frag(const char *bampath, int64_t n_ranges, const int32_t *seq_c
                      const int32_t *tlen_filter, int32_t n_tlen_filter,
                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t len_bin,
                      int32_t maxgap, int32_t device, int64_t *out);
+/* The depth histogram over the ranges (bsig_plan_create_hist): out receives max_value + 1 + BSIG_HIST_MOMENTS int64, the
+ * histogram then the moments.  bsig_pileup_hist: the 5' ends (ss 0 / 1); bsig_coverage_hist: the per-base coverage.
+ * max_value and the parameters are checked before the BAM is opened or decoded.  With several GPUs each takes its block of
+ * the (rid, loc)-sorted ranges and the host adds the vectors (bsig_last_call_route(): "sum", as bsig_pileup_sum).       */
+int bsig_pileup_hist(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                     int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                     const int32_t *width, const int32_t *strand,
+                     const int32_t *tlen_filter, int32_t n_tlen_filter,
+                     int32_t mapqual, int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t max_value,
+                     int32_t maxgap, int32_t device, int64_t *out);
+int bsig_coverage_hist(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                       int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                       const int32_t *width, const int32_t *strand,
+                       const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t max_value,
+                       int32_t maxgap, int32_t device, int64_t *out);
 /* The file-level calls with the result as RUNS (bsig_runs_*): bsig_pileup_core's / bsig_coverage_core_ex's arguments
  * without out / off; binsize <= 0 (bamCount) fails with BSIG_ERR_ARG, and all parameters are checked before the BAM is
  * opened.  The per-base cells live only in HBM, and only for one block of the (rid, loc)-sorted ranges at a time: a block
