@@ -113,30 +113,15 @@ def load():
     lib.bsig_plan_overflowed.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.bsig_plan_free.argtypes = [C.c_void_p]
     lib.bsig_plan_free.restype = None
-    lib.bsig_plan_create_sum.argtypes = lib.bsig_plan_create.argtypes
-    lib.bsig_plan_sum_cells.argtypes = [C.c_void_p]
-    lib.bsig_plan_sum_cells.restype = C.c_int64
-    lib.bsig_plan_run_sum.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_run_sum_host.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_create_xcorr.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
-    lib.bsig_plan_xcorr_cells.argtypes = [C.c_void_p]
-    lib.bsig_plan_xcorr_cells.restype = C.c_int64
-    lib.bsig_plan_run_xcorr.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_run_xcorr_host.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_create_frag.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
-    lib.bsig_plan_frag_cells.argtypes = [C.c_void_p]
-    lib.bsig_plan_frag_cells.restype = C.c_int64
-    lib.bsig_plan_frag_runs.argtypes = [C.c_void_p]
-    lib.bsig_plan_frag_runs.restype = C.c_int64
-    lib.bsig_plan_run_frag.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_run_frag_host.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_create_hist.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
-    lib.bsig_plan_hist_cells.argtypes = [C.c_void_p]
-    lib.bsig_plan_hist_cells.restype = C.c_int64
-    lib.bsig_plan_hist_runs.argtypes = [C.c_void_p]
-    lib.bsig_plan_hist_runs.restype = C.c_int64
-    lib.bsig_plan_run_hist.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bsig_plan_run_hist_host.argtypes = [C.c_void_p, C.c_void_p]
+    # the reduction plans: (kind, has an int32 argument of its own, has a runs query)
+    for kind, extra, runs in (("sum", False, False), ("xcorr", True, False), ("frag", True, True), ("hist", True, True)):
+        create = lib.bsig_plan_create.argtypes
+        getattr(lib, f"bsig_plan_create_{kind}").argtypes = create[:-1] + [C.c_int32, create[-1]] if extra else create
+        for query in ("cells", "runs") if runs else ("cells",):
+            getattr(lib, f"bsig_plan_{kind}_{query}").argtypes = [C.c_void_p]
+            getattr(lib, f"bsig_plan_{kind}_{query}").restype = C.c_int64
+        getattr(lib, f"bsig_plan_run_{kind}").argtypes = [C.c_void_p, C.c_void_p]
+        getattr(lib, f"bsig_plan_run_{kind}_host").argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_runs_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.bsig_runs_n_seg.argtypes = [C.c_void_p]
     lib.bsig_runs_n_seg.restype = C.c_int64

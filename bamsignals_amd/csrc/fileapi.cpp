@@ -632,19 +632,24 @@ bool regions_covered(const Resident &R, int64_t n, const int32_t *rid, const int
     return true;
 }
 
-// A sum over ranges of one width (bsig_pileup_sum / bsig_coverage_sum): one GPU sums them all; with several, each sums
-// its block of the (rid, loc)-sorted ranges and the host adds the int64 vectors -- no per-range cell leaves a GPU
-int sum_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                 const int32_t *width, const int32_t *strand, const bsig_params &prm, int64_t cells, int64_t *sum, double *X,
-                 std::string &route)
+// A reduction over the ranges -- the sum (bsig_pileup_sum / bsig_coverage_sum), the strand cross-correlation
+// (bsig_pileup_xcorr), the fragment-length histogram (bsig_pileup_frag), the depth histogram (bsig_pileup_hist /
+// bsig_coverage_hist): every cell of the int64 result is a sum over ranges.  One GPU takes them all; several take a block
+// of the (rid, loc)-sorted ranges each and the host adds the int64 vectors -- no per-range cell leaves a GPU.
+// make_plan(ctx, reads, n, rid, loc, width, strand, &plan) is the kind's bsig_plan_create_* call.
+using MakePlan = std::function<int(bsig_ctx *, const bsig_reads *, int64_t, const int32_t *, const int32_t *, const int32_t *,
+                                   const int32_t *, bsig_plan **)>;
+int reduced_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                     const int32_t *width, const int32_t *strand, int64_t cells, int64_t *out, double *X, std::string &route,
+                     const MakePlan &make_plan)
 {
     const size_t nd = reads.size();
     if (nd == 1) {
         const double t0 = now_s();
         bsig_plan *plan = nullptr;
-        int rc = bsig_plan_create_sum(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, &plan);
+        int rc = make_plan(sl.ctx[0], reads[0], n, rid, loc, width, strand, &plan);
         X[3] = now_s() - t0;
-        if (rc == BSIG_OK) rc = bsig::plan_run_to_host(plan, nullptr, sum, false, &X[4], &X[5]);
+        if (rc == BSIG_OK) rc = bsig::plan_run_reduced_to_host(plan, out, &X[4], &X[5]);
         if (plan) bsig_plan_free(plan);
         route = "sum";
         return rc;
@@ -661,142 +666,8 @@ int sum_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, c
             r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
         }
         bsig_plan *plan = nullptr;
-        int rk = bsig_plan_create_sum(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &prm, &plan);
-        if (rk == BSIG_OK) rk = bsig_plan_run_sum_host(plan, part[k].data());
-        if (plan) bsig_plan_free(plan);
-        return rk;
-    });
-    if (rc != BSIG_OK) return rc;
-    for (int64_t c = 0; c < cells; ++c) {
-        int64_t t = 0;
-        for (size_t k = 0; k < nd; ++k) t += part[k][(size_t)c];
-        sum[c] = t;
-    }
-    route = "sum of " + std::to_string(nd) + " blocks of ranges, added on the host";
-    return BSIG_OK;
-}
-
-// The strand cross-correlation over the ranges (bsig_pileup_xcorr): as sum_on_slots -- one GPU takes them all; several
-// take a block of the (rid, loc)-sorted ranges each and the host adds the int64 vectors (cross and moments are sums
-// over ranges)
-int xcorr_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                   const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t max_lag, int64_t cells,
-                   int64_t *out, double *X, std::string &route)
-{
-    const size_t nd = reads.size();
-    if (nd == 1) {
-        const double t0 = now_s();
-        bsig_plan *plan = nullptr;
-        int rc = bsig_plan_create_xcorr(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, max_lag, &plan);
-        X[3] = now_s() - t0;
-        if (rc == BSIG_OK) rc = bsig::plan_run_xcorr_to_host(plan, out, &X[4], &X[5]);
-        if (plan) bsig_plan_free(plan);
-        route = "sum";
-        return rc;
-    }
-    std::vector<int64_t> order;
-    bsig::sort_ranges(n, rid, loc, order);
-    std::vector<std::vector<int64_t>> part(nd, std::vector<int64_t>((size_t)cells, 0));
-    const int rc = for_each_slot(nd, [&](size_t k) -> int {
-        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
-        if (a >= b) return BSIG_OK;
-        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
-        for (int64_t i = a; i < b; ++i) {
-            const int64_t j = order[(size_t)i];
-            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
-        }
-        bsig_plan *plan = nullptr;
-        int rk = bsig_plan_create_xcorr(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &prm, max_lag, &plan);
-        if (rk == BSIG_OK) rk = bsig_plan_run_xcorr_host(plan, part[k].data());
-        if (plan) bsig_plan_free(plan);
-        return rk;
-    });
-    if (rc != BSIG_OK) return rc;
-    for (int64_t c = 0; c < cells; ++c) {
-        int64_t t = 0;
-        for (size_t k = 0; k < nd; ++k) t += part[k][(size_t)c];
-        out[c] = t;
-    }
-    route = "sum of " + std::to_string(nd) + " blocks of ranges, added on the host";
-    return BSIG_OK;
-}
-
-// The fragment-length histogram over the ranges (bsig_pileup_frag): as xcorr_on_slots -- one GPU takes all ranges; several
-// take a block of the (rid, loc)-sorted ranges each and the host adds the int64 vectors (every row is a sum over ranges)
-int frag_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                  const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t len_bin, int64_t cells,
-                  int64_t *out, double *X, std::string &route)
-{
-    const size_t nd = reads.size();
-    if (nd == 1) {
-        const double t0 = now_s();
-        bsig_plan *plan = nullptr;
-        int rc = bsig_plan_create_frag(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, len_bin, &plan);
-        X[3] = now_s() - t0;
-        if (rc == BSIG_OK) rc = bsig::plan_run_frag_to_host(plan, out, &X[4], &X[5]);
-        if (plan) bsig_plan_free(plan);
-        route = "sum";
-        return rc;
-    }
-    std::vector<int64_t> order;
-    bsig::sort_ranges(n, rid, loc, order);
-    std::vector<std::vector<int64_t>> part(nd, std::vector<int64_t>((size_t)cells, 0));
-    const int rc = for_each_slot(nd, [&](size_t k) -> int {
-        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
-        if (a >= b) return BSIG_OK;
-        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
-        for (int64_t i = a; i < b; ++i) {
-            const int64_t j = order[(size_t)i];
-            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
-        }
-        bsig_plan *plan = nullptr;
-        int rk = bsig_plan_create_frag(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &prm, len_bin, &plan);
-        if (rk == BSIG_OK) rk = bsig_plan_run_frag_host(plan, part[k].data());
-        if (plan) bsig_plan_free(plan);
-        return rk;
-    });
-    if (rc != BSIG_OK) return rc;
-    for (int64_t c = 0; c < cells; ++c) {
-        int64_t t = 0;
-        for (size_t k = 0; k < nd; ++k) t += part[k][(size_t)c];
-        out[c] = t;
-    }
-    route = "sum of " + std::to_string(nd) + " blocks of ranges, added on the host";
-    return BSIG_OK;
-}
-
-// The depth histogram over the ranges (bsig_pileup_hist / bsig_coverage_hist): as frag_on_slots -- one GPU takes all ranges;
-// several take a block of the (rid, loc)-sorted ranges each and the host adds the int64 vectors (every row and both moments
-// are sums over ranges)
-int hist_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                  const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t max_value, int64_t cells,
-                  int64_t *out, double *X, std::string &route)
-{
-    const size_t nd = reads.size();
-    if (nd == 1) {
-        const double t0 = now_s();
-        bsig_plan *plan = nullptr;
-        int rc = bsig_plan_create_hist(sl.ctx[0], reads[0], n, rid, loc, width, strand, &prm, max_value, &plan);
-        X[3] = now_s() - t0;
-        if (rc == BSIG_OK) rc = bsig::plan_run_hist_to_host(plan, out, &X[4], &X[5]);
-        if (plan) bsig_plan_free(plan);
-        route = "sum";
-        return rc;
-    }
-    std::vector<int64_t> order;
-    bsig::sort_ranges(n, rid, loc, order);
-    std::vector<std::vector<int64_t>> part(nd, std::vector<int64_t>((size_t)cells, 0));
-    const int rc = for_each_slot(nd, [&](size_t k) -> int {
-        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
-        if (a >= b) return BSIG_OK;
-        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
-        for (int64_t i = a; i < b; ++i) {
-            const int64_t j = order[(size_t)i];
-            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
-        }
-        bsig_plan *plan = nullptr;
-        int rk = bsig_plan_create_hist(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &prm, max_value, &plan);
-        if (rk == BSIG_OK) rk = bsig_plan_run_hist_host(plan, part[k].data());
+        int rk = make_plan(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &plan);
+        if (rk == BSIG_OK) rk = bsig::plan_run_reduced_to_host(plan, part[k].data());
         if (plan) bsig_plan_free(plan);
         return rk;
     });
@@ -830,7 +701,7 @@ int64_t runs_block_cells()
 }
 
 // The per-range result as runs (bsig_pileup_runs / bsig_coverage_runs).  Each GPU takes a contiguous share of the
-// (rid, loc)-sorted ranges, as sum_on_slots deals them, and cuts it into blocks of at most runs_block_cells() cells (a
+// (rid, loc)-sorted ranges, as reduced_on_slots deals them, and cuts it into blocks of at most runs_block_cells() cells (a
 // single larger range is a block of its own): a block's plan runs into a device buffer, the overflow flag is checked,
 // the buffer is encoded (runs.hip) and only the runs are downloaded.  The host puts the segments in the caller's order.
 int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
@@ -940,75 +811,84 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
 }
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
-// layout is one vector, dst[0]), or the sum over the ranges
+// layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, or runs
+enum class Reduce { none, sum, xcorr, frag, hist };
 struct FileDest {
     int32_t *out = nullptr;
     const int64_t *off = nullptr;
     int32_t *const *dst = nullptr;
-    int64_t *sum = nullptr;
-    int64_t *xcorr = nullptr;       // max_lag + 1 + BSIG_XCORR_MOMENTS cells: the cross-correlation over the ranges
-    int32_t max_lag = 0;
-    int64_t *frag = nullptr;        // tlen_filter[1] / len_bin + 1 cells: the fragment-length histogram over the ranges
-    int32_t len_bin = 0;
-    int64_t *hist = nullptr;        // max_value + 1 + BSIG_HIST_MOMENTS cells: the depth histogram over the ranges
-    int32_t max_value = 0;
+    Reduce kind = Reduce::none;
+    int64_t *reduced = nullptr;     // the kind's cells: the sum's bins, max_lag + 1 + BSIG_XCORR_MOMENTS, tlen_filter[1] / len_bin + 1
+                                    // rows, max_value + 1 + BSIG_HIST_MOMENTS
+    int32_t arg = 0;                // xcorr: max_lag; frag: len_bin; hist: max_value
     bsig_runs_result *runs = nullptr;   // the per-range result as runs, in the caller's range order
+    static FileDest reduce(Reduce kind, int64_t *cells, int32_t arg = 0)
+    {
+        FileDest to;
+        to.kind = kind; to.reduced = cells; to.arg = arg;
+        return to;
+    }
 };
 
 int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                const char *const *levels, const int32_t *start, const int32_t *width,
                const int32_t *strand, const bsig_params &prm, int32_t device, const FileDest &to)
 {
+    g_call_route[0] = 0;        // (a refused call has no route)
     if (!bampath) return fail(BSIG_ERR_ARG, "bampath is NULL");
     if (n < 0 || (n > 0 && (!seq_code || !start || !width || !strand || !levels)))
         return fail(BSIG_ERR_ARG, "range arrays missing");
-    if (!to.off && !to.dst && !to.sum && !to.xcorr && !to.frag && !to.hist && !to.runs) return fail(BSIG_ERR_ARG, "offsets missing");
-    if (to.runs) {
-        // runs: bamCount has none; the plan's rule, before the BAM is opened
-        g_call_route[0] = 0;
-        if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
+    if (!to.off && !to.dst && !to.reduced && !to.runs) return fail(BSIG_ERR_ARG, "offsets missing");
+    // a kind's own conditions, before any I/O; where it says so the plan's rule as well, before the BAM is opened
+    int64_t cells = 0;              // of a reduction
+    MakePlan make_plan;
+    // (xcorr, frag, hist: the kind's create call with the kind's own argument in its place)
+    auto with_arg = [&prm, arg = to.arg](auto create) -> MakePlan {
+        return [&prm, arg, create](bsig_ctx *c, const bsig_reads *rd, int64_t m, const int32_t *r, const int32_t *l, const int32_t *w,
+                                   const int32_t *s, bsig_plan **plan) { return create(c, rd, m, r, l, w, s, &prm, arg, plan); };
+    };
+    {
+        int rc = BSIG_OK;
         bsig::PlanRule early;
-        const int rc = bsig::check_params(prm, n, width, &early);
+        bsig::SumShape sum{};
+        bsig::XcorrShape xcorr{};
+        bsig::FragShape frag{};
+        bsig::HistShape hist{};
+        switch (to.kind) {
+        case Reduce::none:
+            if (!to.runs) break;
+            if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
+            rc = bsig::check_params(prm, n, width, &early);
+            break;
+        case Reduce::sum:
+            rc = bsig::sum_shape(prm, n, width, &sum);
+            cells = sum.cells;
+            make_plan = [&prm](bsig_ctx *c, const bsig_reads *rd, int64_t m, const int32_t *r, const int32_t *l, const int32_t *w,
+                               const int32_t *s, bsig_plan **plan) { return bsig_plan_create_sum(c, rd, m, r, l, w, s, &prm, plan); };
+            break;
+        case Reduce::xcorr:
+            rc = bsig::xcorr_shape(prm, to.arg, &xcorr);
+            cells = xcorr.cells;
+            make_plan = with_arg(bsig_plan_create_xcorr);
+            break;
+        case Reduce::frag:
+            rc = bsig::frag_shape(prm, to.arg, &frag);
+            cells = frag.cells;
+            make_plan = with_arg(bsig_plan_create_frag);
+            break;
+        case Reduce::hist:
+            rc = bsig::hist_shape(prm, to.arg, &hist);
+            if (rc == BSIG_OK) rc = bsig::check_params(hist.tiles, n, width, &early);
+            cells = hist.cells;
+            make_plan = with_arg(bsig_plan_create_hist);
+            break;
+        }
         if (rc) return rc;
-    }
-    int64_t *sum = to.sum;
-    bsig::SumShape shape{};
-    if (sum) {
-        // the sum's own conditions, before any I/O
-        const int rc = bsig::sum_shape(prm, n, width, &shape);
-        if (rc) return rc;
-        std::fill(sum, sum + shape.cells, (int64_t)0);
-    }
-    bsig::XcorrShape xshape{};
-    if (to.xcorr) {
-        // ... and the cross-correlation's
-        const int rc = bsig::xcorr_shape(prm, to.max_lag, &xshape);
-        if (rc) return rc;
-        std::fill(to.xcorr, to.xcorr + xshape.cells, (int64_t)0);
-    }
-    bsig::FragShape fshape{};
-    if (to.frag) {
-        // ... and the fragment-length histogram's
-        g_call_route[0] = 0;
-        const int rc = bsig::frag_shape(prm, to.len_bin, &fshape);
-        if (rc) return rc;
-        std::fill(to.frag, to.frag + fshape.cells, (int64_t)0);
-    }
-    bsig::HistShape hshape{};
-    if (to.hist) {
-        // ... and the depth histogram's
-        g_call_route[0] = 0;
-        int rc = bsig::hist_shape(prm, to.max_value, &hshape);
-        // (the plan's rule as well, before the BAM is opened)
-        bsig::PlanRule early;
-        if (rc == BSIG_OK) rc = bsig::check_params(hshape.tiles, n, width, &early);
-        if (rc) return rc;
-        std::fill(to.hist, to.hist + hshape.cells, (int64_t)0);
+        if (to.reduced) std::fill(to.reduced, to.reduced + cells, (int64_t)0);
     }
     double *T = g_call_timing, *X = g_call_timing_ex;
     for (int k = 0; k < 6; ++k) T[k] = 0;
     for (int k = 0; k < 10; ++k) X[k] = 0;
-    g_call_route[0] = 0;
     const double t_begin = now_s();
     const AllocSnap a_begin = AllocSnap::now();
     // ref: Bamfile ctor :200-214 opens file + index on every call; here an unchanged file (same
@@ -1298,14 +1178,8 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     std::string gather;
     for (int attempt = 0; attempt < 2; ++attempt) {
     if (attempt) drop_spare_device_memory(slots.get());        // (out of device memory: once more with the cache's spare memory given back)
-    if (sum) {
-        rc = sum_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, shape.cells, sum, X, gather);
-    } else if (to.xcorr) {
-        rc = xcorr_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.max_lag, xshape.cells, to.xcorr, X, gather);
-    } else if (to.frag) {
-        rc = frag_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.len_bin, fshape.cells, to.frag, X, gather);
-    } else if (to.hist) {
-        rc = hist_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, to.max_value, hshape.cells, to.hist, X, gather);
+    if (to.reduced) {
+        rc = reduced_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, cells, to.reduced, X, gather, make_plan);
     } else if (to.runs) {
         rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, rule, *to.runs, X, gather);
     } else if (!many) {
@@ -1315,7 +1189,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         X[3] = now_s() - t_run;
         if (rc == BSIG_OK && memcmp(off, bsig_plan_offsets(plan), (size_t)(n + 1) * sizeof(int64_t)) != 0)
             rc = fail(BSIG_ERR_ARG, "offsets do not match bsig_layout() for these parameters");
-        if (rc == BSIG_OK) rc = bsig::plan_run_to_host(plan, &dest, nullptr, false, &X[4], &X[5]);
+        if (rc == BSIG_OK) rc = bsig::plan_run_to_host(plan, &dest, false, &X[4], &X[5]);
         if (plan) bsig_plan_free(plan);
     } else {
         rc = run_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, dest, gather);
@@ -1332,7 +1206,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (rc == BSIG_OK) rc = bam_index_wait(bam);      // a damaged index fails the call, as it does in the reference's open
     T[4] = now_s() - t_begin;
     snprintf(g_call_route, sizeof g_call_route, "%zu GPU slot(s); reads: %s; result: %s", nd, how_decoded.c_str(),
-             many || sum || to.xcorr || to.frag || to.hist || to.runs ? gather.c_str() : "download");
+             many || to.reduced || to.runs ? gather.c_str() : "download");
     return rc;
 }
 
@@ -1601,7 +1475,7 @@ int bsig_pileup_sum(const char *bampath, int64_t n, const int32_t *seq_code, int
     if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
                       pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device,
-                      {nullptr, nullptr, nullptr, sum});
+                      FileDest::reduce(Reduce::sum, sum));
 }
 
 int bsig_pileup_xcorr(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1611,11 +1485,9 @@ int bsig_pileup_xcorr(const char *bampath, int64_t n, const int32_t *seq_code, i
                       int32_t device, int64_t *out)
 {
     if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
-    FileDest to;
-    to.xcorr = out;
-    to.max_lag = max_lag;
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
-                      pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, 1, requiredF, filteredF, 0), device, to);
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, 1, requiredF, filteredF, 0), device,
+                      FileDest::reduce(Reduce::xcorr, out, max_lag));
 }
 
 int bsig_pileup_frag(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1625,11 +1497,9 @@ int bsig_pileup_frag(const char *bampath, int64_t n, const int32_t *seq_code, in
                      int32_t device, int64_t *out)
 {
     if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
-    FileDest to;
-    to.frag = out;
-    to.len_bin = len_bin;
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
-                      pileup_params(tlen_filter, n_tlen_filter, mapqual, -1, 0, 0, requiredF, filteredF, pe_mid != 0), device, to);
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, -1, 0, 0, requiredF, filteredF, pe_mid != 0), device,
+                      FileDest::reduce(Reduce::frag, out, len_bin));
 }
 
 int bsig_pileup_hist(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1639,11 +1509,9 @@ int bsig_pileup_hist(const char *bampath, int64_t n, const int32_t *seq_code, in
                      int32_t maxgap, int32_t device, int64_t *out)
 {
     if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
-    FileDest to;
-    to.hist = out;
-    to.max_value = max_value;
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
-                      pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, ss != 0, requiredF, filteredF, pe_mid != 0), device, to);
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, ss != 0, requiredF, filteredF, pe_mid != 0), device,
+                      FileDest::reduce(Reduce::hist, out, max_value));
 }
 
 int bsig_coverage_hist(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1653,11 +1521,9 @@ int bsig_coverage_hist(const char *bampath, int64_t n, const int32_t *seq_code, 
                        int32_t maxgap, int32_t device, int64_t *out)
 {
     if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
-    FileDest to;
-    to.hist = out;
-    to.max_value = max_value;
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
-                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device, to);
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device,
+                      FileDest::reduce(Reduce::hist, out, max_value));
 }
 
 int bsig_pileup_runs(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
@@ -1722,7 +1588,7 @@ int bsig_coverage_sum(const char *bampath, int64_t n, const int32_t *seq_code, i
     if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
                       coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device,
-                      {nullptr, nullptr, nullptr, sum});
+                      FileDest::reduce(Reduce::sum, sum));
 }
 
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath)

@@ -245,49 +245,56 @@ void block_cache_release()
 }  // namespace bsig
 
 namespace { enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 }; }      // launch_sum_tiles' kinds (kernels.h)
-// a SUM plan's own (bsig_plan_create_sum): per-base tiles ordered by c0, summed over the ranges by k_sum_tiles
-struct SumState {
-    bsig::SumShape shape;
-    int kind = kSumProfile, S = 1;
-    uint2 *runs = nullptr;              // runs of the main tiles, then those of the heavy slices: [t0, t1) of one c0
-    int64_t n_runs_main = 0, n_runs_heavy = 0;
-    BsigSumChunk *chunks = nullptr;
-    int64_t n_chunks = 0;
-    int32_t max_nvals = 0;
-    int32_t slab_vals = 0;              // int32 per slab (tile_cells * S rounded up to 4)
-    int32_t *slab = nullptr;            // one slab per run
-    long long *base = nullptr;          // per-base sums (binsize > 1; binsize 1 reduces straight into the result)
-    int64_t *d_sum = nullptr;           // device result of bsig_plan_run_sum_host
+// What a plan is: a plain one gives every range its own int32 cells; the others reduce all ranges to one short int64 vector.
+// The order is the one the wrong-kind refusals are worded by (wrong_kind).
+enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist };
+// per kind: the noun with its article, the device run call, the host run call, the bytes of a result cell
+struct KindRow { const char *a, *run_dev, *run_host; int cell_bytes; };
+static const KindRow kKinds[] = {
+    {"a plain", "bsig_plan_run", "bsig_plan_run_host", 4},
+    {"a sum", "bsig_plan_run_sum", "bsig_plan_run_sum_host", 8},
+    {"an xcorr", "bsig_plan_run_xcorr", "bsig_plan_run_xcorr_host", 8},
+    {"a frag", "bsig_plan_run_frag", "bsig_plan_run_frag_host", 8},
+    {"a hist", "bsig_plan_run_hist", "bsig_plan_run_hist_host", 8},
 };
-
-// an XCORR plan's own (bsig_plan_create_xcorr): tiles of body + halo in genomic order, cut into one round of runs
-struct XcorrState {
-    bsig::XcorrShape shape;
-    int body = 0;                       // body cells of a tile (the image holds body + max_lag: the plan's tile_cells)
-    uint2 *runs = nullptr;              // runs of the main tiles, then those of the wide tiles (one tile each)
-    int64_t n_runs_main = 0, n_runs_wide = 0;
-    int64_t n_cells = 0;                // moments[0]: the sum of the ranges' widths
-    int64_t *d_out = nullptr;           // device result of bsig_plan_run_xcorr_host
-};
-
-// a FRAG plan's own (bsig_plan_create_frag): count tiles in genomic order, cut into one round of runs
-struct FragState {
-    bsig::FragShape shape;
-    bool merge = false;                 // k_frag_tiles' form: equal rows of a wave merged before the LDS atomic (see frag_setup)
-    uint2 *runs = nullptr;
-    int64_t n_runs = 0;
-    int64_t *d_out = nullptr;           // device result of bsig_plan_run_frag_host
-};
-
-// a HIST plan's own (bsig_plan_create_hist): per-base tiles in genomic order, cut into one round of runs
-struct HistState {
-    bsig::HistShape shape;
-    bool coverage = false;              // the signal: coverage, else 5' ends
-    bool merge = false;                 // k_hist_tiles' form: zero cells by ballot, equal rows of a wave merged (see hist_setup)
-    uint2 *runs = nullptr;              // runs of the main tiles, then those of the wide tiles (one tile each)
-    int64_t n_runs_main = 0, n_runs_wide = 0;
-    int64_t n_cells = 0;                // moments[0]: the cells of all ranges
-    int64_t *d_out = nullptr;           // device result of bsig_plan_run_hist_host
+// A reduction plan's own (every kind but kPlain): the result's cells, the device buffer its _host call runs into, and the
+// tiles cut into runs (a workgroup each) -- the main tiles' runs, then the extra ones': a sum plan's heavy slices, an xcorr or
+// hist plan's wide tiles (32-bit image, one tile a run), none for a frag plan.  Beside them what only one kind has.
+struct Reduced {
+    int64_t cells = 0;
+    int64_t *d_out = nullptr;           // device result of bsig_plan_run_<kind>_host, kept between calls
+    uint2 *runs = nullptr;              // [t0, t1) of the items, the extra runs of the heavy items
+    int64_t n_runs_main = 0, n_runs_extra = 0;
+    // sum (bsig_plan_create_sum): per-base tiles ordered by c0, a run of one c0, summed over the ranges by k_sum_tiles
+    struct {
+        int kind = kSumProfile, S = 1;
+        int nw = 0;                     // waves per k_sum_tiles workgroup
+        int32_t width = 0, binsize = 1; // every range's width; the caller's bins (the per-base sums are binned at the end)
+        BsigSumChunk *chunks = nullptr;
+        int64_t n_chunks = 0;
+        int32_t max_nvals = 0;
+        int32_t slab_vals = 0;          // int32 per slab (tile_cells * S rounded up to 4)
+        int32_t *slab = nullptr;        // one slab per run
+        long long *base = nullptr;      // per-base sums (binsize > 1; binsize 1 reduces straight into the result)
+    } sum;
+    // xcorr (bsig_plan_create_xcorr): tiles of body + halo in genomic order
+    struct {
+        int body = 0;                   // body cells of a tile (the image holds body + max_lag: the plan's tile_cells)
+        int max_lag = 0;
+        int64_t n_cells = 0;            // moments[0]: the sum of the ranges' widths
+    } xcorr;
+    // frag (bsig_plan_create_frag): count tiles in genomic order
+    struct {
+        bool merge = false;             // k_frag_tiles' form: equal rows of a wave merged before the LDS atomic (see frag_setup)
+        int32_t len_bin = 1;            // lengths per row
+    } frag;
+    // hist (bsig_plan_create_hist): per-base tiles in genomic order
+    struct {
+        bool coverage = false;          // the signal: coverage, else 5' ends
+        bool merge = false;             // k_hist_tiles' form: zero cells by ballot, equal rows of a wave merged (see hist_setup)
+        int32_t max_value = 0;          // V: the overflow row
+        int64_t n_cells = 0;            // moments[0]: the cells of all ranges
+    } hist;
 };
 
 struct bsig_plan {
@@ -321,10 +328,8 @@ struct bsig_plan {
     uint64_t made_for_gen = 0;          // the layout the plan was made on: its tiles' heavy slices and the packed class's filter
                                         // table are read off that layout, so a plan does not outlive it
     int64_t runs = 0;                   // runs so far (a plan that is run AGAIN is a resident one: plan_two_launches)
-    std::unique_ptr<SumState> sum;      // a sum plan's (bsig_plan_create_sum), else null
-    std::unique_ptr<XcorrState> xcorr;  // an xcorr plan's (bsig_plan_create_xcorr), else null
-    std::unique_ptr<FragState> frag;    // a frag plan's (bsig_plan_create_frag), else null
-    std::unique_ptr<HistState> hist;    // a hist plan's (bsig_plan_create_hist), else null
+    PlanKind kind = kPlain;
+    std::unique_ptr<Reduced> red;       // a reduction plan's own: there if and only if kind != kPlain
 };
 static int64_t g_resolve_min_override = -1;     // bsig_debug_set_knob(4, n): two launches from n tiles on (sweeps)
 // does a run of this plan look its windows up in a launch of its own?  (measured at the north star's read density,
@@ -1520,18 +1525,33 @@ int bsig::hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out)
 
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
 static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells);
-static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &tile_reads);
+static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &reads_of_tile);
 static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells);
-// sum: a plan for bsig_plan_create_sum -- its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
-// xc: a plan for bsig_plan_create_xcorr -- tiles of a body and an antisense halo, none of them cut into slices
-// fr: a plan for bsig_plan_create_frag -- count tiles, none of them cut into slices (they have no image)
-// hs: a plan for bsig_plan_create_hist -- the mode's per-base tiles, none of them cut into slices
-// (a plan is at most one of the four)
+// Which plan plan_create_impl is to make, and what that kind's *_shape call worked out for it:
+// kSum: its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
+// kXcorr: tiles of a body and an antisense halo, none of them cut into slices
+// kFrag: count tiles, none of them cut into slices (they have no image)
+// kHist: the mode's per-base tiles, none of them cut into slices
+struct PlanRequest {
+    PlanKind kind = kPlain;
+    union {
+        const void *none = nullptr;
+        const bsig::SumShape *sum;
+        const bsig::XcorrShape *xcorr;
+        const bsig::FragShape *frag;
+        const bsig::HistShape *hist;
+    };
+};
+// the reads in tile t's windows (win: BSIG_MAX_CLASSES index ranges a tile, k_resolve_tiles' output)
+static int64_t tile_reads(const std::vector<uint2> &win, size_t t)
+{
+    int64_t total = 0;
+    for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
+    return total;
+}
 static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
                             const int32_t *loc, const int32_t *len, const int32_t *strand,
-                            const bsig_params *prm, const bsig::SumShape *sum, bsig_plan **out,
-                            const bsig::XcorrShape *xc = nullptr, const bsig::FragShape *fr = nullptr,
-                            const bsig::HistShape *hs = nullptr)
+                            const bsig_params *prm, const PlanRequest &rq, bsig_plan **out)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
     *out = nullptr;
@@ -1542,7 +1562,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         if (rid[i] < 0 || rid[i] >= reads->n_ref) return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", rid[i]);
     const int mode = r.mode;
 
-    bsig_plan *P = new bsig_plan;
+    std::unique_ptr<bsig_plan> owner(new bsig_plan);
+    bsig_plan *P = owner.get();
     P->ctx = ctx; P->reads = reads; P->mode = mode; P->n_ranges = n;
     P->made_for_gen = reads->layout_gen;
     // default tile: the widest range if it fits 2048 cells (less LDS per workgroup = more
@@ -1569,10 +1590,10 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     P->tile_cells = std::min(std::max(P->tile_cells, min_cells), split_ss ? 4096 : 8192);
     P->tile_cells = (P->tile_cells + 3) & ~3;
     // cross-correlation: a body no wider than the widest range, and an image of the body and a halo of max_lag cells
-    const int xbody = xc ? (int)std::min<int64_t>(xc->body, widest) : 0;
-    if (xc) P->tile_cells = (xbody + xc->max_lag + 3) & ~3;
+    const int xbody = rq.kind == kXcorr ? (int)std::min<int64_t>(rq.xcorr->body, widest) : 0;
+    if (rq.kind == kXcorr) P->tile_cells = (xbody + rq.xcorr->max_lag + 3) & ~3;
     // depth histogram: the caller's tile (16 .. 2,048 cells, checked by hist_shape), whatever the widest range
-    if (hs) P->tile_cells = (hs->tiles.tile_cells + 3) & ~3;
+    if (rq.kind == kHist) P->tile_cells = (rq.hist->tiles.tile_cells + 3) & ~3;
     P->threads = r.threads;
     BsigKParams &K = P->kp;
     K.mapqual = prm->mapqual;
@@ -1615,7 +1636,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         K.packed_half = half ? 1 : 0;
     }
     // (a frag plan's tiles are count tiles, which divide by no binsize: the multiplier is its row width's)
-    bsig::magic_u31(fr ? fr->len_bin : K.binsize, &K.div_magic, &K.div_shift);
+    bsig::magic_u31(rq.kind == kFrag ? rq.frag->len_bin : K.binsize, &K.div_magic, &K.div_shift);
     K.div_m15 = 0; K.div_s15 = 0;
     if (K.binsize >= 2 && K.binsize <= 8192) {
         // s = 15 + ceil(log2 b), m = ceil(2^s / b): n * m / 2^s = n / b + n * e / (b * 2^s) with e < b, and the second
@@ -1639,7 +1660,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // count mode: bases per workgroup (with the window's reach on both sides still one chunk of the packed
     // class's position bits: one index lookup per tile)
     // (a frag plan's tile_cells: bases per tile, for tests of the tiles' seams)
-    const int count_split = fr && prm->tile_cells > 0 ? std::min(std::max(prm->tile_cells, 16), 1 << (BSIG_PACK_POS_BITS - 1))
+    const int count_split = rq.kind == kFrag && prm->tile_cells > 0 ? std::min(std::max(prm->tile_cells, 16), 1 << (BSIG_PACK_POS_BITS - 1))
                                                       : 1 << (BSIG_PACK_POS_BITS - 1);
     // bins wider than a workgroup should stream on its own: every bin becomes bamCount-style
     // sub-intervals that add into the (zeroed) result with integer atomics
@@ -1679,13 +1700,13 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
                 if (split) { w.units_strand |= BSIG_ITEM_ATOMIC; P->needs_zero = true; }
                 items.push_back(w);
             }
-        } else if (xc) {
+        } else if (rq.kind == kXcorr) {
             // a body of the range's cells and, behind it, as much of max_lag cells as the range still has: the tile is
             // piled up over body + halo (nc) and correlated over the body, whose length rides in out_off
             for (int64_t c0 = 0; c0 < len[i]; c0 += xbody) {
                 const int64_t nb = std::min<int64_t>(xbody, len[i] - c0);
                 w.c0 = (int32_t)c0;
-                w.nc = (int32_t)(nb + std::min<int64_t>(xc->max_lag, len[i] - c0 - nb));
+                w.nc = (int32_t)(nb + std::min<int64_t>(rq.xcorr->max_lag, len[i] - c0 - nb));
                 w.out_off = nb;
                 items.push_back(w);
             }
@@ -1700,9 +1721,9 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         }
     }
     // a sum plan adds up all tiles of one c0 (every range has the same width, so also the same nc): consecutive
-    if (sum) std::stable_sort(items.begin(), items.end(), [](const BsigWorkItem &a, const BsigWorkItem &b) { return a.c0 < b.c0; });
+    if (rq.kind == kSum) std::stable_sort(items.begin(), items.end(), [](const BsigWorkItem &a, const BsigWorkItem &b) { return a.c0 < b.c0; });
     P->n_items = (int64_t)items.size();
-    if (P->n_items >= (1ll << 31)) { delete P; return fail(BSIG_ERR_ARG, "too many tiles for one launch"); }
+    if (P->n_items >= (1ll << 31)) return fail(BSIG_ERR_ARG, "too many tiles for one launch");
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = P->pool.alloc(&P->items, std::max<size_t>(items.size(), 1));
     // the packed class's filter table for these parameters (kernels.hip: k_make_ptab)
@@ -1738,51 +1759,44 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         if (e == hipSuccess) e = hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         // the windows themselves are only fetched when there is something to slice (a frag plan cuts its runs by them)
-        if (e == hipSuccess && (n_heavy_dev || fr || hs)) {
+        if (e == hipSuccess && (n_heavy_dev || rq.kind == kFrag || rq.kind == kHist)) {
             win.resize(items.size() * BSIG_MAX_CLASSES);
             e = hipMemcpyAsync(win.data(), d_win, win.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
         std::vector<uint2> hwin;
         long double xc_heavy_sq = 0;
-        if (e == hipSuccess && fr) {
+        if (e == hipSuccess && rq.kind == kFrag) {
             // a tile of a histogram has no image that its reads could overflow: none is heavy, none is sliced
             frag_reads.resize(items.size());
-            for (size_t t = 0; t < items.size(); ++t) {
-                int64_t total = 0;
-                for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
-                frag_reads[t] = total;
-            }
+            for (size_t t = 0; t < items.size(); ++t) frag_reads[t] = tile_reads(win, t);
         }
-        if (e == hipSuccess && hs) {
+        if (e == hipSuccess && rq.kind == kHist) {
             // The depth histogram's proof that its sum moment stays below 2^63: a read in a tile's windows adds at most 1 to
             // one cell of the tile (5' ends) or to each of its cells (coverage)
             long double bound = 0;
             for (size_t t = 0; t < items.size(); ++t) {
-                int64_t total = 0;
-                for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
+                const int64_t total = tile_reads(win, t);
                 bound += mode == BSIG_MODE_COVERAGE ? (long double)total * (long double)items[t].nc : (long double)total;
             }
             if (bound >= 9223372036854775808.0L) {
-                delete P;
                 return fail(BSIG_ERR_ARG, "the summed depth of these ranges could exceed 2^63 - 1 (the reads of their tiles add up "
                                           "to %.3Lg): take fewer ranges per call", bound);
             }
         }
-        if (e == hipSuccess && n_heavy_dev && !fr) {
+        if (e == hipSuccess && n_heavy_dev && rq.kind != kFrag) {
             for (size_t t = 0; t < items.size(); ++t) {
-                int64_t total = 0;
-                for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
+                const int64_t total = tile_reads(win, t);
                 if (total <= heavy_reads) continue;
                 ++P->n_heavy_tiles;
-                if (hs) {
+                if (rq.kind == kHist) {
                     // a cell's value must be complete before it is counted: such a tile is walked whole, by one workgroup
                     // of the second launch, into an image of 32-bit cells
                     hitems.push_back(items[t]);
                     items[t].units_strand |= BSIG_ITEM_HEAVY;
                     continue;
                 }
-                if (xc) {
+                if (rq.kind == kXcorr) {
                     // a product of two counts is not linear in slices of the reads: such a tile is walked whole, by one
                     // workgroup of the second launch, into an image of 32-bit cells
                     hitems.push_back(items[t]);
@@ -1822,42 +1836,90 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         // The cross-correlation's proof that no 64-bit sum wraps.  A tile with n reads in its windows counts each of
         // them in at most one cell, so sum(S) + sum(A) <= n and every sum the tile adds to -- a lag's S[x] A[x + d], a
         // strand's squares -- is at most n^2.  The tiles that are not heavy have n <= 2^15; the heavy ones' n is known.
-        if (e == hipSuccess && xc) {
+        if (e == hipSuccess && rq.kind == kXcorr) {
             const long double bound = (long double)(P->n_items - P->n_heavy_tiles) * 1073741824.0L + xc_heavy_sq;
             if (bound >= 9223372036854775808.0L) {
-                delete P;
                 return fail(BSIG_ERR_ARG, "the cross-correlation of these ranges could exceed 2^63 - 1 (the squared read counts "
                                           "of their tiles add up to %.3Lg): correlate fewer ranges per call", bound);
             }
         }
     }
-    if (e != hipSuccess) {
-        delete P;
+    if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "plan upload failed: %s", hipGetErrorString(e));
+    P->kind = rq.kind;
+    if (rq.kind != kPlain) P->red.reset(new Reduced);
+    int64_t widths = 0;             // (moments[0] of an xcorr plan; with strands twice that many cells for a hist plan's)
+    for (int64_t i = 0; i < n; ++i) widths += len[i];
+    int rc = BSIG_OK;
+    switch (rq.kind) {
+    case kPlain: break;
+    case kSum: rc = sum_setup(P, *rq.sum, items, hitems); break;
+    case kXcorr: rc = xcorr_setup(P, *rq.xcorr, xbody, (int64_t)hitems.size(), widths); break;
+    case kFrag: rc = frag_setup(P, *rq.frag, frag_reads); break;
+    case kHist: rc = hist_setup(P, *rq.hist, items, (int64_t)hitems.size(), widths * mult); break;
     }
-    if (xc) {
-        int64_t n_cells = 0;
-        for (int64_t i = 0; i < n; ++i) n_cells += len[i];
-        const int rc = xcorr_setup(P, *xc, xbody, (int64_t)hitems.size(), n_cells);
-        if (rc != BSIG_OK) { delete P; return rc; }
-    }
-    if (sum) {
-        const int rc = sum_setup(P, *sum, items, hitems);
-        if (rc != BSIG_OK) { delete P; return rc; }
-    }
-    if (fr) {
-        const int rc = frag_setup(P, *fr, frag_reads);
-        if (rc != BSIG_OK) { delete P; return rc; }
-    }
-    if (hs) {
-        int64_t n_cells = 0;
-        for (int64_t i = 0; i < n; ++i) n_cells += (int64_t)len[i] * mult;
-        const int rc = hist_setup(P, *hs, items, (int64_t)hitems.size(), n_cells);
-        if (rc != BSIG_OK) { delete P; return rc; }
-    }
-    *out = P;
+    if (rc != BSIG_OK) return rc;
+    *out = owner.release();
     return BSIG_OK;
 }
+// ---- what the four *_setup functions share ------------------------------------------------------------------------
+// the device's compute units and the LDS a workgroup may hold
+static int device_limits(const bsig_plan *P, int *n_cu, int *lds_max)
+{
+    HIP_TRY(hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
+    HIP_TRY(hipDeviceGetAttribute(lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    return BSIG_OK;
+}
+// Tiles per run: as many runs as workgroups are resident at a time (`per_cu` a CU, by occupancy), so that one round of
+// workgroups walks the whole plan, and at least `least` tiles a run -- unless env `name` > 0 says otherwise (tests: read
+// when the plan is made)
+static int64_t tiles_per_run(const bsig_plan *P, int n_cu, int per_cu, int64_t least, const char *name)
+{
+    if (const char *v = getenv(name)) {
+        const long long forced = atoll(v);
+        if (forced > 0) return forced;
+    }
+    const int64_t resident = (int64_t)std::max(n_cu, 1) * per_cu;
+    return std::max<int64_t>(least, (P->n_items + resident - 1) / resident);
+}
+// The plan's tiles, in their order, cut into runs of at most `per` tiles whose weights add up to `ceiling` at most (a tile
+// heavier than the ceiling makes a run of its own)
+template <typename Weight>
+static void cut_runs(int64_t n_items, int64_t per, int64_t ceiling, Weight &&weight, std::vector<uint2> &runs)
+{
+    int64_t a = 0, in_run = 0;
+    for (int64_t t = 0; t < n_items; ++t) {
+        const int64_t w = weight(t);
+        if (t > a && (t - a >= per || in_run + w > ceiling)) {
+            runs.push_back(make_uint2((uint32_t)a, (uint32_t)t));
+            a = t; in_run = 0;
+        }
+        in_run += w;
+    }
+    if (a < n_items) runs.push_back(make_uint2((uint32_t)a, (uint32_t)n_items));
+}
+// the wide tiles (32-bit image) follow the main runs as runs of one tile each: they are few and long
+static void append_wide_runs(int64_t n_wide, std::vector<uint2> &runs)
+{
+    for (int64_t k = 0; k < n_wide; ++k) runs.push_back(make_uint2((uint32_t)k, (uint32_t)k + 1u));
+}
+static int upload_runs(bsig_plan *P, const std::vector<uint2> &runs)
+{
+    if (runs.empty()) return BSIG_OK;
+    hipStream_t st = P->ctx->stream;
+    HIP_TRY(P->pool.alloc(&P->red->runs, runs.size()));
+    HIP_TRY(hipMemcpyAsync(P->red->runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BSIG_OK;
+}
+// a lowered ceiling for what a run's 32-bit counters see (tests: env `name`, read when the plan is made)
+constexpr int64_t kCounterMax = 4294967295ll;
+static int64_t counter_ceiling(const char *name)
+{
+    const char *v = getenv(name);
+    return v ? std::min<long long>(kCounterMax, std::max<long long>(1, atoll(v))) : kCounterMax;
+}
+
 // The runs of a sum plan: tiles of one c0 cut into runs of at most `per` (a workgroup each, one slab each), the runs of
 // the heavy slices behind those of the main tiles; chunks of at most kSumChunkSlots slabs of one c0 for k_sum_reduce.
 // `per` fills the chip once (workgroups resident at a time, by occupancy) and never exceeds 65,536 tiles, which keeps
@@ -1865,32 +1927,27 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems)
 {
     constexpr int64_t kSumChunkSlots = 32, kMaxRunTiles = 65536;
-    P->sum.reset(new SumState);
-    SumState &Q = *P->sum;
-    Q.shape = shape;
+    Reduced &R = *P->red;
+    auto &Q = R.sum;
+    R.cells = shape.cells;
+    Q.width = shape.width; Q.binsize = shape.binsize; Q.nw = shape.nw;
     Q.S = P->kp.ss ? 2 : 1;
     Q.kind = P->kernel_mode == BSIG_MODE_PROFILE ? kSumProfile : P->kp.ss ? kSumCoverSS : kSumCover;
     Q.slab_vals = (P->tile_cells * Q.S + 3) & ~3;
     int n_cu = 0, lds_max = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
-    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
     // The accumulator and one image per wave must fit a workgroup's LDS (a tile size of the caller's can ask for more:
     // strand-split coverage, 4,096 cells, four waves = 160.5 KiB): fewer waves per workgroup, and if one is too many,
     // no plan.  The library's own tile sizes (at most 2,048 cells, 1,024 with strands) need 40.5 KiB at most.
-    int &nw = Q.shape.nw;
+    int &nw = Q.nw;
     while (nw > 1 && bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells) > (size_t)lds_max) nw /= 2;
     if (bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells) > (size_t)lds_max)
         return fail(BSIG_ERR_ARG, "tile_cells %d needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells,
                     bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells), lds_max);
-    const int64_t resident = (int64_t)std::max(n_cu, 1) *
-                             bsig::sum_blocks_per_cu(Q.kind, Q.S == 2, nw, P->kp.packed_half != 0, P->tile_cells);
-    int64_t per = std::min<int64_t>(kMaxRunTiles, std::max<int64_t>(nw, (P->n_items + resident - 1) / resident));
-    // (tests: BAMSIGNALS_SUM_RUN_TILES = tiles per run instead of the occupancy's, read when a sum plan is made; shorter
-    // or longer runs, never past the cap that keeps a slab exact)
-    if (const char *v = getenv("BAMSIGNALS_SUM_RUN_TILES")) {
-        const long long forced = atoll(v);
-        if (forced > 0) per = std::min<long long>(kMaxRunTiles, std::max<long long>(1, forced));
-    }
+    // (BAMSIGNALS_SUM_RUN_TILES: shorter or longer runs, never past the cap that keeps a slab exact)
+    const int64_t per = std::min<int64_t>(kMaxRunTiles,
+                                          tiles_per_run(P, n_cu, bsig::sum_blocks_per_cu(Q.kind, Q.S == 2, nw, P->kp.packed_half != 0, P->tile_cells),
+                                                        nw, "BAMSIGNALS_SUM_RUN_TILES"));
     std::vector<uint2> runs;
     std::vector<BsigSumChunk> chunks;
     auto cut = [&](const std::vector<BsigWorkItem> &it) {
@@ -1912,131 +1969,86 @@ static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vecto
         }
     };
     cut(items);
-    Q.n_runs_main = (int64_t)runs.size();
+    R.n_runs_main = (int64_t)runs.size();
     cut(hitems);
-    Q.n_runs_heavy = (int64_t)runs.size() - Q.n_runs_main;
+    R.n_runs_extra = (int64_t)runs.size() - R.n_runs_main;
     Q.n_chunks = (int64_t)chunks.size();
     hipStream_t st = P->ctx->stream;
     if (!runs.empty()) {
-        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
         HIP_TRY(P->pool.alloc(&Q.chunks, chunks.size()));
         HIP_TRY(P->pool.alloc(&Q.slab, runs.size() * (size_t)Q.slab_vals));
-        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(Q.chunks, chunks.data(), chunks.size() * sizeof(BsigSumChunk), hipMemcpyHostToDevice, st));
     }
     if (shape.binsize != 1 && shape.width > 0) HIP_TRY(P->pool.alloc(&Q.base, (size_t)shape.width * Q.S));
-    HIP_TRY(hipStreamSynchronize(st));
-    return BSIG_OK;
+    return upload_runs(P, runs);            // (waits for the chunks as well: one stream)
 }
 
 // The runs of an xcorr plan: the tiles, in genomic order, cut into as many runs as workgroups are resident at a time (by
 // occupancy), so that one round of workgroups walks the whole plan and each keeps its per-lag sums in LDS across its run
-// -- a whole-genome call then ends in one 64-bit atomic per lag and workgroup instead of one per lag and tile.  The wide
-// tiles (32-bit image) follow as runs of one tile each: they are few and long.
+// -- a whole-genome call then ends in one 64-bit atomic per lag and workgroup instead of one per lag and tile.
 static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells)
 {
-    P->xcorr.reset(new XcorrState);
-    XcorrState &Q = *P->xcorr;
-    Q.shape = shape;
-    Q.body = body;
-    Q.n_cells = n_cells;
+    Reduced &R = *P->red;
+    R.cells = shape.cells;
+    R.xcorr.body = body;
+    R.xcorr.max_lag = shape.max_lag;
+    R.xcorr.n_cells = n_cells;
     int n_cu = 0, lds_max = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
-    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
     const size_t lds = bsig::xcorr_tiles_lds(n_wide > 0, P->tile_cells, body, shape.max_lag);
     if (lds > (size_t)lds_max)
         return fail(BSIG_ERR_ARG, "a tile of %d + %d cells needs %zu bytes of LDS per workgroup, the device has %d", body,
                     shape.max_lag, lds, lds_max);
-    const int64_t resident = (int64_t)std::max(n_cu, 1) *
-                             bsig::xcorr_blocks_per_cu(P->threads, P->kp.packed_half != 0, P->tile_cells, body, shape.max_lag);
-    int64_t per = std::max<int64_t>(1, (P->n_items + resident - 1) / resident);
-    // (tests: BAMSIGNALS_XCORR_RUN_TILES = tiles per run instead of the occupancy's, read when the plan is made)
-    if (const char *v = getenv("BAMSIGNALS_XCORR_RUN_TILES")) {
-        const long long forced = atoll(v);
-        if (forced > 0) per = forced;
-    }
+    const int64_t per = tiles_per_run(P, n_cu, bsig::xcorr_blocks_per_cu(P->threads, P->kp.packed_half != 0, P->tile_cells, body, shape.max_lag),
+                                      1, "BAMSIGNALS_XCORR_RUN_TILES");
     std::vector<uint2> runs;
-    for (int64_t a = 0; a < P->n_items; a += per) runs.push_back(make_uint2((uint32_t)a, (uint32_t)std::min<int64_t>(P->n_items, a + per)));
-    Q.n_runs_main = (int64_t)runs.size();
-    for (int64_t a = 0; a < n_wide; ++a) runs.push_back(make_uint2((uint32_t)a, (uint32_t)a + 1u));
-    Q.n_runs_wide = n_wide;
-    if (!runs.empty()) {
-        hipStream_t st = P->ctx->stream;
-        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
-        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return BSIG_OK;
+    cut_runs(P->n_items, per, 0, [](int64_t) { return (int64_t)0; }, runs);      // (no counter of a run can wrap: plan_create_impl's proof)
+    R.n_runs_main = (int64_t)runs.size();
+    append_wide_runs(n_wide, runs);
+    R.n_runs_extra = n_wide;
+    return upload_runs(P, runs);
 }
 
-// The runs of a frag plan: the tiles, in genomic order, cut into as many runs as workgroups are resident at a time (by
-// occupancy), as an xcorr plan's are -- a workgroup keeps its histogram in LDS across its run and ends with one 64-bit
-// atomic per non-zero row.  The histogram's counters have 32 bits and every read in a tile's windows adds at most 1 to
-// one of them, so a run also ends where the reads in its tiles' windows would pass the ceiling of 2^32 - 1: no counter
-// wraps.  (A single tile cannot hold that many: its windows are index ranges of 32 bits in five classes, and the plan
-// refuses the one that would.)
-static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &tile_reads)
+// The runs of a frag plan: cut as an xcorr plan's are -- a workgroup keeps its histogram in LDS across its run and ends
+// with one 64-bit atomic per non-zero row.  The histogram's counters have 32 bits and every read in a tile's windows adds
+// at most 1 to one of them, so a run also ends where the reads in its tiles' windows would pass the ceiling of 2^32 - 1
+// (tests: BAMSIGNALS_FRAG_FLUSH_READS lowers it): no counter wraps.  (A single tile cannot hold that many: its windows are
+// index ranges of 32 bits in five classes, and the plan refuses the one that would.)
+static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &reads_of_tile)
 {
-    constexpr int64_t kCounterMax = 4294967295ll;
-    P->frag.reset(new FragState);
-    FragState &Q = *P->frag;
-    Q.shape = shape;
+    Reduced &R = *P->red;
+    auto &Q = R.frag;
+    R.cells = shape.cells;
+    Q.len_bin = shape.len_bin;
     // The form: one LDS atomic per accepted read ("plain", the default), or the rows equal to the wave's first accepted
     // lane's merged before it ("merge").  The merging form becomes the default only where scripts/fragsizes_times.py
     // shows it faster than the plain one by more than the runs' spread: BAMSIGNALS_FRAG_FORM chooses, read
     // when the plan is made.
     if (const char *v = getenv("BAMSIGNALS_FRAG_FORM")) Q.merge = strcmp(v, "merge") == 0;
     int n_cu = 0, lds_max = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
-    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
     const size_t lds = bsig::frag_tiles_lds((int)shape.cells);
     if (lds > (size_t)lds_max)
         return fail(BSIG_ERR_ARG, "%lld rows need %zu bytes of LDS per workgroup, the device has %d", (long long)shape.cells, lds, lds_max);
-    const int64_t resident = (int64_t)std::max(n_cu, 1) * bsig::frag_blocks_per_cu(P->threads, Q.merge, (int)shape.cells);
-    int64_t per = std::max<int64_t>(1, (P->n_items + resident - 1) / resident);
-    // (tests: BAMSIGNALS_FRAG_RUN_TILES = tiles per run instead of the occupancy's, BAMSIGNALS_FRAG_FLUSH_READS = a lower
-    // ceiling for the reads of a run; both read when the plan is made)
-    if (const char *v = getenv("BAMSIGNALS_FRAG_RUN_TILES")) {
-        const long long forced = atoll(v);
-        if (forced > 0) per = forced;
-    }
-    int64_t ceiling = kCounterMax;
-    if (const char *v = getenv("BAMSIGNALS_FRAG_FLUSH_READS")) ceiling = std::min<long long>(kCounterMax, std::max<long long>(1, atoll(v)));
-    std::vector<uint2> runs;
-    int64_t a = 0, in_run = 0;
-    for (int64_t t = 0; t < P->n_items; ++t) {
-        const int64_t nr = tile_reads[(size_t)t];
+    const int64_t per = tiles_per_run(P, n_cu, bsig::frag_blocks_per_cu(P->threads, Q.merge, (int)shape.cells), 1, "BAMSIGNALS_FRAG_RUN_TILES");
+    for (const int64_t nr : reads_of_tile)
         if (nr > kCounterMax)
             return fail(BSIG_ERR_ARG, "a tile of these ranges sees %lld reads, more than a 32-bit counter holds", (long long)nr);
-        // (a tile with more reads than a LOWERED ceiling makes a run of its own: it is the real ceiling that counters need)
-        if (t > a && (t - a >= per || in_run + nr > ceiling)) {
-            runs.push_back(make_uint2((uint32_t)a, (uint32_t)t));
-            a = t; in_run = 0;
-        }
-        in_run += nr;
-    }
-    if (a < P->n_items) runs.push_back(make_uint2((uint32_t)a, (uint32_t)P->n_items));
-    Q.n_runs = (int64_t)runs.size();
-    if (!runs.empty()) {
-        hipStream_t st = P->ctx->stream;
-        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
-        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return BSIG_OK;
+    std::vector<uint2> runs;
+    cut_runs(P->n_items, per, counter_ceiling("BAMSIGNALS_FRAG_FLUSH_READS"), [&](int64_t t) { return reads_of_tile[(size_t)t]; }, runs);
+    R.n_runs_main = (int64_t)runs.size();
+    return upload_runs(P, runs);
 }
 
-// The runs of a hist plan: the tiles, in genomic order, cut into as many runs as workgroups are resident at a time (by
-// occupancy), as a frag plan's are -- a workgroup keeps its histogram in LDS across its run and ends with one 64-bit atomic
-// per non-zero row.  The histogram's counters have 32 bits and every cell of a tile adds 1 to one of them, so a run also
-// ends where the cells of its tiles would pass the ceiling of 2^32 - 1: no counter wraps.  The wide tiles (32-bit image)
-// follow as runs of one tile each: they are few and long.
+// The runs of a hist plan: cut as a frag plan's are.  Every cell of a tile adds 1 to one of the histogram's 32-bit
+// counters, so a run also ends where the cells of its tiles would pass the ceiling of 2^32 - 1 (tests:
+// BAMSIGNALS_HIST_FLUSH_CELLS lowers it; a tile holds at most 2 x 2,048 cells): no counter wraps.
 static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells)
 {
-    constexpr int64_t kCounterMax = 4294967295ll;
-    P->hist.reset(new HistState);
-    HistState &Q = *P->hist;
-    Q.shape = shape;
+    Reduced &R = *P->red;
+    auto &Q = R.hist;
+    R.cells = shape.cells;
+    Q.max_value = shape.max_value;
     Q.coverage = P->mode == BSIG_MODE_COVERAGE;
     Q.n_cells = n_cells;
     // The form: one LDS atomic per cell ("plain", the default), or the zero cells of a wave counted by ballot and the rows
@@ -2046,47 +2058,20 @@ static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vec
     if (const char *v = getenv("BAMSIGNALS_HIST_FORM")) Q.merge = strcmp(v, "merge") == 0;
     const int n_rows = shape.max_value + 1;
     int n_cu = 0, lds_max = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, P->ctx->device));
-    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, P->ctx->device));
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
     const size_t lds = bsig::hist_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells, n_rows);
     if (lds > (size_t)lds_max)
         return fail(BSIG_ERR_ARG, "%d rows and a tile of %d cells need %zu bytes of LDS per workgroup, the device has %d", n_rows,
                     P->tile_cells, lds, lds_max);
-    const int64_t resident = (int64_t)std::max(n_cu, 1) *
-                             bsig::hist_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, Q.merge, P->tile_cells, n_rows);
-    int64_t per = std::max<int64_t>(1, (P->n_items + resident - 1) / resident);
-    // (tests: BAMSIGNALS_HIST_RUN_TILES = tiles per run instead of the occupancy's, BAMSIGNALS_HIST_FLUSH_CELLS = a lower
-    // ceiling for the cells of a run; both read when the plan is made)
-    if (const char *v = getenv("BAMSIGNALS_HIST_RUN_TILES")) {
-        const long long forced = atoll(v);
-        if (forced > 0) per = forced;
-    }
-    int64_t ceiling = kCounterMax;
-    if (const char *v = getenv("BAMSIGNALS_HIST_FLUSH_CELLS")) ceiling = std::min<long long>(kCounterMax, std::max<long long>(1, atoll(v)));
+    const int64_t per = tiles_per_run(P, n_cu, bsig::hist_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, Q.merge, P->tile_cells, n_rows),
+                                      1, "BAMSIGNALS_HIST_RUN_TILES");
     const int64_t S = P->kp.ss ? 2 : 1;
     std::vector<uint2> runs;
-    int64_t a = 0, in_run = 0;
-    for (int64_t t = 0; t < P->n_items; ++t) {
-        // (a tile holds at most 2 x 2,048 cells: it is the real ceiling that counters need, a lowered one may be passed
-        // by a run of one tile)
-        const int64_t nc = (int64_t)items[(size_t)t].nc * S;
-        if (t > a && (t - a >= per || in_run + nc > ceiling)) {
-            runs.push_back(make_uint2((uint32_t)a, (uint32_t)t));
-            a = t; in_run = 0;
-        }
-        in_run += nc;
-    }
-    if (a < P->n_items) runs.push_back(make_uint2((uint32_t)a, (uint32_t)P->n_items));
-    Q.n_runs_main = (int64_t)runs.size();
-    for (int64_t k = 0; k < n_wide; ++k) runs.push_back(make_uint2((uint32_t)k, (uint32_t)k + 1u));
-    Q.n_runs_wide = n_wide;
-    if (!runs.empty()) {
-        hipStream_t st = P->ctx->stream;
-        HIP_TRY(P->pool.alloc(&Q.runs, runs.size()));
-        HIP_TRY(hipMemcpyAsync(Q.runs, runs.data(), runs.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return BSIG_OK;
+    cut_runs(P->n_items, per, counter_ceiling("BAMSIGNALS_HIST_FLUSH_CELLS"), [&](int64_t t) { return (int64_t)items[(size_t)t].nc * S; }, runs);
+    R.n_runs_main = (int64_t)runs.size();
+    append_wide_runs(n_wide, runs);
+    R.n_runs_extra = n_wide;
+    return upload_runs(P, runs);
 }
 
 extern "C" {
@@ -2095,7 +2080,7 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
                      const int32_t *loc, const int32_t *len, const int32_t *strand,
                      const bsig_params *prm, bsig_plan **out)
 {
-    return plan_create_impl(ctx, reads, n, rid, loc, len, strand, prm, nullptr, out);
+    return plan_create_impl(ctx, reads, n, rid, loc, len, strand, prm, PlanRequest{}, out);
 }
 
 const int64_t *bsig_plan_offsets(const bsig_plan *p) { return p ? p->off.data() : nullptr; }
@@ -2127,15 +2112,39 @@ static int run_main(bsig_plan *p, Launch &&launch)
     p->resolved_gen = p->reads->layout_gen;
     return BSIG_OK;
 }
+// The one refusal of a run call of kind `want` for a plan of another kind (BSIG_OK: it is that kind).  A plan of a later
+// kind is told which call runs it, one of an earlier kind what it is not; host: the entry is a _host one, so the call named
+// is too (bsig_plan_run_host_async names the device calls).
+static int wrong_kind(const bsig_plan *p, PlanKind want, bool host)
+{
+    if (p->kind == want) return BSIG_OK;
+    const char *call = host ? kKinds[p->kind].run_host : kKinds[p->kind].run_dev;
+    if (p->kind > want) return fail(BSIG_ERR_ARG, "%s plan runs with %s", kKinds[p->kind].a, call);
+    return fail(BSIG_ERR_ARG, "not %s plan: %s runs it", kKinds[want].a, call);
+}
+// What the four int64 device run calls do around their launches: the checks in the order every one of them made them, the
+// plan's GPU made current, then body(the plan's Reduced, its stream) -- the launches -- and the run counted.
+template <typename Body>
+static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
+{
+    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
+    if (const int rc = wrong_kind(p, want, false)) return rc;
+    if (p->red->cells == 0) return BSIG_OK;      // (a sum over ranges without width: the other kinds always have cells)
+    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
+    if (p->reads->layout_gen != p->made_for_gen)
+        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
+    HIP_TRY(hipSetDevice(p->ctx->device));      // the caller's thread may have another GPU current
+    if (const int rc = body(*p->red, p->ctx->stream)) return rc;
+    ++p->runs;
+    return BSIG_OK;
+}
 extern "C" {
 
 int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
-    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
+    if (const int rc = wrong_kind(p, kPlain, false)) return rc;
     const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
     if (!out_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
@@ -2167,12 +2176,9 @@ int bsig_plan_run(bsig_plan *p, int32_t *out_dev)
 int bsig_plan_run_host(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum_host");
-    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
+    if (const int rc = wrong_kind(p, kPlain, true)) return rc;
     const bsig::HostDest dst{out_host};
-    return bsig::plan_run_to_host(p, &dst, nullptr);
+    return bsig::plan_run_to_host(p, &dst);
 }
 
 int bsig_plan_overflowed(bsig_plan *p, int32_t *flag)
@@ -2187,96 +2193,57 @@ int bsig_plan_overflowed(bsig_plan *p, int32_t *flag)
 }
 
 }  // extern "C"
-int bsig::plan_run_to_host(bsig_plan *p, const HostDest *dst, int64_t *sum, bool async, double *t_kernels, double *t_download)
+int bsig::plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async, double *t_kernels, double *t_download)
 {
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-    SumState *Q = p->sum.get();
-    const int64_t cells = Q ? Q->shape.cells : p->off.back();
+    const int64_t cells = p->off.back();
     if (cells == 0) return BSIG_OK;
-    if (Q ? !sum : !dst || (!dst->flat && !dst->ptrs)) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    if (!dst || (!dst->flat && !dst->ptrs)) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
-    if (Q && !Q->d_sum) HIP_TRY(p->pool.alloc(&Q->d_sum, (size_t)cells));
-    if (!Q && !p->d_out) HIP_TRY(p->pool.alloc(&p->d_out, (size_t)cells));
-    int rc = Q ? bsig_plan_run_sum(p, Q->d_sum) : bsig_plan_run(p, p->d_out);
+    if (!p->d_out) HIP_TRY(p->pool.alloc(&p->d_out, (size_t)cells));
+    int rc = bsig_plan_run(p, p->d_out);
     if (rc != BSIG_OK) return rc;
     if (t_kernels) {
         HIP_TRY(hipStreamSynchronize(st));
         *t_kernels = since(t0);
     }
     const auto t1 = std::chrono::steady_clock::now();
-    if (Q) {
-        HIP_TRY(hipMemcpyAsync(sum, Q->d_sum, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else if (async) {
+    if (async) {
         HIP_TRY(hipMemcpyAsync(dst->flat, p->d_out, (size_t)cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         return BSIG_OK;
-    } else {
-        rc = download_to_dest(p->ctx, p->d_out, *dst, cells);
     }
+    rc = download_to_dest(p->ctx, p->d_out, *dst, cells);
     if (t_download) *t_download = since(t1);
-    return rc != BSIG_OK || Q ? rc : plan_check_overflow(p);
+    return rc != BSIG_OK ? rc : plan_check_overflow(p);
 }
-int bsig::plan_run_xcorr_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
+int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
 {
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-    XcorrState *Q = p->xcorr.get();
+    Reduced *Q = p->red.get();
+    if (!Q) return fail(BSIG_ERR_ARG, "not a reduction plan: %s runs it", kKinds[kPlain].run_host);
+    if (Q->cells == 0) return BSIG_OK;
     if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
-    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->shape.cells));
-    const int rc = bsig_plan_run_xcorr(p, Q->d_out);
+    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->cells));
+    int rc = BSIG_OK;
+    switch (p->kind) {
+    case kPlain: break;
+    case kSum: rc = bsig_plan_run_sum(p, Q->d_out); break;
+    case kXcorr: rc = bsig_plan_run_xcorr(p, Q->d_out); break;
+    case kFrag: rc = bsig_plan_run_frag(p, Q->d_out); break;
+    case kHist: rc = bsig_plan_run_hist(p, Q->d_out); break;
+    }
     if (rc != BSIG_OK) return rc;
     if (t_kernels) {
         HIP_TRY(hipStreamSynchronize(st));
         *t_kernels = since(t0);
     }
     const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->shape.cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (t_download) *t_download = since(t1);
-    return BSIG_OK;
-}
-int bsig::plan_run_frag_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-    FragState *Q = p->frag.get();
-    if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->shape.cells));
-    const int rc = bsig_plan_run_frag(p, Q->d_out);
-    if (rc != BSIG_OK) return rc;
-    if (t_kernels) {
-        HIP_TRY(hipStreamSynchronize(st));
-        *t_kernels = since(t0);
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->shape.cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (t_download) *t_download = since(t1);
-    return BSIG_OK;
-}
-int bsig::plan_run_hist_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-    HistState *Q = p->hist.get();
-    if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->shape.cells));
-    const int rc = bsig_plan_run_hist(p, Q->d_out);
-    if (rc != BSIG_OK) return rc;
-    if (t_kernels) {
-        HIP_TRY(hipStreamSynchronize(st));
-        *t_kernels = since(t0);
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->shape.cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (t_download) *t_download = since(t1);
     return BSIG_OK;
@@ -2295,12 +2262,9 @@ extern "C" {
 int bsig_plan_run_host_async(bsig_plan *p, int32_t *out_host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->sum) return fail(BSIG_ERR_ARG, "a sum plan runs with bsig_plan_run_sum");
-    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
+    if (const int rc = wrong_kind(p, kPlain, false)) return rc;
     const bsig::HostDest dst{out_host};
-    return bsig::plan_run_to_host(p, &dst, nullptr, true);
+    return bsig::plan_run_to_host(p, &dst, true);
 }
 
 // The visit counts are taken once (a launch of k_visits); what follows from them is worked out at every call from the
@@ -2325,7 +2289,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     bsig_plan_stats t{};
     t.n_ranges = p->n_ranges;
     t.n_items = p->n_items;
-    t.cells = p->sum ? p->sum->shape.cells : p->xcorr ? p->xcorr->shape.cells : p->frag ? p->frag->shape.cells : p->hist ? p->hist->shape.cells : p->off.back();
+    t.cells = p->red ? p->red->cells : p->off.back();
     t.visits_packed = (int64_t)acc[BSIG_CLASS_PACKED];   // one word per read
     t.visits_short = (int64_t)(acc[0] + acc[1]);         // classes 0 and 1: no end column
     t.visits = (int64_t)(acc[0] + acc[1] + acc[2] + acc[3] + acc[BSIG_CLASS_PACKED]);
@@ -2338,7 +2302,7 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     const int64_t per_item = (int64_t)sizeof(BsigWorkItem);
     t.algorithmic_bytes = t.bytes_per_visit_packed * t.visits_packed + t.bytes_per_visit_short * t.visits_short +
                           t.bytes_per_visit_long * (t.visits - t.visits_short - t.visits_packed) + per_item * t.n_items +
-                          (p->sum || p->xcorr || p->frag || p->hist ? 8 : 4) * t.cells;
+                          kKinds[p->kind].cell_bytes * t.cells;
     if (plan_two_launches(p) && windows_kept()) {
         // a resident plan's step reads the windows kept from its first run: no index entry is touched
         t.algorithmic_bytes += (int64_t)sizeof(BsigResolved) * t.n_items;
@@ -2363,59 +2327,10 @@ int bsig_plan_create_sum(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, cons
     bsig::PlanRule caller;          // (the caller's binsize and threads; the per-base tiles' are the plan's)
     int rc = bsig::sum_shape(*prm, n, len, &shape);
     if (rc == BSIG_OK) rc = bsig::check_params(*prm, n, len, &caller);
-    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, &shape, out);
-}
-
-int64_t bsig_plan_sum_cells(const bsig_plan *p) { return p && p->sum ? p->sum->shape.cells : 0; }
-
-int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
-{
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
-    if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run runs it");
-    const SumState &Q = *p->sum;
-    const int64_t cells = Q.shape.cells;
-    if (cells == 0) return BSIG_OK;
-    if (!sum_dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    if (((uintptr_t)sum_dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
-    if (p->reads->layout_gen != p->made_for_gen)
-        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    const int ss = Q.S == 2, nw = Q.shape.nw;
-    if (Q.n_runs_main) {
-        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-            return bsig::launch_sum_tiles(Q.kind, ss, nw, p->reads->dev, kp, p->items, p->n_items, Q.runs, Q.n_runs_main,
-                                          resolved, lookup, Q.slab, st);
-        });
-        if (rc != BSIG_OK) return rc;
-    }
-    // the slices of heavy tiles: one more addend each, with their fixed windows, into slabs of their own
-    if (Q.n_runs_heavy)
-        HIP_TRY(bsig::launch_sum_tiles(Q.kind, ss, nw, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                       Q.runs + Q.n_runs_main, Q.n_runs_heavy, p->heavy_windows, false,
-                                       Q.slab + (size_t)Q.n_runs_main * (size_t)Q.slab_vals, st));
-    const int32_t width = Q.shape.width, binsize = Q.shape.binsize;
-    long long *base = binsize == 1 ? reinterpret_cast<long long *>(sum_dev) : Q.base;
-    HIP_TRY(hipMemsetAsync(base, 0, (size_t)width * Q.S * sizeof(long long), st));
-    HIP_TRY(bsig::launch_sum_reduce(Q.kind != kSumProfile, Q.slab, Q.slab_vals, Q.chunks, Q.n_chunks, Q.max_nvals,
-                                    reinterpret_cast<unsigned long long *>(base), st));
-    if (Q.kind != kSumProfile) HIP_TRY(bsig::launch_sum_scan(base, width, p->tile_cells, Q.S, st));
-    if (binsize != 1) HIP_TRY(bsig::launch_sum_bins(base, width, binsize, Q.S, cells, reinterpret_cast<long long *>(sum_dev), st));
-    ++p->runs;
-    return BSIG_OK;
-}
-
-int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host)
-{
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->xcorr) return fail(BSIG_ERR_ARG, "an xcorr plan runs with bsig_plan_run_xcorr_host");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
-    if (!p->sum) return fail(BSIG_ERR_ARG, "not a sum plan: bsig_plan_run_host runs it");
-    return bsig::plan_run_to_host(p, nullptr, sum_host);
+    PlanRequest rq;
+    rq.kind = kSum;
+    rq.sum = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
 int bsig_plan_create_xcorr(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
@@ -2425,50 +2340,10 @@ int bsig_plan_create_xcorr(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, co
     *out = nullptr;
     bsig::XcorrShape shape;
     const int rc = bsig::xcorr_shape(*prm, max_lag, &shape);
-    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, nullptr, out, &shape);
-}
-
-int64_t bsig_plan_xcorr_cells(const bsig_plan *p) { return p && p->xcorr ? p->xcorr->shape.cells : 0; }
-
-int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
-{
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
-    if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum runs it" : "not an xcorr plan: bsig_plan_run runs it");
-    const XcorrState &Q = *p->xcorr;
-    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
-    if (p->reads->layout_gen != p->made_for_gen)
-        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    const int max_lag = Q.shape.max_lag;
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
-    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)Q.shape.cells * sizeof(int64_t), st));
-    if (Q.n_runs_main) {
-        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-            return bsig::launch_xcorr_tiles(p->threads, false, p->reads->dev, kp, p->items, p->n_items, Q.runs, Q.n_runs_main,
-                                            resolved, lookup, Q.body, max_lag, (unsigned long long)Q.n_cells, out, st);
-        });
-        if (rc != BSIG_OK) return rc;
-    }
-    // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
-    // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
-    if (Q.n_runs_wide)
-        HIP_TRY(bsig::launch_xcorr_tiles(p->threads, true, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                         Q.runs + Q.n_runs_main, Q.n_runs_wide, nullptr, false, Q.body, max_lag, 0ull, out, st));
-    ++p->runs;
-    return BSIG_OK;
-}
-
-int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host)
-{
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->frag) return fail(BSIG_ERR_ARG, "a frag plan runs with bsig_plan_run_frag_host");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
-    if (!p->xcorr) return fail(BSIG_ERR_ARG, p->sum ? "not an xcorr plan: bsig_plan_run_sum_host runs it" : "not an xcorr plan: bsig_plan_run_host runs it");
-    return bsig::plan_run_xcorr_to_host(p, host);
+    PlanRequest rq;
+    rq.kind = kXcorr;
+    rq.xcorr = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
 int bsig_plan_create_frag(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
@@ -2478,52 +2353,10 @@ int bsig_plan_create_frag(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, con
     *out = nullptr;
     bsig::FragShape shape;
     const int rc = bsig::frag_shape(*prm, len_bin, &shape);
-    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, nullptr, out, nullptr, &shape);
-}
-
-int64_t bsig_plan_frag_cells(const bsig_plan *p) { return p && p->frag ? p->frag->shape.cells : 0; }
-int64_t bsig_plan_frag_runs(const bsig_plan *p) { return p && p->frag ? p->frag->n_runs : 0; }
-
-// which run call a plan takes (the refusals' wording)
-static const char *run_call_of(const bsig_plan *p, bool host)
-{
-    if (p->sum) return host ? "bsig_plan_run_sum_host" : "bsig_plan_run_sum";
-    if (p->xcorr) return host ? "bsig_plan_run_xcorr_host" : "bsig_plan_run_xcorr";
-    if (p->frag) return host ? "bsig_plan_run_frag_host" : "bsig_plan_run_frag";
-    if (p->hist) return host ? "bsig_plan_run_hist_host" : "bsig_plan_run_hist";
-    return host ? "bsig_plan_run_host" : "bsig_plan_run";
-}
-
-int bsig_plan_run_frag(bsig_plan *p, int64_t *dev)
-{
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist");
-    if (!p->frag) return fail(BSIG_ERR_ARG, "not a frag plan: %s runs it", run_call_of(p, false));
-    const FragState &Q = *p->frag;
-    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
-    if (p->reads->layout_gen != p->made_for_gen)
-        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)Q.shape.cells * sizeof(int64_t), st));
-    if (Q.n_runs) {
-        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-            return bsig::launch_frag_tiles(p->threads, Q.merge, p->reads->dev, kp, p->items, p->n_items, Q.runs, Q.n_runs, resolved,
-                                           lookup, (int)Q.shape.cells, Q.shape.len_bin, reinterpret_cast<unsigned long long *>(dev), st);
-        });
-        if (rc != BSIG_OK) return rc;
-    }
-    ++p->runs;
-    return BSIG_OK;
-}
-
-int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host)
-{
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (p->hist) return fail(BSIG_ERR_ARG, "a hist plan runs with bsig_plan_run_hist_host");
-    if (!p->frag) return fail(BSIG_ERR_ARG, "not a frag plan: %s runs it", run_call_of(p, true));
-    return bsig::plan_run_frag_to_host(p, host);
+    PlanRequest rq;
+    rq.kind = kFrag;
+    rq.frag = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
 int bsig_plan_create_hist(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
@@ -2533,48 +2366,121 @@ int bsig_plan_create_hist(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, con
     *out = nullptr;
     bsig::HistShape shape;
     const int rc = bsig::hist_shape(*prm, max_value, &shape);
-    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, nullptr, out, nullptr, nullptr, &shape);
+    PlanRequest rq;
+    rq.kind = kHist;
+    rq.hist = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
-int64_t bsig_plan_hist_cells(const bsig_plan *p) { return p && p->hist ? p->hist->shape.cells : 0; }
-int64_t bsig_plan_hist_runs(const bsig_plan *p) { return p && p->hist ? p->hist->n_runs_main + p->hist->n_runs_wide : 0; }
+// a kind's queries answer 0 for a plan of another kind (and for no plan)
+static int64_t cells_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->cells : 0; }
+static int64_t runs_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->n_runs_main + p->red->n_runs_extra : 0; }
+int64_t bsig_plan_sum_cells(const bsig_plan *p) { return cells_if(p, kSum); }
+int64_t bsig_plan_xcorr_cells(const bsig_plan *p) { return cells_if(p, kXcorr); }
+int64_t bsig_plan_frag_cells(const bsig_plan *p) { return cells_if(p, kFrag); }
+int64_t bsig_plan_frag_runs(const bsig_plan *p) { return runs_if(p, kFrag); }
+int64_t bsig_plan_hist_cells(const bsig_plan *p) { return cells_if(p, kHist); }
+int64_t bsig_plan_hist_runs(const bsig_plan *p) { return runs_if(p, kHist); }
+
+int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
+{
+    return run_reduced(p, kSum, sum_dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.sum;
+        const int ss = Q.S == 2, nw = Q.nw;
+        if (R.n_runs_main) {
+            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+                return bsig::launch_sum_tiles(Q.kind, ss, nw, p->reads->dev, kp, p->items, p->n_items, R.runs, R.n_runs_main,
+                                              resolved, lookup, Q.slab, st);
+            });
+            if (rc != BSIG_OK) return rc;
+        }
+        // the slices of heavy tiles: one more addend each, with their fixed windows, into slabs of their own
+        if (R.n_runs_extra)
+            HIP_TRY(bsig::launch_sum_tiles(Q.kind, ss, nw, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                           R.runs + R.n_runs_main, R.n_runs_extra, p->heavy_windows, false,
+                                           Q.slab + (size_t)R.n_runs_main * (size_t)Q.slab_vals, st));
+        const int32_t width = Q.width, binsize = Q.binsize;
+        long long *base = binsize == 1 ? reinterpret_cast<long long *>(sum_dev) : Q.base;
+        HIP_TRY(hipMemsetAsync(base, 0, (size_t)width * Q.S * sizeof(long long), st));
+        HIP_TRY(bsig::launch_sum_reduce(Q.kind != kSumProfile, Q.slab, Q.slab_vals, Q.chunks, Q.n_chunks, Q.max_nvals,
+                                        reinterpret_cast<unsigned long long *>(base), st));
+        if (Q.kind != kSumProfile) HIP_TRY(bsig::launch_sum_scan(base, width, p->tile_cells, Q.S, st));
+        if (binsize != 1) HIP_TRY(bsig::launch_sum_bins(base, width, binsize, Q.S, R.cells, reinterpret_cast<long long *>(sum_dev), st));
+        return BSIG_OK;
+    });
+}
+
+int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
+{
+    return run_reduced(p, kXcorr, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.xcorr;
+        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
+        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+        if (R.n_runs_main) {
+            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+                return bsig::launch_xcorr_tiles(p->threads, false, p->reads->dev, kp, p->items, p->n_items, R.runs, R.n_runs_main,
+                                                resolved, lookup, Q.body, Q.max_lag, (unsigned long long)Q.n_cells, out, st);
+            });
+            if (rc != BSIG_OK) return rc;
+        }
+        // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
+        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
+        if (R.n_runs_extra)
+            HIP_TRY(bsig::launch_xcorr_tiles(p->threads, true, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                             R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, Q.body, Q.max_lag, 0ull, out, st));
+        return BSIG_OK;
+    });
+}
+
+int bsig_plan_run_frag(bsig_plan *p, int64_t *dev)
+{
+    return run_reduced(p, kFrag, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+        if (R.n_runs_main) {
+            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+                return bsig::launch_frag_tiles(p->threads, R.frag.merge, p->reads->dev, kp, p->items, p->n_items, R.runs, R.n_runs_main,
+                                               resolved, lookup, (int)R.cells, R.frag.len_bin, reinterpret_cast<unsigned long long *>(dev), st);
+            });
+            if (rc != BSIG_OK) return rc;
+        }
+        return BSIG_OK;
+    });
+}
 
 int bsig_plan_run_hist(bsig_plan *p, int64_t *dev)
 {
-    if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (!p->hist) return fail(BSIG_ERR_ARG, "not a hist plan: %s runs it", run_call_of(p, false));
-    const HistState &Q = *p->hist;
-    if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
-    if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
-    if (p->reads->layout_gen != p->made_for_gen)
-        return fail(BSIG_ERR_ARG, "the reads were laid out again after this plan was made: make a new plan");
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    const int n_rows = Q.shape.max_value + 1;
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
-    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)Q.shape.cells * sizeof(int64_t), st));
-    if (Q.n_runs_main) {
-        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-            return bsig::launch_hist_tiles(p->threads, Q.coverage, false, Q.merge, p->reads->dev, kp, p->items, p->n_items, Q.runs,
-                                           Q.n_runs_main, resolved, lookup, n_rows, (unsigned long long)Q.n_cells, out, st);
-        });
-        if (rc != BSIG_OK) return rc;
-    }
-    // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
-    // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
-    if (Q.n_runs_wide)
-        HIP_TRY(bsig::launch_hist_tiles(p->threads, Q.coverage, true, Q.merge, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                        Q.runs + Q.n_runs_main, Q.n_runs_wide, nullptr, false, n_rows, 0ull, out, st));
-    ++p->runs;
-    return BSIG_OK;
+    return run_reduced(p, kHist, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.hist;
+        const int n_rows = Q.max_value + 1;
+        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
+        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+        if (R.n_runs_main) {
+            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+                return bsig::launch_hist_tiles(p->threads, Q.coverage, false, Q.merge, p->reads->dev, kp, p->items, p->n_items, R.runs,
+                                               R.n_runs_main, resolved, lookup, n_rows, (unsigned long long)Q.n_cells, out, st);
+            });
+            if (rc != BSIG_OK) return rc;
+        }
+        // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
+        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
+        if (R.n_runs_extra)
+            HIP_TRY(bsig::launch_hist_tiles(p->threads, Q.coverage, true, Q.merge, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                            R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, n_rows, 0ull, out, st));
+        return BSIG_OK;
+    });
 }
 
-int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host)
+// the four _host calls: the kind checked, then the one run into the plan's own device buffer and its download
+static int run_reduced_host(bsig_plan *p, PlanKind want, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
-    if (!p->hist) return fail(BSIG_ERR_ARG, "not a hist plan: %s runs it", run_call_of(p, true));
-    return bsig::plan_run_hist_to_host(p, host);
+    if (const int rc = wrong_kind(p, want, true)) return rc;
+    return bsig::plan_run_reduced_to_host(p, host);
 }
+int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host) { return run_reduced_host(p, kSum, sum_host); }
+int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kXcorr, host); }
+int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kFrag, host); }
+int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kHist, host); }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
 // The run-length encoder (runs.hip) of a plan's own layout: range i's cells off[i] .. off[i + 1] are one segment, or with
@@ -2583,8 +2489,8 @@ int bsig_plan_runs_create(const bsig_plan *p, bsig_runs **out)
 {
     if (!p || !out) return fail(BSIG_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (p->sum || p->xcorr || p->frag || p->hist)
-        return fail(BSIG_ERR_ARG, "a %s plan has no per-range result to encode", p->sum ? "sum" : p->xcorr ? "xcorr" : p->frag ? "frag" : "hist");
+    if (p->kind != kPlain)      // (the kind's noun without its article)
+        return fail(BSIG_ERR_ARG, "a %s plan has no per-range result to encode", strchr(kKinds[p->kind].a, ' ') + 1);
     if (p->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
     const int S = p->kp.ss ? 2 : 1;
     std::vector<int64_t> base((size_t)(p->n_ranges * S));

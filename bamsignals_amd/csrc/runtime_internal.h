@@ -228,12 +228,13 @@ int download_slice_to_dest(bsig_ctx *ctx, const int32_t *src_dev, const HostDest
 // ... several slices as ONE pipelined stream: slice k = cells[k] int32 at src_dev + src_c0[k], bound for cell dst_c0[k]
 int download_slices_to_dest(bsig_ctx *ctx, const int32_t *src_dev, int64_t n_slices, const int64_t *src_c0, const int64_t *dst_c0,
                             const int64_t *cells, const HostDest &dst, int copy_threads);
-// bsig_plan_run (dst: an ordinary plan's int32 result) or bsig_plan_run_sum (sum: a sum plan's int64 cells) into the
-// plan's own device buffer, then the download to the host.  async: the copy is only enqueued.  With timers the kernels
-// are waited for first and the two stages timed apart; without them nothing waits between kernels and download.  The
-// caller has checked which kind of plan p is (runtime.hip)
-int plan_run_to_host(bsig_plan *p, const HostDest *dst, int64_t *sum, bool async = false, double *t_kernels = nullptr,
-                     double *t_download = nullptr);
+// bsig_plan_run (a plain plan's int32 result) into the plan's own device buffer, then the download to the host.  async:
+// the copy is only enqueued.  With timers the kernels are waited for first and the two stages timed apart; without them
+// nothing waits between kernels and download.  The caller has checked that p is a plain plan (runtime.hip)
+int plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async = false, double *t_kernels = nullptr, double *t_download = nullptr);
+// ... and a reduction plan's (sum, xcorr, frag, hist): its kind's device run call into the plan's own int64 buffer (made
+// at the first call), then the download; timed as above.  A sum plan without cells has nothing to run
+int plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // bsig_params as every entry point reads them (runtime.hip: check_params)
 struct PlanRule {
     int mode;               // the kernel family: BSIG_MODE_COVERAGE_EX is BSIG_MODE_COVERAGE with bins and / or strands
@@ -264,8 +265,6 @@ struct XcorrShape {
     int64_t cells;          // max_lag + 1 + BSIG_XCORR_MOMENTS
 };
 int xcorr_shape(const bsig_params &prm, int32_t max_lag, XcorrShape *out);
-// bsig_plan_run_xcorr into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
-int plan_run_xcorr_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // what only a fragment-length histogram asks, ahead of check_params (runtime.hip: frag_shape): bamCount's tiles, no shift,
 // a length filter, a row width >= 1, at most BSIG_FRAG_MAX_ROWS rows
 struct FragShape {
@@ -274,8 +273,6 @@ struct FragShape {
     int64_t cells;          // rows: tlen_filter[1] / len_bin + 1
 };
 int frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out);
-// bsig_plan_run_frag into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
-int plan_run_frag_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // what only a depth histogram asks, ahead of check_params (runtime.hip: hist_shape): per-base 5' ends or plain coverage, no
 // shift, 1 <= max_value < BSIG_HIST_MAX_ROWS, threads and tile_cells the kernel's LDS holds
 struct HistShape {
@@ -284,8 +281,6 @@ struct HistShape {
     int64_t cells;          // V + 1 + BSIG_HIST_MOMENTS
 };
 int hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out);
-// bsig_plan_run_hist into the plan's own device buffer + the download, timed apart where asked (runtime.hip)
-int plan_run_hist_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

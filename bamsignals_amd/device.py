@@ -252,21 +252,43 @@ def make_params(mode, tlen_filter=(), mapqual=0, binsize=1, shift=0, ss=False, r
     return p
 
 
-class Plan:
-    """Ranges + call parameters resident in HBM; run it any number of times."""
+class _PlanBase:
+    """What every kind of plan shares: the range arrays as contiguous int32 of one length, the handle's life, ``stats``."""
 
-    def __init__(self, ctx, reads, rid, loc, length, strand, params):
+    def _ranges(self, ctx, reads, rid, loc, length, strand):
+        """Keeps ``ctx`` and ``reads``; (n, the four arrays' pointers) for the kind's ``bsig_plan_create*`` call (a
+        pointer keeps its array alive)."""
         self._lib = _lib.load()
         self.ctx, self.reads = ctx, reads
         rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
         n = len(rid)
         if not (len(loc) == len(length) == len(strand) == n):
             raise ValueError("range arrays differ in length")
-        h = C.c_void_p()
-        _lib.check(self._lib.bsig_plan_create(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
-                                              _ptr(strand), C.byref(params), C.byref(h)))
-        self._h = h
         self.n_ranges = n
+        return n, [_ptr(a) for a in (rid, loc, length, strand)]
+
+    def stats(self):
+        s = _lib.PlanStats()
+        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class Plan(_PlanBase):
+    """Ranges + call parameters resident in HBM; run it any number of times."""
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params):
+        n, ptrs = self._ranges(ctx, reads, rid, loc, length, strand)
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_create(ctx._h, reads._h, n, *ptrs, C.byref(params), C.byref(h)))
+        self._h = h
         self.cells = int(self._lib.bsig_plan_cells(h))
         self.offsets = np.ctypeslib.as_array(self._lib.bsig_plan_offsets(h), shape=(n + 1,)).copy()
 
@@ -300,166 +322,77 @@ class Plan:
         _lib.check(self._lib.bsig_plan_runs_create(self._h, C.byref(h)))
         return RunEncoder._adopt(self.ctx, h)
 
-    def stats(self):
-        s = _lib.PlanStats()
-        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.bsig_plan_free(self._h)
-            self._h = None
+class _ReducedPlan(_PlanBase):
+    """A plan that reduces all its ranges to ``cells`` int64 (bsig_plan_create_<_KIND>, bsig_plan_run_<_KIND>[_host])."""
 
-    def __del__(self):
-        self.close()
+    _KIND = None
 
-
-class SumPlan:
-    """Ranges of one width + call parameters resident in HBM, summed over the ranges (bsig_plan_create_sum): each run
-    gives the int64 sum of what ``Plan`` returns for the ranges, cell by cell -- ``n_bins`` cells, or ``2 x n_bins``
-    (cell ``2 * bin + antisense``) with strands.  ``params.threads`` 64 / 128 / 256: tiles in flight per workgroup."""
-
-    def __init__(self, ctx, reads, rid, loc, length, strand, params):
-        self._lib = _lib.load()
-        self.ctx, self.reads = ctx, reads
-        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
-        n = len(rid)
-        if not (len(loc) == len(length) == len(strand) == n):
-            raise ValueError("range arrays differ in length")
+    def _create(self, ctx, reads, rid, loc, length, strand, params, *extra):
+        """``extra``: the kind's own int32 arguments, between the parameters and the handle."""
+        n, ptrs = self._ranges(ctx, reads, rid, loc, length, strand)
         h = C.c_void_p()
-        _lib.check(self._lib.bsig_plan_create_sum(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
-                                                  _ptr(strand), C.byref(params), C.byref(h)))
+        create = getattr(self._lib, f"bsig_plan_create_{self._KIND}")
+        _lib.check(create(ctx._h, reads._h, n, *ptrs, C.byref(params), *extra, C.byref(h)))
         self._h = h
-        self.n_ranges = n
-        self.cells = int(self._lib.bsig_plan_sum_cells(h))
+        self.cells = int(getattr(self._lib, f"bsig_plan_{self._KIND}_cells")(h))
 
     def run_host(self, out=None):
-        """Run and return the int64 sum in host memory (``out``: a reusable contiguous int64 array of ``cells``)."""
+        """Run and return the int64 result in host memory, laid out as the class says (``out``: a reusable contiguous
+        int64 array of ``cells``)."""
         if out is None:
             out = np.empty(self.cells, dtype=np.int64)
         elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
             raise ValueError("out must be a contiguous int64 array of plan.cells elements")
-        _lib.check(self._lib.bsig_plan_run_sum_host(self._h, _ptr(out)))
+        _lib.check(getattr(self._lib, f"bsig_plan_run_{self._KIND}_host")(self._h, _ptr(out)))
         return out
 
     def run_device(self, out_ptr):
         """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
-        _lib.check(self._lib.bsig_plan_run_sum(self._h, C.c_void_p(out_ptr)))
-
-    def stats(self):
-        s = _lib.PlanStats()
-        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.bsig_plan_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
+        _lib.check(getattr(self._lib, f"bsig_plan_run_{self._KIND}")(self._h, C.c_void_p(out_ptr)))
 
 
-class XcorrPlan:
+class SumPlan(_ReducedPlan):
+    """Ranges of one width + call parameters resident in HBM, summed over the ranges (bsig_plan_create_sum): each run
+    gives the int64 sum of what ``Plan`` returns for the ranges, cell by cell -- ``n_bins`` cells, or ``2 x n_bins``
+    (cell ``2 * bin + antisense``) with strands.  ``params.threads`` 64 / 128 / 256: tiles in flight per workgroup."""
+
+    _KIND = "sum"
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params):
+        self._create(ctx, reads, rid, loc, length, strand, params)
+
+
+class XcorrPlan(_ReducedPlan):
     """Ranges + call parameters resident in HBM for the strand cross-correlation (bsig_plan_create_xcorr): each run gives
     ``max_lag + 1 + 5`` int64 -- ``cross[d]``, the sum over ranges and cells of sense[x] * antisense[x + d] of the ranges'
     per-base, strand-split, unshifted ``Plan`` result, then the moments [cells, sum S, sum A, sum S^2, sum A^2].
     ``params``: a per-base profile without shift or midpoint; ``tile_cells`` = body cells of a tile, ``threads`` per
     workgroup.  ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit image."""
 
+    _KIND = "xcorr"
+
     def __init__(self, ctx, reads, rid, loc, length, strand, params, max_lag):
-        self._lib = _lib.load()
-        self.ctx, self.reads = ctx, reads
-        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
-        n = len(rid)
-        if not (len(loc) == len(length) == len(strand) == n):
-            raise ValueError("range arrays differ in length")
-        h = C.c_void_p()
-        _lib.check(self._lib.bsig_plan_create_xcorr(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
-                                                    _ptr(strand), C.byref(params), int(max_lag), C.byref(h)))
-        self._h = h
-        self.n_ranges = n
+        self._create(ctx, reads, rid, loc, length, strand, params, int(max_lag))
         self.max_lag = int(max_lag)
-        self.cells = int(self._lib.bsig_plan_xcorr_cells(h))
-
-    def run_host(self, out=None):
-        """Run and return the int64 result in host memory: ``out[:max_lag + 1]`` is cross, the rest the moments."""
-        if out is None:
-            out = np.empty(self.cells, dtype=np.int64)
-        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
-        _lib.check(self._lib.bsig_plan_run_xcorr_host(self._h, _ptr(out)))
-        return out
-
-    def run_device(self, out_ptr):
-        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
-        _lib.check(self._lib.bsig_plan_run_xcorr(self._h, C.c_void_p(out_ptr)))
-
-    def stats(self):
-        s = _lib.PlanStats()
-        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.bsig_plan_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
 
-class FragPlan:
+class FragPlan(_ReducedPlan):
     """Ranges + call parameters resident in HBM for the fragment-length histogram (bsig_plan_create_frag): each run gives
     ``tlen_filter[1] // len_bin + 1`` int64 -- row r counts the reads that ``Plan``'s bamCount (shift 0, unstranded) counts
     over all ranges with ``|tlen| // len_bin == r``.  ``params``: mode COUNT without shift, with a 2-element
     ``tlen_filter``; ``tile_cells`` = bases of a tile, ``threads`` per workgroup.  ``runs``: the runs of tiles (a
     workgroup each) the plan was cut into."""
 
+    _KIND = "frag"
+
     def __init__(self, ctx, reads, rid, loc, length, strand, params, len_bin=1):
-        self._lib = _lib.load()
-        self.ctx, self.reads = ctx, reads
-        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
-        n = len(rid)
-        if not (len(loc) == len(length) == len(strand) == n):
-            raise ValueError("range arrays differ in length")
-        h = C.c_void_p()
-        _lib.check(self._lib.bsig_plan_create_frag(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
-                                                   _ptr(strand), C.byref(params), int(len_bin), C.byref(h)))
-        self._h = h
-        self.n_ranges = n
+        self._create(ctx, reads, rid, loc, length, strand, params, int(len_bin))
         self.len_bin = int(len_bin)
-        self.cells = int(self._lib.bsig_plan_frag_cells(h))
-        self.runs = int(self._lib.bsig_plan_frag_runs(h))
-
-    def run_host(self, out=None):
-        """Run and return the int64 histogram in host memory."""
-        if out is None:
-            out = np.empty(self.cells, dtype=np.int64)
-        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
-        _lib.check(self._lib.bsig_plan_run_frag_host(self._h, _ptr(out)))
-        return out
-
-    def run_device(self, out_ptr):
-        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
-        _lib.check(self._lib.bsig_plan_run_frag(self._h, C.c_void_p(out_ptr)))
-
-    def stats(self):
-        s = _lib.PlanStats()
-        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.bsig_plan_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
+        self.runs = int(self._lib.bsig_plan_frag_runs(self._h))
 
 
-class HistPlan:
+class HistPlan(_ReducedPlan):
     """Ranges + call parameters resident in HBM for the depth histogram (bsig_plan_create_hist): each run gives
     ``max_value + 1 + 2`` int64 -- row r counts the cells of value r that ``Plan`` returns for the ranges under the same
     parameters, the last row those of value >= ``max_value``; then the moments [cells, sum of the cell values].
@@ -467,47 +400,12 @@ class HistPlan:
     ``tile_cells`` = cells of a tile (16 .. 2,048), ``threads`` per workgroup.  ``runs``: the runs of tiles (a workgroup
     each) the plan was cut into.  ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit image."""
 
+    _KIND = "hist"
+
     def __init__(self, ctx, reads, rid, loc, length, strand, params, max_value):
-        self._lib = _lib.load()
-        self.ctx, self.reads = ctx, reads
-        rid, loc, length, strand = _i32(rid), _i32(loc), _i32(length), _i32(strand)
-        n = len(rid)
-        if not (len(loc) == len(length) == len(strand) == n):
-            raise ValueError("range arrays differ in length")
-        h = C.c_void_p()
-        _lib.check(self._lib.bsig_plan_create_hist(ctx._h, reads._h, n, _ptr(rid), _ptr(loc), _ptr(length),
-                                                   _ptr(strand), C.byref(params), int(max_value), C.byref(h)))
-        self._h = h
-        self.n_ranges = n
+        self._create(ctx, reads, rid, loc, length, strand, params, int(max_value))
         self.max_value = int(max_value)
-        self.cells = int(self._lib.bsig_plan_hist_cells(h))
-        self.runs = int(self._lib.bsig_plan_hist_runs(h))
-
-    def run_host(self, out=None):
-        """Run and return the int64 result in host memory: ``out[:max_value + 1]`` is the histogram, the rest the moments."""
-        if out is None:
-            out = np.empty(self.cells, dtype=np.int64)
-        elif out.dtype != np.int64 or out.size != self.cells or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous int64 array of plan.cells elements")
-        _lib.check(self._lib.bsig_plan_run_hist_host(self._h, _ptr(out)))
-        return out
-
-    def run_device(self, out_ptr):
-        """Asynchronous launch on the context's stream; ``out_ptr``: device address of ``cells`` int64."""
-        _lib.check(self._lib.bsig_plan_run_hist(self._h, C.c_void_p(out_ptr)))
-
-    def stats(self):
-        s = _lib.PlanStats()
-        _lib.check(self._lib.bsig_plan_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.bsig_plan_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
+        self.runs = int(self._lib.bsig_plan_hist_runs(self._h))
 
 
 class RunEncoder:
