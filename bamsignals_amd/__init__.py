@@ -4,7 +4,8 @@ User API (mirrors R/wrappers.R and R/zzzCountSignals.R of the reference):
     bamCount, bamProfile, bamCoverage, CountSignals, GRanges, writeSamAsBamAndIndex
 Beyond it: bamCrossCorr, the strand cross-correlation over ranges (the data's own value for ``shift``), and
 bamFragSizes, the fragment-length histogram over ranges (the data's own ``tlenFilter``); bamDepthHist, the histogram of
-the per-base depth over ranges (breadth at 20x, mean and median depth, the duplication histogram); RunSignals, what
+the per-base depth over ranges (breadth at 20x, mean and median depth, the duplication histogram); bamSummary, every
+range's own sum, max, summit and breadth at thresholds (peak heights, per-target QC); RunSignals, what
 bamProfile / bamCoverage return with ``runs=True``: the signals as runs, encoded on the GPU.
 Handle-level API for resident data and benchmarking: ``bamsignals_amd.device``.
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
@@ -17,8 +18,9 @@ from .depthhist import DepthHist, bamDepthHist  # noqa: F401
 from .fragsizes import FragSizes, bamFragSizes  # noqa: F401
 from .granges import GRanges  # noqa: F401
 from .runsignals import RunSignals  # noqa: F401
+from .summary import RangeSummary, bamSummary  # noqa: F401
 from .wrappers import bamCount, bamCoverage, bamProfile, coverage_core, pileup_core  # noqa: F401
 
 __all__ = ["bamCount", "bamProfile", "bamCoverage", "bamCrossCorr", "CrossCorr", "bamFragSizes",
-           "FragSizes", "bamDepthHist", "DepthHist", "CountSignals", "RunSignals", "GRanges", "BamFile",
+           "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "CountSignals", "RunSignals", "GRanges", "BamFile",
            "writeSamAsBamAndIndex", "write_columns_as_bam", "pileup_core", "coverage_core"]

@@ -7,6 +7,12 @@
 #include "../../include/bamsignals_abi.h"
 #include "bsig_types.h"
 
+// k_summary_tiles' thresholds, a kernel argument: t[0 .. k) rising, the rest 2^32 - 1
+struct BsigThresholds {
+    uint32_t t[BSIG_SUMMARY_MAX_THRESHOLDS];
+    int32_t k;
+};
+
 namespace bsig {
 
 struct ScatterPtrs {
@@ -103,6 +109,17 @@ int hist_blocks_per_cu(int threads, bool coverage, bool half, bool merge, int ti
 hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, const BsigReadsDev &R, const BsigKParams &P,
                              const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                              bool resolve_first, int n_rows, unsigned long long n_cells, unsigned long long *out, hipStream_t st);
+// Per-range summaries (bsig_plan_create_summary).  k_summary_tiles: run r = per-base tiles [runs[r].x, runs[r].y) as
+// k_hist_tiles walks them; a tile's out_off is its range's first result row (range x S, S = 2 for 5' ends with P.ss).  Every
+// workgroup ADDS into row q of out, 3 + T.k int64 a row: [0] the cells' sum, [3 + j] the cells >= T.t[j], and takes the MAX
+// of [1] with the key value << 32 | (2^32 - 1 - cell): zero `out` first, launch_summary_finish last ([1] max, [2] summit, -1
+// for a row no tile wrote).  T.t past T.k must be 2^32 - 1.  wide / half / windows / resolve_first as in launch_hist_tiles.
+size_t summary_tiles_lds(bool coverage, bool wide, int tile_cells);
+int summary_blocks_per_cu(int threads, bool coverage, bool half, int tile_cells);
+hipError_t launch_summary_tiles(int threads, bool coverage, bool wide, const BsigReadsDev &R, const BsigKParams &P,
+                                const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                                bool resolve_first, const BsigThresholds &T, unsigned long long *out, hipStream_t st);
+hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

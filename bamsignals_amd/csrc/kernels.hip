@@ -2163,6 +2163,9 @@ struct HistCounter {
             if (ok) atomicAdd(&hist[row], 1u);
         }
     }
+    // walk_tile_cells' consumer: the histogram asks neither for the cell's place nor for its strand
+    template <int ROW>
+    __device__ __forceinline__ void at(uint32_t v, bool ok, int) { (*this)(v, ok); }
     // once per tile
     __device__ __forceinline__ void flush_zeros()
     {
@@ -2172,6 +2175,116 @@ struct HistCounter {
         }
     }
 };
+
+// The walk k_hist_tiles and k_summary_tiles share: tile w's image is built in `img` (which arrives zeroed) by the existing
+// read bodies, coverage's difference image is scanned, and every cell goes to the consumer ONCE, as
+// cnt.at<ROW>(value, ok, x): x the cell's index in the tile (range orientation; lanes take ascending x within a call and
+// from call to call), ok whether x < nc (a cell behind the tile is handed over with ok false and no meaning), ROW 1 the
+// antisense cell of a strand-split tile and 0 everything else.  All lanes of a wave call it together.  A lane clears the
+// image cells it has read; the caller's barrier ends the tile.
+template <int NT, int KIND, bool WIDE, typename Cells>
+__device__ __forceinline__ void walk_tile_cells(const BsigWorkItem &w, uint32_t t, const BsigWorkItem *__restrict__ items,
+                                                const uint2 *__restrict__ windows, const BsigReadsDev &R, const BsigKParams &P,
+                                                uint32_t *img, int32_t *wtot, const uint8_t *ptab, int tid, Cells &cnt)
+{
+    const int lane = tid & (kWave - 1);
+    uint2 win[BSIG_MAX_CLASSES], clip;
+    PackedWin pk;
+    const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
+    const int nc = w.nc;
+    if constexpr (KIND == kHistCover) {
+        load_windows<false>(R, P, BSIG_MODE_COVERAGE, w, items, windows, win, t, pk, clip);
+        const int rend1 = w.loc + w.len - 1;
+        if constexpr (WIDE) {
+            const CoverWideOne one{P, reinterpret_cast<int32_t *>(img), w.loc, w.c0, nc, neg_range, rend1};
+            for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+            if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
+        } else {
+            const CoverOne one{P, reinterpret_cast<int32_t *>(img), w.loc, w.c0, nc, 0, neg_range, rend1};
+            for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+            if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
+        }
+        __syncthreads();
+        // k_coverage's scan: each lane owns 4 consecutive cells, wave scan of the lane totals, carry across waves
+        // and passes; the cells are handed over instead of stored
+        const int nvec = (nc + 3) >> 2;
+        auto lo16 = [](uint32_t d) { return (int)(int16_t)(uint16_t)d; };
+        auto hi16 = [](uint32_t d) { return (int)(int16_t)(uint16_t)((d + 0x8000u) >> 16); };
+        int carry = 0;
+        for (int base = 0; base < nvec; base += NT) {
+            const int v = base + tid;
+            int4 x = make_int4(0, 0, 0, 0);
+            if (v < nvec) {
+                if constexpr (WIDE) {
+                    int4 *p4 = reinterpret_cast<int4 *>(img) + v;
+                    x = *p4;
+                    *p4 = make_int4(0, 0, 0, 0);
+                } else {
+                    uint2 *p2 = reinterpret_cast<uint2 *>(img) + v;
+                    const uint2 d = *p2;
+                    *p2 = make_uint2(0u, 0u);
+                    x = make_int4(lo16(d.x), hi16(d.x), lo16(d.y), hi16(d.y));
+                }
+            }
+            x.y += x.x; x.z += x.y; x.w += x.z;
+            const int tot = x.w;
+            const int incl = wave_inclusive_scan(tot);
+            int pre = carry;
+            int all = __builtin_amdgcn_readlane(incl, kWave - 1);
+            if (NT > kWave) {
+                if (lane == kWave - 1) wtot[tid / kWave] = incl;
+                __syncthreads();
+                all = 0;
+                for (int k = 0; k < NT / kWave; ++k) {
+                    const int s = wtot[k];
+                    if (k < tid / kWave) pre += s;
+                    all += s;
+                }
+                __syncthreads();
+            }
+            const int add = pre + incl - tot;
+            const int c = 4 * v;
+            cnt.template at<0>((uint32_t)(x.x + add), c < nc, c);
+            cnt.template at<0>((uint32_t)(x.y + add), c + 1 < nc, c + 1);
+            cnt.template at<0>((uint32_t)(x.z + add), c + 2 < nc, c + 2);
+            cnt.template at<0>((uint32_t)(x.w + add), c + 3 < nc, c + 3);
+            carry += all;
+        }
+    } else {
+        load_windows<false>(R, P, BSIG_MODE_PROFILE, w, items, windows, win, t, pk, clip);
+        if constexpr (WIDE) {
+            const XcorrWideOne one{P, img, w.loc, w.len, w.c0, nc, neg_range};
+            for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+            if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+        } else {
+            constexpr bool HALF = KIND == kHistEndsHalf;
+            const ProfileOne<true> one{P, img, w.loc, w.len, w.c0, nc, 0, neg_range};
+            for_each_read<NT, 2, HALF>(R, P, win, pk.base, ptab, tid, one);
+            if (!HALF && pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+        }
+        __syncthreads();
+        const bool ss = P.ss != 0;                                  // (uniform)
+        for (int base = 0; base < nc; base += NT) {
+            const int x = base + tid;
+            const bool ok = x < nc;
+            uint32_t s = 0, a = 0;
+            if (ok) {
+                if constexpr (WIDE) {
+                    uint2 *p2 = reinterpret_cast<uint2 *>(img) + x;
+                    const uint2 d = *p2;
+                    *p2 = make_uint2(0u, 0u);
+                    s = d.x; a = d.y;
+                } else {
+                    const uint32_t d = img[x];
+                    img[x] = 0u;
+                    s = d & 0xFFFFu; a = d >> 16;
+                }
+            }
+            if (ss) { cnt.template at<0>(s, ok, x); cnt.template at<1>(a, ok, x); }
+            else cnt.template at<0>(s + a, ok, x);
+        }
+    }
+}
 
 template <int NT, int KIND, bool WIDE, int FORM>
 __global__ __launch_bounds__(NT) void k_hist_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
@@ -2200,102 +2313,7 @@ __global__ __launch_bounds__(NT) void k_hist_tiles(const BsigWorkItem *__restric
         const BsigWorkItem w = items[t];
         // (a tile listed apart for the wide launch: its cells are counted there, none here)
         if (!WIDE && (w.units_strand & BSIG_ITEM_HEAVY)) continue;
-        uint2 win[BSIG_MAX_CLASSES], clip;
-        PackedWin pk;
-        const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
-        const int nc = w.nc;
-        if constexpr (KIND == kHistCover) {
-            load_windows<false>(R, P, BSIG_MODE_COVERAGE, w, items, windows, win, t, pk, clip);
-            const int rend1 = w.loc + w.len - 1;
-            if constexpr (WIDE) {
-                const CoverWideOne one{P, reinterpret_cast<int32_t *>(img), w.loc, w.c0, nc, neg_range, rend1};
-                for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
-                if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
-            } else {
-                const CoverOne one{P, reinterpret_cast<int32_t *>(img), w.loc, w.c0, nc, 0, neg_range, rend1};
-                for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
-                if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
-            }
-            __syncthreads();
-            // k_coverage's scan: each lane owns 4 consecutive cells, wave scan of the lane totals, carry across waves
-            // and passes; the cells are counted instead of stored
-            const int nvec = (nc + 3) >> 2;
-            auto lo16 = [](uint32_t d) { return (int)(int16_t)(uint16_t)d; };
-            auto hi16 = [](uint32_t d) { return (int)(int16_t)(uint16_t)((d + 0x8000u) >> 16); };
-            int carry = 0;
-            for (int base = 0; base < nvec; base += NT) {
-                const int v = base + tid;
-                int4 x = make_int4(0, 0, 0, 0);
-                if (v < nvec) {
-                    if constexpr (WIDE) {
-                        int4 *p4 = reinterpret_cast<int4 *>(img) + v;
-                        x = *p4;
-                        *p4 = make_int4(0, 0, 0, 0);
-                    } else {
-                        uint2 *p2 = reinterpret_cast<uint2 *>(img) + v;
-                        const uint2 d = *p2;
-                        *p2 = make_uint2(0u, 0u);
-                        x = make_int4(lo16(d.x), hi16(d.x), lo16(d.y), hi16(d.y));
-                    }
-                }
-                x.y += x.x; x.z += x.y; x.w += x.z;
-                const int tot = x.w;
-                const int incl = wave_inclusive_scan(tot);
-                int pre = carry;
-                int all = __builtin_amdgcn_readlane(incl, kWave - 1);
-                if (NT > kWave) {
-                    if (lane == kWave - 1) wtot[tid / kWave] = incl;
-                    __syncthreads();
-                    all = 0;
-                    for (int k = 0; k < NT / kWave; ++k) {
-                        const int s = wtot[k];
-                        if (k < tid / kWave) pre += s;
-                        all += s;
-                    }
-                    __syncthreads();
-                }
-                const int add = pre + incl - tot;
-                const int c = 4 * v;
-                cnt((uint32_t)(x.x + add), c < nc);
-                cnt((uint32_t)(x.y + add), c + 1 < nc);
-                cnt((uint32_t)(x.z + add), c + 2 < nc);
-                cnt((uint32_t)(x.w + add), c + 3 < nc);
-                carry += all;
-            }
-        } else {
-            load_windows<false>(R, P, BSIG_MODE_PROFILE, w, items, windows, win, t, pk, clip);
-            if constexpr (WIDE) {
-                const XcorrWideOne one{P, img, w.loc, w.len, w.c0, nc, neg_range};
-                for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
-                if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
-            } else {
-                constexpr bool HALF = KIND == kHistEndsHalf;
-                const ProfileOne<true> one{P, img, w.loc, w.len, w.c0, nc, 0, neg_range};
-                for_each_read<NT, 2, HALF>(R, P, win, pk.base, ptab, tid, one);
-                if (!HALF && pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
-            }
-            __syncthreads();
-            const bool ss = P.ss != 0;                                  // (uniform)
-            for (int base = 0; base < nc; base += NT) {
-                const int x = base + tid;
-                const bool ok = x < nc;
-                uint32_t s = 0, a = 0;
-                if (ok) {
-                    if constexpr (WIDE) {
-                        uint2 *p2 = reinterpret_cast<uint2 *>(img) + x;
-                        const uint2 d = *p2;
-                        *p2 = make_uint2(0u, 0u);
-                        s = d.x; a = d.y;
-                    } else {
-                        const uint32_t d = img[x];
-                        img[x] = 0u;
-                        s = d & 0xFFFFu; a = d >> 16;
-                    }
-                }
-                if (ss) { cnt(s, ok); cnt(a, ok); }
-                else cnt(s + a, ok);
-            }
-        }
+        walk_tile_cells<NT, KIND, WIDE>(w, t, items, windows, R, P, img, wtot, ptab, tid, cnt);
         cnt.flush_zeros();
         __syncthreads();
     }
@@ -2311,6 +2329,156 @@ __global__ __launch_bounds__(NT) void k_hist_tiles(const BsigWorkItem *__restric
         if (blockIdx.x == 0 && tid == 0 && n_cells) atomicAdd(mo, n_cells);
         if (m_sum) atomicAdd(mo + 1, m_sum);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-range summaries (bsig_plan_create_summary)
+// ------------------------------------------------------------------------------------------
+// The first kind that reduces every range BY ITSELF: per (range, row) the sum of the per-base cells, their maximum, the
+// first cell that holds it, and the number of cells at or above each of K thresholds.  Tiles, images and the scan are the
+// depth histogram's (walk_tile_cells); the tile's work item carries the result row of its range (out_off = range x S).
+// Consumer.  A lane keeps per row a 64-bit sum, a 64-bit key value << 32 | (2^32 - 1 - cell) -- the largest key is the
+// largest value at the smallest cell, and a cell that exists has a key above 0 -- and one 32-bit counter per threshold.
+// The thresholds are kernel arguments and stay in SGPRs.  Counters per lane, not ballot + popcount: read off the ISA, a
+// counter costs v_cmp_le_u32 + v_addc_co_u32 a cell (two VALU), the ballot form v_cmp + s_bcnt1_i32_b64 + s_add_u32 with
+// the K x S running counts wave-uniform -- and these kernels already sit at the SGPR ceiling with dozens of SGPRs spilled
+// into VGPR lanes (the walk's windows and read columns), so every such count would live in a spill lane and pay a
+// v_readlane / v_writelane pair per cell step.  VGPRs are free here.  Thresholds past K are 2^32 - 1, and their counters
+// are never written out.
+// Combining.  A workgroup owns a run of consecutive tiles; a range's tiles are consecutive.  The lanes carry their
+// accumulators from tile to tile while the row is the same.  When it changes, or the run ends, the workgroup flushes:
+// shuffle reduction in the wave, lane 0 of every wave into 2 + K LDS qwords per row (ds_add_u64 / ds_max_u64), then one
+// 64-bit global atomic per non-zero qword into the range's row -- add for sum and counts, max for the key -- because a
+// range may straddle runs and the wide launch.  A whole-chromosome range costs 2 + K atomics per run per row.
+// Exactness.  A lane's counter grows by at most the cells of its run, which the plan keeps below 2^32 (summary_setup);
+// the plan proves every range's sum below 2^63.  k_summary_finish turns the key into max and summit.
+struct SummaryCells {
+    const BsigThresholds &T;
+    uint32_t c0 = 0;                                    // the tile's first cell in its range
+    unsigned long long sum[2] = {0ull, 0ull}, key[2] = {0ull, 0ull};
+    uint32_t cnt[2][BSIG_SUMMARY_MAX_THRESHOLDS] = {};
+    template <int ROW>
+    __device__ __forceinline__ void at(uint32_t v, bool ok, int x)
+    {
+        v = ok ? v : 0u;
+        sum[ROW] += v;
+        const unsigned long long k = ok ? ((unsigned long long)v << 32) | (0xFFFFFFFFu - (c0 + (uint32_t)x)) : 0ull;
+        key[ROW] = k > key[ROW] ? k : key[ROW];
+#pragma unroll
+        for (int j = 0; j < BSIG_SUMMARY_MAX_THRESHOLDS; ++j) cnt[ROW][j] += v >= T.t[j] ? 1u : 0u;
+    }
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            sum[r] = 0ull; key[r] = 0ull;
+#pragma unroll
+            for (int j = 0; j < BSIG_SUMMARY_MAX_THRESHOLDS; ++j) cnt[r][j] = 0u;
+        }
+    }
+};
+
+// LDS of one k_summary_tiles workgroup: the histogram kernel's, with the flush's qwords (kSummarySlots per row, two rows)
+// where its histogram is
+constexpr int kSummarySlots = 2 + BSIG_SUMMARY_MAX_THRESHOLDS;       // sum | key | counts
+__host__ __device__ inline HistLds summary_lds(int kind, bool wide, int tile_cells)
+{
+    return hist_lds(kind, wide, tile_cells, 2 * 2 * kSummarySlots);
+}
+
+template <int NT, int KIND, bool WIDE>
+__global__ __launch_bounds__(NT) void k_summary_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                      unsigned long long *__restrict__ out, const uint2 *__restrict__ windows,
+                                                      const BsigReadsDev R, const BsigKParams P, const BsigThresholds T)
+{
+    static_assert(!(WIDE && KIND == kHistEndsHalf), "a wide tile reads the packed words");
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const HistLds L = summary_lds(KIND, WIDE, P.tile_cells);
+    uint32_t *img = reinterpret_cast<uint32_t *>(lds) + L.img;
+    int32_t *wtot = lds + L.wtot;
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds + L.ptab);
+    unsigned long long *slot = reinterpret_cast<unsigned long long *>(lds + L.hist);      // (16-byte aligned: hist_lds)
+    for (int v = tid; v < L.ptab; v += NT) lds[v] = 0;
+    for (int v = tid; v < 2 * kSummarySlots; v += NT) slot[v] = 0ull;
+    if (KIND != kHistEndsHalf) build_ptab<NT>(ptab, R, P, tid);
+    const uint2 run = runs[blockIdx.x];
+    const int K = T.k;
+    const int S = KIND != kHistCover && P.ss ? 2 : 1;                 // (uniform)
+    const int stride = BSIG_SUMMARY_FIXED + K;                        // int64 per (range, row) of the result
+    SummaryCells cnt{T};
+    __syncthreads();
+
+    // the lanes' accumulators into result row `row0` (and row0 + 1 with strands), and cleared; uniform over the workgroup
+    // (the row is a compile-time index, so that the accumulators stay in registers)
+    auto flush_row = [&](auto row) {
+        constexpr int r = decltype(row)::value;
+        unsigned long long s = cnt.sum[r], k = cnt.key[r];
+        for (int m = kWave / 2; m >= 1; m /= 2) {
+            s += __shfl_xor(s, m);
+            const unsigned long long o = __shfl_xor(k, m);
+            k = o > k ? o : k;
+        }
+        if (lane == 0) {
+            if (s) atomicAdd(&slot[r * kSummarySlots], s);
+            atomicMax(&slot[r * kSummarySlots + 1], k);
+        }
+#pragma unroll
+        for (int j = 0; j < BSIG_SUMMARY_MAX_THRESHOLDS; ++j) {
+            if (j >= K) break;                                    // (uniform)
+            uint32_t c = cnt.cnt[r][j];
+            for (int m = kWave / 2; m >= 1; m /= 2) c += __shfl_xor(c, m);
+            if (lane == 0 && c) atomicAdd(&slot[r * kSummarySlots + 2 + j], (unsigned long long)c);
+        }
+    };
+    auto flush = [&](long long row0) {
+        flush_row(std::integral_constant<int, 0>{});
+        if constexpr (KIND != kHistCover) {
+            if (S == 2) flush_row(std::integral_constant<int, 1>{});
+        }
+        __syncthreads();
+        if (tid < 2 * kSummarySlots) {
+            const int r = tid / kSummarySlots, f = tid - r * kSummarySlots;
+            if (r < S && f < 2 + K) {
+                const unsigned long long v = slot[tid];
+                slot[tid] = 0ull;
+                unsigned long long *dst = out + (size_t)(row0 + r) * (size_t)stride + (f < 2 ? f : f + 1);
+                if (f == 1) { if (v) atomicMax(dst, v); }
+                else if (v) atomicAdd(dst, v);
+            }
+        }
+        __syncthreads();
+        cnt.clear();
+    };
+
+    long long cur = -1;
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        // (a tile listed apart for the wide launch: its cells are summed up there, none here)
+        if (!WIDE && (w.units_strand & BSIG_ITEM_HEAVY)) continue;
+        if (w.out_off != cur) {
+            if (cur >= 0) flush(cur);
+            cur = w.out_off;
+        }
+        cnt.c0 = (uint32_t)w.c0;
+        walk_tile_cells<NT, KIND, WIDE>(w, t, items, windows, R, P, img, wtot, ptab, tid, cnt);
+        __syncthreads();
+    }
+    if (cur >= 0) flush(cur);
+}
+
+// One thread per (range, row): the key at [1] becomes the maximum at [1] and the summit at [2] -- -1 where no cell was
+// seen (key 0: a range without width).  The rows already lie in the caller's order.
+__global__ __launch_bounds__(256) void k_summary_finish(long long *__restrict__ out, long long n_rows, int stride)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows) return;
+    long long *row = out + i * stride;
+    const unsigned long long key = (unsigned long long)row[1];
+    row[1] = (long long)(key >> 32);
+    row[2] = key ? (long long)(0xFFFFFFFFu - (uint32_t)key) : -1ll;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3133,6 +3301,63 @@ hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, 
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, n_cells);
         return hipGetLastError();
     });
+}
+
+// ---- per-range summaries -------------------------------------------------------------------------------------------
+size_t summary_tiles_lds(bool coverage, bool wide, int tile_cells)
+{
+    return (size_t)summary_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells).total * 4;
+}
+
+// one k_summary_tiles instantiation by its run-time choices (f receives the kernel's address)
+template <typename Fn>
+static hipError_t with_summary_kernel(int threads, bool coverage, bool half, bool wide, Fn &&f)
+{
+#define BSIG_SK(NT_) do { if (coverage) { if (wide) return f(k_summary_tiles<NT_, kHistCover, true>); return f(k_summary_tiles<NT_, kHistCover, false>); } \
+                          if (wide) return f(k_summary_tiles<NT_, kHistEnds, true>); \
+                          if (half) return f(k_summary_tiles<NT_, kHistEndsHalf, false>); \
+                          return f(k_summary_tiles<NT_, kHistEnds, false>); } while (0)
+    if (threads == 64) BSIG_SK(64);
+    if (threads == 128) BSIG_SK(128);
+    if (threads == 256) BSIG_SK(256);
+#undef BSIG_SK
+    return hipErrorInvalidValue;
+}
+
+int summary_blocks_per_cu(int threads, bool coverage, bool half, int tile_cells)
+{
+    int nb = 0;
+    const size_t lds = summary_tiles_lds(coverage, false, tile_cells);
+    const hipError_t e = with_summary_kernel(threads, coverage, half, false, [&](auto k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
+    });
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+hipError_t launch_summary_tiles(int threads, bool coverage, bool wide, const BsigReadsDev &R, const BsigKParams &P,
+                                const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                                bool resolve_first, const BsigThresholds &T, unsigned long long *out, hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE, items, (uint32_t)n_items,
+                           reinterpret_cast<BsigResolved *>(windows));
+    }
+    const size_t lds = summary_tiles_lds(coverage, wide, P.tile_cells);
+    return with_summary_kernel(threads, coverage, !wide && P.packed_half != 0, wide, [&](auto k) {
+        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, T);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hipStream_t st)
+{
+    if (n_rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_summary_finish, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, out, (long long)n_rows, stride);
+    return hipGetLastError();
 }
 
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)

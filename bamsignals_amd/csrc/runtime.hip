@@ -245,9 +245,10 @@ void block_cache_release()
 }  // namespace bsig
 
 namespace { enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 }; }      // launch_sum_tiles' kinds (kernels.h)
-// What a plan is: a plain one gives every range its own int32 cells; the others reduce all ranges to one short int64 vector.
+// What a plan is: a plain one gives every range its own int32 cells; sum, xcorr, frag and hist reduce all ranges to one short
+// int64 vector, a summary reduces every range by itself to a few int64.
 // The order is the one the wrong-kind refusals are worded by (wrong_kind).
-enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist };
+enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary };
 // per kind: the noun with its article, the device run call, the host run call, the bytes of a result cell
 struct KindRow { const char *a, *run_dev, *run_host; int cell_bytes; };
 static const KindRow kKinds[] = {
@@ -256,10 +257,11 @@ static const KindRow kKinds[] = {
     {"an xcorr", "bsig_plan_run_xcorr", "bsig_plan_run_xcorr_host", 8},
     {"a frag", "bsig_plan_run_frag", "bsig_plan_run_frag_host", 8},
     {"a hist", "bsig_plan_run_hist", "bsig_plan_run_hist_host", 8},
+    {"a summary", "bsig_plan_run_summary", "bsig_plan_run_summary_host", 8},
 };
 // A reduction plan's own (every kind but kPlain): the result's cells, the device buffer its _host call runs into, and the
 // tiles cut into runs (a workgroup each) -- the main tiles' runs, then the extra ones': a sum plan's heavy slices, an xcorr or
-// hist plan's wide tiles (32-bit image, one tile a run), none for a frag plan.  Beside them what only one kind has.
+// hist or summary plan's wide tiles (32-bit image, one tile a run), none for a frag plan.  Beside them what only one kind has.
 struct Reduced {
     int64_t cells = 0;
     int64_t *d_out = nullptr;           // device result of bsig_plan_run_<kind>_host, kept between calls
@@ -295,6 +297,12 @@ struct Reduced {
         int32_t max_value = 0;          // V: the overflow row
         int64_t n_cells = 0;            // moments[0]: the cells of all ranges
     } hist;
+    // summary (bsig_plan_create_summary): per-base tiles in genomic order, their out_off the range's first result row
+    struct {
+        bool coverage = false;          // the signal: coverage, else 5' ends
+        int S = 1;                      // rows per range
+        BsigThresholds thr{};           // the kernel's argument: K thresholds, the rest 2^32 - 1
+    } summary;
 };
 
 struct bsig_plan {
@@ -1523,7 +1531,42 @@ int bsig::hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out)
     return BSIG_OK;
 }
 
+// What only the per-range summaries ask, ahead of check_params: the depth histogram's parameter rule in their own words, and
+// K thresholds that rise from 1.
+int bsig::summary_shape(const bsig_params &prm, int32_t n_thresholds, const int32_t *thresholds, SummaryShape *out)
+{
+    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the range summary reduces per-base cells: bamCount has one cell per range");
+    if (prm.mode == BSIG_MODE_COVERAGE_EX)
+        return fail(BSIG_ERR_ARG, "the range summary of coverage is per base and unstranded: mode BSIG_MODE_COVERAGE");
+    if (prm.mode == BSIG_MODE_PROFILE && prm.binsize != 1) return fail(BSIG_ERR_ARG, "the range summary is per base: binsize must be 1");
+    if (prm.shift != 0) return fail(BSIG_ERR_ARG, "the range summary reduces unshifted positions: shift must be 0");
+    if (prm.mode == BSIG_MODE_COVERAGE && prm.ss != 0) return fail(BSIG_ERR_ARG, "the range summary of coverage has no strands: ss must be 0");
+    if (n_thresholds < 0 || n_thresholds > BSIG_SUMMARY_MAX_THRESHOLDS)
+        return fail(BSIG_ERR_ARG, "n_thresholds must be between 0 and %d", BSIG_SUMMARY_MAX_THRESHOLDS);
+    if (n_thresholds > 0 && !thresholds) return fail(BSIG_ERR_ARG, "thresholds is NULL");
+    for (int k = 0; k < n_thresholds; ++k) {
+        if (thresholds[k] < 1) return fail(BSIG_ERR_ARG, "thresholds must be at least 1 (%d given)", thresholds[k]);
+        if (k > 0 && thresholds[k] <= thresholds[k - 1]) return fail(BSIG_ERR_ARG, "thresholds must be strictly increasing");
+    }
+    if (prm.threads != 0 && prm.threads != 64 && prm.threads != 128 && prm.threads != 256)
+        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
+    if (prm.tile_cells != 0 && (prm.tile_cells < 16 || prm.tile_cells > 2048))
+        return fail(BSIG_ERR_ARG, "tile_cells must be between 16 and 2048");
+    SummaryShape s;
+    s.tiles = prm;
+    s.tiles.ss = prm.mode == BSIG_MODE_PROFILE && prm.ss != 0;
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.tiles.tile_cells = prm.tile_cells != 0 ? prm.tile_cells : 2048;
+    s.S = s.tiles.ss ? 2 : 1;
+    s.n_thresholds = n_thresholds;
+    for (int k = 0; k < BSIG_SUMMARY_MAX_THRESHOLDS; ++k) s.thresholds[k] = k < n_thresholds ? thresholds[k] : 0;
+    s.row = BSIG_SUMMARY_FIXED + n_thresholds;
+    *out = s;
+    return BSIG_OK;
+}
+
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells);
 static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &reads_of_tile);
 static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells);
@@ -1532,6 +1575,7 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
 // kXcorr: tiles of a body and an antisense halo, none of them cut into slices
 // kFrag: count tiles, none of them cut into slices (they have no image)
 // kHist: the mode's per-base tiles, none of them cut into slices
+// kSummary: the same tiles, each carrying its range's result row
 struct PlanRequest {
     PlanKind kind = kPlain;
     union {
@@ -1540,6 +1584,7 @@ struct PlanRequest {
         const bsig::XcorrShape *xcorr;
         const bsig::FragShape *frag;
         const bsig::HistShape *hist;
+        const bsig::SummaryShape *summary;
     };
 };
 // the reads in tile t's windows (win: BSIG_MAX_CLASSES index ranges a tile, k_resolve_tiles' output)
@@ -1594,6 +1639,9 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     if (rq.kind == kXcorr) P->tile_cells = (xbody + rq.xcorr->max_lag + 3) & ~3;
     // depth histogram: the caller's tile (16 .. 2,048 cells, checked by hist_shape), whatever the widest range
     if (rq.kind == kHist) P->tile_cells = (rq.hist->tiles.tile_cells + 3) & ~3;
+    if (rq.kind == kSummary) P->tile_cells = (rq.summary->tiles.tile_cells + 3) & ~3;
+    // a tile of these kinds is walked whole: a cell's value must be complete before it is counted or compared
+    const bool whole_tiles = rq.kind == kHist || rq.kind == kSummary;
     P->threads = r.threads;
     BsigKParams &K = P->kp;
     K.mapqual = prm->mapqual;
@@ -1715,7 +1763,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             for (int64_t c0 = 0; c0 < cells; c0 += P->tile_cells) {
                 w.c0 = (int32_t)c0;
                 w.nc = (int32_t)std::min<int64_t>(P->tile_cells, cells - c0);
-                w.out_off = P->off[i] + c0 * mult;
+                // (a summary tile writes no cell: it carries its range's first result row)
+                w.out_off = rq.kind == kSummary ? i * mult : P->off[i] + c0 * mult;
                 items.push_back(w);
             }
         }
@@ -1759,7 +1808,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         if (e == hipSuccess) e = hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         // the windows themselves are only fetched when there is something to slice (a frag plan cuts its runs by them)
-        if (e == hipSuccess && (n_heavy_dev || rq.kind == kFrag || rq.kind == kHist)) {
+        if (e == hipSuccess && (n_heavy_dev || rq.kind == kFrag || whole_tiles)) {
             win.resize(items.size() * BSIG_MAX_CLASSES);
             e = hipMemcpyAsync(win.data(), d_win, win.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1784,14 +1833,31 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
                                           "to %.3Lg): take fewer ranges per call", bound);
             }
         }
+        if (e == hipSuccess && rq.kind == kSummary) {
+            // The summaries' proof, range by range, that a sum stays below 2^63: the depth histogram's bound over the
+            // range's own tiles (they are consecutive, and out_off is the range's row)
+            for (size_t t = 0; t < items.size();) {
+                long double bound = 0;
+                size_t u = t;
+                for (; u < items.size() && items[u].out_off == items[t].out_off; ++u) {
+                    const int64_t total = tile_reads(win, u);
+                    bound += mode == BSIG_MODE_COVERAGE ? (long double)total * (long double)items[u].nc : (long double)total;
+                }
+                if (bound >= 9223372036854775808.0L) {
+                    return fail(BSIG_ERR_ARG, "the summed depth of range %lld could exceed 2^63 - 1 (the reads of its tiles add up "
+                                              "to %.3Lg): cut the range", (long long)(items[t].out_off / mult), bound);
+                }
+                t = u;
+            }
+        }
         if (e == hipSuccess && n_heavy_dev && rq.kind != kFrag) {
             for (size_t t = 0; t < items.size(); ++t) {
                 const int64_t total = tile_reads(win, t);
                 if (total <= heavy_reads) continue;
                 ++P->n_heavy_tiles;
-                if (rq.kind == kHist) {
-                    // a cell's value must be complete before it is counted: such a tile is walked whole, by one workgroup
-                    // of the second launch, into an image of 32-bit cells
+                if (whole_tiles) {
+                    // a cell's value must be complete before it is counted (and a max is not linear in slices of the
+                    // reads): such a tile is walked whole, by one workgroup of the second launch, into an image of 32-bit cells
                     hitems.push_back(items[t]);
                     items[t].units_strand |= BSIG_ITEM_HEAVY;
                     continue;
@@ -1857,12 +1923,13 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     case kXcorr: rc = xcorr_setup(P, *rq.xcorr, xbody, (int64_t)hitems.size(), widths); break;
     case kFrag: rc = frag_setup(P, *rq.frag, frag_reads); break;
     case kHist: rc = hist_setup(P, *rq.hist, items, (int64_t)hitems.size(), widths * mult); break;
+    case kSummary: rc = summary_setup(P, *rq.summary, items, (int64_t)hitems.size()); break;
     }
     if (rc != BSIG_OK) return rc;
     *out = owner.release();
     return BSIG_OK;
 }
-// ---- what the four *_setup functions share ------------------------------------------------------------------------
+// ---- what the five *_setup functions share ------------------------------------------------------------------------
 // the device's compute units and the LDS a workgroup may hold
 static int device_limits(const bsig_plan *P, int *n_cu, int *lds_max)
 {
@@ -2074,6 +2141,34 @@ static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vec
     return upload_runs(P, runs);
 }
 
+// The runs of a summary plan: cut as a hist plan's are.  A lane's 32-bit threshold counters grow by at most the cells its
+// workgroup walks between two flushes, so a run also ends where the cells of its tiles would pass the ceiling of 2^32 - 1
+// (a tile holds at most 2,048 cells): no counter wraps.  A run may hold many ranges (a flush at every change of range) or a
+// part of one (the rows are combined with 64-bit atomics).
+static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide)
+{
+    Reduced &R = *P->red;
+    auto &Q = R.summary;
+    Q.coverage = P->mode == BSIG_MODE_COVERAGE;
+    Q.S = shape.S;
+    R.cells = P->n_ranges * shape.S * shape.row;
+    Q.thr.k = shape.n_thresholds;
+    for (int k = 0; k < BSIG_SUMMARY_MAX_THRESHOLDS; ++k) Q.thr.t[k] = k < shape.n_thresholds ? (uint32_t)shape.thresholds[k] : 0xFFFFFFFFu;
+    int n_cu = 0, lds_max = 0;
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
+    const size_t lds = bsig::summary_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells);
+    if (lds > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "a tile of %d cells needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells, lds, lds_max);
+    const int64_t per = tiles_per_run(P, n_cu, bsig::summary_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, P->tile_cells),
+                                      1, "BAMSIGNALS_SUMMARY_RUN_TILES");
+    std::vector<uint2> runs;
+    cut_runs(P->n_items, per, kCounterMax, [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, runs);
+    R.n_runs_main = (int64_t)runs.size();
+    append_wide_runs(n_wide, runs);
+    R.n_runs_extra = n_wide;
+    return upload_runs(P, runs);
+}
+
 extern "C" {
 
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
@@ -2122,7 +2217,7 @@ static int wrong_kind(const bsig_plan *p, PlanKind want, bool host)
     if (p->kind > want) return fail(BSIG_ERR_ARG, "%s plan runs with %s", kKinds[p->kind].a, call);
     return fail(BSIG_ERR_ARG, "not %s plan: %s runs it", kKinds[want].a, call);
 }
-// What the four int64 device run calls do around their launches: the checks in the order every one of them made them, the
+// What the five int64 device run calls do around their launches: the checks in the order every one of them made them, the
 // plan's GPU made current, then body(the plan's Reduced, its stream) -- the launches -- and the run counted.
 template <typename Body>
 static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
@@ -2236,6 +2331,7 @@ int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernel
     case kXcorr: rc = bsig_plan_run_xcorr(p, Q->d_out); break;
     case kFrag: rc = bsig_plan_run_frag(p, Q->d_out); break;
     case kHist: rc = bsig_plan_run_hist(p, Q->d_out); break;
+    case kSummary: rc = bsig_plan_run_summary(p, Q->d_out); break;
     }
     if (rc != BSIG_OK) return rc;
     if (t_kernels) {
@@ -2372,6 +2468,20 @@ int bsig_plan_create_hist(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, con
     return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
+int bsig_plan_create_summary(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                             const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t n_thresholds,
+                             const int32_t *thresholds, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_summary");
+    *out = nullptr;
+    bsig::SummaryShape shape;
+    const int rc = bsig::summary_shape(*prm, n_thresholds, thresholds, &shape);
+    PlanRequest rq;
+    rq.kind = kSummary;
+    rq.summary = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
+}
+
 // a kind's queries answer 0 for a plan of another kind (and for no plan)
 static int64_t cells_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->cells : 0; }
 static int64_t runs_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->n_runs_main + p->red->n_runs_extra : 0; }
@@ -2381,6 +2491,8 @@ int64_t bsig_plan_frag_cells(const bsig_plan *p) { return cells_if(p, kFrag); }
 int64_t bsig_plan_frag_runs(const bsig_plan *p) { return runs_if(p, kFrag); }
 int64_t bsig_plan_hist_cells(const bsig_plan *p) { return cells_if(p, kHist); }
 int64_t bsig_plan_hist_runs(const bsig_plan *p) { return runs_if(p, kHist); }
+int64_t bsig_plan_summary_cells(const bsig_plan *p) { return cells_if(p, kSummary); }
+int64_t bsig_plan_summary_runs(const bsig_plan *p) { return runs_if(p, kSummary); }
 
 int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
@@ -2470,7 +2582,30 @@ int bsig_plan_run_hist(bsig_plan *p, int64_t *dev)
     });
 }
 
-// the four _host calls: the kind checked, then the one run into the plan's own device buffer and its download
+int bsig_plan_run_summary(bsig_plan *p, int64_t *dev)
+{
+    return run_reduced(p, kSummary, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.summary;
+        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
+        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+        if (R.n_runs_main) {
+            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+                return bsig::launch_summary_tiles(p->threads, Q.coverage, false, p->reads->dev, kp, p->items, p->n_items, R.runs,
+                                                  R.n_runs_main, resolved, lookup, Q.thr, out, st);
+            });
+            if (rc != BSIG_OK) return rc;
+        }
+        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
+        if (R.n_runs_extra)
+            HIP_TRY(bsig::launch_summary_tiles(p->threads, Q.coverage, true, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                               R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, Q.thr, out, st));
+        // every row's key into its max and summit (rows no tile wrote -- ranges without width -- get summit -1)
+        HIP_TRY(bsig::launch_summary_finish(p->n_ranges * Q.S, BSIG_SUMMARY_FIXED + Q.thr.k, reinterpret_cast<long long *>(dev), st));
+        return BSIG_OK;
+    });
+}
+
+// the five _host calls: the kind checked, then the one run into the plan's own device buffer and its download
 static int run_reduced_host(bsig_plan *p, PlanKind want, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
@@ -2481,6 +2616,7 @@ int bsig_plan_run_sum_host(bsig_plan *p, int64_t *sum_host) { return run_reduced
 int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kXcorr, host); }
 int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kFrag, host); }
 int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kHist, host); }
+int bsig_plan_run_summary_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kSummary, host); }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
 // The run-length encoder (runs.hip) of a plan's own layout: range i's cells off[i] .. off[i + 1] are one segment, or with

@@ -408,6 +408,29 @@ class HistPlan(_ReducedPlan):
         self.runs = int(self._lib.bsig_plan_hist_runs(self._h))
 
 
+class SummaryPlan(_ReducedPlan):
+    """Ranges + call parameters resident in HBM for the per-range summaries (bsig_plan_create_summary): each run gives
+    ``(n_ranges, S, 3 + K)`` int64 in the caller's range order -- per (range, row) the sum of the cells that ``Plan``
+    returns for the range under the same parameters, their max, the index of the first cell holding it (-1 for a range
+    without width), and the cells ``>= thresholds[k]``.  ``params``: as ``HistPlan``'s; S = 2 (sense, antisense) for
+    mode PROFILE with ss, else 1.  ``thresholds``: 0 .. 8 whole numbers rising from 1.  ``runs``: the runs of tiles (a
+    workgroup each) the plan was cut into.  ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit image."""
+
+    _KIND = "summary"
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, thresholds=()):
+        thr = np.ascontiguousarray(thresholds, dtype=np.int32).reshape(-1)
+        self._create(ctx, reads, rid, loc, length, strand, params, len(thr), _ptr(thr) if len(thr) else None)
+        self.thresholds = tuple(int(t) for t in thr)
+        self.n_ranges = len(_i32(length))
+        self.rows = 2 if params.mode == _lib.MODE_PROFILE and params.ss else 1
+        self.runs = int(self._lib.bsig_plan_summary_runs(self._h))
+
+    def run_host(self, out=None):
+        """Run and return the ``(n_ranges, S, 3 + K)`` int64 result in host memory (``out``: as the base class's)."""
+        return super().run_host(out).reshape(self.n_ranges, self.rows, _lib.SUMMARY_FIXED + len(self.thresholds))
+
+
 class RunEncoder:
     """Run-length encoder of int32 device buffers (bsig_runs_*): segment k is the ``length[k]`` cells
     ``src[base[k] + p * stride]``; ``stride`` 1, or 2 for one row of the interleaved ``2 * bin + antisense`` layout.

@@ -246,6 +246,38 @@ def coverage_hist(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1
     return out
 
 
+def _summary_call(fn, bampath, gr, tlen_filter, head, thresholds, rows, maxgap, device):
+    """the two file-level summary calls: ``head`` = the int32 arguments between the length filter and the thresholds"""
+    _check_gr(gr)
+    levels, codes, start, width, strand = gr.flatten()
+    thr = np.ascontiguousarray([int(t) for t in thresholds], dtype=np.int32)
+    k = min(len(thr), _lib.SUMMARY_MAX_THRESHOLDS)          # (more are refused by the call: the buffer need not hold them)
+    out = np.zeros((len(gr), rows, _lib.SUMMARY_FIXED + k), dtype=np.int64)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), *head,
+                  len(thr), thr.ctypes.data if len(thr) else None, int(maxgap), _dev(device), out.ctypes.data))
+    return out
+
+
+def pileup_summary(bampath, gr, tlen_filter, mapqual=0, ss=False, requiredF=0, filteredF=-1, pe_mid=False,
+                   thresholds=(), maxgap=16385, device=None):
+    """The per-range summaries of the 5' ends (bsig_pileup_summary): ``(n, S, 3 + K)`` int64 in the ranges' order, S = 2
+    (sense, antisense) with ``ss``; a row is [sum, max, summit, cells >= thresholds[0], ...]."""
+    head = (int(mapqual), int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)))
+    return _summary_call(_lib.load().bsig_pileup_summary, bampath, gr, tlen_filter, head, thresholds, 2 if ss else 1,
+                         maxgap, device)
+
+
+def coverage_summary(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False, thresholds=(),
+                     maxgap=16385, device=None):
+    """The per-range summaries of the per-base coverage (bsig_coverage_summary): ``(n, 1, 3 + K)`` int64, as
+    ``pileup_summary``."""
+    head = (int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)))
+    return _summary_call(_lib.load().bsig_coverage_summary, bampath, gr, tlen_filter, head, thresholds, 1, maxgap, device)
+
+
 def _take_runs(lib, handle, ss):
     """a bsig_runs_result handle -> RunSignals (the arrays are allocated once the handle says how large they are)"""
     try:

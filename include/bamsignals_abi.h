@@ -313,6 +313,41 @@ int64_t bsig_plan_hist_runs(const bsig_plan *plan);              /* runs of tile
 int bsig_plan_run_hist(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_hist_host(bsig_plan *plan, int64_t *host);
 
+/* Per-range summaries: what a set of peaks or capture targets is usually asked -- every peak's height, summit and reads,
+ * every target's mean depth and its bases at >= 1x / 10x / 20x / 30x -- without the per-base result.  The first kind that
+ * reduces every range BY ITSELF.  The signals and the parameter rule are the depth histogram's: mode BSIG_MODE_COVERAGE
+ * (S = 1 row per range; ss must be 0) and mode BSIG_MODE_PROFILE (5'-end counts, binsize 1, shift 0; ss = 0: S = 1, a cell
+ * is a base and its value the sum of both strands; ss = 1: S = 2, row 0 sense and row 1 antisense).  With K thresholds
+ * 1 <= t_1 < ... < t_K <= 2^31 - 1, 0 <= K <= BSIG_SUMMARY_MAX_THRESHOLDS, and cells the w cells of one row that
+ * bsig_plan_create's plan returns for the range under the same parameters (range orientation: a '-' range mirrored), every
+ * (range, row) receives BSIG_SUMMARY_FIXED + K int64:
+ *   [0]     sum of the cells
+ *   [1]     max of the cells
+ *   [2]     summit: the 0-based index of the FIRST cell that holds the max (ties go to the smallest index in range
+ *           orientation); an all-zero range gives (0, 0, 0), a range without width (0, 0, -1) and zero counts
+ *   [3 + k] #{cells >= t_(k+1)}
+ * The result is bsig_plan_summary_cells() = n_ranges * S * (BSIG_SUMMARY_FIXED + K) int64, row-major, in the CALLER'S range
+ * order.  Ranges may differ in width, overlap, repeat, overhang their reference (cells of an overhang are cells of value
+ * 0) or be empty.
+ * params: as for bsig_plan_create_hist (tile_cells 16 .. 2,048, 0: 2,048; threads 64 / 128 / 256, 0: 256); thresholds may be
+ * NULL only with n_thresholds == 0; anything else: BSIG_ERR_ARG.  No count wraps (a lane's 32-bit counters see fewer than
+ * 2^32 cells: the plan cuts its runs of tiles by their cells, bsig_plan_summary_runs() shows the cut; env
+ * BAMSIGNALS_SUMMARY_RUN_TILES, read when the plan is made, forces the tiles per run), and the plan proves for every range
+ * from the reads in its tiles' windows that its sum stays below 2^63, or bsig_plan_create_summary fails with BSIG_ERR_ARG
+ * and names the range.  bsig_plan_get_stats: cells as above, heavy_tiles = the tiles that took the 32-bit image (never cut
+ * into slices: a max is not linear in slices of the reads).  A summary plan runs with bsig_plan_run_summary* only, and no
+ * other plan does (BSIG_ERR_ARG). */
+#define BSIG_SUMMARY_FIXED 3
+#define BSIG_SUMMARY_MAX_THRESHOLDS 8
+int bsig_plan_create_summary(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                             const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t n_thresholds,
+                             const int32_t *thresholds, bsig_plan **plan);
+int64_t bsig_plan_summary_cells(const bsig_plan *plan);          /* n_ranges * S * (3 + K), 0 for any other plan and NULL */
+int64_t bsig_plan_summary_runs(const bsig_plan *plan);           /* runs of tiles, 0 for any other plan and NULL */
+/* asynchronous, on the context's stream; dev: bsig_plan_summary_cells() int64 on the device, 8-B aligned (zeroed by the call) */
+int bsig_plan_run_summary(bsig_plan *plan, int64_t *dev);
+int bsig_plan_run_summary_host(bsig_plan *plan, int64_t *host);
+
 /* Run-length encoding on the device: a per-range result as runs (value, length), the form of an Rle / a bedGraph.  The
  * encoder works on ANY int32 device buffer plus a table of segments: segment k is the len[k] cells
  * src[base[k] + p * stride], p = 0 .. len[k] - 1; stride 1, or 2 for one row of the 2 * bin + antisense layout (else
@@ -338,7 +373,8 @@ int bsig_runs_fetch(bsig_runs *runs, int64_t *seg_off, int32_t *values, int32_t 
 void bsig_runs_free(bsig_runs *runs);
 /* The encoder of a plan's own result layout (bsig_plan_offsets): n_seg = n_ranges * S segments, S = 2 with strands (segment
  * S * i + antisense, stride 2), else 1; encode what bsig_plan_run wrote.  For ordinary plans of mode BSIG_MODE_PROFILE,
- * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr, frag or hist plan fail with BSIG_ERR_ARG. */
+ * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr, frag, hist or summary plan fail
+ * with BSIG_ERR_ARG. */
 int bsig_plan_runs_create(const bsig_plan *plan, bsig_runs **runs);
 
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
@@ -524,6 +560,25 @@ int bsig_coverage_hist(const char *bampath, int64_t n_ranges, const int32_t *seq
                        const int32_t *tlen_filter, int32_t n_tlen_filter,
                        int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t max_value,
                        int32_t maxgap, int32_t device, int64_t *out);
+/* The per-range summaries (bsig_plan_create_summary): out receives n_ranges * S * (BSIG_SUMMARY_FIXED + n_thresholds) int64
+ * in the caller's range order.  bsig_pileup_summary: the 5' ends (ss 0 / 1: S = 1 / 2); bsig_coverage_summary: the per-base
+ * coverage (S = 1).  The thresholds and the parameters are checked before the BAM is opened or decoded.  With several GPUs
+ * each takes its block of the (rid, loc)-sorted ranges and the host PLACES each block's rows at the caller's indices --
+ * nothing is added (bsig_last_call_route(): "summary of N blocks of ranges, rows placed on the host"; one GPU: "summary"). */
+int bsig_pileup_summary(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                        int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                        const int32_t *width, const int32_t *strand,
+                        const int32_t *tlen_filter, int32_t n_tlen_filter,
+                        int32_t mapqual, int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid,
+                        int32_t n_thresholds, const int32_t *thresholds,
+                        int32_t maxgap, int32_t device, int64_t *out);
+int bsig_coverage_summary(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                          int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                          const int32_t *width, const int32_t *strand,
+                          const int32_t *tlen_filter, int32_t n_tlen_filter,
+                          int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                          int32_t n_thresholds, const int32_t *thresholds,
+                          int32_t maxgap, int32_t device, int64_t *out);
 /* The file-level calls with the result as RUNS (bsig_runs_*): bsig_pileup_core's / bsig_coverage_core_ex's arguments
  * without out / off; binsize <= 0 (bamCount) fails with BSIG_ERR_ARG, and all parameters are checked before the BAM is
  * opened.  The per-base cells live only in HBM, and only for one block of the (rid, loc)-sorted ranges at a time: a block
