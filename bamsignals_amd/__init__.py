@@ -5,7 +5,8 @@ User API (mirrors R/wrappers.R and R/zzzCountSignals.R of the reference):
 Beyond it: bamCrossCorr, the strand cross-correlation over ranges (the data's own value for ``shift``), and
 bamFragSizes, the fragment-length histogram over ranges (the data's own ``tlenFilter``); bamDepthHist, the histogram of
 the per-base depth over ranges (breadth at 20x, mean and median depth, the duplication histogram); bamSummary, every
-range's own sum, max, summit and breadth at thresholds (peak heights, per-target QC); RunSignals, what
+range's own sum, max, summit and breadth at thresholds (peak heights, per-target QC); bamScaled, every range cut into
+the same number of bins whatever its width (the heatmap matrix, metaprofiles over genes of unequal length); RunSignals, what
 bamProfile / bamCoverage return with ``runs=True``: the signals as runs, encoded on the GPU.
 Handle-level API for resident data and benchmarking: ``bamsignals_amd.device``.
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
@@ -18,9 +19,11 @@ from .depthhist import DepthHist, bamDepthHist  # noqa: F401
 from .fragsizes import FragSizes, bamFragSizes  # noqa: F401
 from .granges import GRanges  # noqa: F401
 from .runsignals import RunSignals  # noqa: F401
+from .scaled import ScaledSignals, bamScaled  # noqa: F401
 from .summary import RangeSummary, bamSummary  # noqa: F401
 from .wrappers import bamCount, bamCoverage, bamProfile, coverage_core, pileup_core  # noqa: F401
 
 __all__ = ["bamCount", "bamProfile", "bamCoverage", "bamCrossCorr", "CrossCorr", "bamFragSizes",
-           "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "CountSignals", "RunSignals", "GRanges", "BamFile",
+           "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "bamScaled", "ScaledSignals",
+           "CountSignals", "RunSignals", "GRanges", "BamFile",
            "writeSamAsBamAndIndex", "write_columns_as_bam", "pileup_core", "coverage_core"]

@@ -22,6 +22,8 @@ FRAG_MAX_ROWS = 16384
 HIST_MAX_ROWS, HIST_MOMENTS = 8192, 2
 # include/bamsignals_abi.h: BSIG_SUMMARY_FIXED, BSIG_SUMMARY_MAX_THRESHOLDS
 SUMMARY_FIXED, SUMMARY_MAX_THRESHOLDS = 3, 8
+# include/bamsignals_abi.h: BSIG_SCALED_MAX_BINS
+SCALED_MAX_BINS = 2048
 
 ERR_NAMES = {-1: "BSIG_ERR_ARG", -2: "BSIG_ERR_IO", -3: "BSIG_ERR_NOINDEX", -4: "BSIG_ERR_CHROM",
              -5: "BSIG_ERR_EXT", -6: "BSIG_ERR_DEVICE", -7: "BSIG_ERR_NOMEM", -8: "BSIG_ERR_FORMAT"}
@@ -131,6 +133,15 @@ def load():
         getattr(lib, f"bsig_plan_summary_{query}").restype = C.c_int64
     lib.bsig_plan_run_summary.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_summary_host.argtypes = [C.c_void_p, C.c_void_p]
+    # ... and the scaled plan: its own argument is the number of bins
+    lib.bsig_plan_create_scaled.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
+    for query in ("cells", "runs"):
+        getattr(lib, f"bsig_plan_scaled_{query}").argtypes = [C.c_void_p]
+        getattr(lib, f"bsig_plan_scaled_{query}").restype = C.c_int64
+    lib.bsig_plan_scaled_segmented.argtypes = [C.c_void_p]
+    lib.bsig_plan_scaled_segmented.restype = C.c_int32
+    lib.bsig_plan_run_scaled.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_run_scaled_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_runs_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.bsig_runs_n_seg.argtypes = [C.c_void_p]
     lib.bsig_runs_n_seg.restype = C.c_int64
@@ -182,6 +193,8 @@ def load():
     lib.bsig_coverage_hist.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
     lib.bsig_pileup_summary.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p]
     lib.bsig_coverage_summary.argtypes = core_head + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p]
+    lib.bsig_pileup_scaled.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
+    lib.bsig_coverage_scaled.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
     lib.bsig_pileup_runs.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
     lib.bsig_coverage_runs.argtypes = core_head + [C.c_int32] * 8 + [C.POINTER(C.c_void_p)]
     lib.bsig_runs_result_n_seg.argtypes = [C.c_void_p]

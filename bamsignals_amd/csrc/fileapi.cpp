@@ -681,12 +681,13 @@ int reduced_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t 
     return BSIG_OK;
 }
 
-// reduced_on_slots' sibling for the per-range summaries (bsig_pileup_summary / bsig_coverage_summary): a range's row is its
-// own, so several GPUs' results are not added.  Each takes a block of the (rid, loc)-sorted ranges, as reduced_on_slots deals
-// them, and the host PLACES the block's rows (`row` int64 per range: S * (3 + K)) at the caller's indices.
+// reduced_on_slots' sibling for the kinds that reduce every range by itself (the per-range summaries and the scaled regions:
+// bsig_*_summary, bsig_*_scaled; `what` names the kind in the route): a range's row is its own, so several GPUs' results are
+// not added.  Each takes a block of the (rid, loc)-sorted ranges, as reduced_on_slots deals them, and the host PLACES the
+// block's rows (`row` int64 per range: S * (3 + K), S * n_bins) at the caller's indices.
 int placed_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
                     const int32_t *width, const int32_t *strand, int64_t row, int64_t *out, double *X, std::string &route,
-                    const MakePlan &make_plan)
+                    const MakePlan &make_plan, const char *what)
 {
     const size_t nd = reads.size();
     if (nd == 1) {
@@ -696,7 +697,7 @@ int placed_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n
         X[3] = now_s() - t0;
         if (rc == BSIG_OK) rc = bsig::plan_run_reduced_to_host(plan, out, &X[4], &X[5]);
         if (plan) bsig_plan_free(plan);
-        route = "summary";
+        route = what;
         return rc;
     }
     std::vector<int64_t> order;
@@ -709,7 +710,12 @@ int placed_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n
             const int64_t j = order[(size_t)i];
             r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
         }
-        std::vector<int64_t> part((size_t)((b - a) * row));
+        std::vector<int64_t> part;
+        try {
+            part.resize((size_t)((b - a) * row));
+        } catch (const std::bad_alloc &) {
+            return fail(BSIG_ERR_NOMEM, "out of host memory for %lld result cells", (long long)((b - a) * row));
+        }
         bsig_plan *plan = nullptr;
         int rk = make_plan(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &plan);
         if (rk == BSIG_OK) rk = bsig::plan_run_reduced_to_host(plan, part.data());
@@ -720,7 +726,7 @@ int placed_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n
         return rk;
     });
     if (rc != BSIG_OK) return rc;
-    route = "summary of " + std::to_string(nd) + " blocks of ranges, rows placed on the host";
+    route = std::string(what) + " of " + std::to_string(nd) + " blocks of ranges, rows placed on the host";
     return BSIG_OK;
 }
 
@@ -855,7 +861,7 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
 // layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, or runs
-enum class Reduce { none, sum, xcorr, frag, hist, summary };
+enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled };
 struct FileDest {
     int32_t *out = nullptr;
     const int64_t *off = nullptr;
@@ -863,7 +869,7 @@ struct FileDest {
     Reduce kind = Reduce::none;
     int64_t *reduced = nullptr;     // the kind's cells: the sum's bins, max_lag + 1 + BSIG_XCORR_MOMENTS, tlen_filter[1] / len_bin + 1
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
-    int32_t arg = 0;                // xcorr: max_lag; frag: len_bin; hist: max_value; summary: the number of thresholds
+    int32_t arg = 0;                // xcorr: max_lag; frag: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins
     const int32_t *thresholds = nullptr;    // summary: arg of them
     bsig_runs_result *runs = nullptr;   // the per-range result as runs, in the caller's range order
     static FileDest reduce(Reduce kind, int64_t *cells, int32_t arg = 0)
@@ -885,9 +891,9 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     if (!to.off && !to.dst && !to.reduced && !to.runs) return fail(BSIG_ERR_ARG, "offsets missing");
     // a kind's own conditions, before any I/O; where it says so the plan's rule as well, before the BAM is opened
     int64_t cells = 0;              // of a reduction
-    int64_t row = 0;                // ... of one range of the per-range summaries
+    int64_t row = 0;                // ... of one range of the per-range summaries and the scaled regions
     MakePlan make_plan;
-    // (xcorr, frag, hist: the kind's create call with the kind's own argument in its place)
+    // (xcorr, frag, hist, scaled: the kind's create call with the kind's own argument in its place)
     auto with_arg = [&prm, arg = to.arg](auto create) -> MakePlan {
         return [&prm, arg, create](bsig_ctx *c, const bsig_reads *rd, int64_t m, const int32_t *r, const int32_t *l, const int32_t *w,
                                    const int32_t *s, bsig_plan **plan) { return create(c, rd, m, r, l, w, s, &prm, arg, plan); };
@@ -900,6 +906,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         bsig::FragShape frag{};
         bsig::HistShape hist{};
         bsig::SummaryShape summary{};
+        bsig::ScaledShape scaled{};
         switch (to.kind) {
         case Reduce::none:
             if (!to.runs) break;
@@ -937,6 +944,13 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
                                     const int32_t *s, bsig_plan **plan) {
                 return bsig_plan_create_summary(c, rd, m, r, l, w, s, &prm, to.arg, to.thresholds, plan);
             };
+            break;
+        case Reduce::scaled:
+            rc = bsig::scaled_shape(prm, to.arg, &scaled);
+            if (rc == BSIG_OK) rc = bsig::check_params(scaled.tiles, n, width, &early);
+            row = (int64_t)scaled.S * scaled.n_bins;
+            cells = n * row;
+            make_plan = with_arg(bsig_plan_create_scaled);
             break;
         }
         if (rc) return rc;
@@ -1234,8 +1248,9 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     std::string gather;
     for (int attempt = 0; attempt < 2; ++attempt) {
     if (attempt) drop_spare_device_memory(slots.get());        // (out of device memory: once more with the cache's spare memory given back)
-    if (to.kind == Reduce::summary) {
-        rc = placed_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, row, to.reduced, X, gather, make_plan);
+    if (to.kind == Reduce::summary || to.kind == Reduce::scaled) {
+        rc = placed_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, row, to.reduced, X, gather, make_plan,
+                             to.kind == Reduce::scaled ? "scaled" : "summary");
     } else if (to.reduced) {
         rc = reduced_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, cells, to.reduced, X, gather, make_plan);
     } else if (to.runs) {
@@ -1608,6 +1623,30 @@ int bsig_coverage_summary(const char *bampath, int64_t n, const int32_t *seq_cod
     to.thresholds = thresholds;
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
                       coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device, to);
+}
+
+int bsig_pileup_scaled(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                       const char *const *levels, const int32_t *start, const int32_t *width,
+                       const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid,
+                       int32_t n_bins, int32_t maxgap, int32_t device, int64_t *out)
+{
+    if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, ss != 0, requiredF, filteredF, pe_mid != 0), device,
+                      FileDest::reduce(Reduce::scaled, out, n_bins));
+}
+
+int bsig_coverage_scaled(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                         const char *const *levels, const int32_t *start, const int32_t *width,
+                         const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                         int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                         int32_t n_bins, int32_t maxgap, int32_t device, int64_t *out)
+{
+    if (!out) return fail(BSIG_ERR_ARG, "out is NULL");
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan), device,
+                      FileDest::reduce(Reduce::scaled, out, n_bins));
 }
 
 int bsig_pileup_runs(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,

@@ -120,6 +120,15 @@ hipError_t launch_summary_tiles(int threads, bool coverage, bool wide, const Bsi
                                 const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                                 bool resolve_first, const BsigThresholds &T, unsigned long long *out, hipStream_t st);
 hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hipStream_t st);
+// Scaled regions (bsig_plan_create_scaled).  k_scaled_tiles: runs, tiles and out_off (the range's first result row) as for
+// launch_summary_tiles; a row of out is n_bins int64, and every workgroup ADDS the cells of a tile into the bins
+// floor(c * n_bins / w) of its range's row(s): zero `out` first.  segmented: the wave sums the lanes of one bin before the
+// LDS add (16-bit images only; a wide launch ignores it).  wide / half / windows / resolve_first as in launch_hist_tiles.
+size_t scaled_tiles_lds(bool coverage, bool wide, int tile_cells, int rows, int n_bins);
+int scaled_blocks_per_cu(int threads, bool coverage, bool half, bool segmented, int tile_cells, int rows, int n_bins);
+hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segmented, const BsigReadsDev &R, const BsigKParams &P,
+                               const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                               bool resolve_first, int n_bins, unsigned long long *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

@@ -2482,6 +2482,161 @@ __global__ __launch_bounds__(256) void k_summary_finish(long long *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
+// Scaled regions (bsig_plan_create_scaled)
+// ------------------------------------------------------------------------------------------
+// Every range cut into the same number N of bins whatever its width w: cell c of the range (range orientation) belongs to
+// bin floor(c * N / w), and every (range, row) receives the N sums of its bins' cells.  Tiles, images, the scan and the
+// work item's result row (out_off = range x S) are the summaries' (walk_tile_cells); a result row is N int64.
+// Bin index.  No 64-bit division per cell.  Once per tile, uniform over the workgroup: c0 * N = q0 * w + r0 (one 64-bit
+// division, none for a range's first tile).  Cell x of the tile then lies in bin q0 + floor(u / w), u = r0 + x * N.  With
+// x < 2,048 and N <= 2,048, u < w + 2^22: it fits 32 bits unsigned, but not 31.  Two exact forms, chosen by the uniform w:
+//   w >= 2^23: u < 2 w, so the quotient is u >= w.
+//   w <  2^23: u < 2^24 is exact as a float, and so is w.  q' = trunc(float(u) * (1 / float(w))) with the reciprocal
+//     rounded to nearest (1 / w below is IEEE division) and the product rounded once: the relative error is below 2^-23 and
+//     the quotient below 1 + 2^22, so q' is floor(u / w) - 1, floor(u / w) or floor(u / w) + 1, and the remainder
+//     u - q' w, which fits 32 bits signed (q' w < 2^25), says which: one fix-up step down, one up.
+// The bin is clamped to N - 1, which an exact quotient never needs (c < w): no address depends on the arithmetic being right.
+// Accumulation.  S * N 64-bit accumulators in LDS.  Plain form: one ds_add_u64 per non-zero cell.  Within a call of `at`
+// lanes take ascending x, so the bins do not decrease across the wave and a bin is a contiguous run of lanes.  Segmented
+// form (SEG; 16-bit images only): a wave whose 64 cells lie in ONE bin -- where the plain form puts 64 lanes on one LDS
+// address; the 64 cells of a call are neighbours for 5' ends (the rule from w / N >= 64 on) and four apart for coverage,
+// where a lane owns four consecutive cells (w / N >= 256) -- adds them up with xor shuffles and issues one LDS add; any
+// other wave runs a segmented inclusive scan keyed on the bin (shuffle up by 1, 2, .. 32; a lane adds while the lane that
+// far below holds its bin) and the last lane of every bin adds the bin's sum.  The plan picks the form (runtime.hip: scaled_setup).
+// Combining.  As in k_summary_tiles: a workgroup carries its accumulators while out_off stays the same and flushes when it
+// changes and when the run ends, one 64-bit global atomic add per non-zero accumulator into out[row * N + j], because a
+// range may straddle runs and the wide launch.  The flush visits the bins [lo, hi] the tiles since the last flush touched:
+// an interval, since those tiles are neighbours in one range, and uniform over the workgroup.
+// Exactness.  Nothing is narrower than 64 bits but the segmented form's 32-bit wave sums: 64 cells of a 16-bit image, each
+// at most 2 * 65,535 (both strands of a 5'-end cell), stay below 2^23.  A wide tile takes the plain form.  The plan proves
+// every range's sum below 2^63 (the summaries' proof).
+template <bool SEG>
+struct ScaledCells {
+    unsigned long long *acc;            // LDS: S rows of N accumulators
+    uint32_t N;
+    int lane;
+    uint32_t w = 1u, q0 = 0u, r0 = 0u;  // the tile's range width; c0 * N = q0 * w + r0
+    float rcp = 1.f;                    // 1 / w
+    // once per tile, uniform
+    __device__ __forceinline__ void tile(const BsigWorkItem &t)
+    {
+        w = (uint32_t)t.len;
+        rcp = 1.0f / (float)w;
+        q0 = 0u; r0 = 0u;
+        if (t.c0 != 0) {
+            const unsigned long long p = (unsigned long long)(uint32_t)t.c0 * N;
+            q0 = (uint32_t)(p / w);
+            r0 = (uint32_t)(p - (unsigned long long)q0 * w);
+        }
+    }
+    __device__ __forceinline__ uint32_t bin(uint32_t x) const
+    {
+        const uint32_t u = r0 + x * N;
+        uint32_t q;
+        if (w >= (1u << 23)) {                                      // (uniform)
+            q = u >= w ? 1u : 0u;
+        } else {
+            q = (uint32_t)((float)u * rcp);
+            int32_t r = (int32_t)(u - q * w);
+            if (r < 0) { --q; r += (int32_t)w; }
+            if (r >= (int32_t)w) ++q;
+        }
+        const uint32_t b = q0 + q;
+        return b < N ? b : N - 1u;
+    }
+    template <int ROW>
+    __device__ __forceinline__ void at(uint32_t v, bool ok, int x)
+    {
+        if constexpr (!SEG) {
+            if (ok && v) atomicAdd(&acc[ROW * N + bin((uint32_t)x)], (unsigned long long)v);
+        } else {
+            // (all lanes of the wave are here: the loops around the call are uniform)
+            const uint32_t b = ok ? bin((uint32_t)x) : 0xFFFFFFFFu;
+            uint32_t s = ok ? v : 0u;
+            const uint32_t b_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+            const uint32_t b_last = (uint32_t)__builtin_amdgcn_readlane((int)b, kWave - 1);
+            if (b_first == b_last) {                                // (uniform) one bin, or no cell at all
+                if (b_first == 0xFFFFFFFFu) return;
+                for (int m = kWave / 2; m >= 1; m /= 2) s += __shfl_xor(s, m);
+                if (lane == 0 && s) atomicAdd(&acc[ROW * N + b], (unsigned long long)s);
+                return;
+            }
+#pragma unroll
+            for (int d = 1; d < kWave; d *= 2) {
+                const uint32_t os = __shfl_up(s, d), ob = __shfl_up(b, d);
+                if (lane >= d && ob == b) s += os;
+            }
+            const uint32_t nb = __shfl_down(b, 1);
+            if (ok && s && (lane == kWave - 1 || nb != b)) atomicAdd(&acc[ROW * N + b], (unsigned long long)s);
+        }
+    }
+};
+
+// LDS of one k_scaled_tiles workgroup: the histogram kernel's, with rows * n_bins qwords where its histogram is
+__host__ __device__ inline HistLds scaled_lds(int kind, bool wide, int tile_cells, int rows, int n_bins)
+{
+    return hist_lds(kind, wide, tile_cells, 2 * rows * n_bins);
+}
+
+template <int NT, int KIND, bool WIDE, bool SEG>
+__global__ __launch_bounds__(NT) void k_scaled_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                     unsigned long long *__restrict__ out, const uint2 *__restrict__ windows,
+                                                     const BsigReadsDev R, const BsigKParams P, const int n_bins)
+{
+    static_assert(!(WIDE && KIND == kHistEndsHalf), "a wide tile reads the packed words");
+    static_assert(!(WIDE && SEG), "the segmented form's wave sums are 32 bits wide: 16-bit images only");
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const int tid = threadIdx.x;
+    const int S = KIND != kHistCover && P.ss ? 2 : 1;                 // (uniform)
+    const HistLds L = scaled_lds(KIND, WIDE, P.tile_cells, S, n_bins);
+    uint32_t *img = reinterpret_cast<uint32_t *>(lds) + L.img;
+    int32_t *wtot = lds + L.wtot;
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds + L.ptab);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(lds + L.hist);       // (16-byte aligned: hist_lds)
+    for (int v = tid; v < L.ptab; v += NT) lds[v] = 0;
+    for (int v = tid; v < S * n_bins; v += NT) acc[v] = 0ull;
+    if (KIND != kHistEndsHalf) build_ptab<NT>(ptab, R, P, tid);
+    const uint2 run = runs[blockIdx.x];
+    ScaledCells<SEG> cnt{acc, (uint32_t)n_bins, tid & (kWave - 1)};
+    __syncthreads();
+
+    // the bins the tiles since the last flush touched (uniform), added into result row `row0` (and row0 + 1 with strands)
+    int lo = n_bins, hi = -1;
+    auto flush = [&](long long row0) {
+        for (int r = 0; r < S; ++r) {
+            for (int j = lo + tid; j <= hi; j += NT) {
+                const unsigned long long v = acc[r * n_bins + j];
+                if (v) {
+                    acc[r * n_bins + j] = 0ull;
+                    atomicAdd(out + (size_t)(row0 + r) * (size_t)n_bins + (size_t)j, v);
+                }
+            }
+        }
+        __syncthreads();
+        lo = n_bins; hi = -1;
+    };
+
+    long long cur = -1;
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        // (a tile listed apart for the wide launch: its cells are binned there, none here)
+        if (!WIDE && (w.units_strand & BSIG_ITEM_HEAVY)) continue;
+        if (w.out_off != cur) {
+            if (cur >= 0) flush(cur);
+            cur = w.out_off;
+        }
+        cnt.tile(w);
+        const int b0 = (int)(cnt.q0 < (uint32_t)n_bins ? cnt.q0 : (uint32_t)n_bins - 1u), b1 = (int)cnt.bin((uint32_t)(w.nc - 1));
+        lo = b0 < lo ? b0 : lo;
+        hi = b1 > hi ? b1 : hi;
+        walk_tile_cells<NT, KIND, WIDE>(w, t, items, windows, R, P, img, wtot, ptab, tid, cnt);
+        __syncthreads();
+    }
+    if (cur >= 0) flush(cur);
+}
+
+// ------------------------------------------------------------------------------------------
 // one-time layout of the reads in HBM
 // ------------------------------------------------------------------------------------------
 
@@ -3358,6 +3513,62 @@ hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hip
     if (n_rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_summary_finish, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, out, (long long)n_rows, stride);
     return hipGetLastError();
+}
+
+// ---- scaled regions ------------------------------------------------------------------------------------------------
+size_t scaled_tiles_lds(bool coverage, bool wide, int tile_cells, int rows, int n_bins)
+{
+    return (size_t)scaled_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells, rows, n_bins).total * 4;
+}
+
+// one k_scaled_tiles instantiation by its run-time choices (f receives the kernel's address)
+template <typename Fn>
+static hipError_t with_scaled_kernel(int threads, bool coverage, bool half, bool wide, bool seg, Fn &&f)
+{
+#define BSIG_SC(NT_) do { if (coverage) { if (wide) return f(k_scaled_tiles<NT_, kHistCover, true, false>); \
+                                          if (seg) return f(k_scaled_tiles<NT_, kHistCover, false, true>); \
+                                          return f(k_scaled_tiles<NT_, kHistCover, false, false>); } \
+                          if (wide) return f(k_scaled_tiles<NT_, kHistEnds, true, false>); \
+                          if (half) { if (seg) return f(k_scaled_tiles<NT_, kHistEndsHalf, false, true>); \
+                                      return f(k_scaled_tiles<NT_, kHistEndsHalf, false, false>); } \
+                          if (seg) return f(k_scaled_tiles<NT_, kHistEnds, false, true>); \
+                          return f(k_scaled_tiles<NT_, kHistEnds, false, false>); } while (0)
+    if (threads == 64) BSIG_SC(64);
+    if (threads == 128) BSIG_SC(128);
+    if (threads == 256) BSIG_SC(256);
+#undef BSIG_SC
+    return hipErrorInvalidValue;
+}
+
+int scaled_blocks_per_cu(int threads, bool coverage, bool half, bool segmented, int tile_cells, int rows, int n_bins)
+{
+    int nb = 0;
+    const size_t lds = scaled_tiles_lds(coverage, false, tile_cells, rows, n_bins);
+    const hipError_t e = with_scaled_kernel(threads, coverage, half, false, segmented, [&](auto k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
+    });
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segmented, const BsigReadsDev &R, const BsigKParams &P,
+                               const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                               bool resolve_first, int n_bins, unsigned long long *out, hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (n_bins < 1 || n_bins > BSIG_SCALED_MAX_BINS) return hipErrorInvalidValue;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE, items, (uint32_t)n_items,
+                           reinterpret_cast<BsigResolved *>(windows));
+    }
+    const int rows = !coverage && P.ss ? 2 : 1;
+    const size_t lds = scaled_tiles_lds(coverage, wide, P.tile_cells, rows, n_bins);
+    return with_scaled_kernel(threads, coverage, !wide && P.packed_half != 0, wide, !wide && segmented, [&](auto k) {
+        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_bins);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)

@@ -246,9 +246,9 @@ void block_cache_release()
 
 namespace { enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 }; }      // launch_sum_tiles' kinds (kernels.h)
 // What a plan is: a plain one gives every range its own int32 cells; sum, xcorr, frag and hist reduce all ranges to one short
-// int64 vector, a summary reduces every range by itself to a few int64.
+// int64 vector, a summary reduces every range by itself to a few int64, a scaled plan to n_bins int64.
 // The order is the one the wrong-kind refusals are worded by (wrong_kind).
-enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary };
+enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary, kScaled };
 // per kind: the noun with its article, the device run call, the host run call, the bytes of a result cell
 struct KindRow { const char *a, *run_dev, *run_host; int cell_bytes; };
 static const KindRow kKinds[] = {
@@ -258,10 +258,11 @@ static const KindRow kKinds[] = {
     {"a frag", "bsig_plan_run_frag", "bsig_plan_run_frag_host", 8},
     {"a hist", "bsig_plan_run_hist", "bsig_plan_run_hist_host", 8},
     {"a summary", "bsig_plan_run_summary", "bsig_plan_run_summary_host", 8},
+    {"a scaled", "bsig_plan_run_scaled", "bsig_plan_run_scaled_host", 8},
 };
 // A reduction plan's own (every kind but kPlain): the result's cells, the device buffer its _host call runs into, and the
 // tiles cut into runs (a workgroup each) -- the main tiles' runs, then the extra ones': a sum plan's heavy slices, an xcorr or
-// hist or summary plan's wide tiles (32-bit image, one tile a run), none for a frag plan.  Beside them what only one kind has.
+// hist, summary or scaled plan's wide tiles (32-bit image, one tile a run), none for a frag plan.  Beside them what only one kind has.
 struct Reduced {
     int64_t cells = 0;
     int64_t *d_out = nullptr;           // device result of bsig_plan_run_<kind>_host, kept between calls
@@ -303,6 +304,13 @@ struct Reduced {
         int S = 1;                      // rows per range
         BsigThresholds thr{};           // the kernel's argument: K thresholds, the rest 2^32 - 1
     } summary;
+    // scaled (bsig_plan_create_scaled): the summary plan's tiles; a result row is n_bins int64
+    struct {
+        bool coverage = false;          // the signal: coverage, else 5' ends
+        int S = 1;                      // rows per range
+        int32_t n_bins = 0;             // N
+        bool segmented = false;         // the wave sums the lanes of one bin before the LDS add (k_scaled_tiles)
+    } scaled;
 };
 
 struct bsig_plan {
@@ -1565,7 +1573,35 @@ int bsig::summary_shape(const bsig_params &prm, int32_t n_thresholds, const int3
     return BSIG_OK;
 }
 
+// What only the scaled regions ask, ahead of check_params: the depth histogram's parameter rule in their own words, and
+// 1 .. BSIG_SCALED_MAX_BINS bins.
+int bsig::scaled_shape(const bsig_params &prm, int32_t n_bins, ScaledShape *out)
+{
+    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the scaled regions bin per-base cells: bamCount has one cell per range");
+    if (prm.mode == BSIG_MODE_COVERAGE_EX)
+        return fail(BSIG_ERR_ARG, "the scaled regions of coverage are per base and unstranded: mode BSIG_MODE_COVERAGE");
+    if (prm.mode == BSIG_MODE_PROFILE && prm.binsize != 1)
+        return fail(BSIG_ERR_ARG, "the scaled regions cut per-base cells into n_bins bins: binsize must be 1");
+    if (prm.shift != 0) return fail(BSIG_ERR_ARG, "the scaled regions bin unshifted positions: shift must be 0");
+    if (prm.mode == BSIG_MODE_COVERAGE && prm.ss != 0) return fail(BSIG_ERR_ARG, "the scaled regions of coverage have no strands: ss must be 0");
+    if (n_bins < 1 || n_bins > BSIG_SCALED_MAX_BINS) return fail(BSIG_ERR_ARG, "n_bins must be between 1 and %d", BSIG_SCALED_MAX_BINS);
+    if (prm.threads != 0 && prm.threads != 64 && prm.threads != 128 && prm.threads != 256)
+        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
+    if (prm.tile_cells != 0 && (prm.tile_cells < 16 || prm.tile_cells > 2048))
+        return fail(BSIG_ERR_ARG, "tile_cells must be between 16 and 2048");
+    ScaledShape s;
+    s.tiles = prm;
+    s.tiles.ss = prm.mode == BSIG_MODE_PROFILE && prm.ss != 0;
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.tiles.tile_cells = prm.tile_cells != 0 ? prm.tile_cells : 2048;
+    s.S = s.tiles.ss ? 2 : 1;
+    s.n_bins = n_bins;
+    *out = s;
+    return BSIG_OK;
+}
+
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+static int scaled_setup(bsig_plan *P, const bsig::ScaledShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells);
 static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &reads_of_tile);
@@ -1575,7 +1611,7 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
 // kXcorr: tiles of a body and an antisense halo, none of them cut into slices
 // kFrag: count tiles, none of them cut into slices (they have no image)
 // kHist: the mode's per-base tiles, none of them cut into slices
-// kSummary: the same tiles, each carrying its range's result row
+// kSummary, kScaled: the same tiles, each carrying its range's result row
 struct PlanRequest {
     PlanKind kind = kPlain;
     union {
@@ -1585,6 +1621,7 @@ struct PlanRequest {
         const bsig::FragShape *frag;
         const bsig::HistShape *hist;
         const bsig::SummaryShape *summary;
+        const bsig::ScaledShape *scaled;
     };
 };
 // the reads in tile t's windows (win: BSIG_MAX_CLASSES index ranges a tile, k_resolve_tiles' output)
@@ -1640,8 +1677,11 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     // depth histogram: the caller's tile (16 .. 2,048 cells, checked by hist_shape), whatever the widest range
     if (rq.kind == kHist) P->tile_cells = (rq.hist->tiles.tile_cells + 3) & ~3;
     if (rq.kind == kSummary) P->tile_cells = (rq.summary->tiles.tile_cells + 3) & ~3;
+    if (rq.kind == kScaled) P->tile_cells = (rq.scaled->tiles.tile_cells + 3) & ~3;
+    // a summary or scaled tile writes no cell: it carries its range's first result row
+    const bool row_tiles = rq.kind == kSummary || rq.kind == kScaled;
     // a tile of these kinds is walked whole: a cell's value must be complete before it is counted or compared
-    const bool whole_tiles = rq.kind == kHist || rq.kind == kSummary;
+    const bool whole_tiles = rq.kind == kHist || row_tiles;
     P->threads = r.threads;
     BsigKParams &K = P->kp;
     K.mapqual = prm->mapqual;
@@ -1763,8 +1803,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
             for (int64_t c0 = 0; c0 < cells; c0 += P->tile_cells) {
                 w.c0 = (int32_t)c0;
                 w.nc = (int32_t)std::min<int64_t>(P->tile_cells, cells - c0);
-                // (a summary tile writes no cell: it carries its range's first result row)
-                w.out_off = rq.kind == kSummary ? i * mult : P->off[i] + c0 * mult;
+                w.out_off = row_tiles ? i * mult : P->off[i] + c0 * mult;
                 items.push_back(w);
             }
         }
@@ -1833,7 +1872,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
                                           "to %.3Lg): take fewer ranges per call", bound);
             }
         }
-        if (e == hipSuccess && rq.kind == kSummary) {
+        if (e == hipSuccess && row_tiles) {
             // The summaries' proof, range by range, that a sum stays below 2^63: the depth histogram's bound over the
             // range's own tiles (they are consecutive, and out_off is the range's row)
             for (size_t t = 0; t < items.size();) {
@@ -1924,12 +1963,13 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     case kFrag: rc = frag_setup(P, *rq.frag, frag_reads); break;
     case kHist: rc = hist_setup(P, *rq.hist, items, (int64_t)hitems.size(), widths * mult); break;
     case kSummary: rc = summary_setup(P, *rq.summary, items, (int64_t)hitems.size()); break;
+    case kScaled: rc = scaled_setup(P, *rq.scaled, items, (int64_t)hitems.size()); break;
     }
     if (rc != BSIG_OK) return rc;
     *out = owner.release();
     return BSIG_OK;
 }
-// ---- what the five *_setup functions share ------------------------------------------------------------------------
+// ---- what the six *_setup functions share ------------------------------------------------------------------------
 // the device's compute units and the LDS a workgroup may hold
 static int device_limits(const bsig_plan *P, int *n_cu, int *lds_max)
 {
@@ -2169,6 +2209,46 @@ static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const st
     return upload_runs(P, runs);
 }
 
+// The runs of a scaled plan: cut as a summary plan's are.  Its accumulators are 64 bits wide everywhere, so nothing but the
+// shared cutter's ceiling bounds a run.  A workgroup holds S * N qwords of LDS beside its image.  The segmented consumer is
+// chosen per plan: for coverage whose cells lie mostly in ranges with bins of 256 cells or more -- in the coverage walk a
+// lane owns four consecutive cells, so one wave step spans 256 cells, and from that bin size on most steps lie inside one
+// bin and take the segmented form's short path -- the one shape class where it measured faster than the plain form
+// ("Scaled regions"); narrower bins put every wave on the twelve-shuffle scan, and 5' ends are mostly zeros,
+// which the plain form skips.  bsig_plan_scaled_segmented() says which form a plan took.  Env
+// BAMSIGNALS_SCALED_SEGMENTED (0 / 1, read when the plan is made) forces either form.
+static int scaled_setup(bsig_plan *P, const bsig::ScaledShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide)
+{
+    Reduced &R = *P->red;
+    auto &Q = R.scaled;
+    Q.coverage = P->mode == BSIG_MODE_COVERAGE;
+    Q.S = shape.S;
+    Q.n_bins = shape.n_bins;
+    R.cells = P->n_ranges * shape.S * shape.n_bins;
+    int64_t cells = 0, wide_cells = 0;
+    for (const BsigWorkItem &w : items) {
+        cells += w.nc;
+        if ((int64_t)w.len >= 256ll * shape.n_bins) wide_cells += w.nc;
+    }
+    Q.segmented = Q.coverage && 2 * wide_cells > cells;
+    if (const char *v = getenv("BAMSIGNALS_SCALED_SEGMENTED")) Q.segmented = atoi(v) != 0;
+    int n_cu = 0, lds_max = 0;
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
+    const size_t lds = bsig::scaled_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells, Q.S, Q.n_bins);
+    if (lds > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "a tile of %d cells and %d bins need %zu bytes of LDS per workgroup, the device has %d", P->tile_cells,
+                    Q.n_bins, lds, lds_max);
+    const int64_t per = tiles_per_run(P, n_cu, bsig::scaled_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, Q.segmented,
+                                                                           P->tile_cells, Q.S, Q.n_bins),
+                                      1, "BAMSIGNALS_SCALED_RUN_TILES");
+    std::vector<uint2> runs;
+    cut_runs(P->n_items, per, kCounterMax, [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, runs);
+    R.n_runs_main = (int64_t)runs.size();
+    append_wide_runs(n_wide, runs);
+    R.n_runs_extra = n_wide;
+    return upload_runs(P, runs);
+}
+
 extern "C" {
 
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
@@ -2217,7 +2297,7 @@ static int wrong_kind(const bsig_plan *p, PlanKind want, bool host)
     if (p->kind > want) return fail(BSIG_ERR_ARG, "%s plan runs with %s", kKinds[p->kind].a, call);
     return fail(BSIG_ERR_ARG, "not %s plan: %s runs it", kKinds[want].a, call);
 }
-// What the five int64 device run calls do around their launches: the checks in the order every one of them made them, the
+// What the six int64 device run calls do around their launches: the checks in the order every one of them made them, the
 // plan's GPU made current, then body(the plan's Reduced, its stream) -- the launches -- and the run counted.
 template <typename Body>
 static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
@@ -2332,6 +2412,7 @@ int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernel
     case kFrag: rc = bsig_plan_run_frag(p, Q->d_out); break;
     case kHist: rc = bsig_plan_run_hist(p, Q->d_out); break;
     case kSummary: rc = bsig_plan_run_summary(p, Q->d_out); break;
+    case kScaled: rc = bsig_plan_run_scaled(p, Q->d_out); break;
     }
     if (rc != BSIG_OK) return rc;
     if (t_kernels) {
@@ -2482,6 +2563,19 @@ int bsig_plan_create_summary(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, 
     return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
+int bsig_plan_create_scaled(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                            const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t n_bins, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_scaled");
+    *out = nullptr;
+    bsig::ScaledShape shape;
+    const int rc = bsig::scaled_shape(*prm, n_bins, &shape);
+    PlanRequest rq;
+    rq.kind = kScaled;
+    rq.scaled = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
+}
+
 // a kind's queries answer 0 for a plan of another kind (and for no plan)
 static int64_t cells_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->cells : 0; }
 static int64_t runs_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->n_runs_main + p->red->n_runs_extra : 0; }
@@ -2493,6 +2587,9 @@ int64_t bsig_plan_hist_cells(const bsig_plan *p) { return cells_if(p, kHist); }
 int64_t bsig_plan_hist_runs(const bsig_plan *p) { return runs_if(p, kHist); }
 int64_t bsig_plan_summary_cells(const bsig_plan *p) { return cells_if(p, kSummary); }
 int64_t bsig_plan_summary_runs(const bsig_plan *p) { return runs_if(p, kSummary); }
+int64_t bsig_plan_scaled_cells(const bsig_plan *p) { return cells_if(p, kScaled); }
+int64_t bsig_plan_scaled_runs(const bsig_plan *p) { return runs_if(p, kScaled); }
+int32_t bsig_plan_scaled_segmented(const bsig_plan *p) { return p && p->kind == kScaled && p->red->scaled.segmented ? 1 : 0; }
 
 int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
@@ -2605,7 +2702,28 @@ int bsig_plan_run_summary(bsig_plan *p, int64_t *dev)
     });
 }
 
-// the five _host calls: the kind checked, then the one run into the plan's own device buffer and its download
+int bsig_plan_run_scaled(bsig_plan *p, int64_t *dev)
+{
+    return run_reduced(p, kScaled, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.scaled;
+        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
+        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+        if (R.n_runs_main) {
+            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+                return bsig::launch_scaled_tiles(p->threads, Q.coverage, false, Q.segmented, p->reads->dev, kp, p->items, p->n_items,
+                                                 R.runs, R.n_runs_main, resolved, lookup, Q.n_bins, out, st);
+            });
+            if (rc != BSIG_OK) return rc;
+        }
+        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
+        if (R.n_runs_extra)
+            HIP_TRY(bsig::launch_scaled_tiles(p->threads, Q.coverage, true, false, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
+                                              R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, Q.n_bins, out, st));
+        return BSIG_OK;
+    });
+}
+
+// the six _host calls: the kind checked, then the one run into the plan's own device buffer and its download
 static int run_reduced_host(bsig_plan *p, PlanKind want, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
@@ -2617,6 +2735,7 @@ int bsig_plan_run_xcorr_host(bsig_plan *p, int64_t *host) { return run_reduced_h
 int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kFrag, host); }
 int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kHist, host); }
 int bsig_plan_run_summary_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kSummary, host); }
+int bsig_plan_run_scaled_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kScaled, host); }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
 // The run-length encoder (runs.hip) of a plan's own layout: range i's cells off[i] .. off[i + 1] are one segment, or with

@@ -232,7 +232,7 @@ int download_slices_to_dest(bsig_ctx *ctx, const int32_t *src_dev, int64_t n_sli
 // the copy is only enqueued.  With timers the kernels are waited for first and the two stages timed apart; without them
 // nothing waits between kernels and download.  The caller has checked that p is a plain plan (runtime.hip)
 int plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async = false, double *t_kernels = nullptr, double *t_download = nullptr);
-// ... and a reduction plan's (sum, xcorr, frag, hist, summary): its kind's device run call into the plan's own int64 buffer (made
+// ... and a reduction plan's (sum, xcorr, frag, hist, summary, scaled): its kind's device run call into the plan's own int64 buffer (made
 // at the first call), then the download; timed as above.  A sum plan without cells has nothing to run
 int plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // bsig_params as every entry point reads them (runtime.hip: check_params)
@@ -291,6 +291,14 @@ struct SummaryShape {
     int32_t row;            // int64 per (range, row): BSIG_SUMMARY_FIXED + n_thresholds
 };
 int summary_shape(const bsig_params &prm, int32_t n_thresholds, const int32_t *thresholds, SummaryShape *out);
+// what only the scaled regions ask, ahead of check_params (runtime.hip: scaled_shape): the depth histogram's parameter rule,
+// and 1 .. BSIG_SCALED_MAX_BINS bins
+struct ScaledShape {
+    bsig_params tiles;      // the per-base plan the tiles are piled up by (threads and tile_cells resolved)
+    int S;                  // rows per range: 2 for 5' ends with strands
+    int32_t n_bins;         // N: int64 per (range, row)
+};
+int scaled_shape(const bsig_params &prm, int32_t n_bins, ScaledShape *out);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

@@ -431,6 +431,30 @@ class SummaryPlan(_ReducedPlan):
         return super().run_host(out).reshape(self.n_ranges, self.rows, _lib.SUMMARY_FIXED + len(self.thresholds))
 
 
+class ScaledPlan(_ReducedPlan):
+    """Ranges + call parameters resident in HBM for the scaled regions (bsig_plan_create_scaled): each run gives
+    ``(n_ranges, S, n_bins)`` int64 in the caller's range order -- every range cut into ``n_bins`` bins whatever its
+    width ``w``: cell ``c`` of the cells that ``Plan`` returns for the range under the same parameters is added to bin
+    ``c * n_bins // w``.  ``params``: as ``HistPlan``'s; S = 2 (sense, antisense) for mode PROFILE with ss, else 1.
+    ``n_bins``: 1 .. 2,048.  ``runs``: the runs of tiles (a workgroup each) the plan was cut into.  ``segmented``:
+    whether the plan took the segmented consumer (bsig_plan_scaled_segmented; the result does not depend on it).
+    ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit image."""
+
+    _KIND = "scaled"
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, n_bins):
+        self._create(ctx, reads, rid, loc, length, strand, params, int(n_bins))
+        self.n_bins = int(n_bins)
+        self.n_ranges = len(_i32(length))
+        self.rows = 2 if params.mode == _lib.MODE_PROFILE and params.ss else 1
+        self.runs = int(self._lib.bsig_plan_scaled_runs(self._h))
+        self.segmented = bool(self._lib.bsig_plan_scaled_segmented(self._h))
+
+    def run_host(self, out=None):
+        """Run and return the ``(n_ranges, S, n_bins)`` int64 result in host memory (``out``: as the base class's)."""
+        return super().run_host(out).reshape(self.n_ranges, self.rows, self.n_bins)
+
+
 class RunEncoder:
     """Run-length encoder of int32 device buffers (bsig_runs_*): segment k is the ``length[k]`` cells
     ``src[base[k] + p * stride]``; ``stride`` 1, or 2 for one row of the interleaved ``2 * bin + antisense`` layout.

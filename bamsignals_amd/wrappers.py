@@ -278,6 +278,37 @@ def coverage_summary(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF
     return _summary_call(_lib.load().bsig_coverage_summary, bampath, gr, tlen_filter, head, thresholds, 1, maxgap, device)
 
 
+def _scaled_call(fn, bampath, gr, tlen_filter, head, n_bins, rows, maxgap, device):
+    """the two file-level scaled-region calls: ``head`` = the int32 arguments between the length filter and n_bins"""
+    _check_gr(gr)
+    levels, codes, start, width, strand = gr.flatten()
+    n_bins = int(n_bins)
+    # (a number of bins the call refuses: the buffer need not hold them)
+    out = np.zeros((len(gr), rows, n_bins if 1 <= n_bins <= _lib.SCALED_MAX_BINS else 1), dtype=np.int64)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), *head,
+                  n_bins, int(maxgap), _dev(device), out.ctypes.data))
+    return out
+
+
+def pileup_scaled(bampath, gr, tlen_filter, mapqual=0, ss=False, requiredF=0, filteredF=-1, pe_mid=False,
+                  n_bins=100, maxgap=16385, device=None):
+    """The scaled regions of the 5' ends (bsig_pileup_scaled): ``(n, S, n_bins)`` int64 in the ranges' order, S = 2
+    (sense, antisense) with ``ss``; bin ``c * n_bins // w`` holds cell ``c`` of a range of width ``w``."""
+    head = (int(mapqual), int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)))
+    return _scaled_call(_lib.load().bsig_pileup_scaled, bampath, gr, tlen_filter, head, n_bins, 2 if ss else 1, maxgap, device)
+
+
+def coverage_scaled(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False, n_bins=100,
+                    maxgap=16385, device=None):
+    """The scaled regions of the per-base coverage (bsig_coverage_scaled): ``(n, 1, n_bins)`` int64, as
+    ``pileup_scaled``."""
+    head = (int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)))
+    return _scaled_call(_lib.load().bsig_coverage_scaled, bampath, gr, tlen_filter, head, n_bins, 1, maxgap, device)
+
+
 def _take_runs(lib, handle, ss):
     """a bsig_runs_result handle -> RunSignals (the arrays are allocated once the handle says how large they are)"""
     try:

@@ -348,6 +348,42 @@ int64_t bsig_plan_summary_runs(const bsig_plan *plan);           /* runs of tile
 int bsig_plan_run_summary(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_summary_host(bsig_plan *plan, int64_t *host);
 
+/* Scaled regions: every range cut into the SAME number of bins whatever its width -- the heatmap ("scale-regions") matrix
+ * with one row per gene and N columns from TSS to TES, and the metaprofile over ranges of unequal width.  The signals and
+ * the parameter rule are the depth histogram's and the range summary's: mode BSIG_MODE_COVERAGE (S = 1 row per range; ss
+ * must be 0) and mode BSIG_MODE_PROFILE (5'-end counts, binsize 1, shift 0; ss = 0: S = 1, a cell is a base and its value
+ * the sum of both strands; ss = 1: S = 2, row 0 sense and row 1 antisense).  With 1 <= N = n_bins <= BSIG_SCALED_MAX_BINS
+ * and cells c = 0 .. w - 1 the w cells of one row that bsig_plan_create's plan returns for the range under the same
+ * parameters (range orientation: a '-' range mirrored), cell c belongs to bin floor(c * N / w) (a 64-bit product), so that
+ * bin j owns the cells [ceil(j * w / N), ceil((j + 1) * w / N)): floor(w / N) or ceil(w / N) of them, none for some bins
+ * when w < N.  Every (range, row) receives N int64, the sums of the cells of each bin; a range without width N zeros.
+ * The result is bsig_plan_scaled_cells() = n_ranges * S * N int64, row-major (n_ranges, S, N), in the CALLER'S range order.
+ * Ranges may differ in width, overlap, repeat, overhang their reference (cells of an overhang are cells of value 0) or be
+ * empty.
+ * params: as for bsig_plan_create_hist (tile_cells 16 .. 2,048, 0: 2,048; threads 64 / 128 / 256, 0: 256); anything else:
+ * BSIG_ERR_ARG.  A workgroup keeps S * N 64-bit bin accumulators in LDS: 8 * S * N bytes, 32 KiB at S = 2 and
+ * N = BSIG_SCALED_MAX_BINS, beside the widest image of 16 KiB.  Nothing is narrower than 64 bits, and the plan proves for
+ * every range from the reads in its tiles' windows that its sum stays below 2^63, or bsig_plan_create_scaled fails with
+ * BSIG_ERR_ARG and names the range.  bsig_plan_scaled_runs() shows how the tiles were cut into runs (env
+ * BAMSIGNALS_SCALED_RUN_TILES, read when the plan is made, forces the tiles per run).  bsig_plan_get_stats: cells as above,
+ * visits those of the ordinary plan with the same mode, parameters and tile_cells, heavy_tiles = the tiles that took the
+ * 32-bit image (walked whole in a second launch, as for hist and summary).  A scaled plan runs with bsig_plan_run_scaled*
+ * only, and no other plan does (BSIG_ERR_ARG). */
+#define BSIG_SCALED_MAX_BINS 2048
+int bsig_plan_create_scaled(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                            const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t n_bins,
+                            bsig_plan **plan);
+int64_t bsig_plan_scaled_cells(const bsig_plan *plan);           /* n_ranges * S * N, 0 for any other plan and NULL */
+int64_t bsig_plan_scaled_runs(const bsig_plan *plan);            /* runs of tiles, 0 for any other plan and NULL */
+/* 1 if the plan's main launch sums the lanes of one bin in the wave before the LDS add (the segmented consumer: chosen when
+ * the plan is made, for coverage whose cells lie mostly in ranges of width >= 256 * n_bins; env BAMSIGNALS_SCALED_SEGMENTED
+ * = 0 / 1, read then, forces either form), 0 for the plain consumer, for any other plan and for NULL.  Both give the same
+ * integers. */
+int32_t bsig_plan_scaled_segmented(const bsig_plan *plan);
+/* asynchronous, on the context's stream; dev: bsig_plan_scaled_cells() int64 on the device, 8-B aligned (zeroed by the call) */
+int bsig_plan_run_scaled(bsig_plan *plan, int64_t *dev);
+int bsig_plan_run_scaled_host(bsig_plan *plan, int64_t *host);
+
 /* Run-length encoding on the device: a per-range result as runs (value, length), the form of an Rle / a bedGraph.  The
  * encoder works on ANY int32 device buffer plus a table of segments: segment k is the len[k] cells
  * src[base[k] + p * stride], p = 0 .. len[k] - 1; stride 1, or 2 for one row of the 2 * bin + antisense layout (else
@@ -373,8 +409,8 @@ int bsig_runs_fetch(bsig_runs *runs, int64_t *seg_off, int32_t *values, int32_t 
 void bsig_runs_free(bsig_runs *runs);
 /* The encoder of a plan's own result layout (bsig_plan_offsets): n_seg = n_ranges * S segments, S = 2 with strands (segment
  * S * i + antisense, stride 2), else 1; encode what bsig_plan_run wrote.  For ordinary plans of mode BSIG_MODE_PROFILE,
- * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr, frag, hist or summary plan fail
- * with BSIG_ERR_ARG. */
+ * BSIG_MODE_COVERAGE and BSIG_MODE_COVERAGE_EX; a BSIG_MODE_COUNT plan and a sum, xcorr, frag, hist, summary or scaled plan
+ * fail with BSIG_ERR_ARG. */
 int bsig_plan_runs_create(const bsig_plan *plan, bsig_runs **runs);
 
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
@@ -579,6 +615,23 @@ int bsig_coverage_summary(const char *bampath, int64_t n_ranges, const int32_t *
                           int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                           int32_t n_thresholds, const int32_t *thresholds,
                           int32_t maxgap, int32_t device, int64_t *out);
+/* The scaled regions (bsig_plan_create_scaled): out receives n_ranges * S * n_bins int64 in the caller's range order.
+ * bsig_pileup_scaled: the 5' ends (ss 0 / 1: S = 1 / 2); bsig_coverage_scaled: the per-base coverage (S = 1).  n_bins and
+ * the parameters are checked before the BAM is opened or decoded.  With several GPUs each takes its block of the
+ * (rid, loc)-sorted ranges and the host PLACES each block's rows at the caller's indices (bsig_last_call_route():
+ * "scaled of N blocks of ranges, rows placed on the host"; one GPU: "scaled"). */
+int bsig_pileup_scaled(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                       int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                       const int32_t *width, const int32_t *strand,
+                       const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid,
+                       int32_t n_bins, int32_t maxgap, int32_t device, int64_t *out);
+int bsig_coverage_scaled(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                         int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                         const int32_t *width, const int32_t *strand,
+                         const int32_t *tlen_filter, int32_t n_tlen_filter,
+                         int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                         int32_t n_bins, int32_t maxgap, int32_t device, int64_t *out);
 /* The file-level calls with the result as RUNS (bsig_runs_*): bsig_pileup_core's / bsig_coverage_core_ex's arguments
  * without out / off; binsize <= 0 (bamCount) fails with BSIG_ERR_ARG, and all parameters are checked before the BAM is
  * opened.  The per-base cells live only in HBM, and only for one block of the (rid, loc)-sorted ranges at a time: a block
