@@ -24,6 +24,10 @@
 //        p5h  : (5' end & 0x7FFF) | reverse << 15, 16 bits  (5' end = pos, or pos + span - 1 on the reverse strand)
 //     -- all a per-base profile without a template-length rule reads of a packed read when the plan's flag/mapq
 //     filter rejects none of the file's codes (bsig_plan_create: BsigKParams::packed_half).
+//     Classes 0 and 1 have the same column beside pos and fm, at the same read index (span - 1 from fm >> 24 and
+//     fm >> 20, the strand from flag bit 0x10), for the same plans when the filter can reject no read whatever its
+//     flag and mapq (BsigKParams::short_half): 2 bytes a visit instead of 8.  A class that holds a read with pos
+//     outside its reference has none: the index files such a read under a bucket its position does not lie in.
 //     and a bucket index  idx[b] = first read of the class whose global coordinate
 //     g = (ref_unit0[rid] << 16) + pos  falls in bucket >= b, bucket = g >> kshift.
 //     References are laid out back to back in units of 64 kbp, so one flat index
@@ -47,7 +51,8 @@ struct BsigClassCols {
     const int32_t *end;
     const uint32_t *fm;
     const int32_t *tlen;
-    const uint16_t *p5h;     // packed class only (NULL elsewhere, or with BAMSIGNALS_PACKED_HALF=0): see above
+    const uint16_t *p5h;     // packed class and classes 0, 1 (NULL elsewhere, with BAMSIGNALS_PACKED_HALF=0, and for classes
+                             // 0, 1 with BAMSIGNALS_SHORT_HALF=0 or a read outside its reference): see above
     const uint32_t *idx;     // n_buckets + 1 entries
     int64_t n;               // reads in the class
     int32_t maxspan;         // max(end - pos + 1) over the class
@@ -105,6 +110,14 @@ struct BsigKParams {
                             //   take the full-width per-read body instead
     int32_t packed_half;    // 1: the packed class is read from its 16-bit 5'-end column p5h (bamProfile, binsize 1, no
                             //   template-length rule, no code rejected, every packed window one chunk: bsig_plan_create)
+    int32_t short_half;     // 1: ... and so are span classes 0 and 1, from theirs (packed_half, a flag/mapq filter that can
+                            //   reject no read at all, each class's window inside 2^15 bases: bsig_plan_create).  The HOST's
+                            //   record of the decision (stats); the kernels do not read it, they ask short_win[1] != 0
+    uint32_t short_off[2];  // ... where class 0's and 1's columns begin, in half-words from the packed class's (one block
+                            //   holds the three; multiples of 8, so the columns are 16-B aligned)
+    int32_t short_win[2];   // ... (ext + maxspan - 1) << 5 | kshift of class 0 and 1: where the class's window of a tile
+                            //   begins.  0 without short_half and never 0 with it (kshift >= 4; an empty class gets 4):
+                            //   short_win[1] is the flag the kernels branch on
     int32_t ext;            // window extension on both sides (src/bamsignals.cpp:457,487)
     int32_t tile_cells;     // output cells per tile (sizes the dynamic LDS image)
     int32_t accumulate;     // 1: add the tile image into the result with integer atomics (slices of

@@ -32,6 +32,12 @@ hipError_t launch_pileup(int mode, int ss, int threads, const BsigReadsDev &R, c
 // the packed class's 16-bit 5'-end column (bsig_types.h: p5h) from its n words fm and the pair table fmtab: cap
 // (a multiple of 8, >= n + 8) entries at `out`, those from n on zero
 hipError_t launch_make_p5h(const uint32_t *fm, const uint32_t *fmtab, int64_t n, int64_t cap, uint16_t *out, hipStream_t st);
+// ... and span class 0's or 1's, from its pos and fm columns (span - 1 = fm >> span_shift) and its index of n_buckets
+// buckets; *bad is set to 1 if a read lies outside its reference (device arrays of n_ref entries), where the column
+// must not be used
+hipError_t launch_make_short_p5h(const int32_t *pos, const uint32_t *fm, int span_shift, int64_t n, int64_t cap, const uint32_t *idx,
+                                 uint64_t n_buckets, int kshift, const uint32_t *ref_unit0, const uint32_t *ref_units, int n_ref,
+                                 uint16_t *out, int *bad, hipStream_t st);
 // the packed class's filter table for P (BSIG_PACK_CODES bytes at `out`): once per plan
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st);
 hipError_t launch_resolve(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,

@@ -205,6 +205,31 @@ struct ProfileOne {
         rd(w.z & 0xFFFFu, 4u); rd(w.z >> 16, 5u);
         rd(w.w & 0xFFFFu, 6u); rd(w.w >> 16, 7u);
     }
+    // Classes 0 and 1 under BsigKParams::short_half have a 16-bit column of the same format, and their windows obey
+    // the same bound with the class's own maxspan and bucket (bsig_plan_create).  Their chunk starts where the class's
+    // bucket-rounded window of this tile starts -- load_windows' wlo, from the work item alone (scalar arithmetic; a
+    // slice of a heavy tile keeps its tile's cells, so its reads lie in the same window).
+    __device__ __forceinline__ int short_base(int c) const
+    {
+        const int64_t b = (int64_t)c0 + nc < len ? (int64_t)c0 + nc : len;                     // (tile_interval, bins of one base)
+        const int64_t tlo = neg_range ? (int64_t)loc + len - b : (int64_t)loc + c0;
+        const uint32_t sw = (uint32_t)P.short_win[c];                    // ext + maxspan - 1 and the bucket's log2 in one word
+        const int64_t wlo = tlo - (int64_t)(sw >> 5);
+        return wlo > 0 ? (int)((wlo >> (sw & 31u)) << (sw & 31u)) : 0;
+    }
+    // ... and a window of at most one read per lane takes `eight`'s rd for the lane's one half-word h (valid: the
+    // lane has a read)
+    __device__ __forceinline__ void half1(uint32_t h, bool valid, int base) const
+    {
+        const uint32_t d = (h - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u);
+        const uint32_t nm = (uint32_t)((int32_t)(h << 16) >> 31);
+        const uint32_t fwd = d + (nm & (uint32_t)(-2 * P.shift));
+        const uint32_t K = (uint32_t)(neg_range ? len - 1 - c0 - (base - loc + P.shift) : base - loc + P.shift - c0);
+        const uint32_t lc = neg_range ? K - fwd : K + fwd;
+        const bool ok = valid & (lc < (uint32_t)nc);
+        const uint32_t cell = SS ? (uint32_t)sh + 2u * lc + ((neg_range ? ~nm : nm) & 1u) : (uint32_t)sh + lc;
+        if (ok) atomicAdd(&cnt[cell >> 1], 1u << ((cell << 4) & 31u));         // (masked: see four)
+    }
 };
 
 // bamProfile's per-read work on the wide-bin image of k_profile_small: 32-bit cells in the lane's own replica.
@@ -499,6 +524,42 @@ __global__ void k_make_p5h(const uint32_t *__restrict__ fm, const uint32_t *__re
     out[i] = (uint16_t)h;
 }
 
+// The same column for span class 0 or 1 (bsig_types.h), from the class's pos and fm columns: span - 1 = fm >> span_shift
+// (24 / 20), the strand is flag bit 0x10.  These classes also hold the reads whose pos lies outside their reference,
+// which the bucket index files under the reference's first or last bucket: 15 bits of such a 5' end say nothing
+// about where it is, so a class with one gets no column (*bad = 1).  A read is checked against the bucket the index
+// has it in: the bucket idx[b] <= i < idx[b + 1] must be the one of its own position on the bucket's reference.
+__global__ void k_make_short_p5h(const int32_t *__restrict__ pos, const uint32_t *__restrict__ fm, int span_shift, int64_t n, int64_t cap,
+                                 const uint32_t *__restrict__ idx, uint64_t n_buckets, int kshift,
+                                 const uint32_t *__restrict__ ref_unit0, const uint32_t *__restrict__ ref_units, int n_ref,
+                                 uint16_t *__restrict__ out, int *__restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    uint32_t h = 0;
+    if (i < n) {
+        uint64_t lo = 0, hi = n_buckets;                                      // idx[0] = 0 <= i < n = idx[n_buckets]
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if ((int64_t)idx[mid] <= i) lo = mid; else hi = mid;
+        }
+        const uint64_t unit = (lo << kshift) >> BSIG_REF_UNIT_SHIFT;
+        int r0 = 0, r1 = n_ref;                                               // last reference with ref_unit0 <= unit
+        while (r1 - r0 > 1) {
+            const int mid = (r0 + r1) >> 1;
+            if ((uint64_t)ref_unit0[mid] <= unit) r0 = mid; else r1 = mid;
+        }
+        const int64_t p = pos[i], ref_bp = (int64_t)ref_units[r0] << BSIG_REF_UNIT_SHIFT;
+        const bool inside = p >= 0 && p < ref_bp && ((((uint64_t)ref_unit0[r0] << BSIG_REF_UNIT_SHIFT) + (uint64_t)p) >> kshift) == lo;
+        if (!inside) *bad = 1;
+        const uint32_t w = fm[i];
+        const uint32_t rev = (w >> 4) & 1u;
+        const uint32_t p5 = (uint32_t)p + (rev ? w >> span_shift : 0u);
+        h = (p5 & kPackPosMask) | rev << 15;
+    }
+    out[i] = (uint16_t)h;
+}
+
 // The packed class's window of a tile: the reads whose pos lies in the bucket-rounded window [rlo, rhi) of the
 // reference, walked in chunks of kPackChunk bases (nearly always one): inside a chunk that starts at `base`,
 // pos = base + ((word - base) & kPackPosMask).
@@ -737,13 +798,16 @@ __device__ __forceinline__ void four_packed(const uint4 &w, const int4 &t, uint3
 // and 1.  Longer windows and the two long-span classes continue in plain loops.
 // (The packed class's later chunks -- windows wider than kPackChunk bases -- are walked by packed_later_chunks.)
 // HALF (BsigKParams::packed_half, the functor has `oct`): the packed class comes from its 16-bit column p5h, eight
-// reads per lane and 16-B load (passes of 8 * NT reads, no tlen column).
+// reads per lane and 16-B load (passes of 8 * NT reads, no tlen column).  Under P.short_half classes 0 and 1 come from
+// their 16-bit columns too: a window of up to NT reads as one half-word per lane (`half1`), requested where pos and
+// fm are otherwise, a longer one eight reads per lane through `oct` with the class's own base (`short_base`).
 template <int NT, int kPre = 2, bool HALF = false, typename Tab, typename F>
 __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigKParams &P,
                                               const uint2 (&win)[BSIG_MAX_CLASSES], int pbase,
                                               const Tab *__restrict__ ptab, int tid, F &&one)
 {
     constexpr uint32_t kPer = HALF ? 8u : 4u;                        // packed reads per lane and 16-B load
+    const bool use_tlen = !HALF && P.use_tlen;                       // (a plan with a template-length rule has no half form)
     uint4 w0[kPre];
     int4 t0[kPre];
     const BsigClassCols &CP = R.cls[BSIG_CLASS_PACKED];
@@ -772,15 +836,36 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
     int pa = 0, ta = 0, pb = 0, tb = 0;
     uint32_t fa = 0, fb = 0;
     const uint32_t jb0 = win[0].x + (uint32_t)tid, jb1 = win[1].x + (uint32_t)tid;
+    // HALF under P.short_half (uniform): the lane's read is one half-word of the class's 16-bit column, which arrives in
+    // fa / fb inside its dword.  The columns lie behind the packed class's (P.short_off), and the kernels read the flag
+    // as short_win[1] != 0 (a bucket's log2 is never 0), a word they need anyway: with two more pointers and a flag of
+    // its own in scalar registers k_profile_half<64, false, 2, 1, true> took 106 of them and a 33rd vector register
+    // for the spills.
+    auto short_now = [&]() {
+        if constexpr (!HALF) return false;
+        return P.short_win[1] != 0;
+    };
+    // ONE load per class serves both forms: the dword that holds the lane's half-word (the columns are 16-B aligned and
+    // padded), or the lane's fm word -- a select of the column and a shift of the index, both uniform.  (A branch with
+    // a load on either side made the pos + fm side wait for every load in flight before it issued its own: the two
+    // sides share registers, and the wait counters are kept per block, not per path.)
+    const bool sh_on = short_now();
+    const uint32_t hs = sh_on ? 1u : 0u;
+    const uint32_t *col0 = sh_on ? reinterpret_cast<const uint32_t *>(CP.p5h + P.short_off[0]) : R.cls[0].fm;
+    const uint32_t *col1 = sh_on ? reinterpret_cast<const uint32_t *>(CP.p5h + P.short_off[1]) : R.cls[1].fm;
     if (small0 && jb0 < win[0].y) {
-        pa = R.cls[0].pos[jb0];
-        fa = R.cls[0].fm[jb0];
-        if (P.use_tlen) ta = R.cls[0].tlen[jb0];
+        fa = col0[jb0 >> hs];
+        if (!sh_on) {
+            pa = R.cls[0].pos[jb0];
+            if (use_tlen) ta = R.cls[0].tlen[jb0];
+        }
     }
     if (small1 && jb1 < win[1].y) {
-        pb = R.cls[1].pos[jb1];
-        fb = R.cls[1].fm[jb1];
-        if (P.use_tlen) tb = R.cls[1].tlen[jb1];
+        fb = col1[jb1 >> hs];
+        if (!sh_on) {
+            pb = R.cls[1].pos[jb1];
+            if (use_tlen) tb = R.cls[1].tlen[jb1];
+        }
     }
     // The 16-B aligned loads may start before j_lo (possibly on the previous reference) and end
     // after j_hi: only reads in [j_lo, j_hi) count -> `dj < nj` with unsigned wrap-around.
@@ -826,6 +911,25 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
             if (j2 < j_hi) four_packed(wb, xb, j2, j_lo, nj, pbase, ptab, one, inner_pass(jf + 4u * NT));
         }
     }
+    // ---- classes 0 and 1 from their 16-bit columns (P.short_half): the lane's half-word was requested above, the
+    // class's base comes from the work item in scalar arithmetic; nothing but fa / fb and two words of the parameter
+    // block was kept for them across the packed class's work
+    if constexpr (HALF) {
+        if (short_now()) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint32_t j_lo = win[c].x, j_hi = win[c].y, nj = j_hi - j_lo;
+                if (!nj) continue;                                         // (uniform)
+                const int base = one.short_base(c);
+                if (c ? small1 : small0) {
+                    one.half1(c ? fb >> ((jb1 & 1u) << 4) : fa >> ((jb0 & 1u) << 4), (c ? jb1 : jb0) < j_hi, base);
+                } else
+                for (uint32_t j = (j_lo & ~7u) + 8u * tid; j < j_hi; j += 8u * NT)
+                    one.oct(*reinterpret_cast<const uint4 *>(CP.p5h + P.short_off[c] + j), j - j_lo, nj, base);
+            }
+        }
+    }
+    if (!short_now()) {
     {   // ---- class 0 (span <= 256, a rare pair): no end column, end = pos + (fm >> 24) ------------------
         const BsigClassCols &C = R.cls[0];
         const uint32_t j_lo = win[0].x, j_hi = win[0].y, nj = j_hi - j_lo;
@@ -836,7 +940,7 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
             const int4 p = *reinterpret_cast<const int4 *>(C.pos + j);
             const uint4 f = *reinterpret_cast<const uint4 *>(C.fm + j);
             int4 t = make_int4(0, 0, 0, 0);
-            if (P.use_tlen) t = *reinterpret_cast<const int4 *>(C.tlen + j);
+            if (use_tlen) t = *reinterpret_cast<const int4 *>(C.tlen + j);
             const uint32_t dj = j - j_lo;
             one(p.x, p.x + (int)(f.x >> 24), (f.x & 0x10u) != 0u, fm_rejected(P, f.x), t.x, dj < nj);
             one(p.y, p.y + (int)(f.y >> 24), (f.y & 0x10u) != 0u, fm_rejected(P, f.y), t.y, dj + 1u < nj);
@@ -855,7 +959,7 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
             const int4 p = *reinterpret_cast<const int4 *>(C.pos + j);
             const uint4 f = *reinterpret_cast<const uint4 *>(C.fm + j);
             int4 t = make_int4(0, 0, 0, 0);
-            if (P.use_tlen) t = *reinterpret_cast<const int4 *>(C.tlen + j);
+            if (use_tlen) t = *reinterpret_cast<const int4 *>(C.tlen + j);
             const uint32_t dj = j - j_lo;
             const uint32_t gx = fm_of_class1(f.x), gy = fm_of_class1(f.y), gz = fm_of_class1(f.z), gw = fm_of_class1(f.w);
             one(p.x, p.x + (int)(f.x >> 20), (gx & 0x10u) != 0u, fm_rejected(P, gx), t.x, dj < nj);
@@ -864,6 +968,7 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
             one(p.w, p.w + (int)(f.w >> 20), (gw & 0x10u) != 0u, fm_rejected(P, gw), t.w, dj + 3u < nj);
         }
     }
+    }   // (!short_now())
 #pragma unroll
     for (int c = 2; c < BSIG_SPAN_CLASSES; ++c) {   // ---- classes 2-3: pos, end, fm columns ---------
         const BsigClassCols &C = R.cls[c];
@@ -875,7 +980,7 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
                 uint32_t f = 0;
                 if (j < j_hi) {
                     p = C.pos[j]; f = C.fm[j]; e = C.end[j];
-                    if (P.use_tlen) t = C.tlen[j];
+                    if (use_tlen) t = C.tlen[j];
                 }
                 one(p, e, (f & 0x10u) != 0u, fm_rejected(P, f), t, j < j_hi);
             }
@@ -885,7 +990,7 @@ __device__ __forceinline__ void for_each_read(const BsigReadsDev &R, const BsigK
             const uint4 f = *reinterpret_cast<const uint4 *>(C.fm + j);
             const int4 e = *reinterpret_cast<const int4 *>(C.end + j);
             int4 t = make_int4(0, 0, 0, 0);
-            if (P.use_tlen) t = *reinterpret_cast<const int4 *>(C.tlen + j);
+            if (use_tlen) t = *reinterpret_cast<const int4 *>(C.tlen + j);
             const uint32_t dj = j - j_lo;
             one(p.x, e.x, (f.x & 0x10u) != 0u, fm_rejected(P, f.x), t.x, dj < nj);
             one(p.y, e.y, (f.y & 0x10u) != 0u, fm_rejected(P, f.y), t.y, dj + 1u < nj);
@@ -1123,8 +1228,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
     profile_tile<NT, SS, PRE, RES, false>(items, n_tiles, out, windows, R, P, img_vec);
 }
 // k_profile reading the packed class's 16-bit column: a kernel of its own, so that the 4-byte form keeps its code
+// (amdgpu_num_sgpr(102): the 100 scalar registers that eight waves per SIMD leave a wave, VCC included.  Left to itself
+// the allocator takes up to 106 in the instantiations with looked-up windows, where the class-0/1 columns' offsets and
+// window words are live beside the index lookups, and reports seven waves; the headline instantiations stay below
+// the limit by themselves and spill nothing)
 template <int NT, bool SS, int PRE, int WAVES, bool RES>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_profile_half(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, 8), amdgpu_num_sgpr(102))) void k_profile_half(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
                                                 uint32_t img_vec, int32_t *__restrict__ out,
                                                 const uint2 *__restrict__ windows,
                                                 const BsigReadsDev R, const BsigKParams P)
@@ -3581,6 +3690,16 @@ hipError_t launch_make_p5h(const uint32_t *fm, const uint32_t *fmtab, int64_t n,
 {
     if (cap <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_make_p5h, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, fm, fmtab, n, cap, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_make_short_p5h(const int32_t *pos, const uint32_t *fm, int span_shift, int64_t n, int64_t cap, const uint32_t *idx,
+                                 uint64_t n_buckets, int kshift, const uint32_t *ref_unit0, const uint32_t *ref_units, int n_ref,
+                                 uint16_t *out, int *bad, hipStream_t st)
+{
+    if (cap <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_make_short_p5h, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, pos, fm, span_shift, n, cap, idx,
+                       n_buckets, kshift, ref_unit0, ref_units, n_ref, out, bad);
     return hipGetLastError();
 }
 

@@ -513,18 +513,50 @@ uint64_t bsig::next_layout_gen()
 // The packed class's 16-bit 5'-end column (bsig_types.h: p5h), derived from its words and the pair table wherever a
 // bsig_reads is made (laid out, cloned, loaded) and never saved.  +2 bytes per packed read in HBM (R->info.hbm_bytes).
 // env BAMSIGNALS_PACKED_HALF=0, read here: no column, every plan reads the 4-byte words.
+// Span classes 0 and 1 get the same column (+2 bytes per read of theirs), behind the packed class's in ONE block -- the
+// kernels reach them as offsets from the packed column (BsigKParams::short_off: a scalar register each instead of a
+// pointer's two) -- unless the class holds a read outside its reference (kernels.hip: k_make_short_p5h).
+// env BAMSIGNALS_SHORT_HALF=0, read here as well: the packed class's column only.
 static int make_packed_half(bsig_reads *R, hipStream_t st)
 {
-    BsigClassCols &C = R->dev.cls[BSIG_CLASS_PACKED];
-    C.p5h = nullptr;
+    for (int c = 0; c < BSIG_MAX_CLASSES; ++c) R->dev.cls[c].p5h = nullptr;
     const char *e = getenv("BAMSIGNALS_PACKED_HALF");
+    BsigClassCols &C = R->dev.cls[BSIG_CLASS_PACKED];
     if (C.n == 0 || !R->dev.fmtab || (e && !strcmp(e, "0"))) return BSIG_OK;
-    const int64_t cap = (C.n + 7) / 8 * 8 + 8;           // the 16-B loads of the last reads stay inside, and read zeros
+    const char *es = getenv("BAMSIGNALS_SHORT_HALF");
+    auto cap_of = [](int64_t n) { return n ? (n + 7) / 8 * 8 + 8 : (int64_t)0; };     // the 16-B loads of the last reads stay inside, and read zeros
+    const int64_t cap = cap_of(C.n);
+    int64_t cap_s[2] = {cap_of(R->dev.cls[0].n), cap_of(R->dev.cls[1].n)};
+    if ((es && !strcmp(es, "0")) || cap + cap_s[0] + cap_s[1] >= ((int64_t)1 << 32)) cap_s[0] = cap_s[1] = 0;
     uint16_t *p = nullptr;
-    HIP_TRY(R->pool.alloc(&p, (size_t)cap));
+    HIP_TRY(R->pool.alloc(&p, (size_t)(cap + cap_s[0] + cap_s[1]), cap_s[0] + cap_s[1] != 0));
     HIP_TRY(bsig::launch_make_p5h(C.fm, R->dev.fmtab, C.n, cap, p, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    int bad[2] = {0, 0};
+    if (cap_s[0] + cap_s[1]) {
+        // one small scratch block: the references' first units, their unit counts, the two flags
+        const size_t nr = (size_t)R->n_ref;
+        uint32_t *d_tab = nullptr;
+        HIP_TRY(hipMalloc((void **)&d_tab, (2 * nr + 2) * sizeof(uint32_t)));
+        int *d_bad = reinterpret_cast<int *>(d_tab + 2 * nr);
+        hipError_t he = hipMemcpyAsync(d_tab, R->ref_unit0.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (he == hipSuccess) he = hipMemcpyAsync(d_tab + nr, R->ref_units.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (he == hipSuccess) he = hipMemsetAsync(d_bad, 0, sizeof bad, st);
+        for (int c = 0; c < 2 && he == hipSuccess; ++c) {
+            const BsigClassCols &S = R->dev.cls[c];
+            if (!cap_s[c]) continue;
+            he = bsig::launch_make_short_p5h(S.pos, S.fm, c == 0 ? 24 : 20, S.n, cap_s[c], S.idx, R->idx_entries[c] - 2, S.kshift, d_tab,
+                                             d_tab + nr, R->n_ref, p + cap + (c ? cap_s[0] : 0), d_bad + c, st);
+        }
+        if (he == hipSuccess) he = hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        (void)hipFree(d_tab);
+        HIP_TRY(he);
+    } else {
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     C.p5h = p;
+    for (int c = 0; c < 2; ++c)
+        if (cap_s[c] && !bad[c]) R->dev.cls[c].p5h = p + cap + (c ? cap_s[0] : 0);
     R->info.hbm_bytes = R->pool.footprint();
     return BSIG_OK;
 }
@@ -1723,6 +1755,32 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
         half = half && (int64_t)K.tile_cells + 2 * r.ext + C.maxspan + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
         K.packed_half = half ? 1 : 0;
     }
+    // Span classes 0 and 1 from their own 16-bit columns (kernels.hip: for_each_read under P.short_half).  Their reads'
+    // (flag, mapq) pairs are not the pair table's, so the filter must be one that rejects no read by its parameters
+    // alone: no mapq bound, no required flag, and a filtered-flag bit above the 16 a flag has (then filteredF & ~flag is
+    // never 0).  The window of class c for a tile holds pos in [wlo, whi) rounded outwards to buckets, wlo = tile start
+    // - ext - (maxspan - 1), whi = tile end + ext: at most tile bases + 2 ext + (maxspan - 1) + two buckets wide from its
+    // base, the rounded wlo (ProfileOne::short_base).  A reverse read's 5' end lies up to maxspan - 1 behind its pos -- or
+    // 255 behind it where class 0's 8-bit span field holds a span below 1, which the 256 spare bases cover.  So with
+    // tile bases + 2 ext + 2 (maxspan - 1) + two buckets <= 2^15 - 256 every 5' end is less than 2^15 from the base
+    // and base + ((h - base) & 0x7FFF) is the 5' end.  Anything else reads pos and fm as before.
+    {
+        bool sh = K.packed_half && K.mapqual <= 0 && K.requiredF == 0u && (K.filteredF >> 16) != 0u;
+        for (int c = 0; sh && c < 2; ++c) {
+            const BsigClassCols &C = reads->dev.cls[c];
+            if (C.n == 0) continue;
+            sh = C.p5h != nullptr &&
+                 (int64_t)K.tile_cells + 2 * r.ext + 2 * ((int64_t)C.maxspan - 1) + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
+        }
+        K.short_half = sh ? 1 : 0;
+        // what the kernels read: where a class's column begins behind the packed class's, and ext + maxspan - 1 with
+        // the bucket's log2 (never 0: short_win[1] != 0 is the kernels' form of short_half)
+        for (int c = 0; c < 2; ++c) {
+            const BsigClassCols &C = reads->dev.cls[c];
+            K.short_off[c] = sh && C.p5h ? (uint32_t)(C.p5h - reads->dev.cls[BSIG_CLASS_PACKED].p5h) : 0u;
+            K.short_win[c] = sh ? (int32_t)((uint32_t)(r.ext + (C.n ? C.maxspan - 1 : 0)) << 5 | (uint32_t)(C.n ? C.kshift : 4)) : 0;
+        }
+    }
     // (a frag plan's tiles are count tiles, which divide by no binsize: the multiplier is its row width's)
     bsig::magic_u31(rq.kind == kFrag ? rq.frag->len_bin : K.binsize, &K.div_magic, &K.div_shift);
     K.div_m15 = 0; K.div_s15 = 0;
@@ -2473,7 +2531,8 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
     t.streamed = (int64_t)acc[BSIG_MAX_CLASSES];
     t.heavy_tiles = (int32_t)std::min<int64_t>(p->n_heavy_tiles, INT32_MAX);
     t.bytes_per_visit_packed = p->kp.packed_half ? 2 : p->kp.use_tlen ? 8 : 4;     // the half-word, or the packed word [+ tlen]
-    t.bytes_per_visit_short = p->kp.use_tlen ? 12 : 8;     // span <= 4096: pos + flag/mapq/span in one word [+ tlen]
+    // span <= 4096: the half-word, or pos + flag/mapq/span in one word [+ tlen]
+    t.bytes_per_visit_short = p->kp.short_half ? 2 : p->kp.use_tlen ? 12 : 8;
     t.bytes_per_visit_long = p->kp.use_tlen ? 16 : 12;     // pos + end + flag/mapq [+ tlen]
     // reads + work items + index entries + result cells (a sum plan: 8 B a cell of the sum, none per range)
     const int64_t per_item = (int64_t)sizeof(BsigWorkItem);

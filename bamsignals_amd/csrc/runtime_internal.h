@@ -99,8 +99,12 @@ struct DevPool {
         res = (uint8_t *)p;
         res_left = got;
     }
+    // own_block: never out of a slab -- a block of the request's size, which footprint() (and so hbm_bytes) then shows
+    // whatever the size.  make_packed_half asks for it when the block holds class-0/1 columns, so a layout with them and
+    // one without differ in hbm_bytes even where the packed column alone would fit a slab; a pool that still has room
+    // in an adopted reservation carves the block out of that, and footprint() shows nothing either way
     template <typename T>
-    hipError_t alloc(T **p, size_t count)
+    hipError_t alloc(T **p, size_t count, bool own_block = false)
     {
         const size_t nbytes = (std::max<size_t>(count * sizeof(T), 16) + 255) & ~(size_t)255;
         bytes += (int64_t)nbytes;
@@ -113,7 +117,7 @@ struct DevPool {
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) { *p = nullptr; return e; }
-        if (nbytes <= kSmall) {
+        if (nbytes <= kSmall && !own_block) {
             if (nbytes > slab_left) {
                 void *q = nullptr;
                 size_t got = 0;

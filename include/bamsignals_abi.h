@@ -184,7 +184,7 @@ typedef struct {
                                 * or + 48*items (the resolved form of large launches and of every later run: the windows
                                 * kept with the plan; with BAMSIGNALS_CACHE_WINDOWS=0, looked up by a launch of their own
                                 * in every run: 8*items*classes + (32 + 2*48)*items) */
-    int32_t bytes_per_visit_short;   /* 8  (pos + flag|mapq|span - 1), 12 with the tlen column  */
+    int32_t bytes_per_visit_short;   /* 8  (pos + flag|mapq|span - 1), 12 with the tlen column; 2 from the 16-bit 5'-end columns */
     int32_t bytes_per_visit_long;    /* 12 (pos + end + flag|mapq), 16 with the tlen column     */
     int64_t visits_packed;     /* ... of V in the packed class (not part of visits_short)       */
     int32_t bytes_per_visit_packed;  /* 4  (one word), 8 with the tlen column                   */
