@@ -6,7 +6,8 @@ Beyond it: bamCrossCorr, the strand cross-correlation over ranges (the data's ow
 bamFragSizes, the fragment-length histogram over ranges (the data's own ``tlenFilter``); bamDepthHist, the histogram of
 the per-base depth over ranges (breadth at 20x, mean and median depth, the duplication histogram); bamSummary, every
 range's own sum, max, summit and breadth at thresholds (peak heights, per-target QC); bamScaled, every range cut into
-the same number of bins whatever its width (the heatmap matrix, metaprofiles over genes of unequal length); RunSignals, what
+the same number of bins whatever its width (the heatmap matrix, metaprofiles over genes of unequal length); bamOverlaps,
+the reads or fragments that overlap each range (countOverlaps / featureCounts / multicov counting); RunSignals, what
 bamProfile / bamCoverage return with ``runs=True``: the signals as runs, encoded on the GPU.
 Handle-level API for resident data and benchmarking: ``bamsignals_amd.device``.
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
@@ -18,6 +19,7 @@ from .crosscorr import CrossCorr, bamCrossCorr  # noqa: F401
 from .depthhist import DepthHist, bamDepthHist  # noqa: F401
 from .fragsizes import FragSizes, bamFragSizes  # noqa: F401
 from .granges import GRanges  # noqa: F401
+from .overlaps import bamOverlaps  # noqa: F401
 from .runsignals import RunSignals  # noqa: F401
 from .scaled import ScaledSignals, bamScaled  # noqa: F401
 from .summary import RangeSummary, bamSummary  # noqa: F401
@@ -25,5 +27,6 @@ from .wrappers import bamCount, bamCoverage, bamProfile, coverage_core, pileup_c
 
 __all__ = ["bamCount", "bamProfile", "bamCoverage", "bamCrossCorr", "CrossCorr", "bamFragSizes",
            "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "bamScaled", "ScaledSignals",
+           "bamOverlaps",
            "CountSignals", "RunSignals", "GRanges", "BamFile",
            "writeSamAsBamAndIndex", "write_columns_as_bam", "pileup_core", "coverage_core"]

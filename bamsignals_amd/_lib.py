@@ -14,6 +14,8 @@ SO_PATH = os.environ.get("BSIG_LIB_PATH") or os.path.join(_HERE, "libbamsignals_
 
 BSIG_OK = 0
 MODE_PROFILE, MODE_COUNT, MODE_COVERAGE, MODE_COVERAGE_EX = 0, 1, 2, 3
+# bamOverlaps: Params.binsize carries minoverlap in these modes
+MODE_OVERLAP_ANY, MODE_OVERLAP_WITHIN = 4, 5
 # include/bamsignals_abi.h: BSIG_XCORR_MAX_LAG, BSIG_XCORR_MOMENTS
 XCORR_MAX_LAG, XCORR_MOMENTS = 2047, 5
 # include/bamsignals_abi.h: BSIG_FRAG_MAX_ROWS
@@ -181,6 +183,10 @@ def load():
     lib.bsig_bam_decode_timing.restype = None
     lib.bsig_pileup_core.argtypes = core_head + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
     lib.bsig_coverage_core.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]
+    # (BSIG_LIB_PATH may name a build from before bamOverlaps -- the yardstick of scripts/overlaps_times.py --, which
+    # lacks this one entry: bamOverlaps then raises AttributeError where it would call it)
+    if hasattr(lib, "bsig_overlap_core"):
+        lib.bsig_overlap_core.argtypes = core_head + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
     lib.bsig_pileup_core_into.argtypes = core_head + [C.c_int32] * 9 + [C.c_void_p]
     lib.bsig_coverage_core_into.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
     lib.bsig_coverage_core_ex.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]

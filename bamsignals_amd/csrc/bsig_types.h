@@ -130,6 +130,11 @@ struct BsigKParams {
                             // device: bit 0 rejected, bit 1 reverse strand), made once per plan by k_make_ptab
     int32_t *overflow;      // binned coverage: set to 1 by a heavy tile's slice whose atomic add took a bin past
                             // INT32_MAX (the plan's device flag; NULL where no add can)
+    int32_t minoverlap;     // bamOverlaps (k_overlap*): bases a read must share with its range, >= 1; 0: no overlap plan
+    int32_t within;         // ... 1: and the read must lie inside the range (type "within")
+    int32_t overlap_wide;   // ... 1: packed reads take the per-read 64-bit body too, not OverlapOne::quad's 32-bit one
+                            //   (BAMSIGNALS_OVERLAP_QUAD=0 at plan time: what scripts/overlaps_times.py compares)
+    int32_t pad_;
 };
 
 // Sums over ranges (kernels.hip: k_sum_reduce): slabs [slot_lo, slot_hi) of runs of one tile position, added into the

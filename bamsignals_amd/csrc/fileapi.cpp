@@ -1495,6 +1495,28 @@ int bsig_pileup_core_into(const char *bampath, int64_t n, const int32_t *seq_cod
                       {nullptr, nullptr, dst});
 }
 
+// bamOverlaps: a plain plan of one of the overlap modes (min_overlap in the binsize field); its parameters are judged
+// here, before file_level opens the BAM
+int bsig_overlap_core(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                      const char *const *levels, const int32_t *start, const int32_t *width,
+                      const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t overlap_type, int32_t min_overlap, int32_t ss,
+                      int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t maxgap, int32_t device,
+                      int32_t *out, const int64_t *off)
+{
+    (void)maxgap;
+    if (overlap_type != 0 && overlap_type != 1) return fail(BSIG_ERR_ARG, "overlap type must be 0 (any) or 1 (within)");
+    if (n_tlen_filter > 0 && !tlen_filter) return fail(BSIG_ERR_ARG, "tlen_filter missing");
+    bsig_params p{};
+    p.mode = overlap_type ? BSIG_MODE_OVERLAP_WITHIN : BSIG_MODE_OVERLAP_ANY;
+    p.mapqual = mapqual; p.binsize = min_overlap; p.ss = ss;
+    p.requiredF = requiredF; p.filteredF = filteredF; p.tspan = tspan;
+    p = with_filter(p, tlen_filter, n_tlen_filter);
+    bsig::PlanRule early;
+    if (const int rc = bsig::check_params(p, n > 0 && width ? n : 0, width, &early)) return rc;
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, {out, off});
+}
+
 int bsig_coverage_core(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                        const char *const *levels, const int32_t *start, const int32_t *width,
                        const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,

@@ -464,6 +464,105 @@ struct CountOne {
     }
 };
 
+// bamOverlaps' per-read work, in count_one's shape (no branch, the same packed counter): a read that passes the filter of
+// Coverager::setRead (:394-399) has the interval [s, e] = [pos, end], or CoverOne's fragment under P.tspan (:404-413);
+// against the range [lo, hi1] (first and last base) it overlaps in ov = min(e, hi1) - max(s, lo) + 1 bases and counts
+// iff ov >= P.minoverlap -- WITHIN: and s >= lo and e <= hi1.  A range wider than one tile is cut into several, and a
+// read may overlap more than one: the tile [glo, glo + gn) counts a read iff the read's ANCHOR a = max(s, lo), its
+// first base inside the range, lies in the tile.  Every counted read has exactly one anchor tile, so sub-intervals,
+// slices of heavy tiles and the shards of several GPUs add up without a read counted twice.
+//
+// The count-mode window of a tile [tlo, thi) (class_window with ext = tspan ? tf1 : 0: pos in
+// [tlo - ext - maxspan + 1, thi + ext)) holds every read anchored in the tile:
+//   * a read anchored in [tlo, thi) has e >= a >= tlo; its own end is >= tlo too (a reverse fragment ends with the
+//     read, e = end; any other has a in [pos, end]), so pos >= tlo - maxspan + 1 -- and a forward fragment that starts
+//     before lo (a = lo = tlo) has pos + tlen - 1 >= lo with tlen <= tf1: pos >= tlo - tf1 + 1;
+//   * without a fragment rule pos = s <= a < thi; a forward fragment has pos = s as well;
+//   * a reverse fragment has s = end + tlen + 1 <= a < thi, so pos <= end = s - tlen - 1 < thi + tf1.
+// glo, gn, lo, hi1 and P.minoverlap are wave-uniform.  No sum here wraps: pos, end and tlen are any int32 and
+// tf1 <= 2^30 (bsig_plan_create), so operator() takes a fragment's sums in 64 bits; quad, which sees packed reads only
+// (0 <= pos < 2^31, span <= 256, no template length), works in 32 bits relative to its chunk (see there).
+template <bool WITHIN>
+struct OverlapOne {
+    const BsigKParams &P;
+    int glo, gn;
+    int64_t lo, hi1;
+    uint32_t &acc;
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        bool ok = valid & !rej;
+        if (P.has_tlen_filter) {                               // (uniform)
+            const int64_t a = tl < 0 ? -(int64_t)tl : (int64_t)tl;
+            ok = ok & (a >= P.tf0) & (a <= P.tf1);
+        }
+        if (!P.tspan) {                                        // (uniform)
+            // the read is its own interval: nothing is summed, and 32 bits do.  lo is an int32 (loc); a last base past
+            // INT32_MAX is past every e; with b >= a the difference b - a is below 2^32, so the unsigned subtraction
+            // is exact; a - glo lies in [-c0, 2^32), so its residue is below gn only where it is itself (a >= lo,
+            // glo = lo + c0)
+            const int lo32 = (int)lo, hi32 = hi1 > INT32_MAX ? INT32_MAX : (int)hi1;
+            const int a = p > lo32 ? p : lo32, b = e < hi32 ? e : hi32;
+            ok = ok & (b >= a) & ((uint32_t)b - (uint32_t)a >= (uint32_t)(P.minoverlap - 1)) &
+                 ((uint32_t)a - (uint32_t)glo < (uint32_t)gn);
+            if (WITHIN) ok = ok & (p >= lo32) & (e <= hi32);
+        } else {
+            const int64_t s = (neg & (tl < 0)) ? (int64_t)e + tl + 1 : (int64_t)p;
+            const int64_t f = (!neg & (tl > 0)) ? (int64_t)p + tl - 1 : (int64_t)e;
+            const int64_t a = s > lo ? s : lo, b = f < hi1 ? f : hi1;
+            ok = ok & (b - a >= (int64_t)P.minoverlap - 1) & ((uint64_t)(a - glo) < (uint64_t)gn);
+            if (WITHIN) ok = ok & (s >= lo) & (f <= hi1);
+        }
+        acc += ok ? (neg ? 0x10001u : 1u) : 0u;
+    }
+    // Four reads of the packed class (CountOne::quad's arguments; the table is the overlap forms' own, build_otab: per
+    // code what a counted read ADDS to the packed counter -- 1, 0x10001 on the reverse strand, 0 for a rejected code --
+    // so the filter and the strand cost no instruction per read).  With a template-length rule they go through operator().  Without one everything is taken from the chunk's start:
+    // s = d = (word - base) & mask < 2^15 and e = d + span - 1 < 2^15 + 255, against the range's ends minus `base`,
+    // clamped to [-1, 2^20].  The clamps change no answer -- a first base below 0 is below every s, a last base above
+    // 2^20 is above every e, a last base below -1 or a first base above 2^20 leaves no overlap either way -- and keep
+    // every difference below 2^21 in magnitude.  The anchor test is a subtraction modulo 2^32 of two numbers less than
+    // 2^32 apart (0 <= pos < 2^31, glo an int32).  No multiply, so nothing to gate on P.rel24.
+    __device__ __forceinline__ void quad(const uint4 &w, const int4 &t, uint32_t dj, uint32_t nj, int base,
+                                         const uint32_t *__restrict__ ctab, bool inner) const
+    {
+        const uint32_t b0 = ctab[w.x >> 23], b1 = ctab[w.y >> 23], b2 = ctab[w.z >> 23], b3 = ctab[w.w >> 23];
+        if (P.use_tlen | P.overlap_wide) {                     // (uniform)
+            auto dec = [&](uint32_t x, uint32_t b, int tl, bool valid) {
+                const int pos = base + (int)((x - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u));
+                (*this)(pos, pos + (int)((x >> BSIG_PACK_POS_BITS) & 0xFFu), (b >> 16) != 0u, b == 0u, tl, valid);
+            };
+            dec(w.x, b0, t.x, dj < nj);
+            dec(w.y, b1, t.y, dj + 1u < nj);
+            dec(w.z, b2, t.z, dj + 2u < nj);
+            dec(w.w, b3, t.w, dj + 3u < nj);
+            return;
+        }
+        auto clamp = [](int64_t v) { return (int)(v < -1 ? -1 : v > (1 << 20) ? (1 << 20) : v); };
+        const int lo_b = clamp(lo - base), hi_b = clamp(hi1 - base), m1 = P.minoverlap - 1;
+        const uint32_t g_b = (uint32_t)glo - (uint32_t)base;
+        auto hit = [&](uint32_t x) {
+            const int d = (int)((x - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u));
+            const int f = d + (int)((x >> BSIG_PACK_POS_BITS) & 0xFFu);
+            const int a = d > lo_b ? d : lo_b, bb = f < hi_b ? f : hi_b;
+            bool ok = (bb - a >= m1) & ((uint32_t)a - g_b < (uint32_t)gn);
+            if (WITHIN) ok = ok & (d >= lo_b) & (f <= hi_b);
+            return ok;
+        };
+        // (12 vector instructions a read on an inner pass, CountOne's 11: two for d, span, last base, max, min, the two
+        // differences and their compares, select, add)
+        if (inner) {
+            acc += hit(w.x) ? b0 : 0u;
+            acc += hit(w.y) ? b1 : 0u;
+            acc += hit(w.z) ? b2 : 0u;
+            acc += hit(w.w) ? b3 : 0u;
+        } else {
+            acc += ((dj < nj) & hit(w.x)) ? b0 : 0u;
+            acc += ((dj + 1u < nj) & hit(w.y)) ? b1 : 0u;
+            acc += ((dj + 2u < nj) & hit(w.z)) ? b2 : 0u;
+            acc += ((dj + 3u < nj) & hit(w.w)) ? b3 : 0u;
+        }
+    }
+};
 
 constexpr int kPackChunk = 1 << BSIG_PACK_POS_BITS;        // bases a packed word's position bits span
 constexpr uint32_t kPackPosMask = (uint32_t)kPackChunk - 1u;
@@ -494,6 +593,41 @@ __device__ __forceinline__ void build_ctab(uint32_t *ctab, const BsigKParams &P,
         reinterpret_cast<uint4 *>(ctab)[v] = make_uint4(e(b & 0xFFu), e((b >> 8) & 0xFFu), e((b >> 16) & 0xFFu), e(b >> 24));
     }
 }
+// ... and the overlap forms' (OverlapOne::quad): per code what a counted read adds to the packed counter -- 0 rejected, 1,
+// 0x10001 reverse strand
+template <int NT>
+__device__ __forceinline__ void build_otab(uint32_t *otab, const BsigKParams &P, int tid)
+{
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(P.ptab);
+    for (int v = tid; v < BSIG_PACK_CODES / 4; v += NT) {
+        const uint32_t b = src[v];
+        auto e = [](uint32_t x) { return (x & 1u) ? 0u : (x & 2u) ? 0x10001u : 1u; };
+        reinterpret_cast<uint4 *>(otab)[v] = make_uint4(e(b & 0xFFu), e((b >> 8) & 0xFFu), e((b >> 16) & 0xFFu), e(b >> 24));
+    }
+}
+// what a kernel of the count family is made of: the packed class's table in LDS, its per-read functor for a tile [glo, glo + gn) of the range
+// [loc, loc + len), and how many words of a tile k_count_multi stages (the overlap forms carry loc and len too)
+struct CountFamily {
+    static constexpr int kStage = 16;
+    template <int NT>
+    static __device__ __forceinline__ void table(uint32_t *tab, const BsigKParams &P, int tid) { build_ctab<NT>(tab, P, tid); }
+    static __device__ __forceinline__ CountOne make(const BsigKParams &P, int loc, int len, int glo, int gn, uint32_t &acc)
+    {
+        (void)loc; (void)len;
+        return CountOne{P, glo, gn, acc};
+    }
+};
+template <bool WITHIN>
+struct OverlapFamily {
+    static constexpr int kStage = 18;
+    template <int NT>
+    static __device__ __forceinline__ void table(uint32_t *tab, const BsigKParams &P, int tid) { build_otab<NT>(tab, P, tid); }
+    static __device__ __forceinline__ OverlapOne<WITHIN> make(const BsigKParams &P, int loc, int len, int glo, int gn, uint32_t &acc)
+    {
+        return OverlapOne<WITHIN>{P, glo, gn, (int64_t)loc, (int64_t)loc + len - 1, acc};
+    }
+};
+
 __global__ __launch_bounds__(128) void k_make_ptab(const BsigReadsDev R, const BsigKParams P, uint8_t *__restrict__ out)
 {
     const int v = threadIdx.x;                              // four codes each: BSIG_PACK_CODES = 4 x 128
@@ -1389,21 +1523,22 @@ __global__ __launch_bounds__(NT) void k_profile_small(const BsigWorkItem *__rest
 // ------------------------------------------------------------------------------------------
 // bamCount: one (or two, strand-specific) counters per range
 // ------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(NT) void k_count(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
-                                              int32_t *__restrict__ out,
-                                              const uint2 *__restrict__ windows,
-                                              const BsigReadsDev R, const BsigKParams P)
+// (the body of k_count and of k_overlap: Fam is CountFamily or OverlapFamily<WITHIN>)
+template <int NT, typename Fam>
+__device__ __forceinline__ void count_tile(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                           int32_t *__restrict__ out,
+                                           const uint2 *__restrict__ windows,
+                                           const BsigReadsDev &R, const BsigKParams &P)
 {
     __shared__ int32_t wsum[2 * (NT / kWave)];
-    __shared__ __attribute__((aligned(16))) uint32_t ptab[BSIG_PACK_CODES];      // (the count family's table: build_ctab)
+    __shared__ __attribute__((aligned(16))) uint32_t ptab[BSIG_PACK_CODES];      // (the count family's table: Fam::table)
     const int tid = threadIdx.x;
     const uint32_t tile = tile_of_block(blockIdx.x, n_tiles);
     const BsigWorkItem w = items[tile];
     uint2 win[BSIG_MAX_CLASSES], clip;
     PackedWin pk;
     load_windows(R, P, BSIG_MODE_COUNT, w, items, windows, win, tile, pk, clip);
-    build_ctab<NT>(ptab, P, tid);
+    Fam::template table<NT>(ptab, P, tid);
     block_sync<NT>();
     const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
     const int glo = w.loc + w.c0;           // sub-interval of the range, genomic coordinates
@@ -1413,7 +1548,7 @@ __global__ __launch_bounds__(NT) void k_count(const BsigWorkItem *__restrict__ i
     // that is no read, rejected or outside adds 0 -- and ONE packed counter (all reads in its low half, reverse-strand
     // ones in its high half) that becomes sense and antisense once, behind the loop.
     uint32_t acc = 0;
-    const CountOne one{P, glo, gn, acc};
+    const auto one = Fam::make(P, w.loc, w.len, glo, gn, acc);
     for_each_read<NT>(R, P, win, pk.base, ptab, tid, one);
     if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COUNT, w, pk.n_chunks, clip, ptab, tid, one);
     const int c_all = (int)(acc & 0xFFFFu), c_neg = (int)(acc >> 16);
@@ -1445,20 +1580,39 @@ __global__ __launch_bounds__(NT) void k_count(const BsigWorkItem *__restrict__ i
         }
     }
 }
+template <int NT>
+__global__ __launch_bounds__(NT) void k_count(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                              int32_t *__restrict__ out,
+                                              const uint2 *__restrict__ windows,
+                                              const BsigReadsDev R, const BsigKParams P)
+{
+    count_tile<NT, CountFamily>(items, n_tiles, out, windows, R, P);
+}
+// bamOverlaps: k_count's body with OverlapOne<WITHIN> per read (a tile counts the reads anchored in it)
+template <int NT, bool WITHIN>
+__global__ __launch_bounds__(NT) void k_overlap(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                int32_t *__restrict__ out,
+                                                const uint2 *__restrict__ windows,
+                                                const BsigReadsDev R, const BsigKParams P)
+{
+    count_tile<NT, OverlapFamily<WITHIN>>(items, n_tiles, out, windows, R, P);
+}
 
 // bamCount, several consecutive tiles per wave.  A count tile moves one dword out and has no LDS image,
 // so nothing but the dependent chain item -> index -> reads fills a wave's lifetime.  Here lane t of
 // the wave fetches the work item of tile t of its group and looks up that tile's windows (T chains
 // side by side instead of one behind the other); the tiles are then streamed one after the other
 // with the windows broadcast from their lane, and lane t stores tile t's counters at the end.
-template <int T, int PRE>
-__global__ __launch_bounds__(kWave) void k_count_multi(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
-                                                       int32_t *__restrict__ out,
-                                                       const uint2 *__restrict__ windows,
-                                                       const BsigReadsDev R, const BsigKParams P)
+// (the body of k_count_multi and of k_overlap_multi)
+template <int T, int PRE, typename Fam>
+__device__ __forceinline__ void count_multi_tiles(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                  int32_t *__restrict__ out,
+                                                  const uint2 *__restrict__ windows,
+                                                  const BsigReadsDev &R, const BsigKParams &P)
 {
-    __shared__ uint32_t stage[T][16];      // per tile: 5 windows, first base, bases, flags, packed base and chunks
-    __shared__ __attribute__((aligned(16))) uint32_t ptab[BSIG_PACK_CODES];      // (the count family's table: build_ctab)
+    // per tile: 5 windows, first base, bases, flags, packed base and chunks (the overlap forms: the range's loc and len)
+    __shared__ uint32_t stage[T][Fam::kStage];
+    __shared__ __attribute__((aligned(16))) uint32_t ptab[BSIG_PACK_CODES];      // (the count family's table: Fam::table)
     const int lane = threadIdx.x;
     const uint32_t n_groups = (n_tiles + T - 1) / T;
     const uint32_t first = tile_of_block(blockIdx.x, n_groups) * T;
@@ -1478,10 +1632,11 @@ __global__ __launch_bounds__(kWave) void k_count_multi(const BsigWorkItem *__res
         stage[lane][12] = w.units_strand;
         stage[lane][13] = (uint32_t)pk.base;
         stage[lane][14] = (uint32_t)pk.n_chunks;
+        if constexpr (Fam::kStage > 16) { stage[lane][16] = (uint32_t)w.loc; stage[lane][17] = (uint32_t)w.len; }
         out_off = w.out_off;
         atomic = (w.units_strand & BSIG_ITEM_ATOMIC) != 0u;
     }
-    build_ctab<kWave>(ptab, P, lane);
+    Fam::template table<kWave>(ptab, P, lane);
     block_sync<kWave>();
     int my_sense = 0, my_anti = 0;
 #pragma unroll 1
@@ -1496,8 +1651,13 @@ __global__ __launch_bounds__(kWave) void k_count_multi(const BsigWorkItem *__res
         const bool neg_range = ((uint32_t)__builtin_amdgcn_readfirstlane((int)stage[t][12]) & BSIG_ITEM_NEG) != 0u;
         const int pbase = __builtin_amdgcn_readfirstlane((int)stage[t][13]);
         const int pchunks = __builtin_amdgcn_readfirstlane((int)stage[t][14]);
+        int loc = 0, len = 0;
+        if constexpr (Fam::kStage > 16) {
+            loc = __builtin_amdgcn_readfirstlane((int)stage[t][16]);
+            len = __builtin_amdgcn_readfirstlane((int)stage[t][17]);
+        }
         uint32_t acc = 0;                          // (see k_count: nothing branches per read)
-        const CountOne one{P, glo, gn, acc};
+        const auto one = Fam::make(P, loc, len, glo, gn, acc);
         for_each_read<kWave, PRE>(R, P, wn, pbase, ptab, lane, one);
         if (pchunks > 1) {
             const BsigWorkItem w2 = items[first + t];
@@ -1520,6 +1680,22 @@ __global__ __launch_bounds__(kWave) void k_count_multi(const BsigWorkItem *__res
             else        { o[0] = my_sense + my_anti; }
         }
     }
+}
+template <int T, int PRE>
+__global__ __launch_bounds__(kWave) void k_count_multi(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                       int32_t *__restrict__ out,
+                                                       const uint2 *__restrict__ windows,
+                                                       const BsigReadsDev R, const BsigKParams P)
+{
+    count_multi_tiles<T, PRE, CountFamily>(items, n_tiles, out, windows, R, P);
+}
+template <int T, int PRE, bool WITHIN>
+__global__ __launch_bounds__(kWave) void k_overlap_multi(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
+                                                         int32_t *__restrict__ out,
+                                                         const uint2 *__restrict__ windows,
+                                                         const BsigReadsDev R, const BsigKParams P)
+{
+    count_multi_tiles<T, PRE, OverlapFamily<WITHIN>>(items, n_tiles, out, windows, R, P);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3304,6 +3480,23 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         BSIG_LOG("k_coverage<%d,pre=2,res=%d> acc=%d", NT, P.resolved ? 1 : 0, (int)P.accumulate);
         if (P.resolved) hipLaunchKernelGGL((k_coverage<NT, 2, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
         else hipLaunchKernelGGL((k_coverage<NT, 2, false>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
+    } else if (P.minoverlap > 0 && NT == kWave && (!windows || P.resolved) && count_tiles > 1) {
+        // bamOverlaps (a count plan never comes here: its minoverlap is 0), several tiles per wave as below, in fewer
+        // forms than the count family has: knob 1 (tiles per wave) 2 .. 7 -> 4, 8 and more -> 8 (1: the one-tile kernel);
+        // knob 2 (passes up front) up to 2 -> 2, 3 and more -> 4
+        const int T = count_tiles >= 8 ? 8 : 4;
+        const dim3 g2((unsigned)((n_items + T - 1) / T));
+#define BSIG_OM(T_, PRE_, W_) do { BSIG_LOG("k_overlap_multi<T=%d,pre=%d,within=%d> acc=%d", T_, PRE_, (int)W_, (int)P.accumulate); \
+        hipLaunchKernelGGL((k_overlap_multi<T_, PRE_, W_>), g2, dim3(kWave), 0, st, items, (uint32_t)n_items, out, windows, R, P); } while (0)
+#define BSIG_OMW(T_, PRE_) do { if (P.within) BSIG_OM(T_, PRE_, true); else BSIG_OM(T_, PRE_, false); } while (0)
+        if (count_pre <= 2) { if (T == 8) BSIG_OMW(8, 2); else BSIG_OMW(4, 2); }
+        else                { if (T == 8) BSIG_OMW(8, 4); else BSIG_OMW(4, 4); }
+#undef BSIG_OMW
+#undef BSIG_OM
+    } else if (P.minoverlap > 0) {
+        BSIG_LOG("k_overlap<%d,within=%d> acc=%d", NT, P.within ? 1 : 0, (int)P.accumulate);
+        if (P.within) hipLaunchKernelGGL((k_overlap<NT, true>), grid, block, 0, st, items, (uint32_t)n_items, out, windows, R, P);
+        else hipLaunchKernelGGL((k_overlap<NT, false>), grid, block, 0, st, items, (uint32_t)n_items, out, windows, R, P);
     } else if (NT == kWave && (!windows || P.resolved) && count_tiles > 1) {
         // several consecutive tiles per wave (the slices of heavy tiles, which come with fixed windows, and
         // the wider workgroups keep the one-tile kernel)

@@ -1441,7 +1441,8 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
 // The one rule for a plan's parameters: bsig_plan_create and bsig_plan_create_sum apply it, and the file-level calls
 // before any decode.  Of several faults the first in this order is reported: the mode; the binsize (profile >= 1,
 // coverage_ex 1 .. 65,536); the tlen filter's arity; midpoint / extend without a filter; ext < 0; ext > 2^30; threads;
-// a negative width.
+// a negative width.  The overlap modes (bamOverlaps) are bamCount's family with rules of their own, asked in this order:
+// minoverlap (the binsize field) >= 1; the filter's arity; no shift; no midpoint; extend needs the filter; ext as coverage's.
 int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out)
 {
     // coverage with bins / strands IS coverage from here on (the result layout, ext, tspan, the heavy-tile ceiling);
@@ -1449,19 +1450,24 @@ int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, Pl
     PlanRule r;
     r.cov_ex = prm.mode == BSIG_MODE_COVERAGE_EX;
     r.mode = r.cov_ex ? BSIG_MODE_COVERAGE : prm.mode;
+    r.overlap = prm.mode == BSIG_MODE_OVERLAP_ANY ? 1 : prm.mode == BSIG_MODE_OVERLAP_WITHIN ? 2 : 0;
+    if (r.overlap) r.mode = BSIG_MODE_COUNT;
     if (r.mode != BSIG_MODE_PROFILE && r.mode != BSIG_MODE_COUNT && r.mode != BSIG_MODE_COVERAGE)
         return fail(BSIG_ERR_ARG, "unknown mode %d", r.mode);
     if ((r.mode == BSIG_MODE_PROFILE || r.cov_ex) && prm.binsize < 1)
         return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");       // ref: R/wrappers.R:136-137
     if (r.cov_ex && prm.binsize > kMaxCoverageBin)
         return fail(BSIG_ERR_ARG, "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
+    if (r.overlap && prm.binsize < 1) return fail(BSIG_ERR_ARG, "minoverlap must be at least 1");
     if (prm.n_tlen_filter != 0 && prm.n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "tlen_filter must have 0 or 2 elements");
+    if (r.overlap && prm.shift != 0) return fail(BSIG_ERR_ARG, "bamOverlaps takes no shift: a read overlaps where it lies");
+    if (r.overlap && prm.pe_mid != 0) return fail(BSIG_ERR_ARG, "bamOverlaps has no midpoint rule: a fragment overlaps as a whole (extend)");
     r.mid = r.mode != BSIG_MODE_COVERAGE && prm.pe_mid;
-    r.tspan = r.mode == BSIG_MODE_COVERAGE && prm.tspan;
+    r.tspan = (r.mode == BSIG_MODE_COVERAGE || r.overlap) && prm.tspan;
     if ((r.mid || r.tspan) && prm.n_tlen_filter != 2)
         return fail(BSIG_ERR_ARG, "paired-end midpoint/extend needs a 2-element tlen_filter");
     // ext: ref src/bamsignals.cpp:457 (pileup) and :487 (coverage); :243 rejects negatives
-    if (r.mode == BSIG_MODE_COVERAGE) r.ext = r.tspan ? prm.tlen_filter[1] : 0;
+    if (r.mode == BSIG_MODE_COVERAGE || r.overlap) r.ext = r.tspan ? prm.tlen_filter[1] : 0;
     else r.ext = std::llabs((long long)prm.shift) + (r.mid ? (int64_t)prm.tlen_filter[1] : 0);
     if (r.ext < 0) return fail(BSIG_ERR_EXT, "negative 'ext' values don't make sense");
     if (r.ext > (1ll << 30)) return fail(BSIG_ERR_ARG, "shift / tlen filter too large");
@@ -1472,15 +1478,19 @@ int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, Pl
     r.binsize = r.mode == BSIG_MODE_PROFILE || r.cov_ex ? prm.binsize : 1;
     r.ss = (r.mode != BSIG_MODE_COVERAGE || r.cov_ex) && prm.ss != 0;
     r.lay_binsize = r.mode == BSIG_MODE_COUNT ? -1 : r.binsize;
+    r.minoverlap = r.overlap ? prm.binsize : 0;
     *out = r;
     return BSIG_OK;
 }
+
+// bamCount and bamOverlaps: one cell per range
+static bool count_family(int mode) { return mode == BSIG_MODE_COUNT || mode == BSIG_MODE_OVERLAP_ANY || mode == BSIG_MODE_OVERLAP_WITHIN; }
 
 // What only a sum over ranges asks, ahead of check_params: no bamCount, ranges of one width.  The sum is built on per-base
 // tiles; mode 2 ignores binsize and ss.
 int bsig::sum_shape(const bsig_params &prm, int64_t n, const int32_t *len, SumShape *out)
 {
-    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
+    if (count_family(prm.mode)) return fail(BSIG_ERR_ARG, "bamCount has no sum over ranges (its sum is one number per strand)");
     for (int64_t i = 1; i < n; ++i)
         if (len[i] != len[0]) return fail(BSIG_ERR_ARG, "all signals must have the same length");     // alignSignals
     SumShape s;
@@ -1548,7 +1558,7 @@ int bsig::frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out)
 // its widest image, and a workgroup and tile the kernel is built for.
 int bsig::hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out)
 {
-    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the depth histogram counts per-base cells: bamCount has one cell per range");
+    if (count_family(prm.mode)) return fail(BSIG_ERR_ARG, "the depth histogram counts per-base cells: bamCount has one cell per range");
     if (prm.mode == BSIG_MODE_COVERAGE_EX)
         return fail(BSIG_ERR_ARG, "the depth histogram of coverage is per base and unstranded: mode BSIG_MODE_COVERAGE");
     if (prm.mode == BSIG_MODE_PROFILE && prm.binsize != 1) return fail(BSIG_ERR_ARG, "the depth histogram is per base: binsize must be 1");
@@ -1575,7 +1585,7 @@ int bsig::hist_shape(const bsig_params &prm, int32_t max_value, HistShape *out)
 // K thresholds that rise from 1.
 int bsig::summary_shape(const bsig_params &prm, int32_t n_thresholds, const int32_t *thresholds, SummaryShape *out)
 {
-    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the range summary reduces per-base cells: bamCount has one cell per range");
+    if (count_family(prm.mode)) return fail(BSIG_ERR_ARG, "the range summary reduces per-base cells: bamCount has one cell per range");
     if (prm.mode == BSIG_MODE_COVERAGE_EX)
         return fail(BSIG_ERR_ARG, "the range summary of coverage is per base and unstranded: mode BSIG_MODE_COVERAGE");
     if (prm.mode == BSIG_MODE_PROFILE && prm.binsize != 1) return fail(BSIG_ERR_ARG, "the range summary is per base: binsize must be 1");
@@ -1609,7 +1619,7 @@ int bsig::summary_shape(const bsig_params &prm, int32_t n_thresholds, const int3
 // 1 .. BSIG_SCALED_MAX_BINS bins.
 int bsig::scaled_shape(const bsig_params &prm, int32_t n_bins, ScaledShape *out)
 {
-    if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "the scaled regions bin per-base cells: bamCount has one cell per range");
+    if (count_family(prm.mode)) return fail(BSIG_ERR_ARG, "the scaled regions bin per-base cells: bamCount has one cell per range");
     if (prm.mode == BSIG_MODE_COVERAGE_EX)
         return fail(BSIG_ERR_ARG, "the scaled regions of coverage are per base and unstranded: mode BSIG_MODE_COVERAGE");
     if (prm.mode == BSIG_MODE_PROFILE && prm.binsize != 1)
@@ -1723,6 +1733,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     K.tf0 = prm->tlen_filter[0]; K.tf1 = prm->tlen_filter[1];
     K.shift = mode == BSIG_MODE_COVERAGE ? 0 : prm->shift;
     K.midpoint = r.mid; K.tspan = r.tspan;
+    K.minoverlap = r.minoverlap; K.within = r.overlap == 2;
+    if (const char *v = getenv("BAMSIGNALS_OVERLAP_QUAD")) K.overlap_wide = r.overlap && !strcmp(v, "0");
     K.use_tlen = K.has_tlen_filter || r.mid || r.tspan;
     K.ss = r.ss;
     K.binsize = r.binsize;
@@ -1805,8 +1817,8 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     const int64_t mult = K.ss ? 2 : 1;
     // count mode: bases per workgroup (with the window's reach on both sides still one chunk of the packed
     // class's position bits: one index lookup per tile)
-    // (a frag plan's tile_cells: bases per tile, for tests of the tiles' seams)
-    const int count_split = rq.kind == kFrag && prm->tile_cells > 0 ? std::min(std::max(prm->tile_cells, 16), 1 << (BSIG_PACK_POS_BITS - 1))
+    // (a frag plan's and an overlap plan's tile_cells: bases per tile, for tests of the tiles' seams)
+    const int count_split = (rq.kind == kFrag || r.overlap) && prm->tile_cells > 0 ? std::min(std::max(prm->tile_cells, 16), 1 << (BSIG_PACK_POS_BITS - 1))
                                                       : 1 << (BSIG_PACK_POS_BITS - 1);
     // bins wider than a workgroup should stream on its own: every bin becomes bamCount-style
     // sub-intervals that add into the (zeroed) result with integer atomics

@@ -245,9 +245,11 @@ struct PlanRule {
     bool cov_ex;            // ... that coverage (binned tiles; heavy slices watch its bins for overflow)
     int32_t binsize;        // the result's bins: profile's and coverage_ex's; 1 for coverage and count
     bool ss;                // strand-split result (profile, count, coverage_ex)
-    bool mid, tspan;        // paired-end midpoint (profile, count) / extend (coverage)
+    bool mid, tspan;        // paired-end midpoint (profile, count) / extend (coverage, overlap)
     int64_t ext;            // how far beyond a range a read can count: |shift| + midpoint's tlen_filter[1], or extend's
     int32_t lay_binsize;    // bsig_layout's binsize (-1: count)
+    int overlap;            // bamOverlaps (mode is then the count family's): 0 no, 1 type "any", 2 type "within"
+    int32_t minoverlap;     // ... bases a read must share with its range (the caller's binsize field); 0 otherwise
     int threads;            // per workgroup
 };
 int check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out);

@@ -125,6 +125,27 @@ def pileup_core(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=Fals
     return _split(out, off, ss)
 
 
+def overlap_core(bampath, gr, tlen_filter, mapqual=0, within=False, min_overlap=1, ss=False, requiredF=0,
+                 filteredF=-1, tspan=False, maxgap=16385, device=None):
+    """The native entry point behind bamOverlaps (bsig_overlap_core): the int32 count vector, or the 2 x n matrix
+    (sense, antisense) with ``ss``.  ``maxgap`` is there for the shape of the other entry points; the call ignores it."""
+    _check_gr(gr)
+    lib = _lib.load()
+    levels, codes, start, width, strand = gr.flatten()
+    n = len(gr)
+    off = np.empty(n + 1, dtype=np.int64)
+    cells = lib.bsig_layout(n, width.ctypes.data, -1, int(bool(ss)), off.ctypes.data)
+    out = np.zeros(cells, dtype=np.int32)
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    _lib.check(lib.bsig_overlap_core(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels),
+                                     names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
+                                     tf.ctypes.data, len(tf), int(mapqual), int(bool(within)), int(min_overlap),
+                                     int(bool(ss)), int(requiredF), int(filteredF), int(bool(tspan)),
+                                     int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
+    return out.reshape(-1, 2).T if ss else out
+
+
 def _check_equal_widths(gr):
     """alignSignals' rule (R/zzzCountSignals.R:99-113): a sum over ranges needs ranges of one width."""
     w = np.asarray(gr.width)

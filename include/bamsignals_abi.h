@@ -48,7 +48,18 @@ enum {
  * (a '-' range is mirrored first, binned second, as bamProfile does); with ss, cell 2*bin + antisense, where sense
  * reads have the range's strand ('*' counts as '+') and paired.end = "extend" counts the fragment on the strand of
  * the read that passed the flag mask.  BSIG_MODE_COVERAGE ignores binsize and ss, as it always has.           */
-enum { BSIG_MODE_PROFILE = 0, BSIG_MODE_COUNT = 1, BSIG_MODE_COVERAGE = 2, BSIG_MODE_COVERAGE_EX = 3 };
+enum { BSIG_MODE_PROFILE = 0, BSIG_MODE_COUNT = 1, BSIG_MODE_COVERAGE = 2, BSIG_MODE_COVERAGE_EX = 3,
+       BSIG_MODE_OVERLAP_ANY = 4, BSIG_MODE_OVERLAP_WITHIN = 5 };
+/* BSIG_MODE_OVERLAP_ANY / _WITHIN (bamOverlaps): the reads -- with tspan the fragments -- that overlap each range, in
+ * bamCount's layout (bsig_layout(binsize = -1, ss)) and through the same calls (bsig_plan_create, bsig_plan_run /
+ * _run_host / _run_host_async; no runs, no reductions).  A read passes bamCoverage's filter (flags, mapqual, tlen_filter);
+ * its interval [s, e] is [pos, end], or with tspan bamCoverage's fragment (a reverse read with tlen < 0: s = end + tlen + 1;
+ * a forward read with tlen > 0: e = pos + tlen - 1).  Against range [lo, hi) = [loc, loc + len) it overlaps in
+ * ov = min(e, hi - 1) - max(s, lo) + 1 bases.  ANY counts it iff ov >= minoverlap; WITHIN iff also s >= lo and e <= hi - 1.
+ * bsig_params.binsize carries minoverlap (>= 1) in these modes; shift and pe_mid must be 0; tspan needs the 2-element
+ * tlen_filter; tile_cells = bases per workgroup, 16 .. 16,384 (0: 16,384).  With ss a counted read goes to the antisense
+ * cell iff (flag & 16 != 0) != (range strand '-'); without, the range's strand is not read.  A zero-width range counts 0.
+ * A range that holds 2^31 reads or more is not handled, as for bamCount.                                           */
 
 int bsig_abi_version(void);
 /* CPUs the library sizes its host thread pools by: hardware threads, cut down by the affinity mask and
@@ -153,13 +164,14 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
 typedef struct {
     int32_t mode;              /* BSIG_MODE_*                                                   */
     int32_t mapqual;
-    int32_t binsize;           /* profile: >= 1; coverage_ex: 1 .. 65,536; ignored otherwise    */
+    int32_t binsize;           /* profile: >= 1; coverage_ex: 1 .. 65,536; the overlap modes: minoverlap, >= 1 (the field
+                                * keeps its name and place: the struct does not grow); ignored otherwise */
     int32_t shift;
-    int32_t ss;                /* profile, count, coverage_ex                                   */
+    int32_t ss;                /* profile, count, overlap, coverage_ex                          */
     int32_t requiredF;
     int32_t filteredF;
     int32_t pe_mid;            /* profile/count: paired.end == "midpoint"                       */
-    int32_t tspan;             /* coverage:      paired.end == "extend"                         */
+    int32_t tspan;             /* coverage, overlap: paired.end == "extend"                     */
     int32_t n_tlen_filter;     /* 0 or 2 (ref: R/wrappers.R:84-98)                              */
     int32_t tlen_filter[2];
     /* tuning knobs, 0 = default */
@@ -561,6 +573,16 @@ int bsig_coverage_sum(const char *bampath, int64_t n_ranges, const int32_t *seq_
                       const int32_t *tlen_filter, int32_t n_tlen_filter,
                       int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                       int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum);
+/* bamOverlaps at file level (BSIG_MODE_OVERLAP_ANY / _WITHIN above): overlap_type 0 = any, 1 = within (anything else:
+ * BSIG_ERR_ARG); min_overlap >= 1 travels in bsig_params.binsize.  out / off as bsig_pileup_core's with binsize <= 0
+ * (bsig_layout(-1, ss)).  The parameters are checked before the BAM is opened.  Several GPUs as for bsig_pileup_core.  */
+int bsig_overlap_core(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                      int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                      const int32_t *width, const int32_t *strand,
+                      const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t overlap_type, int32_t min_overlap, int32_t ss,
+                      int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t maxgap,
+                      int32_t device, int32_t *out, const int64_t *off);
 /* The strand cross-correlation over the ranges (bsig_plan_create_xcorr): out receives max_lag + 1 + BSIG_XCORR_MOMENTS
  * int64, cross then moments.  max_lag and the parameters are checked before the BAM is decoded.  With several GPUs each
  * takes its block of the (rid, loc)-sorted ranges and the host adds the vectors (bsig_last_call_route(): "sum", as
