@@ -3350,11 +3350,12 @@ static int knob(int k)
     return g_knobs[k];
 }
 
-// The launch log (bsig_debug_launch_log, for the tests): the name of every pileup and sum-tiles kernel form launched while
-// it is on -- the kernel template, its arguments and the run-time choices that change the code path.  The names are
-// made in the dispatch macros below from the macros' own arguments, so a new branch reports itself.  Host code only; off,
-// a launch pays one load and one branch.  Multi-slot calls launch from several threads: a mutex guards the text, which
-// stops growing at 64 KB.
+// The launch log (bsig_debug_launch_log, for the tests): the name of every pileup, overlap, sum-tiles and reduction-tiles
+// (xcorr, frag, hist, summary, scaled) kernel form launched while it is on -- the kernel template, its arguments and the
+// run-time choices that change the code path.  The names are made in the dispatch macros below from the macros' own
+// arguments, so a new branch reports itself; the occupancy queries (*_blocks_per_cu) share the dispatchers and log
+// nothing.  Host code only; off, a launch pays one load and one branch.  Multi-slot calls launch from several threads: a
+// mutex guards the text, which stops growing at 64 KB.
 static std::atomic<int> g_log_on{0};
 static std::mutex g_log_mu;
 static std::string g_log_text;
@@ -3620,11 +3621,14 @@ size_t xcorr_tiles_lds(bool wide, int tile_cells, int body, int max_lag)
     return (size_t)xcorr_lds(wide, tile_cells, body, max_lag).total * 4;
 }
 
-// one k_xcorr_tiles instantiation by its run-time choices (f receives the kernel's address)
+// one k_xcorr_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
+// form's name)
 template <typename Fn>
 static hipError_t with_xcorr_kernel(int threads, bool half, bool wide, Fn &&f)
 {
-#define BSIG_XK(NT_) do { if (wide) return f(k_xcorr_tiles<NT_, false, true>); else if (half) return f(k_xcorr_tiles<NT_, true, false>); else return f(k_xcorr_tiles<NT_, false, false>); } while (0)
+#define BSIG_XK(NT_) do { if (wide) return f(k_xcorr_tiles<NT_, false, true>, "k_xcorr_tiles<" #NT_ ",half=0,wide=1>"); \
+                          if (half) return f(k_xcorr_tiles<NT_, true, false>, "k_xcorr_tiles<" #NT_ ",half=1,wide=0>"); \
+                          return f(k_xcorr_tiles<NT_, false, false>, "k_xcorr_tiles<" #NT_ ",half=0,wide=0>"); } while (0)
     if (threads == 64) BSIG_XK(64);
     if (threads == 128) BSIG_XK(128);
     if (threads == 256) BSIG_XK(256);
@@ -3636,7 +3640,7 @@ int xcorr_blocks_per_cu(int threads, bool half, int tile_cells, int body, int ma
 {
     int nb = 0;
     const size_t lds = xcorr_tiles_lds(false, tile_cells, body, max_lag);
-    const hipError_t e = with_xcorr_kernel(threads, half, false, [&](auto k) {
+    const hipError_t e = with_xcorr_kernel(threads, half, false, [&](auto k, const char *) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
     });
     return e == hipSuccess && nb > 0 ? nb : 1;
@@ -3654,7 +3658,8 @@ hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, con
                            R, Q, BSIG_MODE_PROFILE, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
     }
     const size_t lds = xcorr_tiles_lds(wide, P.tile_cells, body, max_lag);
-    return with_xcorr_kernel(threads, !wide && P.packed_half != 0, wide, [&](auto k) {
+    return with_xcorr_kernel(threads, !wide && P.packed_half != 0, wide, [&](auto k, const char *name) {
+        BSIG_LOG("%s", name);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, body, max_lag, n_cells);
         return hipGetLastError();
     });
@@ -3667,12 +3672,15 @@ size_t frag_tiles_lds(int n_rows)
     return (size_t)frag_hist_dwords(n_rows) * 4 + (frag_ltab(n_rows) ? BSIG_PACK_CODES : 0);
 }
 
-// one k_frag_tiles instantiation by its run-time choices (f receives the kernel's address)
+// one k_frag_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
+// form's name)
 template <typename Fn>
 static hipError_t with_frag_kernel(int threads, bool merge, bool ltab, Fn &&f)
 {
-#define BSIG_FK(NT_) do { if (merge) { if (ltab) return f(k_frag_tiles<NT_, true, true>); return f(k_frag_tiles<NT_, true, false>); } \
-                          if (ltab) return f(k_frag_tiles<NT_, false, true>); return f(k_frag_tiles<NT_, false, false>); } while (0)
+#define BSIG_FK(NT_) do { if (merge) { if (ltab) return f(k_frag_tiles<NT_, true, true>, "k_frag_tiles<" #NT_ ",merge=1,ltab=1>"); \
+                                       return f(k_frag_tiles<NT_, true, false>, "k_frag_tiles<" #NT_ ",merge=1,ltab=0>"); } \
+                          if (ltab) return f(k_frag_tiles<NT_, false, true>, "k_frag_tiles<" #NT_ ",merge=0,ltab=1>"); \
+                          return f(k_frag_tiles<NT_, false, false>, "k_frag_tiles<" #NT_ ",merge=0,ltab=0>"); } while (0)
     if (threads == 64) BSIG_FK(64);
     if (threads == 128) BSIG_FK(128);
     if (threads == 256) BSIG_FK(256);
@@ -3684,7 +3692,7 @@ int frag_blocks_per_cu(int threads, bool merge, int n_rows)
 {
     int nb = 0;
     const size_t lds = frag_tiles_lds(n_rows);
-    const hipError_t e = with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k) {
+    const hipError_t e = with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k, const char *) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
     });
     return e == hipSuccess && nb > 0 ? nb : 1;
@@ -3702,7 +3710,8 @@ hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, con
                            R, Q, BSIG_MODE_COUNT, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
     }
     const size_t lds = frag_tiles_lds(n_rows);
-    return with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k) {
+    return with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k, const char *name) {
+        BSIG_LOG("%s", name);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, lenbin);
         return hipGetLastError();
     });
@@ -3714,20 +3723,23 @@ size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows)
     return (size_t)hist_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells, n_rows).total * 4;
 }
 
-// one k_hist_tiles instantiation by its run-time choices (f receives the kernel's address)
+// one k_hist_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
+// form's name)
 template <typename Fn>
 static hipError_t with_hist_kernel(int threads, bool coverage, bool half, bool wide, bool merge, Fn &&f)
 {
-#define BSIG_HF(NT_, F_) do { if (coverage) { if (wide) return f(k_hist_tiles<NT_, kHistCover, true, F_>); return f(k_hist_tiles<NT_, kHistCover, false, F_>); } \
-                              if (wide) return f(k_hist_tiles<NT_, kHistEnds, true, F_>); \
-                              if (half) return f(k_hist_tiles<NT_, kHistEndsHalf, false, F_>); \
-                              return f(k_hist_tiles<NT_, kHistEnds, false, F_>); } while (0)
+#define BSIG_HN(NT_, K_, W_, F_) f(k_hist_tiles<NT_, K_, (W_) != 0, F_>, "k_hist_tiles<" #NT_ "," #K_ ",wide=" #W_ ",form=" #F_ ">")
+#define BSIG_HF(NT_, F_) do { if (coverage) { if (wide) return BSIG_HN(NT_, kHistCover, 1, F_); return BSIG_HN(NT_, kHistCover, 0, F_); } \
+                              if (wide) return BSIG_HN(NT_, kHistEnds, 1, F_); \
+                              if (half) return BSIG_HN(NT_, kHistEndsHalf, 0, F_); \
+                              return BSIG_HN(NT_, kHistEnds, 0, F_); } while (0)
 #define BSIG_HK(NT_) do { if (merge) BSIG_HF(NT_, 1); BSIG_HF(NT_, 0); } while (0)
     if (threads == 64) BSIG_HK(64);
     if (threads == 128) BSIG_HK(128);
     if (threads == 256) BSIG_HK(256);
 #undef BSIG_HK
 #undef BSIG_HF
+#undef BSIG_HN
     return hipErrorInvalidValue;
 }
 
@@ -3735,7 +3747,7 @@ int hist_blocks_per_cu(int threads, bool coverage, bool half, bool merge, int ti
 {
     int nb = 0;
     const size_t lds = hist_tiles_lds(coverage, false, tile_cells, n_rows);
-    const hipError_t e = with_hist_kernel(threads, coverage, half, false, merge, [&](auto k) {
+    const hipError_t e = with_hist_kernel(threads, coverage, half, false, merge, [&](auto k, const char *) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
     });
     return e == hipSuccess && nb > 0 ? nb : 1;
@@ -3754,7 +3766,8 @@ hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, 
                            reinterpret_cast<BsigResolved *>(windows));
     }
     const size_t lds = hist_tiles_lds(coverage, wide, P.tile_cells, n_rows);
-    return with_hist_kernel(threads, coverage, !wide && P.packed_half != 0, wide, merge, [&](auto k) {
+    return with_hist_kernel(threads, coverage, !wide && P.packed_half != 0, wide, merge, [&](auto k, const char *name) {
+        BSIG_LOG("%s", name);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, n_cells);
         return hipGetLastError();
     });
@@ -3766,18 +3779,21 @@ size_t summary_tiles_lds(bool coverage, bool wide, int tile_cells)
     return (size_t)summary_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells).total * 4;
 }
 
-// one k_summary_tiles instantiation by its run-time choices (f receives the kernel's address)
+// one k_summary_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
+// form's name)
 template <typename Fn>
 static hipError_t with_summary_kernel(int threads, bool coverage, bool half, bool wide, Fn &&f)
 {
-#define BSIG_SK(NT_) do { if (coverage) { if (wide) return f(k_summary_tiles<NT_, kHistCover, true>); return f(k_summary_tiles<NT_, kHistCover, false>); } \
-                          if (wide) return f(k_summary_tiles<NT_, kHistEnds, true>); \
-                          if (half) return f(k_summary_tiles<NT_, kHistEndsHalf, false>); \
-                          return f(k_summary_tiles<NT_, kHistEnds, false>); } while (0)
+#define BSIG_SN(NT_, K_, W_) f(k_summary_tiles<NT_, K_, (W_) != 0>, "k_summary_tiles<" #NT_ "," #K_ ",wide=" #W_ ">")
+#define BSIG_SK(NT_) do { if (coverage) { if (wide) return BSIG_SN(NT_, kHistCover, 1); return BSIG_SN(NT_, kHistCover, 0); } \
+                          if (wide) return BSIG_SN(NT_, kHistEnds, 1); \
+                          if (half) return BSIG_SN(NT_, kHistEndsHalf, 0); \
+                          return BSIG_SN(NT_, kHistEnds, 0); } while (0)
     if (threads == 64) BSIG_SK(64);
     if (threads == 128) BSIG_SK(128);
     if (threads == 256) BSIG_SK(256);
 #undef BSIG_SK
+#undef BSIG_SN
     return hipErrorInvalidValue;
 }
 
@@ -3785,7 +3801,7 @@ int summary_blocks_per_cu(int threads, bool coverage, bool half, int tile_cells)
 {
     int nb = 0;
     const size_t lds = summary_tiles_lds(coverage, false, tile_cells);
-    const hipError_t e = with_summary_kernel(threads, coverage, half, false, [&](auto k) {
+    const hipError_t e = with_summary_kernel(threads, coverage, half, false, [&](auto k, const char *) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
     });
     return e == hipSuccess && nb > 0 ? nb : 1;
@@ -3804,7 +3820,8 @@ hipError_t launch_summary_tiles(int threads, bool coverage, bool wide, const Bsi
                            reinterpret_cast<BsigResolved *>(windows));
     }
     const size_t lds = summary_tiles_lds(coverage, wide, P.tile_cells);
-    return with_summary_kernel(threads, coverage, !wide && P.packed_half != 0, wide, [&](auto k) {
+    return with_summary_kernel(threads, coverage, !wide && P.packed_half != 0, wide, [&](auto k, const char *name) {
+        BSIG_LOG("%s", name);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, T);
         return hipGetLastError();
     });
@@ -3823,22 +3840,25 @@ size_t scaled_tiles_lds(bool coverage, bool wide, int tile_cells, int rows, int 
     return (size_t)scaled_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells, rows, n_bins).total * 4;
 }
 
-// one k_scaled_tiles instantiation by its run-time choices (f receives the kernel's address)
+// one k_scaled_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
+// form's name)
 template <typename Fn>
 static hipError_t with_scaled_kernel(int threads, bool coverage, bool half, bool wide, bool seg, Fn &&f)
 {
-#define BSIG_SC(NT_) do { if (coverage) { if (wide) return f(k_scaled_tiles<NT_, kHistCover, true, false>); \
-                                          if (seg) return f(k_scaled_tiles<NT_, kHistCover, false, true>); \
-                                          return f(k_scaled_tiles<NT_, kHistCover, false, false>); } \
-                          if (wide) return f(k_scaled_tiles<NT_, kHistEnds, true, false>); \
-                          if (half) { if (seg) return f(k_scaled_tiles<NT_, kHistEndsHalf, false, true>); \
-                                      return f(k_scaled_tiles<NT_, kHistEndsHalf, false, false>); } \
-                          if (seg) return f(k_scaled_tiles<NT_, kHistEnds, false, true>); \
-                          return f(k_scaled_tiles<NT_, kHistEnds, false, false>); } while (0)
+#define BSIG_SN(NT_, K_, W_, S_) f(k_scaled_tiles<NT_, K_, (W_) != 0, (S_) != 0>, "k_scaled_tiles<" #NT_ "," #K_ ",wide=" #W_ ",seg=" #S_ ">")
+#define BSIG_SC(NT_) do { if (coverage) { if (wide) return BSIG_SN(NT_, kHistCover, 1, 0); \
+                                          if (seg) return BSIG_SN(NT_, kHistCover, 0, 1); \
+                                          return BSIG_SN(NT_, kHistCover, 0, 0); } \
+                          if (wide) return BSIG_SN(NT_, kHistEnds, 1, 0); \
+                          if (half) { if (seg) return BSIG_SN(NT_, kHistEndsHalf, 0, 1); \
+                                      return BSIG_SN(NT_, kHistEndsHalf, 0, 0); } \
+                          if (seg) return BSIG_SN(NT_, kHistEnds, 0, 1); \
+                          return BSIG_SN(NT_, kHistEnds, 0, 0); } while (0)
     if (threads == 64) BSIG_SC(64);
     if (threads == 128) BSIG_SC(128);
     if (threads == 256) BSIG_SC(256);
 #undef BSIG_SC
+#undef BSIG_SN
     return hipErrorInvalidValue;
 }
 
@@ -3846,7 +3866,7 @@ int scaled_blocks_per_cu(int threads, bool coverage, bool half, bool segmented, 
 {
     int nb = 0;
     const size_t lds = scaled_tiles_lds(coverage, false, tile_cells, rows, n_bins);
-    const hipError_t e = with_scaled_kernel(threads, coverage, half, false, segmented, [&](auto k) {
+    const hipError_t e = with_scaled_kernel(threads, coverage, half, false, segmented, [&](auto k, const char *) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
     });
     return e == hipSuccess && nb > 0 ? nb : 1;
@@ -3867,7 +3887,8 @@ hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segme
     }
     const int rows = !coverage && P.ss ? 2 : 1;
     const size_t lds = scaled_tiles_lds(coverage, wide, P.tile_cells, rows, n_bins);
-    return with_scaled_kernel(threads, coverage, !wide && P.packed_half != 0, wide, !wide && segmented, [&](auto k) {
+    return with_scaled_kernel(threads, coverage, !wide && P.packed_half != 0, wide, !wide && segmented, [&](auto k, const char *name) {
+        BSIG_LOG("%s", name);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_bins);
         return hipGetLastError();
     });
@@ -4028,7 +4049,8 @@ extern "C" int bsig_debug_set_knob(int which, int value)
 }
 
 // (debug, tests: the launch log.  buf == NULL: cap 1 turns it on, cap 0 off, either way empty.  With a buffer: the names
-// of the pileup and sum-tiles kernel forms launched since the last call, one a line, as many whole lines as fit cap
+// of the pileup, overlap, sum-tiles and reduction-tiles (k_xcorr_tiles, k_frag_tiles, k_hist_tiles, k_summary_tiles,
+// k_scaled_tiles) kernel forms launched since the last call, one a line, as many whole lines as fit cap
 // bytes with their final 0; the log is emptied.  Returns the number of names the log held.)
 extern "C" int bsig_debug_launch_log(char *buf, int cap)
 {

@@ -11,7 +11,14 @@ Reads (coordinate-sorted columns, seeded):
     ISLAND_COUNTS: a reference is its own run of 64-kbp units, so the window of a range over [1024, 3072) holds exactly
     its m reads (for_each_read's nj), and the window starts at the number of reads of that class in front of it;
   * 24 "long" islands with the counts up to 769: m reads of span 257 .. 4,096 (class 1) and m of span 4,097 .. 9,000
-    (class 2) each.
+    (class 2) each;
+  * behind them, for the reductions (tests/test_reduction_forms_gpu.py) and the 16-bit columns of span classes 0 and 1,
+    two groups of 33 islands with the counts up to 2,049 (NT - 1, NT, NT + 1 and 8 NT - 1, 8 NT, 8 NT + 1 for NT = 64,
+    128 and 256), each in a seeded order of its own: "class-0" islands of m reads of span 1 .. 256 whose flags carry bit
+    12 (0x1000 / 0x1010; a seeded half of them first of a proper pair, 0x1063 / 0x1053, with a template length of
+    +-50 .. 600) -- a flag of more than 12 bits has no code, so these stay in class 0 in the default layout too and a
+    range over [1024, 3072) has a class-0 window of exactly m reads --, and "paired" islands of m reads with the flags
+    99 / 83 and a template length, which the default layout packs.
 
 Ranges: every width of WIDTHS 16 times on the bulk references in a seeded order (all strands, one at base 0, one that
 ends on a last base, some hanging over both ends, duplicates, every width at all four values of out_off & 3), then one
@@ -24,6 +31,7 @@ import numpy as np
 ISLAND_KS = (64, 128, 256, 512, 768, 1024, 1536, 2048, 3072, 4096, 6144, 8192, 10240)
 ISLAND_COUNTS = tuple(sorted({0, 1, 2, 3, 4, 5, 7, 8, 9} | {k + d for k in ISLAND_KS for d in (-1, 0, 1)}))
 LONG_COUNTS = tuple(m for m in ISLAND_COUNTS if m <= 769)
+C0_COUNTS = tuple(m for m in ISLAND_COUNTS if m <= 2049)     # the class-0 and the paired islands (33, 19,047 reads a group)
 BULK_REFS = (70_000, 65_536, 65_537)
 BULK_READS = 20_000                      # per bulk reference
 ISLAND_LEN, ISLAND_LO, ISLAND_HI = 4096, 1024, 3072
@@ -92,6 +100,35 @@ def _island(rng, m, lo_span, hi_span):
     return pos, span, flag, np.full(m, ISLAND_MAPQ), np.zeros(m, np.int64)
 
 
+def _tlen(rng, flag):
+    """a template length of +-50 .. 600, negative for a reverse read"""
+    return rng.integers(50, 601, len(flag)) * np.where((np.asarray(flag) & 16) != 0, -1, 1)
+
+
+def _island_c0(rng, m):
+    """m reads that no layout packs (bit 12 of the flag), a seeded half of them first of a proper pair -- the island's
+    first read among them, a forward one: its 5' end lies in the island's range whatever its span"""
+    pos, span, flag, mapq, tlen = _island(rng, m, 1, 256)
+    first = rng.permutation(m) < (m + 1) // 2
+    if m:
+        # read 0 becomes a forward first-of-pair read; if it was none, the earliest one gives up its place: half stay
+        if not first[0]:
+            first[np.flatnonzero(first)[0]] = False
+            first[0] = True
+        flag[0] = 0
+    flag = np.where(first, np.where(flag != 0, 0x1053, 0x1063), 0x1000 | flag)
+    return pos, span, flag, mapq, np.where(first, _tlen(rng, flag), 0)
+
+
+def _island_paired(rng, m):
+    """m first-of-pair reads (99 forward, 83 reverse; the island's first read forward) with a template length: frequent
+    pairs, packed by default"""
+    pos, span, flag, mapq, _ = _island(rng, m, 1, 256)
+    flag[:1] = 0
+    flag = np.where(flag != 0, 83, 99)
+    return pos, span, flag, mapq, _tlen(rng, flag)
+
+
 def _permuted(rng, counts):
     """a seeded order of the islands' counts in which the reads in front of an island -- its window's start, up to the
     bulk references' share -- take every residue modulo 8"""
@@ -105,8 +142,9 @@ def _permuted(rng, counts):
 
 @functools.lru_cache(maxsize=None)
 def reads():
-    """dict(ref_len, ref_off, pos, end, flag, mapq, tlen, short_refs, long_refs, short_m, long_m): the columns, and the
-    islands' reference ids with their read counts (in reference order, a seeded permutation of the counts)."""
+    """dict(ref_len, ref_off, pos, end, flag, mapq, tlen, short_refs, long_refs, c0_refs, pair_refs, short_m, long_m, c0_m,
+    pair_m): the columns, and the islands' reference ids with their read counts (in reference order, a seeded
+    permutation of the counts)."""
     rng = np.random.default_rng(20_250)
     parts, ref_len = [], list(BULK_REFS)
     for L in BULK_REFS:
@@ -119,6 +157,15 @@ def reads():
         a, b = _island(rng, int(m), 257, 4096), _island(rng, int(m), 4097, 9000)
         parts.append(tuple(np.concatenate([x, y]) for x, y in zip(a, b)))
         ref_len.append(ISLAND_LEN)
+    # (the later groups draw from generators of their own: the reads above are what they were before these came)
+    rng0, rng4 = np.random.default_rng(20_251), np.random.default_rng(20_252)
+    c0_m, pair_m = _permuted(rng0, C0_COUNTS), _permuted(rng4, C0_COUNTS)
+    for m in c0_m:
+        parts.append(_island_c0(rng0, int(m)))
+        ref_len.append(ISLAND_LEN)
+    for m in pair_m:
+        parts.append(_island_paired(rng4, int(m)))
+        ref_len.append(ISLAND_LEN)
     cols = {k: [] for k in ("pos", "span", "flag", "mapq", "tlen")}
     counts = []
     for pos, span, flag, mapq, tlen in parts:
@@ -128,12 +175,14 @@ def reads():
         counts.append(len(pos))
     pos, span = np.concatenate(cols["pos"]), np.concatenate(cols["span"])
     nb = len(BULK_REFS)
+    first = np.cumsum([nb, len(short_m), len(long_m), len(c0_m), len(pair_m)])
     return dict(ref_len=np.asarray(ref_len, np.int32), ref_off=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64),
                 pos=pos.astype(np.int32), end=(pos + span - 1).astype(np.int32),
                 flag=np.concatenate(cols["flag"]).astype(np.uint16), mapq=np.concatenate(cols["mapq"]).astype(np.uint8),
                 tlen=np.concatenate(cols["tlen"]).astype(np.int32),
-                short_refs=np.arange(nb, nb + len(short_m)), long_refs=np.arange(nb + len(short_m), nb + len(short_m) + len(long_m)),
-                short_m=short_m, long_m=long_m)
+                short_refs=np.arange(first[0], first[1]), long_refs=np.arange(first[1], first[2]),
+                c0_refs=np.arange(first[2], first[3]), pair_refs=np.arange(first[3], first[4]),
+                short_m=short_m, long_m=long_m, c0_m=c0_m, pair_m=pair_m)
 
 
 def read_classes(packed):
@@ -171,6 +220,12 @@ def oracle_reads(mask=None):
 # ---------------------------------------------------------------------------------------------------------------
 # ranges
 # ---------------------------------------------------------------------------------------------------------------
+def island_refs():
+    """the island references in the order of their ranges: short, long, class-0, paired"""
+    c = reads()
+    return np.concatenate([c["short_refs"], c["long_refs"], c["c0_refs"], c["pair_refs"]])
+
+
 def _island_ranges(refs):
     n = len(refs)
     return dict(rid=np.asarray(refs, np.int32), loc=np.full(n, ISLAND_LO, np.int32), len=np.full(n, ISLAND_HI - ISLAND_LO, np.int32),
@@ -179,8 +234,7 @@ def _island_ranges(refs):
 
 @functools.lru_cache(maxsize=None)
 def ranges():
-    """The deck: len(WIDTHS) * COPIES ranges on the bulk references, then the islands' (short, then long)."""
-    c = reads()
+    """The deck: len(WIDTHS) * COPIES ranges on the bulk references, then the islands' (island_refs' order)."""
     for seed in range(5, 200):
         rng = np.random.default_rng(seed)
         width = rng.permutation(np.repeat(np.asarray(WIDTHS, np.int64), COPIES))
@@ -203,7 +257,7 @@ def ranges():
         k = np.flatnonzero(width == w)[-3:]
         rid[k[1:]], loc[k[1:]] = rid[k[0]], loc[k[0]]
     bulk = dict(rid=rid.astype(np.int32), loc=loc.astype(np.int32), len=width.astype(np.int32), strand=strand.astype(np.int32))
-    isl = _island_ranges(np.concatenate([c["short_refs"], c["long_refs"]]))
+    isl = _island_ranges(island_refs())
     return {k: np.concatenate([bulk[k], isl[k]]) for k in bulk}
 
 
@@ -241,13 +295,12 @@ def cut_expected(name, k):
 @functools.lru_cache(maxsize=None)
 def sum_ranges():
     """Ranges of one width for the sums: the islands' and 60 on the bulk references, strands mixed."""
-    c = reads()
     rng = np.random.default_rng(77)
     n = 60
     rid = rng.integers(0, len(BULK_REFS), n)
     loc = (rng.random(n) * (np.asarray(BULK_REFS)[rid] - SUM_WIDTH)).astype(np.int64)
     loc[:2] = (-5, 0)
-    isl = _island_ranges(np.concatenate([c["short_refs"], c["long_refs"]]))
+    isl = _island_ranges(island_refs())
     bulk = dict(rid=rid.astype(np.int32), loc=loc.astype(np.int32), len=np.full(n, SUM_WIDTH, np.int32),
                 strand=rng.choice(np.asarray([1, -1, 0], np.int32), n))
     return {k: np.concatenate([bulk[k], isl[k]]) for k in bulk}
@@ -321,3 +374,84 @@ def gpu_args(name):
     if a["binsize"] == 1 and not a["ss"]:
         return _lib.MODE_COVERAGE, {}
     return _lib.MODE_COVERAGE_EX, a
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the reductions over ranges (tests/test_reduction_forms_gpu.py): the oracle's per-base cells of the deck's ranges, reduced
+# in numpy by the reductions' own expected sides (tests/*_expected.py), once per parameter set; never a GPU plan
+# ---------------------------------------------------------------------------------------------------------------
+XCORR_MAX_LAG = 2047
+# the fragment-length histogram's shapes, by whether the pair table still fits LDS beside the rows (tlen_filter, len_bin):
+# 16,384 rows leave it no room
+FRAG_SHAPES = {0: ((0, 16383), 1), 1: ((100, 400), 7)}
+THRESHOLDS = (1, 2, 3, 5, 8, 13, 50, 1000)       # (5' ends reach 15 a cell on the deck, coverage 1,397)
+
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def _xcorr_full(mapqual):
+    import crosscorr_expected as xe
+    cross, mom = xe.expected(oracle_reads(), ranges(), XCORR_MAX_LAG, mapqual=mapqual)
+    return _frozen(cross), _frozen(mom)
+
+
+def expected_xcorr(max_lag, mapqual=0):
+    """cross[0 .. max_lag], then the five moments: lag d's sum does not depend on the largest lag asked for, so the
+    result for XCORR_MAX_LAG, computed once, holds every smaller one as a prefix"""
+    cross, mom = _xcorr_full(mapqual)
+    assert 0 <= max_lag <= XCORR_MAX_LAG
+    return np.concatenate([cross[:max_lag + 1], mom])
+
+
+def _some_ranges(which):
+    rg = ranges()
+    if which == "all":
+        return rg
+    c = reads()
+    keep = np.isin(rg["rid"], c[{"c0": "c0_refs", "paired": "pair_refs"}[which]])
+    return {k: v[keep] for k, v in rg.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def expected_frag(tlen_filter, len_bin, midpoint, which="all"):
+    """the fragment-length histogram of the deck's ranges (which: all, or the class-0 / the paired islands' alone).  No
+    template of the deck is longer than 600, which one oracle bamCount over all longer lengths confirms: the rows above
+    600 are zero without an oracle call each."""
+    import fragsizes_expected as fe
+    orc, rg = oracle_reads(), _some_ranges(which)
+    lo, hi = tlen_filter
+    if hi <= 600 * len_bin:
+        return _frozen(fe.expected(orc, rg, (lo, hi), len_bin, midpoint))
+    assert len_bin == 1 and fe.whole_count(orc, rg, (601, hi), midpoint) == 0
+    hist = np.zeros(fe.n_rows((lo, hi), len_bin), np.int64)
+    hist[:601] = fe.expected(orc, rg, (lo, 600), len_bin, midpoint)
+    return _frozen(hist)
+
+
+@functools.lru_cache(maxsize=None)
+def reduction_cells(signal, ss, mapqual=0):
+    """all per-base cells of the deck's ranges in the oracle's order: "coverage", or "ends" (5' ends, shift 0)"""
+    import depthhist_expected as de
+    return _frozen(de.cells(oracle_reads(), ranges(), signal, ss, mapqual=mapqual))
+
+
+@functools.lru_cache(maxsize=None)
+def expected_hist(signal, ss, max_value, mapqual=0):
+    import depthhist_expected as de
+    return _frozen(de.from_cells(reduction_cells(signal, ss, mapqual), max_value))
+
+
+@functools.lru_cache(maxsize=None)
+def expected_summary(signal, ss, thresholds, mapqual=0):
+    import summary_expected as se
+    return _frozen(se.from_cells(reduction_cells(signal, ss, mapqual), ranges(), ss, thresholds))
+
+
+@functools.lru_cache(maxsize=None)
+def expected_scaled(signal, ss, n_bins, mapqual=0):
+    import scaled_expected as sc
+    return _frozen(sc.from_cells(reduction_cells(signal, ss, mapqual), ranges(), ss, n_bins))

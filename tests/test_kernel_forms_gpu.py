@@ -9,7 +9,10 @@ compares it with what the cases saw: a form nobody reached fails it, and so does
 Knobs: 0 k_profile's class-0 passes in flight, 1 / 2 the count family's tiles per wave and passes, 3 the 8-wave build
 (8 always, 1 never), 4 resolve from n tiles on, 5 tiles per wave of the profile forms (1, 2, 4), 6 the half form's passes.
 The half form (k_profile_half, k_profile_multi_half) needs the packed class's 16-bit column: the layout without a packed
-class (BAMSIGNALS_PACK=0) runs the 4-byte forms only, for which it is the one that fills class 0's windows."""
+class (BAMSIGNALS_PACK=0) runs the 4-byte forms only, for which it is the one that fills class 0's windows.  On the
+default layout a half form also reads span classes 0 and 1 from their 16-bit columns (bytes_per_visit_short 2), class 0
+through the deck's class-0 islands; the layout made under BAMSIGNALS_SHORT_HALF=0 keeps those two classes on pos + fm (8)
+under the same half forms."""
 import contextlib
 import ctypes
 import os
@@ -266,24 +269,30 @@ ALL_FORMS = (
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def gpu():
-    """(context, {layout: Reads}): the deck's reads with the packed class (default) and without (BAMSIGNALS_PACK=0)"""
+    """(context, {layout: Reads}): the deck's reads with the packed class (default), with it but without the columns of
+    span classes 0 and 1 (BAMSIGNALS_SHORT_HALF=0), and without a packed class (BAMSIGNALS_PACK=0)"""
     from bamsignals_amd.device import Context, Reads
     c = deck.reads()
     ctx = Context(0)
     out = {}
-    old = os.environ.get("BAMSIGNALS_PACK")
+    switches = {"packed": None, "packed_noshort": "BAMSIGNALS_SHORT_HALF", "nopack": "BAMSIGNALS_PACK"}
+    old = {name: os.environ.get(name) for name in switches.values() if name}
     try:
-        for layout in LAYOUTS:
-            if layout == "nopack":
-                os.environ["BAMSIGNALS_PACK"] = "0"
+        for layout, name in switches.items():
+            for other in old:
+                os.environ.pop(other, None)
+            if name:
+                os.environ[name] = "0"
             out[layout] = Reads(ctx, c["ref_len"], c["ref_off"], c["pos"], c["flag"], c["mapq"], c["tlen"], end=c["end"])
     finally:
-        if old is None:
-            os.environ.pop("BAMSIGNALS_PACK", None)
-        else:
-            os.environ["BAMSIGNALS_PACK"] = old
+        for name, value in old.items():
+            if value is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = value
     info = {k: r.info() for k, r in out.items()}
     assert info["packed"]["class_n"][4] > 0 and info["nopack"]["class_n"][4] == 0
+    assert info["packed"]["class_n"][0] > 19_000 and list(info["packed_noshort"]["class_n"]) == list(info["packed"]["class_n"])
     yield ctx, out
     for r in out.values():
         r.close()
@@ -356,6 +365,9 @@ def _case(gpu, layout, name, expect, knobs, tile_cells=0, threads=0, resolved_fi
     assert set(names) == set(expect), (names, expect)
     if bpv is not None:
         assert st["bytes_per_visit_packed"] == bpv
+    if bpv == 2:                                     # a half form: classes 0 and 1 from their columns where the layout has them
+        assert st["bytes_per_visit_short"] == (8 if layout == "packed_noshort" else 2), (layout, st["bytes_per_visit_short"])
+        assert st["visits_short"] > 0
     if residue is not None:
         assert st["n_items"] % 8 == residue, st["n_items"]
     assert (st["heavy_tiles"] > 0) == heavy
@@ -369,7 +381,7 @@ def _kp(kernel, nt, ss, pre, w, res, acc=0):
 def _profile_kind(layout, kind):
     """(parameter-set prefix, bytes a packed visit, the knob of its passes in flight)"""
     if kind == "half":
-        assert layout == "packed"
+        assert layout in ("packed", "packed_noshort")
         return "half", 2, 6
     return "word", 4, 0
 
@@ -388,7 +400,7 @@ def _kernel(kind, multi=False):
 @pytest.mark.parametrize("tile", [256, 2048])
 @pytest.mark.parametrize("ss", [False, True])
 @pytest.mark.parametrize("nt", [64, 128, 256])
-@pytest.mark.parametrize("layout,kind,pre", PROFILE_KINDS)
+@pytest.mark.parametrize("layout,kind,pre", PROFILE_KINDS + [("packed_noshort", "half", p) for p in (1, 2)])
 def test_profile_one_tile_per_workgroup(gpu, layout, kind, pre, nt, ss, tile):
     """the 1-wave-budget build on narrow and wide tiles: fused, then resolved"""
     K, (pset, bpv, pre_knob) = _kernel(kind), _profile_kind(layout, kind)
@@ -417,6 +429,12 @@ def test_profile_several_tiles_per_wave(gpu, layout, kind, pre, ss, w, per_wave,
     K, (pset, bpv, pre_knob) = _kernel(kind, multi=True), _profile_kind(layout, kind)
     _case(gpu, layout, f"{pset}_ss{int(ss)}", [f"{K}<ss={int(ss)},pre={pre},w={w},T={per_wave}> acc=0"],
           {pre_knob: pre, 3: w, 5: per_wave}, tile_cells=tile, threads=64, resolved_first=True, bpv=bpv, residue=residue)
+
+
+def test_profile_several_tiles_per_wave_without_the_short_columns(gpu):
+    """k_profile_multi_half with four tiles a wave where classes 0 and 1 come from pos + fm"""
+    _case(gpu, "packed_noshort", "half_ss1", ["k_profile_multi_half<ss=1,pre=2,w=1,T=4> acc=0"], {6: 2, 3: 1, 5: 4}, tile_cells=256,
+          threads=64, resolved_first=True, bpv=2, residue=7)
 
 
 @pytest.mark.parametrize("ss", [False, True])
@@ -545,6 +563,8 @@ def test_sum_tiles(gpu, layout, pset, kind, ss, half, nw):
     assert set(names) == {form % 0, form % 1}, names
     if kind == "kSumProfile":
         assert st["bytes_per_visit_packed"] == (2 if half else 4)
+    if half:
+        assert st["bytes_per_visit_short"] == 2 and st["visits_short"] > 0
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -264,6 +264,24 @@ def _reduced(ctx, reads, rg, what):
         plan.close()
 
 
+def _reduced_expected(d, rg, what):
+    """what _reduced's plan must give: the oracle's per-base, strand-split 5' ends of the ranges, reduced in numpy by the
+    reduction's own expected side (tests/*_expected.py; the sum over ranges is the cells' sum, range by range)"""
+    import crosscorr_expected as xe
+    import depthhist_expected as de
+    import scaled_expected as sc
+    import summary_expected as se
+    if what == "sum":
+        return d.oracle("reduced", rg, binsize=1, shift=0, ss=True).astype(np.int64).reshape(len(rg["len"]), -1).sum(axis=0)
+    if what == "xcorr":
+        return xe.flat(*xe.expected(d.orc, rg, 200))
+    if what == "hist":
+        return de.expected(d.orc, rg, "ends", True, 50)
+    if what == "summary":
+        return se.expected(d.orc, rg, "ends", True, [1, 2, 5])
+    return sc.expected(d.orc, rg, "ends", True, 20)
+
+
 @pytest.mark.parametrize("what", ["sum", "xcorr", "hist", "summary", "scaled"])
 def test_reductions_take_the_columns(ctx, data, what):
     rg = _ranges(data.cols, 2000, 600, seed=17)
@@ -271,6 +289,9 @@ def test_reductions_take_the_columns(ctx, data, what):
     got8, st8 = _reduced(ctx, data.off, rg, what)
     assert st["bytes_per_visit_short"] == 2 and st8["bytes_per_visit_short"] == 8 and st["visits_short"] > 0
     assert np.array_equal(got, got8)
+    want = _reduced_expected(data, rg, what)
+    assert want.any() and got.dtype == np.int64 and got.shape == want.shape, (got.shape, want.shape)
+    assert np.array_equal(got, want), int(np.sum(got != want))
 
 
 def test_columns_after_load_and_clone(ctx, data, tmp_path, monkeypatch):
