@@ -108,6 +108,11 @@ def load():
     lib.bsig_last_call_route.restype = C.c_char_p
     lib.bsig_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(C.c_void_p)]
+    # plans of reads resized to the fragment: the fragment length between the parameters and the handle
+    # (BSIG_LIB_PATH may name a build from before them, as for bsig_overlap_core below)
+    for name in ("bsig_plan_create_resized", "bsig_plan_create_sum_resized"):
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
     lib.bsig_plan_offsets.argtypes = [C.c_void_p]
     lib.bsig_plan_offsets.restype = C.POINTER(C.c_int64)
     lib.bsig_plan_cells.argtypes = [C.c_void_p]
@@ -203,6 +208,11 @@ def load():
     lib.bsig_coverage_scaled.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
     lib.bsig_pileup_runs.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
     lib.bsig_coverage_runs.argtypes = core_head + [C.c_int32] * 8 + [C.POINTER(C.c_void_p)]
+    # ... of reads resized to the fragment: frag_len in tspan's place
+    if hasattr(lib, "bsig_coverage_core_resized"):
+        lib.bsig_coverage_core_resized.argtypes = lib.bsig_coverage_core_ex.argtypes
+        lib.bsig_coverage_sum_resized.argtypes = lib.bsig_coverage_sum.argtypes
+        lib.bsig_coverage_runs_resized.argtypes = lib.bsig_coverage_runs.argtypes
     lib.bsig_runs_result_n_seg.argtypes = [C.c_void_p]
     lib.bsig_runs_result_n_seg.restype = C.c_int64
     lib.bsig_runs_result_n_runs.argtypes = [C.c_void_p]

@@ -134,7 +134,9 @@ struct BsigKParams {
     int32_t within;         // ... 1: and the read must lie inside the range (type "within")
     int32_t overlap_wide;   // ... 1: packed reads take the per-read 64-bit body too, not OverlapOne::quad's 32-bit one
                             //   (BAMSIGNALS_OVERLAP_QUAD=0 at plan time: what scripts/overlaps_times.py compares)
-    int32_t pad_;
+    int32_t frag_len;       // bamCoverage of a resized plan (bsig_plan_create_resized): every read covers exactly this many
+                            //   bases from its 5' end in its own direction (kernels.hip: covered_interval); 0: off.  Never
+                            //   set together with tspan; asks for no tlen column (use_tlen stays the filter's)
 };
 
 // Sums over ranges (kernels.hip: k_sum_reduce): slabs [slot_lo, slot_hi) of runs of one tile position, added into the

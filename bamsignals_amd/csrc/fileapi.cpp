@@ -316,6 +316,15 @@ int scatter_segments_to(int64_t n, const int32_t *src, const int64_t *src_off, c
     return BSIG_OK;
 }
 
+// a per-range plan of a file-level call: bsig_plan_create, or for reads resized to the fragment (frag_len != 0, judged by
+// bsig::resized_rule before the BAM was opened) bsig_plan_create_resized
+int plain_plan(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc, const int32_t *len,
+               const int32_t *strand, const bsig_params &prm, int32_t frag_len, bsig_plan **plan)
+{
+    return frag_len ? bsig_plan_create_resized(ctx, reads, n, rid, loc, len, strand, &prm, frag_len, plan)
+                    : bsig_plan_create(ctx, reads, n, rid, loc, len, strand, &prm, plan);
+}
+
 // ---- several GPUs: ranges are independent (each owns its output, ref: src/bamsignals.cpp:164,181,186)
 // The (rid, loc)-sorted ranges (ref: :222-226,246) are dealt round-robin to the GPUs; every GPU plans
 // and runs its shard on its own stream, driven by its own host thread, into a shard buffer the slot
@@ -330,7 +339,7 @@ int scatter_segments_to(int64_t n, const int32_t *src, const int64_t *src_off, c
 //                 buffer, put in place by host threads (bsig_scatter_segments).
 // All device and page-locked buffers are kept in the Slots: a call on a resident BAM allocates nothing here.
 int run_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                 const int32_t *width, const int32_t *strand, const bsig_params &prm, const bsig::HostDest &dest,
+                 const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t frag_len, const bsig::HostDest &dest,
                  std::string &gather_name)
 {
     const int64_t *off = dest.off;
@@ -403,8 +412,8 @@ int run_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, c
     int rc = for_each_slot(nd, [&](size_t k) -> int {
         Shard &S = sh[k];
         SlotScratch &X = sl.scratch[k];
-        int r = bsig_plan_create(sl.ctx[k], reads[k], (int64_t)S.which.size(), S.rid.data(), S.loc.data(), S.len.data(),
-                                 S.strand.data(), &prm, &S.plan);
+        int r = plain_plan(sl.ctx[k], reads[k], (int64_t)S.which.size(), S.rid.data(), S.loc.data(), S.len.data(),
+                           S.strand.data(), prm, frag_len, &S.plan);
         if (r) return r;
         S.cells = bsig_plan_cells(S.plan);
         // every segment must fit its destination: the caller's offsets are only trusted after this check
@@ -754,7 +763,7 @@ int64_t runs_block_cells()
 // single larger range is a block of its own): a block's plan runs into a device buffer, the overflow flag is checked,
 // the buffer is encoded (runs.hip) and only the runs are downloaded.  The host puts the segments in the caller's order.
 int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                  const int32_t *width, const int32_t *strand, const bsig_params &prm, const bsig::PlanRule &rule,
+                  const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t frag_len, const bsig::PlanRule &rule,
                   bsig_runs_result &out, double *X, std::string &route)
 {
     const size_t nd = reads.size();
@@ -810,7 +819,7 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
             const double t0 = now_s();
             bsig_plan *plan = nullptr;
             bsig_runs *enc = nullptr;
-            rk = bsig_plan_create(sl.ctx[k], reads[k], (int64_t)m, r.data(), l.data(), w.data(), s.data(), &prm, &plan);
+            rk = plain_plan(sl.ctx[k], reads[k], (int64_t)m, r.data(), l.data(), w.data(), s.data(), prm, frag_len, &plan);
             if (rk == BSIG_OK && bsig_plan_cells(plan) != B.cells) rk = fail(BSIG_ERR_ARG, "a block's cells do not match its plan's");
             const double t1 = now_s();
             if (rk == BSIG_OK) rk = bsig_plan_run(plan, (int32_t *)buf);
@@ -882,7 +891,7 @@ struct FileDest {
 
 int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                const char *const *levels, const int32_t *start, const int32_t *width,
-               const int32_t *strand, const bsig_params &prm, int32_t device, const FileDest &to)
+               const int32_t *strand, const bsig_params &prm, int32_t device, const FileDest &to, int32_t frag_len = 0)
 {
     g_call_route[0] = 0;        // (a refused call has no route)
     if (!bampath) return fail(BSIG_ERR_ARG, "bampath is NULL");
@@ -911,13 +920,16 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         case Reduce::none:
             if (!to.runs) break;
             if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
-            rc = bsig::check_params(prm, n, width, &early);
+            rc = bsig::check_params(prm, n, width, &early, frag_len);
             break;
         case Reduce::sum:
             rc = bsig::sum_shape(prm, n, width, &sum);
             cells = sum.cells;
-            make_plan = [&prm](bsig_ctx *c, const bsig_reads *rd, int64_t m, const int32_t *r, const int32_t *l, const int32_t *w,
-                               const int32_t *s, bsig_plan **plan) { return bsig_plan_create_sum(c, rd, m, r, l, w, s, &prm, plan); };
+            make_plan = [&prm, frag_len](bsig_ctx *c, const bsig_reads *rd, int64_t m, const int32_t *r, const int32_t *l,
+                                         const int32_t *w, const int32_t *s, bsig_plan **plan) {
+                return frag_len ? bsig_plan_create_sum_resized(c, rd, m, r, l, w, s, &prm, frag_len, plan)
+                                : bsig_plan_create_sum(c, rd, m, r, l, w, s, &prm, plan);
+            };
             break;
         case Reduce::xcorr:
             rc = bsig::xcorr_shape(prm, to.arg, &xcorr);
@@ -1010,7 +1022,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     }
     // bsig_plan_create's rule, before any decode
     bsig::PlanRule rule;
-    rc = bsig::check_params(prm, n, width, &rule);
+    rc = bsig::check_params(prm, n, width, &rule, frag_len);
     if (rc) return rc;
     const int64_t ext = rule.ext;
     bsig::HostDest dest;
@@ -1254,18 +1266,18 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     } else if (to.reduced) {
         rc = reduced_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, cells, to.reduced, X, gather, make_plan);
     } else if (to.runs) {
-        rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, rule, *to.runs, X, gather);
+        rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, frag_len, rule, *to.runs, X, gather);
     } else if (!many) {
         // plan (ranges -> tiles in HBM), kernels, download -- timed apart
         bsig_plan *plan = nullptr;
-        rc = bsig_plan_create(slots->ctx[0], res->reads[0], n, rid.data(), loc.data(), width, strand, &prm, &plan);
+        rc = plain_plan(slots->ctx[0], res->reads[0], n, rid.data(), loc.data(), width, strand, prm, frag_len, &plan);
         X[3] = now_s() - t_run;
         if (rc == BSIG_OK && memcmp(off, bsig_plan_offsets(plan), (size_t)(n + 1) * sizeof(int64_t)) != 0)
             rc = fail(BSIG_ERR_ARG, "offsets do not match bsig_layout() for these parameters");
         if (rc == BSIG_OK) rc = bsig::plan_run_to_host(plan, &dest, false, &X[4], &X[5]);
         if (plan) bsig_plan_free(plan);
     } else {
-        rc = run_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, dest, gather);
+        rc = run_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, frag_len, dest, gather);
     }
     if (rc != BSIG_ERR_NOMEM) break;
     }
@@ -1734,6 +1746,58 @@ int bsig_coverage_sum(const char *bampath, int64_t n, const int32_t *seq_code, i
     return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand,
                       coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device,
                       FileDest::reduce(Reduce::sum, sum));
+}
+
+// bamCoverage of reads resized to the fragment: the three calls above with frag_len in tspan's place.  The length and the
+// mode are judged here (bsig::resized_rule), before file_level opens the BAM; file_level then judges the rest of the
+// parameters with the widened ext and hands frag_len to the resized plan creators on every route.
+int bsig_coverage_core_resized(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                               const char *const *levels, const int32_t *start, const int32_t *width,
+                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *out, const int64_t *off)
+{
+    (void)maxgap;
+    const bsig_params p = coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss);
+    if (const int rc = bsig::resized_rule(p, frag_len)) return rc;
+    bsig::PlanRule early;
+    if (const int rc = bsig::check_params(p, n > 0 && width ? n : 0, width, &early, frag_len)) return rc;
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, {out, off}, frag_len);
+}
+
+int bsig_coverage_sum_resized(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                              const char *const *levels, const int32_t *start, const int32_t *width,
+                              const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                              int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                              int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum)
+{
+    (void)maxgap;
+    if (!sum) return fail(BSIG_ERR_ARG, "sum is NULL");
+    const bsig_params p = coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss);
+    if (const int rc = bsig::resized_rule(p, frag_len)) return rc;
+    bsig::PlanRule early;
+    if (const int rc = bsig::check_params(p, n > 0 && width ? n : 0, width, &early, frag_len)) return rc;
+    return file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, FileDest::reduce(Reduce::sum, sum),
+                      frag_len);
+}
+
+int bsig_coverage_runs_resized(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                               const char *const *levels, const int32_t *start, const int32_t *width,
+                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result)
+{
+    (void)maxgap;
+    if (!result) return fail(BSIG_ERR_ARG, "result is NULL");
+    *result = nullptr;
+    const bsig_params p = coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss);
+    if (const int rc = bsig::resized_rule(p, frag_len)) return rc;
+    std::unique_ptr<bsig_runs_result> res(new bsig_runs_result);
+    FileDest to;
+    to.runs = res.get();
+    const int rc = file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, to, frag_len);
+    if (rc == BSIG_OK) *result = res.release();
+    return rc;
 }
 
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath)

@@ -324,9 +324,35 @@ struct SmallOne {
     }
 };
 
+// The interval [start, end] a read that passed the filter covers (ref: src/bamsignals.cpp:401-413), the one rule of
+// CoverOne, CoverBinsOne and CoverWideOne: the read as it lies, [p, e]; under P.tspan (paired.end = "extend") the
+// fragment its own tlen gives; under P.frag_len = L (a resized plan: single-end reads resized to the fragment) exactly
+// L bases from the 5' end in the read's direction -- forward [p, p + L - 1], reverse [e - L + 1, e].  Nothing is clipped at
+// the reference's last base; a reverse fragment's bases below 0 are dropped (no reference has them, so no range may
+// show them) and a forward fragment's last base saturates at INT32_MAX (a base no read reaches otherwise), which keeps
+// both sums inside int32.  P.tspan and P.frag_len are never both set (check_params).  FRAG is a TEMPLATE flag of the
+// functors and of the kernels built on them (k_coverage, k_coverage_bins, k_sum_tiles' coverage kinds; the launch picks
+// the instantiation by P.frag_len): the coverage launches are bound by their instructions and their kernels sit at the
+// scalar register file's limit, where even a uniform branch a read showed (3 - 9 % of a step, measured), so the forms
+// without the flag are, instruction for instruction, what they were before the rule existed.
+template <bool FRAG>
+__device__ __forceinline__ void covered_interval(const BsigKParams &P, int p, int e, bool neg, int tl, int &start, int &end)
+{
+    start = p; end = e;                                           // :401-403
+    if constexpr (FRAG) {
+        const int l1 = P.frag_len - 1;
+        if (neg) { const int floor0 = e < 0 ? e : 0, s = e - l1; start = s > floor0 ? s : floor0; }
+        else end = p > INT32_MAX - l1 ? INT32_MAX : p + l1;
+    } else if (P.tspan) {                                         // :404-413
+        if (neg && tl < 0) start = end + tl + 1;
+        else if (!neg && tl > 0) end = start + tl - 1;
+    }
+}
+
 // bamCoverage's per-read work (ref: src/bamsignals.cpp:392-438): +1 where the read begins to cover the tile, -1 behind
 // its last covered cell, in the tile's difference array of signed 16-bit cells (two per LDS dword: see k_coverage).
-struct CoverOne {
+template <bool FRAG>
+struct CoverOneT {
     const BsigKParams &P;
     int32_t *lds;
     int loc, c0, nc, sh;
@@ -335,11 +361,8 @@ struct CoverOne {
     __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
     {
         if (!valid || rej || tlen_rejected(P, tl)) return;            // :394-399
-        int start = p, end = e;                                       // :401-403
-        if (P.tspan) {                                                // :404-413
-            if (neg && tl < 0) start = end + tl + 1;
-            else if (!neg && tl > 0) end = start + tl - 1;
-        }
+        int start, end;
+        covered_interval<FRAG>(P, p, e, neg, tl, start, end);        // :401-413
         // covered cells [ra, rb] in range orientation (:423-436), then relative to the tile
         const int ra = neg_range ? rend1 - end : start - loc;
         const int rb = neg_range ? rend1 - start : end - loc;
@@ -364,21 +387,27 @@ struct CoverOne {
         const bool tl_rule = (P.has_tlen_filter | P.tspan) != 0;       // (uniform)
         if (neg_range) {
             const int K = rend1 - c0 - base + sh;
-            if (tl_rule) four<true, true>(w, t, b0, b1, b2, b3, dj, nj, base, K);
+            if constexpr (FRAG) four<true, true, true>(w, t, b0, b1, b2, b3, dj, nj, base, K);      // (a resized plan)
+            else if (tl_rule) four<true, true>(w, t, b0, b1, b2, b3, dj, nj, base, K);
             else four<true, false>(w, t, b0, b1, b2, b3, dj, nj, base, K);
         } else {
             const int K = base - loc - c0 + sh;
-            if (tl_rule) four<false, true>(w, t, b0, b1, b2, b3, dj, nj, base, K);
+            if constexpr (FRAG) four<false, true, true>(w, t, b0, b1, b2, b3, dj, nj, base, K);
+            else if (tl_rule) four<false, true>(w, t, b0, b1, b2, b3, dj, nj, base, K);
             else four<false, false>(w, t, b0, b1, b2, b3, dj, nj, base, K);
         }
     }
     // TL: a template-length rule applies (:398-399 the filter; :404-413 paired.end = "extend": a forward read with
     // tlen > 0 covers tlen bases from its start, a reverse one with tlen < 0 covers -tlen bases up to its end)
-    template <bool REV, bool TL>
+    // RESIZE: a resized plan (covered_interval's P.frag_len rule, from the strand bit of the table byte; no tlen is read for
+    // it: TL is set with RESIZE only so that a tlen FILTER still applies, under its own uniform flag).  Every term is taken
+    // from the chunk's base, and L <= BSIG_FRAG_LEN_MAX = 2^24 keeps each sum below 2^26 (see bsig_plan_create_resized).
+    template <bool REV, bool TL, bool RESIZE = false>
     __device__ __forceinline__ void four(const uint4 &w, const int4 &t, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, uint32_t dj,
                                          uint32_t nj, int base, int K) const
     {
         const int hi = sh + nc;
+        const int l1 = RESIZE ? P.frag_len - 1 : 0;
         auto rd = [&](uint32_t x, uint32_t b, int tl, uint32_t k) {
             const int d = (int)((x - (uint32_t)base) & (((uint32_t)1 << BSIG_PACK_POS_BITS) - 1u));
             const int sp = (int)((x >> BSIG_PACK_POS_BITS) & 0xFFu);
@@ -393,6 +422,12 @@ struct CoverOne {
                     s0 = (nm & (tl < 0 ? -1 : 0)) ? s1 : s0;
                     e0 = (~nm & (tl > 0 ? -1 : 0)) ? e1 : e0;
                 }
+            }
+            if (RESIZE) {
+                const bool rev = (b & 2u) != 0u;                           // reverse strand
+                const int s1 = e0 - l1, floor0 = -base;                    // (a packed read has pos >= 0: base 0 is at -base)
+                s0 = rev ? (s1 > floor0 ? s1 : floor0) : s0;
+                e0 = rev ? e0 : d + l1;
             }
             const int ka = REV ? K - e0 : K + s0;
             const int kb = ((REV ? K - s0 : K + e0) | rj) + 1;             // (a rejected read ends before the tile)
@@ -412,6 +447,7 @@ struct CoverOne {
         rd(w.w, b3, t.w, 3u);
     }
 };
+using CoverOne = CoverOneT<false>;
 
 struct CountOne {
     const BsigKParams &P;
@@ -704,6 +740,10 @@ struct PackedWin {
 
 // Reads of class C that can touch the genomic interval [tlo, thi) lie in [j_lo, j_hi).
 // pos in [tlo - ext - maxspan + 1, thi + ext), rounded outwards to index buckets.
+// A resized plan (P.frag_len = L, covered_interval) has ext = L - 1, and that is enough: a forward read covers
+// [pos, pos + L - 1], so one that reaches tlo has pos >= tlo - (L - 1) and one that starts before thi has pos < thi; a
+// reverse read covers [end - L + 1, end], so one that starts before thi has pos <= end < thi + L - 1, and one that
+// reaches tlo has end >= tlo, i.e. pos >= tlo - maxspan + 1, as a read that is not resized.  L below the span only trims.
 __device__ __forceinline__ bool class_window(const BsigClassCols &C, const BsigWorkItem &w,
                                              int64_t tlo, int64_t thi, int ext,
                                              uint32_t &j_lo, uint32_t &j_hi)
@@ -1708,7 +1748,7 @@ __global__ __launch_bounds__(kWave) void k_overlap_multi(const BsigWorkItem *__r
 // A tile that is not cut into slices has at most 32,767 reads in its windows (bsig_plan_create's
 // ceiling for coverage), so every cell stays inside [-32767, 32767].  4 KiB instead of 8 KiB of
 // LDS per 2,048-cell tile: 24 instead of 18 single-wave workgroups per CU.
-template <int NT, int PRE, bool RES>
+template <int NT, int PRE, bool RES, bool FRAG = false>
 __global__ __launch_bounds__(NT) void k_coverage(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
                                                  int32_t *__restrict__ out,
                                                  const uint2 *__restrict__ windows,
@@ -1739,7 +1779,7 @@ __global__ __launch_bounds__(NT) void k_coverage(const BsigWorkItem *__restrict_
     const bool neg_range = (w.units_strand & BSIG_ITEM_NEG) != 0u;
     const int rend1 = w.loc + w.len - 1;     // last base of the range
 
-    const CoverOne one{P, lds, w.loc, w.c0, w.nc, sh, neg_range, rend1};
+    const CoverOneT<FRAG> one{P, lds, w.loc, w.c0, w.nc, sh, neg_range, rend1};
     for_each_read<NT, PRE>(R, P, win, pk.base, ptab, tid, one);
     if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
     block_sync<NT>();
@@ -1796,7 +1836,7 @@ __global__ __launch_bounds__(NT) void k_coverage(const BsigWorkItem *__restrict_
 // cells, and LDS atomics to one address execute one after the other: the image is kept in P.cov_reps copies (lane l
 // adds to copy l % reps; copies lie an odd number of 16-B vectors apart, so one cell's copies sit in different banks),
 // summed when the scan reads them.
-template <bool SS>
+template <bool SS, bool FRAG = false>
 struct CoverBinsOne {
     const BsigKParams &P;
     int32_t *img;
@@ -1811,11 +1851,8 @@ struct CoverBinsOne {
     __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
     {
         if (!valid || rej || tlen_rejected(P, tl)) return;            // ref: src/bamsignals.cpp:394-399
-        int start = p, end = e;
-        if (P.tspan) {                                                // :404-413 (the fragment keeps this read's strand)
-            if (neg && tl < 0) start = end + tl + 1;
-            else if (!neg && tl > 0) end = start + tl - 1;
-        }
+        int start, end;
+        covered_interval<FRAG>(P, p, e, neg, tl, start, end);        // (a fragment keeps this read's strand)
         int ra = neg_range ? rend1 - end : start - loc;
         int rb = neg_range ? rend1 - start : end - loc;
         ra = ra > lo ? ra : lo;
@@ -1869,7 +1906,7 @@ static int cov_bins_reps(int cells)
     return r;
 }
 
-template <int NT, int PRE, bool RES, bool SS>
+template <int NT, int PRE, bool RES, bool SS, bool FRAG = false>
 __global__ __launch_bounds__(NT) void k_coverage_bins(const BsigWorkItem *__restrict__ items, uint32_t n_tiles,
                                                       int32_t *__restrict__ out,
                                                       const uint2 *__restrict__ windows,
@@ -1901,7 +1938,7 @@ __global__ __launch_bounds__(NT) void k_coverage_bins(const BsigWorkItem *__rest
     const int lo = w.c0 * P.binsize;
     const int64_t tile_end = ((int64_t)w.c0 + w.nc) * P.binsize;
     const int hi = (int)(tile_end < w.len ? tile_end : (int64_t)w.len) - 1;
-    const CoverBinsOne<SS> one{P, lds + 4 * img_vec * (lane & (reps - 1)), w.loc, w.c0, w.nc, sh, neg_range, w.loc + w.len - 1, lo, hi};
+    const CoverBinsOne<SS, FRAG> one{P, lds + 4 * img_vec * (lane & (reps - 1)), w.loc, w.c0, w.nc, sh, neg_range, w.loc + w.len - 1, lo, hi};
     for_each_read<NT, PRE>(R, P, win, pk.base, ptab, tid, one);
     if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COVERAGE, w, pk.n_chunks, clip, ptab, tid, one);
     block_sync<NT>();
@@ -1962,7 +1999,7 @@ __global__ __launch_bounds__(NT) void k_coverage_bins(const BsigWorkItem *__rest
 // magnitude) and a slice of a heavy tile less, so 65,536 tiles stay below 2^32 unsigned (2^31 signed).
 enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 };
 
-template <int NW, int KIND, bool SS, bool HALF, bool RES>
+template <int NW, int KIND, bool SS, bool HALF, bool RES, bool FRAG = false>
 __global__ __launch_bounds__(NW * kWave) void k_sum_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
                                                           int32_t *__restrict__ slab, const uint2 *__restrict__ windows,
                                                           const BsigReadsDev R, const BsigKParams P)
@@ -1997,12 +2034,12 @@ __global__ __launch_bounds__(NW * kWave) void k_sum_tiles(const BsigWorkItem *__
             for_each_read<kWave, 2, HALF>(R, P, win, pk.base, ptab, lane, one);
             if (!HALF && pk.n_chunks > 1) packed_later_chunks<kWave>(R, P, mode, w, pk.n_chunks, clip, ptab, lane, one);
         } else if constexpr (KIND == kSumCover) {
-            const CoverOne one{P, img, w.loc, w.c0, w.nc, 0, neg_range, w.loc + w.len - 1};
+            const CoverOneT<FRAG> one{P, img, w.loc, w.c0, w.nc, 0, neg_range, w.loc + w.len - 1};
             for_each_read<kWave, 2>(R, P, win, pk.base, ptab, lane, one);
             if (pk.n_chunks > 1) packed_later_chunks<kWave>(R, P, mode, w, pk.n_chunks, clip, ptab, lane, one);
         } else {
             const int hi = (w.c0 + w.nc < w.len ? w.c0 + w.nc : w.len) - 1;
-            const CoverBinsOne<true> one{P, img, w.loc, w.c0, w.nc, 0, neg_range, w.loc + w.len - 1, w.c0, hi};
+            const CoverBinsOne<true, FRAG> one{P, img, w.loc, w.c0, w.nc, 0, neg_range, w.loc + w.len - 1, w.c0, hi};
             for_each_read<kWave, 2>(R, P, win, pk.base, ptab, lane, one);
             if (pk.n_chunks > 1) packed_later_chunks<kWave>(R, P, mode, w, pk.n_chunks, clip, ptab, lane, one);
         }
@@ -2385,11 +2422,8 @@ struct CoverWideOne {
     __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
     {
         if (!valid || rej || tlen_rejected(P, tl)) return;
-        int start = p, end = e;
-        if (P.tspan) {
-            if (neg && tl < 0) start = end + tl + 1;
-            else if (!neg && tl > 0) end = start + tl - 1;
-        }
+        int start, end;
+        covered_interval<false>(P, p, e, neg, tl, start, end);       // (no reduction takes a resized plan yet)
         const int ra = neg_range ? rend1 - end : start - loc;
         const int rb = neg_range ? rend1 - start : end - loc;
         const int la = ra - c0, lb = rb - c0;
@@ -3469,8 +3503,13 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         BsigKParams Q = P;
         Q.cov_reps = cov_bins_reps(tile_cells * S);
         const size_t lds = (size_t)cov_bins_vec(tile_cells * S) * Q.cov_reps * 16 + (size_t)((S * NT / 64 + 3) / 4) * 16 + BSIG_PACK_CODES;
-#define BSIG_KB(RES_, SS_) do { BSIG_LOG("k_coverage_bins<%d,pre=2,res=%d,ss=%d> acc=%d cov_reps=%d", NT, (int)RES_, (int)SS_, (int)Q.accumulate, (int)Q.cov_reps); \
-        hipLaunchKernelGGL((k_coverage_bins<NT, 2, RES_, SS_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, Q); } while (0)
+        // (a resized plan, P.frag_len != 0, has instantiations of its own -- covered_interval says why -- and names them)
+#define BSIG_KB(RES_, SS_) do { if (P.frag_len) { \
+            BSIG_LOG("k_coverage_bins<%d,pre=2,res=%d,ss=%d,frag=1> acc=%d cov_reps=%d", NT, (int)RES_, (int)SS_, (int)Q.accumulate, (int)Q.cov_reps); \
+            hipLaunchKernelGGL((k_coverage_bins<NT, 2, RES_, SS_, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, Q); \
+        } else { \
+            BSIG_LOG("k_coverage_bins<%d,pre=2,res=%d,ss=%d> acc=%d cov_reps=%d", NT, (int)RES_, (int)SS_, (int)Q.accumulate, (int)Q.cov_reps); \
+            hipLaunchKernelGGL((k_coverage_bins<NT, 2, RES_, SS_>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, Q); } } while (0)
         if (ss) { if (P.resolved) BSIG_KB(true, true); else BSIG_KB(false, true); }
         else    { if (P.resolved) BSIG_KB(true, false); else BSIG_KB(false, false); }
 #undef BSIG_KB
@@ -3478,6 +3517,12 @@ static hipError_t launch_mode(int mode, int ss, const BsigReadsDev &R, const Bsi
         const size_t lds = (size_t)((tile_cells + 8 + 7) / 8) * 16 + (size_t)((NT / 64 + 3) / 4) * 16 + BSIG_PACK_CODES;   // signed 16-bit cells, scan totals, the packed class's table
         // (the packed class's passes hold 256 reads each: two in flight cover a 2-kb tile at 100-fold coverage; the form
         // for resolved windows has no lookup code in it)
+        if (P.frag_len) {
+            BSIG_LOG("k_coverage<%d,pre=2,res=%d,frag=1> acc=%d", NT, P.resolved ? 1 : 0, (int)P.accumulate);
+            if (P.resolved) hipLaunchKernelGGL((k_coverage<NT, 2, true, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
+            else hipLaunchKernelGGL((k_coverage<NT, 2, false, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
+            return hipGetLastError();
+        }
         BSIG_LOG("k_coverage<%d,pre=2,res=%d> acc=%d", NT, P.resolved ? 1 : 0, (int)P.accumulate);
         if (P.resolved) hipLaunchKernelGGL((k_coverage<NT, 2, true>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
         else hipLaunchKernelGGL((k_coverage<NT, 2, false>), grid, block, lds, st, items, (uint32_t)n_items, out, windows, R, P);
@@ -3539,20 +3584,26 @@ size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells)
 // one k_sum_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
 // form's name as a format of its two flags)
 template <typename Fn>
-static hipError_t with_sum_kernel(int kind, int ss, int nw, bool half, bool res, Fn &&f)
+static hipError_t with_sum_kernel(int kind, int ss, int nw, bool half, bool res, Fn &&f, bool frag = false)
 {
 #define BSIG_SK(NW_, K_, SS_, H_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, H_, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=1>", (int)SS_, (int)H_); \
                                         else return f(k_sum_tiles<NW_, K_, SS_, H_, false>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=0>", (int)SS_, (int)H_); } while (0)
+// (the coverage kinds of a resized plan: instantiations of their own, see covered_interval)
+#define BSIG_SKF(NW_, K_, SS_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, false, true, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=1,frag=1>", (int)SS_, 0); \
+                                     else return f(k_sum_tiles<NW_, K_, SS_, false, false, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=0,frag=1>", (int)SS_, 0); } while (0)
+#define BSIG_SKFN(K_, SS_) do { if (nw == 1) BSIG_SKF(1, K_, SS_); else if (nw == 2) BSIG_SKF(2, K_, SS_); else BSIG_SKF(4, K_, SS_); } while (0)
 #define BSIG_SKN(K_, SS_, H_) do { if (nw == 1) BSIG_SK(1, K_, SS_, H_); else if (nw == 2) BSIG_SK(2, K_, SS_, H_); else BSIG_SK(4, K_, SS_, H_); } while (0)
     if (nw != 1 && nw != 2 && nw != 4) return hipErrorInvalidValue;
     if (kind == kSumProfile) {
         if (ss) { if (half) BSIG_SKN(kSumProfile, true, true); else BSIG_SKN(kSumProfile, true, false); }
         else    { if (half) BSIG_SKN(kSumProfile, false, true); else BSIG_SKN(kSumProfile, false, false); }
     } else if (kind == kSumCover) {
-        BSIG_SKN(kSumCover, false, false);
+        if (frag) BSIG_SKFN(kSumCover, false); else BSIG_SKN(kSumCover, false, false);
     } else if (kind == kSumCoverSS) {
-        BSIG_SKN(kSumCoverSS, true, false);
+        if (frag) BSIG_SKFN(kSumCoverSS, true); else BSIG_SKN(kSumCoverSS, true, false);
     }
+#undef BSIG_SKFN
+#undef BSIG_SKF
 #undef BSIG_SKN
 #undef BSIG_SK
     return hipErrorInvalidValue;
@@ -3585,7 +3636,7 @@ hipError_t launch_sum_tiles(int kind, int ss, int nw, const BsigReadsDev &R, con
         BSIG_LOG(name, s_, h_);
         hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(nw * kWave), lds, st, items, runs, slab, (const uint2 *)windows, R, P);
         return hipGetLastError();
-    });
+    }, P.frag_len != 0);
     return e;
 }
 

@@ -1443,7 +1443,8 @@ int bsig_reads_load(bsig_ctx *ctx, const char *path, const char *stamp, bsig_rea
 // coverage_ex 1 .. 65,536); the tlen filter's arity; midpoint / extend without a filter; ext < 0; ext > 2^30; threads;
 // a negative width.  The overlap modes (bamOverlaps) are bamCount's family with rules of their own, asked in this order:
 // minoverlap (the binsize field) >= 1; the filter's arity; no shift; no midpoint; extend needs the filter; ext as coverage's.
-int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out)
+// frag_len (a resized plan's; resized_rule has judged it ahead of this rule) only widens ext to frag_len - 1.
+int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out, int32_t frag_len)
 {
     // coverage with bins / strands IS coverage from here on (the result layout, ext, tspan, the heavy-tile ceiling);
     // only binsize, ss and cov_ex tell it apart (mode 2 ignores binsize and ss)
@@ -1467,7 +1468,10 @@ int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, Pl
     if ((r.mid || r.tspan) && prm.n_tlen_filter != 2)
         return fail(BSIG_ERR_ARG, "paired-end midpoint/extend needs a 2-element tlen_filter");
     // ext: ref src/bamsignals.cpp:457 (pileup) and :487 (coverage); :243 rejects negatives
-    if (r.mode == BSIG_MODE_COVERAGE || r.overlap) r.ext = r.tspan ? prm.tlen_filter[1] : 0;
+    // a resized plan (resized_rule: coverage, no tspan): a read counts up to frag_len - 1 bases beyond itself, on the side
+    // its strand says -- see the argument at class_window (kernels.hip)
+    r.frag_len = r.mode == BSIG_MODE_COVERAGE && !r.tspan ? frag_len : 0;
+    if (r.mode == BSIG_MODE_COVERAGE || r.overlap) r.ext = r.tspan ? prm.tlen_filter[1] : r.frag_len ? r.frag_len - 1 : 0;
     else r.ext = std::llabs((long long)prm.shift) + (r.mid ? (int64_t)prm.tlen_filter[1] : 0);
     if (r.ext < 0) return fail(BSIG_ERR_EXT, "negative 'ext' values don't make sense");
     if (r.ext > (1ll << 30)) return fail(BSIG_ERR_ARG, "shift / tlen filter too large");
@@ -1480,6 +1484,19 @@ int bsig::check_params(const bsig_params &prm, int64_t n, const int32_t *len, Pl
     r.lay_binsize = r.mode == BSIG_MODE_COUNT ? -1 : r.binsize;
     r.minoverlap = r.overlap ? prm.binsize : 0;
     *out = r;
+    return BSIG_OK;
+}
+
+// What only a resized plan asks, ahead of check_params: bamCoverage (either mode), whose reads are not already extended to
+// their own template length, and a fragment length the packed class's 32-bit sums hold.
+int bsig::resized_rule(const bsig_params &prm, int32_t frag_len)
+{
+    if (prm.mode != BSIG_MODE_COVERAGE && prm.mode != BSIG_MODE_COVERAGE_EX)
+        return fail(BSIG_ERR_ARG, "reads are resized to the fragment for bamCoverage only (mode %d given)", prm.mode);
+    if (prm.tspan != 0)
+        return fail(BSIG_ERR_ARG, "a paired-end fragment already has its length: tspan must be 0 with a fragment length");
+    if (frag_len < 1 || frag_len > BSIG_FRAG_LEN_MAX)
+        return fail(BSIG_ERR_ARG, "the fragment length must be between 1 and %d (%d given)", BSIG_FRAG_LEN_MAX, frag_len);
     return BSIG_OK;
 }
 
@@ -1656,6 +1673,7 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
 // kSummary, kScaled: the same tiles, each carrying its range's result row
 struct PlanRequest {
     PlanKind kind = kPlain;
+    int32_t frag_len = 0;           // kPlain, kSum: a resized plan's fragment length (bsig::resized_rule passed), else 0
     union {
         const void *none = nullptr;
         const bsig::SumShape *sum;
@@ -1681,7 +1699,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     *out = nullptr;
     if (n < 0 || (n > 0 && (!rid || !loc || !len || !strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
     bsig::PlanRule r;
-    if (const int rc = bsig::check_params(*prm, n, len, &r)) return rc;
+    if (const int rc = bsig::check_params(*prm, n, len, &r, rq.frag_len)) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (rid[i] < 0 || rid[i] >= reads->n_ref) return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", rid[i]);
     const int mode = r.mode;
@@ -1733,6 +1751,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     K.tf0 = prm->tlen_filter[0]; K.tf1 = prm->tlen_filter[1];
     K.shift = mode == BSIG_MODE_COVERAGE ? 0 : prm->shift;
     K.midpoint = r.mid; K.tspan = r.tspan;
+    K.frag_len = r.frag_len;        // (no tlen column for it: use_tlen below stays the filter's)
     K.minoverlap = r.minoverlap; K.within = r.overlap == 2;
     if (const char *v = getenv("BAMSIGNALS_OVERLAP_QUAD")) K.overlap_wide = r.overlap && !strcmp(v, "0");
     K.use_tlen = K.has_tlen_filter || r.mid || r.tspan;
@@ -2328,6 +2347,21 @@ int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const in
     return plan_create_impl(ctx, reads, n, rid, loc, len, strand, prm, PlanRequest{}, out);
 }
 
+// A resized plan is an ORDINARY plan whose reads cover frag_len bases from their 5' end (kernels.hip: covered_interval):
+// only the rule's frag_len and the window's ext differ.  The packed class takes every sum from its chunk's base, which
+// lies within ext + maxspan + a bucket of the tile: with frag_len <= BSIG_FRAG_LEN_MAX = 2^24 all of them stay below 2^26.
+int bsig_plan_create_resized(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
+                             const int32_t *loc, const int32_t *len, const int32_t *strand,
+                             const bsig_params *prm, int32_t frag_len, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_resized");
+    *out = nullptr;
+    if (const int rc = bsig::resized_rule(*prm, frag_len)) return rc;
+    PlanRequest rq;
+    rq.frag_len = frag_len;
+    return plan_create_impl(ctx, reads, n, rid, loc, len, strand, prm, rq, out);
+}
+
 const int64_t *bsig_plan_offsets(const bsig_plan *p) { return p ? p->off.data() : nullptr; }
 
 int64_t bsig_plan_cells(const bsig_plan *p) { return p ? p->off.back() : 0; }
@@ -2565,20 +2599,38 @@ int bsig_plan_get_stats(bsig_plan *p, bsig_plan_stats *s)
 
 void bsig_plan_free(bsig_plan *p) { delete p; }
 
+// bsig_plan_create_sum (frag_len 0) and bsig_plan_create_sum_resized (frag_len judged by resized_rule)
+static int plan_create_sum_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                                const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t frag_len, bsig_plan **out)
+{
+    if (n < 0 || (n > 0 && !len)) return fail(BSIG_ERR_ARG, "range arrays missing");
+    bsig::SumShape shape;
+    bsig::PlanRule caller;          // (the caller's binsize and threads; the per-base tiles' are the plan's)
+    int rc = bsig::sum_shape(*prm, n, len, &shape);
+    if (rc == BSIG_OK) rc = bsig::check_params(*prm, n, len, &caller, frag_len);
+    PlanRequest rq;
+    rq.kind = kSum;
+    rq.frag_len = frag_len;
+    rq.sum = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
+}
+
 int bsig_plan_create_sum(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
                          const int32_t *len, const int32_t *strand, const bsig_params *prm, bsig_plan **out)
 {
     if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_sum");
     *out = nullptr;
-    if (n < 0 || (n > 0 && !len)) return fail(BSIG_ERR_ARG, "range arrays missing");
-    bsig::SumShape shape;
-    bsig::PlanRule caller;          // (the caller's binsize and threads; the per-base tiles' are the plan's)
-    int rc = bsig::sum_shape(*prm, n, len, &shape);
-    if (rc == BSIG_OK) rc = bsig::check_params(*prm, n, len, &caller);
-    PlanRequest rq;
-    rq.kind = kSum;
-    rq.sum = &shape;
-    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
+    return plan_create_sum_impl(ctx, reads, n, rid, loc, len, strand, prm, 0, out);
+}
+
+int bsig_plan_create_sum_resized(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                                 const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t frag_len,
+                                 bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_sum_resized");
+    *out = nullptr;
+    if (const int rc = bsig::resized_rule(*prm, frag_len)) return rc;
+    return plan_create_sum_impl(ctx, reads, n, rid, loc, len, strand, prm, frag_len, out);
 }
 
 int bsig_plan_create_xcorr(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,

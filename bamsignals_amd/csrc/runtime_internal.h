@@ -246,13 +246,19 @@ struct PlanRule {
     int32_t binsize;        // the result's bins: profile's and coverage_ex's; 1 for coverage and count
     bool ss;                // strand-split result (profile, count, coverage_ex)
     bool mid, tspan;        // paired-end midpoint (profile, count) / extend (coverage, overlap)
-    int64_t ext;            // how far beyond a range a read can count: |shift| + midpoint's tlen_filter[1], or extend's
+    int32_t frag_len;       // a resized plan (coverage): bases every read covers from its 5' end; 0: off
+    int64_t ext;            // how far beyond a range a read can count: |shift| + midpoint's tlen_filter[1], or extend's; a
+                            // resized plan's frag_len - 1
     int32_t lay_binsize;    // bsig_layout's binsize (-1: count)
     int overlap;            // bamOverlaps (mode is then the count family's): 0 no, 1 type "any", 2 type "within"
     int32_t minoverlap;     // ... bases a read must share with its range (the caller's binsize field); 0 otherwise
     int threads;            // per workgroup
 };
-int check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out);
+// frag_len: what a resized plan's creator was given (resized_rule has judged it), 0 for every other plan
+int check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out, int32_t frag_len = 0);
+// what only a resized plan asks, ahead of check_params (runtime.hip: resized_rule): a coverage mode, no paired-end
+// extension, 1 <= frag_len <= BSIG_FRAG_LEN_MAX
+int resized_rule(const bsig_params &prm, int32_t frag_len);
 // what only a sum over ranges asks (runtime.hip: sum_shape)
 struct SumShape {
     bsig_params tiles;      // the per-base plan the sum is built on

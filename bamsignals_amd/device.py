@@ -282,12 +282,17 @@ class _PlanBase:
 
 
 class Plan(_PlanBase):
-    """Ranges + call parameters resident in HBM; run it any number of times."""
+    """Ranges + call parameters resident in HBM; run it any number of times.  ``frag_len`` (a coverage mode only, 1 ..
+    2**24; 0: off): every read covers exactly that many bases from its 5' end in its own direction
+    (bsig_plan_create_resized) -- an ordinary plan in every other respect."""
 
-    def __init__(self, ctx, reads, rid, loc, length, strand, params):
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, frag_len=0):
         n, ptrs = self._ranges(ctx, reads, rid, loc, length, strand)
         h = C.c_void_p()
-        _lib.check(self._lib.bsig_plan_create(ctx._h, reads._h, n, *ptrs, C.byref(params), C.byref(h)))
+        if frag_len:
+            _lib.check(self._lib.bsig_plan_create_resized(ctx._h, reads._h, n, *ptrs, C.byref(params), int(frag_len), C.byref(h)))
+        else:
+            _lib.check(self._lib.bsig_plan_create(ctx._h, reads._h, n, *ptrs, C.byref(params), C.byref(h)))
         self._h = h
         self.cells = int(self._lib.bsig_plan_cells(h))
         self.offsets = np.ctypeslib.as_array(self._lib.bsig_plan_offsets(h), shape=(n + 1,)).copy()
@@ -328,11 +333,12 @@ class _ReducedPlan(_PlanBase):
 
     _KIND = None
 
-    def _create(self, ctx, reads, rid, loc, length, strand, params, *extra):
-        """``extra``: the kind's own int32 arguments, between the parameters and the handle."""
+    def _create(self, ctx, reads, rid, loc, length, strand, params, *extra, variant=""):
+        """``extra``: the kind's own int32 arguments, between the parameters and the handle; ``variant``: a suffix of the
+        kind's create call (``"_resized"``)."""
         n, ptrs = self._ranges(ctx, reads, rid, loc, length, strand)
         h = C.c_void_p()
-        create = getattr(self._lib, f"bsig_plan_create_{self._KIND}")
+        create = getattr(self._lib, f"bsig_plan_create_{self._KIND}{variant}")
         _lib.check(create(ctx._h, reads._h, n, *ptrs, C.byref(params), *extra, C.byref(h)))
         self._h = h
         self.cells = int(getattr(self._lib, f"bsig_plan_{self._KIND}_cells")(h))
@@ -355,12 +361,16 @@ class _ReducedPlan(_PlanBase):
 class SumPlan(_ReducedPlan):
     """Ranges of one width + call parameters resident in HBM, summed over the ranges (bsig_plan_create_sum): each run
     gives the int64 sum of what ``Plan`` returns for the ranges, cell by cell -- ``n_bins`` cells, or ``2 x n_bins``
-    (cell ``2 * bin + antisense``) with strands.  ``params.threads`` 64 / 128 / 256: tiles in flight per workgroup."""
+    (cell ``2 * bin + antisense``) with strands.  ``params.threads`` 64 / 128 / 256: tiles in flight per workgroup.
+    ``frag_len`` as for ``Plan`` (bsig_plan_create_sum_resized)."""
 
     _KIND = "sum"
 
-    def __init__(self, ctx, reads, rid, loc, length, strand, params):
-        self._create(ctx, reads, rid, loc, length, strand, params)
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, frag_len=0):
+        if frag_len:
+            self._create(ctx, reads, rid, loc, length, strand, params, int(frag_len), variant="_resized")
+        else:
+            self._create(ctx, reads, rid, loc, length, strand, params)
 
 
 class XcorrPlan(_ReducedPlan):

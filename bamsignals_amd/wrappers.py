@@ -179,8 +179,9 @@ def pileup_sum(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False
 
 
 def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                 maxgap=16385, device=None, *, binsize=1, ss=False):
-    """bamCoverage's signals summed over the ranges (bsig_coverage_sum): int64, ``(n_bins,)`` or ``(2, n_bins)``."""
+                 maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+    """bamCoverage's signals summed over the ranges (bsig_coverage_sum): int64, ``(n_bins,)`` or ``(2, n_bins)``.
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_sum_resized)."""
     _check_gr(gr)
     w = _check_equal_widths(gr)
     lib = _lib.load()
@@ -190,11 +191,22 @@ def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1,
     out = np.zeros(n_bins * (2 if ss else 1), dtype=np.int64)
     tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
     names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_coverage_sum(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names,
-                                     start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
-                                     int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap),
-                                     _dev(device), int(binsize), int(bool(ss)), out.ctypes.data))
+    fn, rule = _coverage_rule(lib, "sum", tspan, frag_len)
+    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names,
+                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
+                  int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap),
+                  _dev(device), int(binsize), int(bool(ss)), out.ctypes.data))
     return _sum_shape(out, ss)
+
+
+def _coverage_rule(lib, what, tspan, frag_len):
+    """The file-level coverage call of a kind (``core_ex`` / ``sum`` / ``runs``) and the int32 that travels in its
+    interval-rule slot: ``tspan``, or with ``frag_len`` the resized call (bsig_coverage_<what>_resized) and the length."""
+    if frag_len:
+        if tspan:
+            raise ValueError("a paired-end fragment already has its length: frag_len excludes tspan")
+        return getattr(lib, "bsig_coverage_" + ("core" if what == "core_ex" else what) + "_resized"), int(frag_len)
+    return getattr(lib, "bsig_coverage_" + what), int(bool(tspan))
 
 
 def pileup_xcorr(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, max_lag=500, maxgap=16385, device=None):
@@ -361,18 +373,20 @@ def pileup_runs(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=Fals
 
 
 def coverage_runs(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                  maxgap=16385, device=None, *, binsize=1, ss=False):
-    """bamCoverage's signals as runs (bsig_coverage_runs): a RunSignals; the per-base cells stay on the GPU."""
+                  maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+    """bamCoverage's signals as runs (bsig_coverage_runs): a RunSignals; the per-base cells stay on the GPU.
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_runs_resized)."""
     _check_gr(gr)
     lib = _lib.load()
     levels, codes, start, width, strand = gr.flatten()
     tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
     names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
     h = C.c_void_p()
-    _lib.check(lib.bsig_coverage_runs(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
-                                      start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
-                                      int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap),
-                                      _dev(device), int(binsize), int(bool(ss)), C.byref(h)))
+    fn, rule = _coverage_rule(lib, "runs", tspan, frag_len)
+    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
+                  int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap),
+                  _dev(device), int(binsize), int(bool(ss)), C.byref(h)))
     return _take_runs(lib, h, ss)
 
 
@@ -382,14 +396,15 @@ def _is_ex(binsize, ss):
 
 
 def coverage_core(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                  maxgap=16385, device=None, *, binsize=1, ss=False):
+                  maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
     """The native entry point behind bamCoverage (ref: R/RcppExports.R:16-18).  ``binsize`` / ``ss``:
-    per-base coverage summed over bins / split into sense and antisense rows (bsig_coverage_core_ex)."""
+    per-base coverage summed over bins / split into sense and antisense rows (bsig_coverage_core_ex).
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_core_resized, whatever the bins)."""
     _check_gr(gr)
     lib = _lib.load()
     levels, codes, start, width, strand = gr.flatten()
     n = len(gr)
-    ex = _is_ex(binsize, ss)
+    ex = _is_ex(binsize, ss) or bool(frag_len)
     off = np.empty(n + 1, dtype=np.int64)
     cells = lib.bsig_layout(n, width.ctypes.data, int(binsize) if ex else 1, int(bool(ss)) if ex else 0, off.ctypes.data)
     out = np.zeros(cells, dtype=np.int32)
@@ -397,11 +412,12 @@ def coverage_core(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1
     names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
     head = (os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names, start.ctypes.data,
             width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual), int(requiredF),
-            int(filteredF), int(bool(tspan)), int(maxgap), _dev(device))
+            int(filteredF))
     if ex:
-        _lib.check(lib.bsig_coverage_core_ex(*head, int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
+        fn, rule = _coverage_rule(lib, "core_ex", tspan, frag_len)
+        _lib.check(fn(*head, rule, int(maxgap), _dev(device), int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
     else:
-        _lib.check(lib.bsig_coverage_core(*head, out.ctypes.data, off.ctypes.data))
+        _lib.check(lib.bsig_coverage_core(*head, int(bool(tspan)), int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
     return _split(out, off, ex and bool(ss))
 
 
@@ -542,8 +558,26 @@ def _coverage_binsize(binsize):
     return b
 
 
+# longest fragment reads are resized to (include/bamsignals_abi.h, BSIG_FRAG_LEN_MAX)
+MAX_FRAG_LENGTH = 1 << 24
+
+
+def _frag_length(fragLength):  # noqa: N803
+    if fragLength is None:
+        return 0
+    if isinstance(fragLength, (bool, np.bool_)) or not isinstance(fragLength, (int, float, np.integer, np.floating)) \
+            or not float(fragLength).is_integer():
+        raise ValueError("fragLength must be a whole number of bases")
+    f = int(fragLength)
+    if f < 1:
+        raise ValueError("fragLength must be at least 1")
+    if f > MAX_FRAG_LENGTH:
+        raise ValueError(f"fragLength must be at most {MAX_FRAG_LENGTH}")
+    return f
+
+
 def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFilter=None,  # noqa: N802,N803
-                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False, runs=False):
+                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False, runs=False, fragLength=None):
     """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173).
 
     ``binsize`` (1 .. 65,536): bin j of a range covers its bases [j*binsize, min((j+1)*binsize, width)) in range
@@ -556,9 +590,23 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     A bin whose sum would exceed 2^31 - 1 raises BsigError.  The defaults are the reference's call.
     ``aggregate=True``: the int64 sum over ranges of one width, as in ``bamProfile``.
     ``runs=True``: a RunSignals instead of a CountSignals, as in ``bamProfile`` -- the form of an RleList or a bedGraph
-    (``sig.to_bedgraph``); a whole-genome track without its 4 bytes per base in host memory.  Not with ``aggregate``."""
+    (``sig.to_bedgraph``); a whole-genome track without its 4 bytes per base in host memory.  Not with ``aggregate``.
+    ``fragLength=L`` (a whole number in 1 .. 2**24; ``None``: the read as it lies): single-end reads resized to the
+    fragment, the signal of MACS ``--extsize``, deepTools ``--extendReads N``, csaw ``ext`` and
+    ``coverage(resize(reads, L, fix="start"))``.  A read that passes the filter covers exactly ``L`` bases from its 5' end
+    in its own direction: forward (flag & 16 == 0) ``[pos, pos + L - 1]``, reverse ``[end - L + 1, end]``, ``pos`` and
+    ``end`` its first and last aligned base.  ``L`` below the read's length trims it, ``L = 1`` is its 5' end.  Nothing
+    is clipped at the reference's last base (a range that overhangs it sees the overhang of a forward fragment); bases
+    below 0 exist in no range.  With ``ss`` the fragment counts on the read's own strand; ``binsize``, ``aggregate``
+    and ``runs`` work on it as on plain coverage.  ``paired_end`` must be ``"ignore"``: a paired-end fragment already
+    has its length (``"extend"``).  The length comes from the data:
+    ``fragLength=bamCrossCorr(...).fragment_length()``."""
     if runs and aggregate:
         raise ValueError("runs=True and aggregate=True exclude each other: a sum over ranges has no per-range runs")
+    frag = _frag_length(fragLength)
+    if frag and _match_arg(paired_end, ("ignore", "extend"), "paired.end") != "ignore":
+        raise ValueError('fragLength resizes single-end reads: with paired_end="extend" a fragment already has its length, '
+                         "its template length (use one or the other)")
     if verbose:
         _print_sentence(bampath)
     b = _coverage_binsize(binsize)
@@ -571,10 +619,10 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     pe = _match_arg(paired_end, ("ignore", "extend"), "paired.end")
     if aggregate:
         return coverage_sum(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                            flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
+                            flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
     if runs:
         return coverage_runs(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                             flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
+                             flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
     pu = coverage_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                       flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss))
+                       flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
     return CountSignals(pu, bool(ss), _trusted=True)

@@ -208,6 +208,25 @@ typedef struct {
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
                      const int32_t *rid, const int32_t *loc, const int32_t *len,
                      const int32_t *strand, const bsig_params *params, bsig_plan **plan);
+/* bamCoverage of single-end reads RESIZED TO THE FRAGMENT (MACS --extsize, deepTools --extendReads N, csaw ext,
+ * coverage(resize(reads, N, fix = "start"))): with frag_len = L, a read that passes bamCoverage's filter (flags, mapqual,
+ * the tlen filter if one is given) covers exactly L bases from its 5' end in its own direction -- forward (flag & 16 == 0)
+ * [pos, pos + L - 1], reverse [end - L + 1, end], pos and end its first and last aligned base.  L below the read's span
+ * trims it; L = 1 is the 5' end.  Nothing is clipped at the reference's last base (a range that overhangs it sees the
+ * overhang of a forward fragment); bases below 0 exist in no range.  With ss the fragment counts on the read's own
+ * strand, sense and antisense as BSIG_MODE_COVERAGE_EX defines them; bins, mirrored '-' ranges, the INT32_MAX bin check,
+ * runs and sums are plain coverage's.  The length travels as an argument (bsig_params does not grow), the way max_lag,
+ * max_value and n_bins do: L comes from the data as bsig_plan_create_xcorr's best lag.
+ * params->mode: BSIG_MODE_COVERAGE or BSIG_MODE_COVERAGE_EX; any other mode, tspan != 0 (a paired-end fragment already has
+ * its length) and frag_len outside 1 .. BSIG_FRAG_LEN_MAX fail with BSIG_ERR_ARG, each with its own message.  The result
+ * is an ORDINARY plan: bsig_plan_run / _run_host / _run_host_async, bsig_plan_get_stats, bsig_plan_overflowed and
+ * bsig_plan_runs_create take it.  No tlen column is read for the length: a packed-class visit stays 4 bytes (8 with a
+ * tlen filter, as always) where paired.end = "extend" pays 8; every tile's candidate window widens by L - 1 on both sides.
+ * BSIG_FRAG_LEN_MAX: far beyond any library's fragments, and every tile-relative sum of the packed class stays below 2^26. */
+#define BSIG_FRAG_LEN_MAX (1 << 24)
+int bsig_plan_create_resized(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
+                             const int32_t *rid, const int32_t *loc, const int32_t *len,
+                             const int32_t *strand, const bsig_params *params, int32_t frag_len, bsig_plan **plan);
 const int64_t *bsig_plan_offsets(const bsig_plan *plan);     /* n_ranges+1, host memory          */
 int64_t bsig_plan_cells(const bsig_plan *plan);
 int bsig_plan_get_stats(bsig_plan *plan, bsig_plan_stats *stats);
@@ -236,6 +255,10 @@ void bsig_plan_free(bsig_plan *plan);
  * and none per range.                                                                                              */
 int bsig_plan_create_sum(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
                          const int32_t *len, const int32_t *strand, const bsig_params *params, bsig_plan **plan);
+/* ... of reads resized to the fragment (bsig_plan_create_resized's rule and refusals); runs with bsig_plan_run_sum*    */
+int bsig_plan_create_sum_resized(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid,
+                                 const int32_t *loc, const int32_t *len, const int32_t *strand, const bsig_params *params,
+                                 int32_t frag_len, bsig_plan **plan);
 int64_t bsig_plan_sum_cells(const bsig_plan *plan);              /* n_bins * (ss ? 2 : 1)                       */
 /* asynchronous, on the context's stream; sum_dev: bsig_plan_sum_cells() int64 on the device, 8-B aligned           */
 int bsig_plan_run_sum(bsig_plan *plan, int64_t *sum_dev);
@@ -677,6 +700,30 @@ int bsig_coverage_runs(const char *bampath, int64_t n_ranges, const int32_t *seq
                        const int32_t *tlen_filter, int32_t n_tlen_filter,
                        int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                        int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result);
+/* bamCoverage of reads resized to the fragment at file level (bsig_plan_create_resized above): bsig_coverage_core_ex,
+ * bsig_coverage_sum and bsig_coverage_runs with tspan replaced by frag_len, through the same dispatcher (several GPUs and
+ * the resident cache as for those; an index-driven decode asks for range +- (frag_len - 1)).  The mode is
+ * BSIG_MODE_COVERAGE_EX; frag_len outside 1 .. BSIG_FRAG_LEN_MAX fails with BSIG_ERR_ARG, like every other parameter
+ * before the BAM is opened.                                                                                          */
+int bsig_coverage_core_resized(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                               int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                               const int32_t *width, const int32_t *strand,
+                               const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+                               int32_t *out, const int64_t *off);
+int bsig_coverage_sum_resized(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                              int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                              const int32_t *width, const int32_t *strand,
+                              const int32_t *tlen_filter, int32_t n_tlen_filter,
+                              int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                              int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum);
+int bsig_coverage_runs_resized(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                               int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                               const int32_t *width, const int32_t *strand,
+                               const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result);
 int64_t bsig_runs_result_n_seg(const bsig_runs_result *result);
 int64_t bsig_runs_result_n_runs(const bsig_runs_result *result);
 int bsig_runs_result_copy(const bsig_runs_result *result, int64_t *seg_off, int32_t *values, int32_t *lengths);
