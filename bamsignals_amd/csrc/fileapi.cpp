@@ -641,62 +641,39 @@ bool regions_covered(const Resident &R, int64_t n, const int32_t *rid, const int
     return true;
 }
 
-// A reduction over the ranges -- the sum (bsig_pileup_sum / bsig_coverage_sum), the strand cross-correlation
-// (bsig_pileup_xcorr), the fragment-length histogram (bsig_pileup_frag), the depth histogram (bsig_pileup_hist /
-// bsig_coverage_hist): every cell of the int64 result is a sum over ranges.  One GPU takes them all; several take a block
-// of the (rid, loc)-sorted ranges each and the host adds the int64 vectors -- no per-range cell leaves a GPU.
+// How the (rid, loc)-sorted ranges are dealt to nd GPU slots: slot k takes the contiguous block order[a .. b), empty where
+// there are fewer ranges than slots.
+void slot_block(int64_t n, size_t k, size_t nd, int64_t *a, int64_t *b)
+{
+    *a = n * (int64_t)k / (int64_t)nd;
+    *b = n * (int64_t)(k + 1) / (int64_t)nd;
+}
+// ranges order[a .. b) as the four arrays a plan is made from
+struct RangeBlock {
+    std::vector<int32_t> rid, loc, width, strand;
+    RangeBlock(const std::vector<int64_t> &order, int64_t a, int64_t b, const int32_t *rid_, const int32_t *loc_, const int32_t *width_,
+               const int32_t *strand_)
+        : rid((size_t)(b - a)), loc((size_t)(b - a)), width((size_t)(b - a)), strand((size_t)(b - a))
+    {
+        for (int64_t i = a; i < b; ++i) {
+            const int64_t j = order[(size_t)i];
+            rid[(size_t)(i - a)] = rid_[j]; loc[(size_t)(i - a)] = loc_[j]; width[(size_t)(i - a)] = width_[j]; strand[(size_t)(i - a)] = strand_[j];
+        }
+    }
+};
+
+// A reduction over the ranges, its result `cells` int64.  row == 0: every cell is a sum over ranges -- the sum
+// (bsig_pileup_sum / bsig_coverage_sum), the strand cross-correlation (bsig_pileup_xcorr), the fragment-length histogram
+// (bsig_pileup_frag), the depth histogram (bsig_pileup_hist / bsig_coverage_hist).  row > 0: every range is reduced by itself
+// to a row of `row` int64 (S * (3 + K), S * n_bins) -- the per-range summaries and the scaled regions (bsig_*_summary,
+// bsig_*_scaled).  One GPU takes all ranges (route `what`); several take a block of the sorted ranges each, and the host ADDS
+// the blocks' int64 vectors or PLACES a block's rows at the caller's indices -- no per-base cell leaves a GPU.
 // make_plan(ctx, reads, n, rid, loc, width, strand, &plan) is the kind's bsig_plan_create_* call.
 using MakePlan = std::function<int(bsig_ctx *, const bsig_reads *, int64_t, const int32_t *, const int32_t *, const int32_t *,
                                    const int32_t *, bsig_plan **)>;
 int reduced_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                     const int32_t *width, const int32_t *strand, int64_t cells, int64_t *out, double *X, std::string &route,
-                     const MakePlan &make_plan)
-{
-    const size_t nd = reads.size();
-    if (nd == 1) {
-        const double t0 = now_s();
-        bsig_plan *plan = nullptr;
-        int rc = make_plan(sl.ctx[0], reads[0], n, rid, loc, width, strand, &plan);
-        X[3] = now_s() - t0;
-        if (rc == BSIG_OK) rc = bsig::plan_run_reduced_to_host(plan, out, &X[4], &X[5]);
-        if (plan) bsig_plan_free(plan);
-        route = "sum";
-        return rc;
-    }
-    std::vector<int64_t> order;
-    bsig::sort_ranges(n, rid, loc, order);
-    std::vector<std::vector<int64_t>> part(nd, std::vector<int64_t>((size_t)cells, 0));
-    const int rc = for_each_slot(nd, [&](size_t k) -> int {
-        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
-        if (a >= b) return BSIG_OK;
-        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
-        for (int64_t i = a; i < b; ++i) {
-            const int64_t j = order[(size_t)i];
-            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
-        }
-        bsig_plan *plan = nullptr;
-        int rk = make_plan(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &plan);
-        if (rk == BSIG_OK) rk = bsig::plan_run_reduced_to_host(plan, part[k].data());
-        if (plan) bsig_plan_free(plan);
-        return rk;
-    });
-    if (rc != BSIG_OK) return rc;
-    for (int64_t c = 0; c < cells; ++c) {
-        int64_t t = 0;
-        for (size_t k = 0; k < nd; ++k) t += part[k][(size_t)c];
-        out[c] = t;
-    }
-    route = "sum of " + std::to_string(nd) + " blocks of ranges, added on the host";
-    return BSIG_OK;
-}
-
-// reduced_on_slots' sibling for the kinds that reduce every range by itself (the per-range summaries and the scaled regions:
-// bsig_*_summary, bsig_*_scaled; `what` names the kind in the route): a range's row is its own, so several GPUs' results are
-// not added.  Each takes a block of the (rid, loc)-sorted ranges, as reduced_on_slots deals them, and the host PLACES the
-// block's rows (`row` int64 per range: S * (3 + K), S * n_bins) at the caller's indices.
-int placed_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
-                    const int32_t *width, const int32_t *strand, int64_t row, int64_t *out, double *X, std::string &route,
-                    const MakePlan &make_plan, const char *what)
+                     const int32_t *width, const int32_t *strand, int64_t cells, int64_t row, int64_t *out, double *X,
+                     std::string &route, const MakePlan &make_plan, const char *what)
 {
     const size_t nd = reads.size();
     if (nd == 1) {
@@ -711,31 +688,36 @@ int placed_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n
     }
     std::vector<int64_t> order;
     bsig::sort_ranges(n, rid, loc, order);
+    if (!row) std::fill(out, out + cells, (int64_t)0);     // (a call tried again after BSIG_ERR_NOMEM adds from zero)
+    std::mutex adding;
     const int rc = for_each_slot(nd, [&](size_t k) -> int {
-        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
+        int64_t a, b;
+        slot_block(n, k, nd, &a, &b);
         if (a >= b) return BSIG_OK;
-        std::vector<int32_t> r((size_t)(b - a)), l((size_t)(b - a)), w((size_t)(b - a)), s((size_t)(b - a));
-        for (int64_t i = a; i < b; ++i) {
-            const int64_t j = order[(size_t)i];
-            r[(size_t)(i - a)] = rid[j]; l[(size_t)(i - a)] = loc[j]; w[(size_t)(i - a)] = width[j]; s[(size_t)(i - a)] = strand[j];
-        }
+        const RangeBlock B(order, a, b, rid, loc, width, strand);
+        const int64_t part_cells = row ? (b - a) * row : cells;
         std::vector<int64_t> part;
         try {
-            part.resize((size_t)((b - a) * row));
+            part.resize((size_t)part_cells);
         } catch (const std::bad_alloc &) {
-            return fail(BSIG_ERR_NOMEM, "out of host memory for %lld result cells", (long long)((b - a) * row));
+            return fail(BSIG_ERR_NOMEM, "out of host memory for %lld result cells", (long long)part_cells);
         }
         bsig_plan *plan = nullptr;
-        int rk = make_plan(sl.ctx[k], reads[k], b - a, r.data(), l.data(), w.data(), s.data(), &plan);
+        int rk = make_plan(sl.ctx[k], reads[k], b - a, B.rid.data(), B.loc.data(), B.width.data(), B.strand.data(), &plan);
         if (rk == BSIG_OK) rk = bsig::plan_run_reduced_to_host(plan, part.data());
         if (plan) bsig_plan_free(plan);
-        // (the blocks' ranges are disjoint: every slot writes rows of its own)
-        for (int64_t i = a; rk == BSIG_OK && i < b; ++i)
-            std::copy(part.begin() + (i - a) * row, part.begin() + (i - a + 1) * row, out + order[(size_t)i] * row);
-        return rk;
+        if (rk != BSIG_OK) return rk;
+        if (row) {      // (the blocks' ranges are disjoint: every slot writes rows of its own)
+            for (int64_t i = a; i < b; ++i)
+                std::copy(part.begin() + (i - a) * row, part.begin() + (i - a + 1) * row, out + order[(size_t)i] * row);
+        } else {
+            std::lock_guard<std::mutex> lock(adding);
+            for (int64_t c = 0; c < cells; ++c) out[c] += part[(size_t)c];
+        }
+        return BSIG_OK;
     });
     if (rc != BSIG_OK) return rc;
-    route = std::string(what) + " of " + std::to_string(nd) + " blocks of ranges, rows placed on the host";
+    route = std::string(what) + " of " + std::to_string(nd) + " blocks of ranges, " + (row ? "rows placed on the host" : "added on the host");
     return BSIG_OK;
 }
 
@@ -759,7 +741,7 @@ int64_t runs_block_cells()
 }
 
 // The per-range result as runs (bsig_pileup_runs / bsig_coverage_runs).  Each GPU takes a contiguous share of the
-// (rid, loc)-sorted ranges, as reduced_on_slots deals them, and cuts it into blocks of at most runs_block_cells() cells (a
+// (rid, loc)-sorted ranges (slot_block), and cuts it into blocks of at most runs_block_cells() cells (a
 // single larger range is a block of its own): a block's plan runs into a device buffer, the overflow flag is checked,
 // the buffer is encoded (runs.hip) and only the runs are downloaded.  The host puts the segments in the caller's order.
 int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
@@ -783,7 +765,8 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
     };
     std::vector<Block> blocks;
     for (size_t k = 0; k < nd; ++k) {
-        const int64_t a = n * (int64_t)k / (int64_t)nd, b = n * (int64_t)(k + 1) / (int64_t)nd;
+        int64_t a, b;
+        slot_block(n, k, nd, &a, &b);
         for (int64_t i = a; i < b;) {
             Block B;
             B.a = i; B.slot = k;
@@ -811,15 +794,11 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
         for (Block &B : blocks) {
             if (B.slot != k || rk != BSIG_OK) continue;
             const size_t m = (size_t)(B.b - B.a);
-            std::vector<int32_t> r(m), l(m), w(m), s(m);
-            for (size_t t = 0; t < m; ++t) {
-                const int64_t j = order[(size_t)B.a + t];
-                r[t] = rid[j]; l[t] = loc[j]; w[t] = width[j]; s[t] = strand[j];
-            }
+            const RangeBlock G(order, B.a, B.b, rid, loc, width, strand);
             const double t0 = now_s();
             bsig_plan *plan = nullptr;
             bsig_runs *enc = nullptr;
-            rk = plain_plan(sl.ctx[k], reads[k], (int64_t)m, r.data(), l.data(), w.data(), s.data(), prm, frag_len, &plan);
+            rk = plain_plan(sl.ctx[k], reads[k], (int64_t)m, G.rid.data(), G.loc.data(), G.width.data(), G.strand.data(), prm, frag_len, &plan);
             if (rk == BSIG_OK && bsig_plan_cells(plan) != B.cells) rk = fail(BSIG_ERR_ARG, "a block's cells do not match its plan's");
             const double t1 = now_s();
             if (rk == BSIG_OK) rk = bsig_plan_run(plan, (int32_t *)buf);
@@ -1260,11 +1239,9 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
     std::string gather;
     for (int attempt = 0; attempt < 2; ++attempt) {
     if (attempt) drop_spare_device_memory(slots.get());        // (out of device memory: once more with the cache's spare memory given back)
-    if (to.kind == Reduce::summary || to.kind == Reduce::scaled) {
-        rc = placed_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, row, to.reduced, X, gather, make_plan,
-                             to.kind == Reduce::scaled ? "scaled" : "summary");
-    } else if (to.reduced) {
-        rc = reduced_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, cells, to.reduced, X, gather, make_plan);
+    if (to.reduced) {
+        rc = reduced_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, cells, row, to.reduced, X, gather, make_plan,
+                              to.kind == Reduce::scaled ? "scaled" : to.kind == Reduce::summary ? "summary" : "sum");
     } else if (to.runs) {
         rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, frag_len, rule, *to.runs, X, gather);
     } else if (!many) {

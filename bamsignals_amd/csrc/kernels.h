@@ -68,12 +68,16 @@ hipError_t launch_build_idx(int64_t n, const uint32_t *gb, uint64_t n_buckets, u
 hipError_t launch_checksum(const void *words, uint64_t n_words, uint64_t salt, unsigned long long *acc, hipStream_t st);
 // *bad (device) = 1 unless idx[0..n_buckets] is non-decreasing, <= n_reads, and ends at n_reads
 hipError_t launch_check_idx(const uint32_t *idx, uint64_t n_buckets, uint32_t n_reads, int *bad, hipStream_t st);
+// One instantiation of a reduction's tile kernel, as its launch and the occupancy query of the same form need it: the kernel
+// (NULL: the kind has no such form), its name in the launch log, workgroup size, LDS bytes and k_resolve_tiles' mode.  A
+// kind's *_form maps run-time choices to one; its launch_*_tiles picks a launch's from P (half: !wide && P.packed_half).
+struct TileForm { const void *kernel; const char *name; int threads; size_t lds; int mode; };
+int tile_blocks_per_cu(const TileForm &f);      // workgroups a CU holds at a time (1 if the runtime cannot say); logs nothing
 // Sums over ranges of one width (bsig_plan_create_sum).  kind: 0 bamProfile, 1 coverage, 2 strand-split coverage.
-// k_sum_tiles: run r = tiles [runs[r].x, runs[r].y) of one c0 -> slab r (sum_tiles_lds / 4 int32 rounded: the caller
+// k_sum_tiles: run r = tiles [runs[r].x, runs[r].y) of one c0 -> slab r (the form's lds / 4 int32 rounded: the caller
 // sizes it as tile_cells * S rounded up to 4); windows / resolve_first as in launch_pileup (P.resolved: BsigResolved
-// per tile), or the fixed windows of heavy slices
-size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells);
-int sum_blocks_per_cu(int kind, int ss, int nw, bool half, int tile_cells);
+// per tile), or the fixed windows of heavy slices.  res / frag: P.resolved / P.frag_len of the launch.
+TileForm sum_form(int kind, int ss, int nw, bool half, bool res, bool frag, int tile_cells);
 hipError_t launch_sum_tiles(int kind, int ss, int nw, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                             int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int32_t *slab,
                             hipStream_t st);
@@ -89,8 +93,7 @@ hipError_t launch_sum_bins(const long long *base, int32_t width, int32_t binsize
 // every workgroup ADDS its partial sums into out (max_lag + 1 lags, then the five moments; the first workgroup adds
 // n_cells, the plan's count of cells, to the first moment): zero `out` first.  wide: 32-bit image cells for tiles with
 // more reads than a 16-bit cell may see.  windows / resolve_first as in launch_sum_tiles (no fixed windows).
-size_t xcorr_tiles_lds(bool wide, int tile_cells, int body, int max_lag);
-int xcorr_blocks_per_cu(int threads, bool half, int tile_cells, int body, int max_lag);
+TileForm xcorr_form(int threads, bool half, bool wide, int tile_cells, int body, int max_lag);
 hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                               int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int body,
                               int max_lag, unsigned long long n_cells, unsigned long long *out, hipStream_t st);
@@ -98,8 +101,7 @@ hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, con
 // every workgroup ADDS its non-zero rows into out (n_rows int64): zero `out` first.  P.div_magic / P.div_shift divide by
 // lenbin (>= 2).  merge: equal rows of a wave are merged before the LDS atomic.  windows / resolve_first as in
 // launch_sum_tiles (no fixed windows).
-size_t frag_tiles_lds(int n_rows);
-int frag_blocks_per_cu(int threads, bool merge, int n_rows);
+TileForm frag_form(int threads, bool merge, int n_rows);
 hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                              int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int n_rows,
                              int lenbin, unsigned long long *out, hipStream_t st);
@@ -110,8 +112,7 @@ hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, con
 // reads than a 16-bit cell may see (tiles flagged BSIG_ITEM_HEAVY are skipped by the launch that is not wide).  merge:
 // zero cells counted by ballot, equal rows of a wave merged before the LDS atomic.  half: the form for P.packed_half.
 // windows / resolve_first as in launch_sum_tiles (no fixed windows).
-size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows);
-int hist_blocks_per_cu(int threads, bool coverage, bool half, bool merge, int tile_cells, int n_rows);
+TileForm hist_form(int threads, bool coverage, bool half, bool wide, bool merge, int tile_cells, int n_rows);
 hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, const BsigReadsDev &R, const BsigKParams &P,
                              const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                              bool resolve_first, int n_rows, unsigned long long n_cells, unsigned long long *out, hipStream_t st);
@@ -120,8 +121,7 @@ hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, 
 // workgroup ADDS into row q of out, 3 + T.k int64 a row: [0] the cells' sum, [3 + j] the cells >= T.t[j], and takes the MAX
 // of [1] with the key value << 32 | (2^32 - 1 - cell): zero `out` first, launch_summary_finish last ([1] max, [2] summit, -1
 // for a row no tile wrote).  T.t past T.k must be 2^32 - 1.  wide / half / windows / resolve_first as in launch_hist_tiles.
-size_t summary_tiles_lds(bool coverage, bool wide, int tile_cells);
-int summary_blocks_per_cu(int threads, bool coverage, bool half, int tile_cells);
+TileForm summary_form(int threads, bool coverage, bool half, bool wide, int tile_cells);
 hipError_t launch_summary_tiles(int threads, bool coverage, bool wide, const BsigReadsDev &R, const BsigKParams &P,
                                 const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                                 bool resolve_first, const BsigThresholds &T, unsigned long long *out, hipStream_t st);
@@ -130,8 +130,7 @@ hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hip
 // launch_summary_tiles; a row of out is n_bins int64, and every workgroup ADDS the cells of a tile into the bins
 // floor(c * n_bins / w) of its range's row(s): zero `out` first.  segmented: the wave sums the lanes of one bin before the
 // LDS add (16-bit images only; a wide launch ignores it).  wide / half / windows / resolve_first as in launch_hist_tiles.
-size_t scaled_tiles_lds(bool coverage, bool wide, int tile_cells, int rows, int n_bins);
-int scaled_blocks_per_cu(int threads, bool coverage, bool half, bool segmented, int tile_cells, int rows, int n_bins);
+TileForm scaled_form(int threads, bool coverage, bool half, bool wide, bool segmented, int tile_cells, int rows, int n_bins);
 hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segmented, const BsigReadsDev &R, const BsigKParams &P,
                                const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                                bool resolve_first, int n_bins, unsigned long long *out, hipStream_t st);

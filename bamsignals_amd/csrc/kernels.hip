@@ -3387,7 +3387,7 @@ static int knob(int k)
 // The launch log (bsig_debug_launch_log, for the tests): the name of every pileup, overlap, sum-tiles and reduction-tiles
 // (xcorr, frag, hist, summary, scaled) kernel form launched while it is on -- the kernel template, its arguments and the
 // run-time choices that change the code path.  The names are made in the dispatch macros below from the macros' own
-// arguments, so a new branch reports itself; the occupancy queries (*_blocks_per_cu) share the dispatchers and log
+// arguments, so a new branch reports itself; the occupancy query (tile_blocks_per_cu) shares the selectors and logs
 // nothing.  Host code only; off, a launch pays one load and one branch.  Multi-slot calls launch from several threads: a
 // mutex guards the text, which stops growing at 64 KB.
 static std::atomic<int> g_log_on{0};
@@ -3573,71 +3573,85 @@ hipError_t launch_pileup(int mode, int ss, int threads, const BsigReadsDev &R, c
     }
 }
 
+// ---- a tile-kernel form (kernels.h): every reduction kind below has a selector from its run-time choices to one --------
+// The parameters every tile kernel begins with.  A selector's `f` takes the kernel by its full type, the kind's own
+// parameters after these, so an instantiation that expects other arguments than the kind's launch passes does not compile.
+#define BSIG_TILE_PARAMS(Out_) const BsigWorkItem *, const uint2 *, Out_ *, const uint2 *, BsigReadsDev, BsigKParams
+
+int tile_blocks_per_cu(const TileForm &f)
+{
+    int nb = 0;
+    const hipError_t e = f.kernel ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f.kernel, f.threads, f.lds) : hipErrorInvalidValue;
+    return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+// One workgroup of form f per run.  extra: the kernel's arguments after (items, runs, out, windows, R, P), of exactly its
+// parameter types.  windows && resolve_first: P.resolved is set, and the windows of every tile are looked up first (one
+// lane per tile), with the lookup form of the parameters.
+template <typename... Extra>
+static hipError_t launch_tiles(const TileForm &f, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items, int64_t n_items,
+                               const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, void *out, hipStream_t st,
+                               Extra... extra)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (!f.kernel) return hipErrorInvalidValue;
+    if (windows && resolve_first) {
+        BsigKParams Q = P;
+        Q.resolved = 0;
+        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                           R, Q, f.mode, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
+    }
+    BSIG_LOG("%s", f.name);
+    void *args[] = {&items, &runs, &out, &windows, const_cast<BsigReadsDev *>(&R), const_cast<BsigKParams *>(&P), &extra...};
+    const hipError_t e = hipLaunchKernel(f.kernel, dim3((unsigned)n_runs), dim3((unsigned)f.threads), args, f.lds, st);
+    const hipError_t last = hipGetLastError();      // (the lookup launch's, if that failed)
+    return e != hipSuccess ? e : last;
+}
+
 // ---- sums over ranges -------------------------------------------------------------------------------------------
-size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells)
+static size_t sum_tiles_lds(int kind, int ss, int nw, int tile_cells)
 {
     const int vals = tile_cells * (ss ? 2 : 1);
     const int acc_v = (vals + 3) / 4, img_v = kind == kSumCoverSS ? (vals + 3) / 4 : (vals + 7) / 8;
     return (size_t)(acc_v + img_v * nw) * 16 + BSIG_PACK_CODES;
 }
 
-// one k_sum_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
-// form's name as a format of its two flags)
-template <typename Fn>
-static hipError_t with_sum_kernel(int kind, int ss, int nw, bool half, bool res, Fn &&f, bool frag = false)
+// one k_sum_tiles instantiation by its run-time choices (frag: the coverage kinds of a resized plan)
+TileForm sum_form(int kind, int ss, int nw, bool half, bool res, bool frag, int tile_cells)
 {
-#define BSIG_SK(NW_, K_, SS_, H_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, H_, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=1>", (int)SS_, (int)H_); \
-                                        else return f(k_sum_tiles<NW_, K_, SS_, H_, false>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=0>", (int)SS_, (int)H_); } while (0)
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(int32_t)), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, nw * kWave, sum_tiles_lds(kind, ss, nw, tile_cells),
+                        kind == kSumProfile ? BSIG_MODE_PROFILE : BSIG_MODE_COVERAGE};
+    };
+#define BSIG_SK(NW_, K_, SS_, H_) do { if (res) return f(k_sum_tiles<NW_, K_, (SS_) != 0, (H_) != 0, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=" #SS_ ",half=" #H_ ",res=1>"); \
+                                        else return f(k_sum_tiles<NW_, K_, (SS_) != 0, (H_) != 0, false>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=" #SS_ ",half=" #H_ ",res=0>"); } while (0)
 // (the coverage kinds of a resized plan: instantiations of their own, see covered_interval)
-#define BSIG_SKF(NW_, K_, SS_) do { if (res) return f(k_sum_tiles<NW_, K_, SS_, false, true, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=1,frag=1>", (int)SS_, 0); \
-                                     else return f(k_sum_tiles<NW_, K_, SS_, false, false, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=%d,half=%d,res=0,frag=1>", (int)SS_, 0); } while (0)
+#define BSIG_SKF(NW_, K_, SS_) do { if (res) return f(k_sum_tiles<NW_, K_, (SS_) != 0, false, true, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=" #SS_ ",half=0,res=1,frag=1>"); \
+                                     else return f(k_sum_tiles<NW_, K_, (SS_) != 0, false, false, true>, "k_sum_tiles<nw=" #NW_ "," #K_ ",ss=" #SS_ ",half=0,res=0,frag=1>"); } while (0)
 #define BSIG_SKFN(K_, SS_) do { if (nw == 1) BSIG_SKF(1, K_, SS_); else if (nw == 2) BSIG_SKF(2, K_, SS_); else BSIG_SKF(4, K_, SS_); } while (0)
 #define BSIG_SKN(K_, SS_, H_) do { if (nw == 1) BSIG_SK(1, K_, SS_, H_); else if (nw == 2) BSIG_SK(2, K_, SS_, H_); else BSIG_SK(4, K_, SS_, H_); } while (0)
-    if (nw != 1 && nw != 2 && nw != 4) return hipErrorInvalidValue;
+    if (nw != 1 && nw != 2 && nw != 4) return TileForm{};
     if (kind == kSumProfile) {
-        if (ss) { if (half) BSIG_SKN(kSumProfile, true, true); else BSIG_SKN(kSumProfile, true, false); }
-        else    { if (half) BSIG_SKN(kSumProfile, false, true); else BSIG_SKN(kSumProfile, false, false); }
+        if (ss) { if (half) BSIG_SKN(kSumProfile, 1, 1); else BSIG_SKN(kSumProfile, 1, 0); }
+        else    { if (half) BSIG_SKN(kSumProfile, 0, 1); else BSIG_SKN(kSumProfile, 0, 0); }
     } else if (kind == kSumCover) {
-        if (frag) BSIG_SKFN(kSumCover, false); else BSIG_SKN(kSumCover, false, false);
+        if (frag) BSIG_SKFN(kSumCover, 0); else BSIG_SKN(kSumCover, 0, 0);
     } else if (kind == kSumCoverSS) {
-        if (frag) BSIG_SKFN(kSumCoverSS, true); else BSIG_SKN(kSumCoverSS, true, false);
+        if (frag) BSIG_SKFN(kSumCoverSS, 1); else BSIG_SKN(kSumCoverSS, 1, 0);
     }
 #undef BSIG_SKFN
 #undef BSIG_SKF
 #undef BSIG_SKN
 #undef BSIG_SK
-    return hipErrorInvalidValue;
-}
-
-int sum_blocks_per_cu(int kind, int ss, int nw, bool half, int tile_cells)
-{
-    int nb = 0;
-    const size_t lds = sum_tiles_lds(kind, ss, nw, tile_cells);
-    const hipError_t e = with_sum_kernel(kind, ss, nw, half, true, [&](auto k, const char *, int, int) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, nw * kWave, lds);
-    });
-    return e == hipSuccess && nb > 0 ? nb : 1;
+    return TileForm{};
 }
 
 hipError_t launch_sum_tiles(int kind, int ss, int nw, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                             int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int32_t *slab,
                             hipStream_t st)
 {
-    if (n_runs <= 0) return hipSuccess;
-    if (windows && resolve_first) {
-        BsigKParams Q = P;
-        Q.resolved = 0;
-        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
-                           R, Q, kind == kSumProfile ? BSIG_MODE_PROFILE : BSIG_MODE_COVERAGE, items,
-                           (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
-    }
-    const size_t lds = sum_tiles_lds(kind, ss, nw, P.tile_cells);
-    const hipError_t e = with_sum_kernel(kind, ss, nw, P.packed_half != 0, P.resolved != 0, [&](auto k, const char *name, int s_, int h_) {
-        BSIG_LOG(name, s_, h_);
-        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(nw * kWave), lds, st, items, runs, slab, (const uint2 *)windows, R, P);
-        return hipGetLastError();
-    }, P.frag_len != 0);
-    return e;
+    return launch_tiles(sum_form(kind, ss, nw, P.packed_half != 0, P.resolved != 0, P.frag_len != 0, P.tile_cells), R, P, items, n_items,
+                        runs, n_runs, windows, resolve_first, slab, st);
 }
 
 hipError_t launch_sum_reduce(bool is_signed, const int32_t *slab, int32_t slab_vals, const BsigSumChunk *chunks, int64_t n_chunks,
@@ -3667,16 +3681,17 @@ hipError_t launch_sum_bins(const long long *base, int32_t width, int32_t binsize
 }
 
 // ---- strand cross-correlation --------------------------------------------------------------------------------------
-size_t xcorr_tiles_lds(bool wide, int tile_cells, int body, int max_lag)
+static size_t xcorr_tiles_lds(bool wide, int tile_cells, int body, int max_lag)
 {
     return (size_t)xcorr_lds(wide, tile_cells, body, max_lag).total * 4;
 }
 
-// one k_xcorr_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
-// form's name)
-template <typename Fn>
-static hipError_t with_xcorr_kernel(int threads, bool half, bool wide, Fn &&f)
+// one k_xcorr_tiles instantiation by its run-time choices
+TileForm xcorr_form(int threads, bool half, bool wide, int tile_cells, int body, int max_lag)
 {
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(unsigned long long), int, int, unsigned long long), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads, xcorr_tiles_lds(wide, tile_cells, body, max_lag), BSIG_MODE_PROFILE};
+    };
 #define BSIG_XK(NT_) do { if (wide) return f(k_xcorr_tiles<NT_, false, true>, "k_xcorr_tiles<" #NT_ ",half=0,wide=1>"); \
                           if (half) return f(k_xcorr_tiles<NT_, true, false>, "k_xcorr_tiles<" #NT_ ",half=1,wide=0>"); \
                           return f(k_xcorr_tiles<NT_, false, false>, "k_xcorr_tiles<" #NT_ ",half=0,wide=0>"); } while (0)
@@ -3684,50 +3699,31 @@ static hipError_t with_xcorr_kernel(int threads, bool half, bool wide, Fn &&f)
     if (threads == 128) BSIG_XK(128);
     if (threads == 256) BSIG_XK(256);
 #undef BSIG_XK
-    return hipErrorInvalidValue;
-}
-
-int xcorr_blocks_per_cu(int threads, bool half, int tile_cells, int body, int max_lag)
-{
-    int nb = 0;
-    const size_t lds = xcorr_tiles_lds(false, tile_cells, body, max_lag);
-    const hipError_t e = with_xcorr_kernel(threads, half, false, [&](auto k, const char *) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
-    });
-    return e == hipSuccess && nb > 0 ? nb : 1;
+    return TileForm{};
 }
 
 hipError_t launch_xcorr_tiles(int threads, bool wide, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                               int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int body,
                               int max_lag, unsigned long long n_cells, unsigned long long *out, hipStream_t st)
 {
-    if (n_runs <= 0) return hipSuccess;
-    if (windows && resolve_first) {
-        BsigKParams Q = P;
-        Q.resolved = 0;
-        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
-                           R, Q, BSIG_MODE_PROFILE, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
-    }
-    const size_t lds = xcorr_tiles_lds(wide, P.tile_cells, body, max_lag);
-    return with_xcorr_kernel(threads, !wide && P.packed_half != 0, wide, [&](auto k, const char *name) {
-        BSIG_LOG("%s", name);
-        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, body, max_lag, n_cells);
-        return hipGetLastError();
-    });
+    return launch_tiles(xcorr_form(threads, !wide && P.packed_half != 0, wide, P.tile_cells, body, max_lag), R, P, items, n_items, runs,
+                        n_runs, windows, resolve_first, out, st, body, max_lag, n_cells);
 }
 
 // ---- fragment-length histogram --------------------------------------------------------------------------------------
 static bool frag_ltab(int n_rows) { return (size_t)frag_hist_dwords(n_rows) * 4 + BSIG_PACK_CODES <= 65536; }
-size_t frag_tiles_lds(int n_rows)
+static size_t frag_tiles_lds(int n_rows)
 {
     return (size_t)frag_hist_dwords(n_rows) * 4 + (frag_ltab(n_rows) ? BSIG_PACK_CODES : 0);
 }
 
-// one k_frag_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
-// form's name)
-template <typename Fn>
-static hipError_t with_frag_kernel(int threads, bool merge, bool ltab, Fn &&f)
+// one k_frag_tiles instantiation by its run-time choices (ltab: by n_rows, whether the filter table fits beside the rows)
+TileForm frag_form(int threads, bool merge, int n_rows)
 {
+    const bool ltab = frag_ltab(n_rows);
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(unsigned long long), int, int), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads, frag_tiles_lds(n_rows), BSIG_MODE_COUNT};
+    };
 #define BSIG_FK(NT_) do { if (merge) { if (ltab) return f(k_frag_tiles<NT_, true, true>, "k_frag_tiles<" #NT_ ",merge=1,ltab=1>"); \
                                        return f(k_frag_tiles<NT_, true, false>, "k_frag_tiles<" #NT_ ",merge=1,ltab=0>"); } \
                           if (ltab) return f(k_frag_tiles<NT_, false, true>, "k_frag_tiles<" #NT_ ",merge=0,ltab=1>"); \
@@ -3736,49 +3732,30 @@ static hipError_t with_frag_kernel(int threads, bool merge, bool ltab, Fn &&f)
     if (threads == 128) BSIG_FK(128);
     if (threads == 256) BSIG_FK(256);
 #undef BSIG_FK
-    return hipErrorInvalidValue;
-}
-
-int frag_blocks_per_cu(int threads, bool merge, int n_rows)
-{
-    int nb = 0;
-    const size_t lds = frag_tiles_lds(n_rows);
-    const hipError_t e = with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k, const char *) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
-    });
-    return e == hipSuccess && nb > 0 ? nb : 1;
+    return TileForm{};
 }
 
 hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                              int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int n_rows,
                              int lenbin, unsigned long long *out, hipStream_t st)
 {
-    if (n_runs <= 0) return hipSuccess;
-    if (windows && resolve_first) {
-        BsigKParams Q = P;
-        Q.resolved = 0;
-        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
-                           R, Q, BSIG_MODE_COUNT, items, (uint32_t)n_items, reinterpret_cast<BsigResolved *>(windows));
-    }
-    const size_t lds = frag_tiles_lds(n_rows);
-    return with_frag_kernel(threads, merge, frag_ltab(n_rows), [&](auto k, const char *name) {
-        BSIG_LOG("%s", name);
-        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, lenbin);
-        return hipGetLastError();
-    });
+    return launch_tiles(frag_form(threads, merge, n_rows), R, P, items, n_items, runs, n_runs, windows, resolve_first, out, st, n_rows,
+                        lenbin);
 }
 
 // ---- depth histogram -----------------------------------------------------------------------------------------------
-size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows)
+static size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows)
 {
     return (size_t)hist_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells, n_rows).total * 4;
 }
 
-// one k_hist_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
-// form's name)
-template <typename Fn>
-static hipError_t with_hist_kernel(int threads, bool coverage, bool half, bool wide, bool merge, Fn &&f)
+// one k_hist_tiles instantiation by its run-time choices
+TileForm hist_form(int threads, bool coverage, bool half, bool wide, bool merge, int tile_cells, int n_rows)
 {
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(unsigned long long), int, unsigned long long), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads, hist_tiles_lds(coverage, wide, tile_cells, n_rows),
+                        coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE};
+    };
 #define BSIG_HN(NT_, K_, W_, F_) f(k_hist_tiles<NT_, K_, (W_) != 0, F_>, "k_hist_tiles<" #NT_ "," #K_ ",wide=" #W_ ",form=" #F_ ">")
 #define BSIG_HF(NT_, F_) do { if (coverage) { if (wide) return BSIG_HN(NT_, kHistCover, 1, F_); return BSIG_HN(NT_, kHistCover, 0, F_); } \
                               if (wide) return BSIG_HN(NT_, kHistEnds, 1, F_); \
@@ -3791,50 +3768,30 @@ static hipError_t with_hist_kernel(int threads, bool coverage, bool half, bool w
 #undef BSIG_HK
 #undef BSIG_HF
 #undef BSIG_HN
-    return hipErrorInvalidValue;
-}
-
-int hist_blocks_per_cu(int threads, bool coverage, bool half, bool merge, int tile_cells, int n_rows)
-{
-    int nb = 0;
-    const size_t lds = hist_tiles_lds(coverage, false, tile_cells, n_rows);
-    const hipError_t e = with_hist_kernel(threads, coverage, half, false, merge, [&](auto k, const char *) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
-    });
-    return e == hipSuccess && nb > 0 ? nb : 1;
+    return TileForm{};
 }
 
 hipError_t launch_hist_tiles(int threads, bool coverage, bool wide, bool merge, const BsigReadsDev &R, const BsigKParams &P,
                              const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                              bool resolve_first, int n_rows, unsigned long long n_cells, unsigned long long *out, hipStream_t st)
 {
-    if (n_runs <= 0) return hipSuccess;
-    if (windows && resolve_first) {
-        BsigKParams Q = P;
-        Q.resolved = 0;
-        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
-                           R, Q, coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE, items, (uint32_t)n_items,
-                           reinterpret_cast<BsigResolved *>(windows));
-    }
-    const size_t lds = hist_tiles_lds(coverage, wide, P.tile_cells, n_rows);
-    return with_hist_kernel(threads, coverage, !wide && P.packed_half != 0, wide, merge, [&](auto k, const char *name) {
-        BSIG_LOG("%s", name);
-        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_rows, n_cells);
-        return hipGetLastError();
-    });
+    return launch_tiles(hist_form(threads, coverage, !wide && P.packed_half != 0, wide, merge, P.tile_cells, n_rows), R, P, items, n_items,
+                        runs, n_runs, windows, resolve_first, out, st, n_rows, n_cells);
 }
 
 // ---- per-range summaries -------------------------------------------------------------------------------------------
-size_t summary_tiles_lds(bool coverage, bool wide, int tile_cells)
+static size_t summary_tiles_lds(bool coverage, bool wide, int tile_cells)
 {
     return (size_t)summary_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells).total * 4;
 }
 
-// one k_summary_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
-// form's name)
-template <typename Fn>
-static hipError_t with_summary_kernel(int threads, bool coverage, bool half, bool wide, Fn &&f)
+// one k_summary_tiles instantiation by its run-time choices
+TileForm summary_form(int threads, bool coverage, bool half, bool wide, int tile_cells)
 {
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(unsigned long long), BsigThresholds), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads, summary_tiles_lds(coverage, wide, tile_cells),
+                        coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE};
+    };
 #define BSIG_SN(NT_, K_, W_) f(k_summary_tiles<NT_, K_, (W_) != 0>, "k_summary_tiles<" #NT_ "," #K_ ",wide=" #W_ ">")
 #define BSIG_SK(NT_) do { if (coverage) { if (wide) return BSIG_SN(NT_, kHistCover, 1); return BSIG_SN(NT_, kHistCover, 0); } \
                           if (wide) return BSIG_SN(NT_, kHistEnds, 1); \
@@ -3845,37 +3802,15 @@ static hipError_t with_summary_kernel(int threads, bool coverage, bool half, boo
     if (threads == 256) BSIG_SK(256);
 #undef BSIG_SK
 #undef BSIG_SN
-    return hipErrorInvalidValue;
-}
-
-int summary_blocks_per_cu(int threads, bool coverage, bool half, int tile_cells)
-{
-    int nb = 0;
-    const size_t lds = summary_tiles_lds(coverage, false, tile_cells);
-    const hipError_t e = with_summary_kernel(threads, coverage, half, false, [&](auto k, const char *) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
-    });
-    return e == hipSuccess && nb > 0 ? nb : 1;
+    return TileForm{};
 }
 
 hipError_t launch_summary_tiles(int threads, bool coverage, bool wide, const BsigReadsDev &R, const BsigKParams &P,
                                 const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                                 bool resolve_first, const BsigThresholds &T, unsigned long long *out, hipStream_t st)
 {
-    if (n_runs <= 0) return hipSuccess;
-    if (windows && resolve_first) {
-        BsigKParams Q = P;
-        Q.resolved = 0;
-        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
-                           R, Q, coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE, items, (uint32_t)n_items,
-                           reinterpret_cast<BsigResolved *>(windows));
-    }
-    const size_t lds = summary_tiles_lds(coverage, wide, P.tile_cells);
-    return with_summary_kernel(threads, coverage, !wide && P.packed_half != 0, wide, [&](auto k, const char *name) {
-        BSIG_LOG("%s", name);
-        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, T);
-        return hipGetLastError();
-    });
+    return launch_tiles(summary_form(threads, coverage, !wide && P.packed_half != 0, wide, P.tile_cells), R, P, items, n_items, runs,
+                        n_runs, windows, resolve_first, out, st, T);
 }
 
 hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hipStream_t st)
@@ -3886,16 +3821,18 @@ hipError_t launch_summary_finish(int64_t n_rows, int stride, long long *out, hip
 }
 
 // ---- scaled regions ------------------------------------------------------------------------------------------------
-size_t scaled_tiles_lds(bool coverage, bool wide, int tile_cells, int rows, int n_bins)
+static size_t scaled_tiles_lds(bool coverage, bool wide, int tile_cells, int rows, int n_bins)
 {
     return (size_t)scaled_lds(coverage ? kHistCover : kHistEnds, wide, tile_cells, rows, n_bins).total * 4;
 }
 
-// one k_scaled_tiles instantiation by its run-time choices (f receives the kernel's address and, for the launch log, the
-// form's name)
-template <typename Fn>
-static hipError_t with_scaled_kernel(int threads, bool coverage, bool half, bool wide, bool seg, Fn &&f)
+// one k_scaled_tiles instantiation by its run-time choices (rows: 2 for 5' ends with strands, else 1)
+TileForm scaled_form(int threads, bool coverage, bool half, bool wide, bool seg, int tile_cells, int rows, int n_bins)
 {
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(unsigned long long), int), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads, scaled_tiles_lds(coverage, wide, tile_cells, rows, n_bins),
+                        coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE};
+    };
 #define BSIG_SN(NT_, K_, W_, S_) f(k_scaled_tiles<NT_, K_, (W_) != 0, (S_) != 0>, "k_scaled_tiles<" #NT_ "," #K_ ",wide=" #W_ ",seg=" #S_ ">")
 #define BSIG_SC(NT_) do { if (coverage) { if (wide) return BSIG_SN(NT_, kHistCover, 1, 0); \
                                           if (seg) return BSIG_SN(NT_, kHistCover, 0, 1); \
@@ -3910,17 +3847,7 @@ static hipError_t with_scaled_kernel(int threads, bool coverage, bool half, bool
     if (threads == 256) BSIG_SC(256);
 #undef BSIG_SC
 #undef BSIG_SN
-    return hipErrorInvalidValue;
-}
-
-int scaled_blocks_per_cu(int threads, bool coverage, bool half, bool segmented, int tile_cells, int rows, int n_bins)
-{
-    int nb = 0;
-    const size_t lds = scaled_tiles_lds(coverage, false, tile_cells, rows, n_bins);
-    const hipError_t e = with_scaled_kernel(threads, coverage, half, false, segmented, [&](auto k, const char *) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds);
-    });
-    return e == hipSuccess && nb > 0 ? nb : 1;
+    return TileForm{};
 }
 
 hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segmented, const BsigReadsDev &R, const BsigKParams &P,
@@ -3929,20 +3856,9 @@ hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segme
 {
     if (n_runs <= 0) return hipSuccess;
     if (n_bins < 1 || n_bins > BSIG_SCALED_MAX_BINS) return hipErrorInvalidValue;
-    if (windows && resolve_first) {
-        BsigKParams Q = P;
-        Q.resolved = 0;
-        hipLaunchKernelGGL(k_resolve_tiles, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
-                           R, Q, coverage ? BSIG_MODE_COVERAGE : BSIG_MODE_PROFILE, items, (uint32_t)n_items,
-                           reinterpret_cast<BsigResolved *>(windows));
-    }
-    const int rows = !coverage && P.ss ? 2 : 1;
-    const size_t lds = scaled_tiles_lds(coverage, wide, P.tile_cells, rows, n_bins);
-    return with_scaled_kernel(threads, coverage, !wide && P.packed_half != 0, wide, !wide && segmented, [&](auto k, const char *name) {
-        BSIG_LOG("%s", name);
-        hipLaunchKernelGGL(k, dim3((unsigned)n_runs), dim3(threads), lds, st, items, runs, out, (const uint2 *)windows, R, P, n_bins);
-        return hipGetLastError();
-    });
+    return launch_tiles(scaled_form(threads, coverage, !wide && P.packed_half != 0, wide, !wide && segmented, P.tile_cells,
+                                    !coverage && P.ss ? 2 : 1, n_bins),
+                        R, P, items, n_items, runs, n_runs, windows, resolve_first, out, st, n_bins);
 }
 
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)

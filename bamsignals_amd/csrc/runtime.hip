@@ -2115,6 +2115,25 @@ static int64_t counter_ceiling(const char *name)
     const char *v = getenv(name);
     return v ? std::min<long long>(kCounterMax, std::max<long long>(1, atoll(v))) : kCounterMax;
 }
+// What the setup of every kind but sum ends with.  `lds` bytes are what its launches ask of a workgroup: more than the device
+// has and there is no plan (refuse(lds_max) words the kind's refusal).  Then the tiles are cut into runs -- tiles_per_run
+// by the occupancy of `form`, the main launch's, and env `run_tiles`; cut_runs' `ceiling` and `weight` --, the n_wide wide
+// tiles follow as runs of their own, and the runs go to the device.
+template <typename Refuse, typename Weight>
+static int setup_runs(bsig_plan *P, size_t lds, Refuse &&refuse, const bsig::TileForm &form, const char *run_tiles, int64_t ceiling,
+                      Weight &&weight, int64_t n_wide)
+{
+    int n_cu = 0, lds_max = 0;
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
+    if (lds > (size_t)lds_max) return refuse(lds_max);
+    const int64_t per = tiles_per_run(P, n_cu, bsig::tile_blocks_per_cu(form), 1, run_tiles);
+    std::vector<uint2> runs;
+    cut_runs(P->n_items, per, ceiling, weight, runs);
+    P->red->n_runs_main = (int64_t)runs.size();
+    append_wide_runs(n_wide, runs);
+    P->red->n_runs_extra = n_wide;
+    return upload_runs(P, runs);
+}
 
 // The runs of a sum plan: tiles of one c0 cut into runs of at most `per` (a workgroup each, one slab each), the runs of
 // the heavy slices behind those of the main tiles; chunks of at most kSumChunkSlots slabs of one c0 for k_sum_reduce.
@@ -2136,14 +2155,13 @@ static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vecto
     // strand-split coverage, 4,096 cells, four waves = 160.5 KiB): fewer waves per workgroup, and if one is too many,
     // no plan.  The library's own tile sizes (at most 2,048 cells, 1,024 with strands) need 40.5 KiB at most.
     int &nw = Q.nw;
-    while (nw > 1 && bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells) > (size_t)lds_max) nw /= 2;
-    if (bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells) > (size_t)lds_max)
-        return fail(BSIG_ERR_ARG, "tile_cells %d needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells,
-                    bsig::sum_tiles_lds(Q.kind, Q.S == 2, nw, P->tile_cells), lds_max);
+    // (the occupancy of the form that runs on looked-up windows, not resized: all forms of a kind and nw ask for the same LDS)
+    const auto form = [&] { return bsig::sum_form(Q.kind, Q.S == 2, nw, P->kp.packed_half != 0, true, false, P->tile_cells); };
+    while (nw > 1 && form().lds > (size_t)lds_max) nw /= 2;
+    if (form().lds > (size_t)lds_max)
+        return fail(BSIG_ERR_ARG, "tile_cells %d needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells, form().lds, lds_max);
     // (BAMSIGNALS_SUM_RUN_TILES: shorter or longer runs, never past the cap that keeps a slab exact)
-    const int64_t per = std::min<int64_t>(kMaxRunTiles,
-                                          tiles_per_run(P, n_cu, bsig::sum_blocks_per_cu(Q.kind, Q.S == 2, nw, P->kp.packed_half != 0, P->tile_cells),
-                                                        nw, "BAMSIGNALS_SUM_RUN_TILES"));
+    const int64_t per = std::min<int64_t>(kMaxRunTiles, tiles_per_run(P, n_cu, bsig::tile_blocks_per_cu(form()), nw, "BAMSIGNALS_SUM_RUN_TILES"));
     std::vector<uint2> runs;
     std::vector<BsigSumChunk> chunks;
     auto cut = [&](const std::vector<BsigWorkItem> &it) {
@@ -2189,20 +2207,14 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
     R.xcorr.body = body;
     R.xcorr.max_lag = shape.max_lag;
     R.xcorr.n_cells = n_cells;
-    int n_cu = 0, lds_max = 0;
-    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
-    const size_t lds = bsig::xcorr_tiles_lds(n_wide > 0, P->tile_cells, body, shape.max_lag);
-    if (lds > (size_t)lds_max)
+    const auto form = [&](bool wide) { return bsig::xcorr_form(P->threads, P->kp.packed_half != 0, wide, P->tile_cells, body, shape.max_lag); };
+    const size_t lds = form(n_wide > 0).lds;
+    const auto refuse = [&](int lds_max) {
         return fail(BSIG_ERR_ARG, "a tile of %d + %d cells needs %zu bytes of LDS per workgroup, the device has %d", body,
                     shape.max_lag, lds, lds_max);
-    const int64_t per = tiles_per_run(P, n_cu, bsig::xcorr_blocks_per_cu(P->threads, P->kp.packed_half != 0, P->tile_cells, body, shape.max_lag),
-                                      1, "BAMSIGNALS_XCORR_RUN_TILES");
-    std::vector<uint2> runs;
-    cut_runs(P->n_items, per, 0, [](int64_t) { return (int64_t)0; }, runs);      // (no counter of a run can wrap: plan_create_impl's proof)
-    R.n_runs_main = (int64_t)runs.size();
-    append_wide_runs(n_wide, runs);
-    R.n_runs_extra = n_wide;
-    return upload_runs(P, runs);
+    };
+    // (no counter of a run can wrap: plan_create_impl's proof)
+    return setup_runs(P, lds, refuse, form(false), "BAMSIGNALS_XCORR_RUN_TILES", 0, [](int64_t) { return (int64_t)0; }, n_wide);
 }
 
 // The runs of a frag plan: cut as an xcorr plan's are -- a workgroup keeps its histogram in LDS across its run and ends
@@ -2221,19 +2233,15 @@ static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vec
     // shows it faster than the plain one by more than the runs' spread: BAMSIGNALS_FRAG_FORM chooses, read
     // when the plan is made.
     if (const char *v = getenv("BAMSIGNALS_FRAG_FORM")) Q.merge = strcmp(v, "merge") == 0;
-    int n_cu = 0, lds_max = 0;
-    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
-    const size_t lds = bsig::frag_tiles_lds((int)shape.cells);
-    if (lds > (size_t)lds_max)
-        return fail(BSIG_ERR_ARG, "%lld rows need %zu bytes of LDS per workgroup, the device has %d", (long long)shape.cells, lds, lds_max);
-    const int64_t per = tiles_per_run(P, n_cu, bsig::frag_blocks_per_cu(P->threads, Q.merge, (int)shape.cells), 1, "BAMSIGNALS_FRAG_RUN_TILES");
     for (const int64_t nr : reads_of_tile)
         if (nr > kCounterMax)
             return fail(BSIG_ERR_ARG, "a tile of these ranges sees %lld reads, more than a 32-bit counter holds", (long long)nr);
-    std::vector<uint2> runs;
-    cut_runs(P->n_items, per, counter_ceiling("BAMSIGNALS_FRAG_FLUSH_READS"), [&](int64_t t) { return reads_of_tile[(size_t)t]; }, runs);
-    R.n_runs_main = (int64_t)runs.size();
-    return upload_runs(P, runs);
+    const bsig::TileForm form = bsig::frag_form(P->threads, Q.merge, (int)shape.cells);
+    const auto refuse = [&](int lds_max) {
+        return fail(BSIG_ERR_ARG, "%lld rows need %zu bytes of LDS per workgroup, the device has %d", (long long)shape.cells, form.lds, lds_max);
+    };
+    return setup_runs(P, form.lds, refuse, form, "BAMSIGNALS_FRAG_RUN_TILES", counter_ceiling("BAMSIGNALS_FRAG_FLUSH_READS"),
+                      [&](int64_t t) { return reads_of_tile[(size_t)t]; }, 0);
 }
 
 // The runs of a hist plan: cut as a frag plan's are.  Every cell of a tile adds 1 to one of the histogram's 32-bit
@@ -2253,21 +2261,15 @@ static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vec
     // BAMSIGNALS_HIST_FORM chooses, read when the plan is made.
     if (const char *v = getenv("BAMSIGNALS_HIST_FORM")) Q.merge = strcmp(v, "merge") == 0;
     const int n_rows = shape.max_value + 1;
-    int n_cu = 0, lds_max = 0;
-    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
-    const size_t lds = bsig::hist_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells, n_rows);
-    if (lds > (size_t)lds_max)
+    const auto form = [&](bool wide) { return bsig::hist_form(P->threads, Q.coverage, P->kp.packed_half != 0, wide, Q.merge, P->tile_cells, n_rows); };
+    const size_t lds = form(n_wide > 0).lds;
+    const auto refuse = [&](int lds_max) {
         return fail(BSIG_ERR_ARG, "%d rows and a tile of %d cells need %zu bytes of LDS per workgroup, the device has %d", n_rows,
                     P->tile_cells, lds, lds_max);
-    const int64_t per = tiles_per_run(P, n_cu, bsig::hist_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, Q.merge, P->tile_cells, n_rows),
-                                      1, "BAMSIGNALS_HIST_RUN_TILES");
+    };
     const int64_t S = P->kp.ss ? 2 : 1;
-    std::vector<uint2> runs;
-    cut_runs(P->n_items, per, counter_ceiling("BAMSIGNALS_HIST_FLUSH_CELLS"), [&](int64_t t) { return (int64_t)items[(size_t)t].nc * S; }, runs);
-    R.n_runs_main = (int64_t)runs.size();
-    append_wide_runs(n_wide, runs);
-    R.n_runs_extra = n_wide;
-    return upload_runs(P, runs);
+    return setup_runs(P, lds, refuse, form(false), "BAMSIGNALS_HIST_RUN_TILES", counter_ceiling("BAMSIGNALS_HIST_FLUSH_CELLS"),
+                      [&](int64_t t) { return (int64_t)items[(size_t)t].nc * S; }, n_wide);
 }
 
 // The runs of a summary plan: cut as a hist plan's are.  A lane's 32-bit threshold counters grow by at most the cells its
@@ -2283,19 +2285,13 @@ static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const st
     R.cells = P->n_ranges * shape.S * shape.row;
     Q.thr.k = shape.n_thresholds;
     for (int k = 0; k < BSIG_SUMMARY_MAX_THRESHOLDS; ++k) Q.thr.t[k] = k < shape.n_thresholds ? (uint32_t)shape.thresholds[k] : 0xFFFFFFFFu;
-    int n_cu = 0, lds_max = 0;
-    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
-    const size_t lds = bsig::summary_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells);
-    if (lds > (size_t)lds_max)
+    const auto form = [&](bool wide) { return bsig::summary_form(P->threads, Q.coverage, P->kp.packed_half != 0, wide, P->tile_cells); };
+    const size_t lds = form(n_wide > 0).lds;
+    const auto refuse = [&](int lds_max) {
         return fail(BSIG_ERR_ARG, "a tile of %d cells needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells, lds, lds_max);
-    const int64_t per = tiles_per_run(P, n_cu, bsig::summary_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, P->tile_cells),
-                                      1, "BAMSIGNALS_SUMMARY_RUN_TILES");
-    std::vector<uint2> runs;
-    cut_runs(P->n_items, per, kCounterMax, [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, runs);
-    R.n_runs_main = (int64_t)runs.size();
-    append_wide_runs(n_wide, runs);
-    R.n_runs_extra = n_wide;
-    return upload_runs(P, runs);
+    };
+    return setup_runs(P, lds, refuse, form(false), "BAMSIGNALS_SUMMARY_RUN_TILES", kCounterMax,
+                      [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, n_wide);
 }
 
 // The runs of a scaled plan: cut as a summary plan's are.  Its accumulators are 64 bits wide everywhere, so nothing but the
@@ -2321,21 +2317,16 @@ static int scaled_setup(bsig_plan *P, const bsig::ScaledShape &shape, const std:
     }
     Q.segmented = Q.coverage && 2 * wide_cells > cells;
     if (const char *v = getenv("BAMSIGNALS_SCALED_SEGMENTED")) Q.segmented = atoi(v) != 0;
-    int n_cu = 0, lds_max = 0;
-    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
-    const size_t lds = bsig::scaled_tiles_lds(Q.coverage, n_wide > 0, P->tile_cells, Q.S, Q.n_bins);
-    if (lds > (size_t)lds_max)
+    const auto form = [&](bool wide) {
+        return bsig::scaled_form(P->threads, Q.coverage, P->kp.packed_half != 0, wide, Q.segmented, P->tile_cells, Q.S, Q.n_bins);
+    };
+    const size_t lds = form(n_wide > 0).lds;
+    const auto refuse = [&](int lds_max) {
         return fail(BSIG_ERR_ARG, "a tile of %d cells and %d bins need %zu bytes of LDS per workgroup, the device has %d", P->tile_cells,
                     Q.n_bins, lds, lds_max);
-    const int64_t per = tiles_per_run(P, n_cu, bsig::scaled_blocks_per_cu(P->threads, Q.coverage, P->kp.packed_half != 0, Q.segmented,
-                                                                           P->tile_cells, Q.S, Q.n_bins),
-                                      1, "BAMSIGNALS_SCALED_RUN_TILES");
-    std::vector<uint2> runs;
-    cut_runs(P->n_items, per, kCounterMax, [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, runs);
-    R.n_runs_main = (int64_t)runs.size();
-    append_wide_runs(n_wide, runs);
-    R.n_runs_extra = n_wide;
-    return upload_runs(P, runs);
+    };
+    return setup_runs(P, lds, refuse, form(false), "BAMSIGNALS_SCALED_RUN_TILES", kCounterMax,
+                      [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, n_wide);
 }
 
 extern "C" {
@@ -2416,6 +2407,24 @@ static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
     HIP_TRY(hipSetDevice(p->ctx->device));      // the caller's thread may have another GPU current
     if (const int rc = body(*p->red, p->ctx->stream)) return rc;
     ++p->runs;
+    return BSIG_OK;
+}
+// The body of the run calls whose kernels ADD into the result (xcorr, frag, hist, summary, scaled): the result zeroed, the
+// main launch in the form run_main chose, then the extra runs -- the tiles with more reads than a 16-bit cell may see: whole,
+// with 32-bit cells, their windows looked up in place.  launch(wide, kp, items, n_items, runs, n_runs, windows, lookup) is the
+// kind's launch_*_tiles.
+template <typename Launch>
+static int run_added(bsig_plan *p, const Reduced &R, int64_t *dev, hipStream_t st, Launch &&launch)
+{
+    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+    if (R.n_runs_main) {
+        const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
+            return launch(false, kp, p->items, p->n_items, R.runs, R.n_runs_main, resolved, lookup);
+        });
+        if (rc != BSIG_OK) return rc;
+    }
+    if (R.n_runs_extra)
+        HIP_TRY(launch(true, p->kp, p->heavy_items, p->n_heavy_slices, R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false));
     return BSIG_OK;
 }
 extern "C" {
@@ -2745,37 +2754,24 @@ int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 int bsig_plan_run_xcorr(bsig_plan *p, int64_t *dev)
 {
     return run_reduced(p, kXcorr, dev, [&](const Reduced &R, hipStream_t st) -> int {
-        const auto &Q = R.xcorr;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
-        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
-        if (R.n_runs_main) {
-            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-                return bsig::launch_xcorr_tiles(p->threads, false, p->reads->dev, kp, p->items, p->n_items, R.runs, R.n_runs_main,
-                                                resolved, lookup, Q.body, Q.max_lag, (unsigned long long)Q.n_cells, out, st);
-            });
-            if (rc != BSIG_OK) return rc;
-        }
         // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
-        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
-        if (R.n_runs_extra)
-            HIP_TRY(bsig::launch_xcorr_tiles(p->threads, true, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                             R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, Q.body, Q.max_lag, 0ull, out, st));
-        return BSIG_OK;
+        return run_added(p, R, dev, st, [&](bool wide, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items, const uint2 *runs,
+                                            int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_xcorr_tiles(p->threads, wide, p->reads->dev, kp, items, n_items, runs, n_runs, windows, lookup, R.xcorr.body,
+                                            R.xcorr.max_lag, wide ? 0ull : (unsigned long long)R.xcorr.n_cells,
+                                            reinterpret_cast<unsigned long long *>(dev), st);
+        });
     });
 }
 
 int bsig_plan_run_frag(bsig_plan *p, int64_t *dev)
 {
     return run_reduced(p, kFrag, dev, [&](const Reduced &R, hipStream_t st) -> int {
-        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
-        if (R.n_runs_main) {
-            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-                return bsig::launch_frag_tiles(p->threads, R.frag.merge, p->reads->dev, kp, p->items, p->n_items, R.runs, R.n_runs_main,
-                                               resolved, lookup, (int)R.cells, R.frag.len_bin, reinterpret_cast<unsigned long long *>(dev), st);
-            });
-            if (rc != BSIG_OK) return rc;
-        }
-        return BSIG_OK;
+        return run_added(p, R, dev, st, [&](bool, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items, const uint2 *runs,
+                                            int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_frag_tiles(p->threads, R.frag.merge, p->reads->dev, kp, items, n_items, runs, n_runs, windows, lookup,
+                                           (int)R.cells, R.frag.len_bin, reinterpret_cast<unsigned long long *>(dev), st);
+        });
     });
 }
 
@@ -2783,22 +2779,13 @@ int bsig_plan_run_hist(bsig_plan *p, int64_t *dev)
 {
     return run_reduced(p, kHist, dev, [&](const Reduced &R, hipStream_t st) -> int {
         const auto &Q = R.hist;
-        const int n_rows = Q.max_value + 1;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
-        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
-        if (R.n_runs_main) {
-            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-                return bsig::launch_hist_tiles(p->threads, Q.coverage, false, Q.merge, p->reads->dev, kp, p->items, p->n_items, R.runs,
-                                               R.n_runs_main, resolved, lookup, n_rows, (unsigned long long)Q.n_cells, out, st);
-            });
-            if (rc != BSIG_OK) return rc;
-        }
         // (moments[0], the ranges' cells, is the main launch's first workgroup's to add: ranges with cells have tiles)
-        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
-        if (R.n_runs_extra)
-            HIP_TRY(bsig::launch_hist_tiles(p->threads, Q.coverage, true, Q.merge, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                            R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, n_rows, 0ull, out, st));
-        return BSIG_OK;
+        return run_added(p, R, dev, st, [&](bool wide, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items, const uint2 *runs,
+                                            int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_hist_tiles(p->threads, Q.coverage, wide, Q.merge, p->reads->dev, kp, items, n_items, runs, n_runs, windows,
+                                           lookup, Q.max_value + 1, wide ? 0ull : (unsigned long long)Q.n_cells,
+                                           reinterpret_cast<unsigned long long *>(dev), st);
+        });
     });
 }
 
@@ -2806,19 +2793,12 @@ int bsig_plan_run_summary(bsig_plan *p, int64_t *dev)
 {
     return run_reduced(p, kSummary, dev, [&](const Reduced &R, hipStream_t st) -> int {
         const auto &Q = R.summary;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
-        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
-        if (R.n_runs_main) {
-            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-                return bsig::launch_summary_tiles(p->threads, Q.coverage, false, p->reads->dev, kp, p->items, p->n_items, R.runs,
-                                                  R.n_runs_main, resolved, lookup, Q.thr, out, st);
-            });
-            if (rc != BSIG_OK) return rc;
-        }
-        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
-        if (R.n_runs_extra)
-            HIP_TRY(bsig::launch_summary_tiles(p->threads, Q.coverage, true, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                               R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, Q.thr, out, st));
+        const int rc = run_added(p, R, dev, st, [&](bool wide, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items,
+                                                    const uint2 *runs, int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_summary_tiles(p->threads, Q.coverage, wide, p->reads->dev, kp, items, n_items, runs, n_runs, windows, lookup,
+                                              Q.thr, reinterpret_cast<unsigned long long *>(dev), st);
+        });
+        if (rc != BSIG_OK) return rc;
         // every row's key into its max and summit (rows no tile wrote -- ranges without width -- get summit -1)
         HIP_TRY(bsig::launch_summary_finish(p->n_ranges * Q.S, BSIG_SUMMARY_FIXED + Q.thr.k, reinterpret_cast<long long *>(dev), st));
         return BSIG_OK;
@@ -2829,20 +2809,11 @@ int bsig_plan_run_scaled(bsig_plan *p, int64_t *dev)
 {
     return run_reduced(p, kScaled, dev, [&](const Reduced &R, hipStream_t st) -> int {
         const auto &Q = R.scaled;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(dev);
-        HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
-        if (R.n_runs_main) {
-            const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
-                return bsig::launch_scaled_tiles(p->threads, Q.coverage, false, Q.segmented, p->reads->dev, kp, p->items, p->n_items,
-                                                 R.runs, R.n_runs_main, resolved, lookup, Q.n_bins, out, st);
-            });
-            if (rc != BSIG_OK) return rc;
-        }
-        // the tiles with more reads than a 16-bit cell may see: whole, with 32-bit cells, their windows looked up in place
-        if (R.n_runs_extra)
-            HIP_TRY(bsig::launch_scaled_tiles(p->threads, Q.coverage, true, false, p->reads->dev, p->kp, p->heavy_items, p->n_heavy_slices,
-                                              R.runs + R.n_runs_main, R.n_runs_extra, nullptr, false, Q.n_bins, out, st));
-        return BSIG_OK;
+        return run_added(p, R, dev, st, [&](bool wide, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items, const uint2 *runs,
+                                            int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_scaled_tiles(p->threads, Q.coverage, wide, Q.segmented, p->reads->dev, kp, items, n_items, runs, n_runs,
+                                             windows, lookup, Q.n_bins, reinterpret_cast<unsigned long long *>(dev), st);
+        });
     });
 }
 

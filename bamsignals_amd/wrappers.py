@@ -84,6 +84,23 @@ def _check_gr(gr):
         raise TypeError("must provide a GRanges object")        # ref: src/bamsignals.cpp:93-94
 
 
+class _Head(tuple):
+    """The ten leading arguments of a file-level call -- path, n, the ranges' codes, the number of levels, their names,
+    start, width, strand, the length filter and its count.  The arrays they point into live as long as it does;
+    ``width`` and ``tf`` are the flattened widths and the filter as the call sees them."""
+
+
+def _head(bampath, gr, tlen_filter):
+    _check_gr(gr)
+    levels, codes, start, width, strand = gr.flatten()
+    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
+    head = _Head((os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
+                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf)))
+    head.keep, head.width, head.tf = (codes, start, strand), width, tf
+    return head
+
+
 def _split(out, off, ss):
     out.setflags(write=False)          # the signals are views of this buffer: read-only container
     n = len(off) - 1
@@ -106,20 +123,15 @@ def pileup_core(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=Fals
     """The native entry point behind bamCount/bamProfile (ref: R/RcppExports.R:12-14).  Returns the
     R list as a Python list: per-range vectors / 2 x w matrices, or, for binsize <= 0, a list of
     length one holding the count vector / 2 x n matrix."""
-    _check_gr(gr)
+    head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
     n = len(gr)
     off = np.empty(n + 1, dtype=np.int64)
-    cells = lib.bsig_layout(n, width.ctypes.data, int(binsize), int(bool(ss)), off.ctypes.data)
+    cells = lib.bsig_layout(n, head.width.ctypes.data, int(binsize), int(bool(ss)), off.ctypes.data)
     out = np.zeros(cells, dtype=np.int32)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_pileup_core(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels),
-                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                    tf.ctypes.data, len(tf), int(mapqual), int(binsize), int(shift),
-                                    int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
-                                    int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
+    _lib.check(lib.bsig_pileup_core(*head, int(mapqual), int(binsize), int(shift), int(bool(ss)), int(requiredF),
+                                    int(filteredF), int(bool(pe_mid)), int(maxgap), _dev(device), out.ctypes.data,
+                                    off.ctypes.data))
     if binsize <= 0:
         return [out.reshape(-1, 2).T if ss else out]
     return _split(out, off, ss)
@@ -129,20 +141,15 @@ def overlap_core(bampath, gr, tlen_filter, mapqual=0, within=False, min_overlap=
                  filteredF=-1, tspan=False, maxgap=16385, device=None):
     """The native entry point behind bamOverlaps (bsig_overlap_core): the int32 count vector, or the 2 x n matrix
     (sense, antisense) with ``ss``.  ``maxgap`` is there for the shape of the other entry points; the call ignores it."""
-    _check_gr(gr)
+    head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
     n = len(gr)
     off = np.empty(n + 1, dtype=np.int64)
-    cells = lib.bsig_layout(n, width.ctypes.data, -1, int(bool(ss)), off.ctypes.data)
+    cells = lib.bsig_layout(n, head.width.ctypes.data, -1, int(bool(ss)), off.ctypes.data)
     out = np.zeros(cells, dtype=np.int32)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_overlap_core(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels),
-                                     names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                     tf.ctypes.data, len(tf), int(mapqual), int(bool(within)), int(min_overlap),
-                                     int(bool(ss)), int(requiredF), int(filteredF), int(bool(tspan)),
-                                     int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
+    _lib.check(lib.bsig_overlap_core(*head, int(mapqual), int(bool(within)), int(min_overlap), int(bool(ss)), int(requiredF),
+                                     int(filteredF), int(bool(tspan)), int(maxgap), _dev(device), out.ctypes.data,
+                                     off.ctypes.data))
     return out.reshape(-1, 2).T if ss else out
 
 
@@ -163,18 +170,11 @@ def pileup_sum(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False
     """bamProfile's signals summed over the ranges (bsig_pileup_sum): int64, ``(n_bins,)`` or ``(2, n_bins)``."""
     _check_gr(gr)
     w = _check_equal_widths(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
-    n = len(gr)
-    n_bins = (w + int(binsize) - 1) // int(binsize) if n and w > 0 else 0
+    head = _head(bampath, gr, tlen_filter)
+    n_bins = (w + int(binsize) - 1) // int(binsize) if len(gr) and w > 0 else 0
     out = np.zeros(n_bins * (2 if ss else 1), dtype=np.int64)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_pileup_sum(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels),
-                                   names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                   tf.ctypes.data, len(tf), int(mapqual), int(binsize), int(shift),
-                                   int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
-                                   int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(_lib.load().bsig_pileup_sum(*head, int(mapqual), int(binsize), int(shift), int(bool(ss)), int(requiredF),
+                                           int(filteredF), int(bool(pe_mid)), int(maxgap), _dev(device), out.ctypes.data))
     return _sum_shape(out, ss)
 
 
@@ -184,18 +184,12 @@ def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1,
     ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_sum_resized)."""
     _check_gr(gr)
     w = _check_equal_widths(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
-    n = len(gr)
-    n_bins = (w + int(binsize) - 1) // int(binsize) if n and w > 0 else 0
+    head = _head(bampath, gr, tlen_filter)
+    n_bins = (w + int(binsize) - 1) // int(binsize) if len(gr) and w > 0 else 0
     out = np.zeros(n_bins * (2 if ss else 1), dtype=np.int64)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    fn, rule = _coverage_rule(lib, "sum", tspan, frag_len)
-    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names,
-                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
-                  int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap),
-                  _dev(device), int(binsize), int(bool(ss)), out.ctypes.data))
+    fn, rule = _coverage_rule(_lib.load(), "sum", tspan, frag_len)
+    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
+                  int(bool(ss)), out.ctypes.data))
     return _sum_shape(out, ss)
 
 
@@ -211,33 +205,22 @@ def _coverage_rule(lib, what, tspan, frag_len):
 
 def pileup_xcorr(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, max_lag=500, maxgap=16385, device=None):
     """The strand cross-correlation over the ranges (bsig_pileup_xcorr): ``max_lag + 1 + 5`` int64, cross then moments."""
-    _check_gr(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
+    head = _head(bampath, gr, tlen_filter)
     out = np.zeros(max(int(max_lag), 0) + 1 + _lib.XCORR_MOMENTS, dtype=np.int64)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_pileup_xcorr(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
-                                     names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                     tf.ctypes.data, len(tf), int(mapqual), int(requiredF), int(filteredF),
-                                     int(max_lag), int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(_lib.load().bsig_pileup_xcorr(*head, int(mapqual), int(requiredF), int(filteredF), int(max_lag), int(maxgap),
+                                             _dev(device), out.ctypes.data))
     return out
 
 
 def pileup_frag(bampath, gr, tlen_filter, mapqual=0, requiredF=66, filteredF=-1, pe_mid=False, len_bin=1, maxgap=16385,
                 device=None):
     """The fragment-length histogram over the ranges (bsig_pileup_frag): ``tlen_filter[1] // len_bin + 1`` int64."""
-    _check_gr(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
+    head = _head(bampath, gr, tlen_filter)
+    tf = head.tf
     rows = int(tf[1]) // int(len_bin) + 1 if len(tf) == 2 and int(len_bin) >= 1 and tf[1] >= 0 else 1
     out = np.zeros(min(max(rows, 1), _lib.FRAG_MAX_ROWS), dtype=np.int64)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_pileup_frag(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
-                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                    tf.ctypes.data, len(tf), int(mapqual), int(requiredF), int(filteredF),
-                                    int(bool(pe_mid)), int(len_bin), int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(_lib.load().bsig_pileup_frag(*head, int(mapqual), int(requiredF), int(filteredF), int(bool(pe_mid)), int(len_bin),
+                                            int(maxgap), _dev(device), out.ctypes.data))
     return out
 
 
@@ -250,47 +233,30 @@ def pileup_hist(bampath, gr, tlen_filter, mapqual=0, ss=False, requiredF=0, filt
                 maxgap=16385, device=None):
     """The depth histogram of the 5' ends over the ranges (bsig_pileup_hist): ``max_value + 1 + 2`` int64, the histogram
     (last row: values >= ``max_value``) then the moments [cells, sum of the values]."""
-    _check_gr(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
+    head = _head(bampath, gr, tlen_filter)
     out = _hist_out(max_value)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_pileup_hist(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
-                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                    tf.ctypes.data, len(tf), int(mapqual), int(bool(ss)), int(requiredF), int(filteredF),
-                                    int(bool(pe_mid)), int(max_value), int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(_lib.load().bsig_pileup_hist(*head, int(mapqual), int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
+                                            int(max_value), int(maxgap), _dev(device), out.ctypes.data))
     return out
 
 
 def coverage_hist(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False, max_value=1000,
                   maxgap=16385, device=None):
     """The depth histogram of the per-base coverage over the ranges (bsig_coverage_hist): as ``pileup_hist``."""
-    _check_gr(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
+    head = _head(bampath, gr, tlen_filter)
     out = _hist_out(max_value)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_coverage_hist(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
-                                      start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
-                                      int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(max_value),
-                                      int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(_lib.load().bsig_coverage_hist(*head, int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(max_value),
+                                              int(maxgap), _dev(device), out.ctypes.data))
     return out
 
 
 def _summary_call(fn, bampath, gr, tlen_filter, head, thresholds, rows, maxgap, device):
     """the two file-level summary calls: ``head`` = the int32 arguments between the length filter and the thresholds"""
-    _check_gr(gr)
-    levels, codes, start, width, strand = gr.flatten()
+    lead = _head(bampath, gr, tlen_filter)
     thr = np.ascontiguousarray([int(t) for t in thresholds], dtype=np.int32)
     k = min(len(thr), _lib.SUMMARY_MAX_THRESHOLDS)          # (more are refused by the call: the buffer need not hold them)
     out = np.zeros((len(gr), rows, _lib.SUMMARY_FIXED + k), dtype=np.int64)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
-                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), *head,
-                  len(thr), thr.ctypes.data if len(thr) else None, int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(fn(*lead, *head, len(thr), thr.ctypes.data if len(thr) else None, int(maxgap), _dev(device), out.ctypes.data))
     return out
 
 
@@ -313,16 +279,11 @@ def coverage_summary(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF
 
 def _scaled_call(fn, bampath, gr, tlen_filter, head, n_bins, rows, maxgap, device):
     """the two file-level scaled-region calls: ``head`` = the int32 arguments between the length filter and n_bins"""
-    _check_gr(gr)
-    levels, codes, start, width, strand = gr.flatten()
+    lead = _head(bampath, gr, tlen_filter)
     n_bins = int(n_bins)
     # (a number of bins the call refuses: the buffer need not hold them)
     out = np.zeros((len(gr), rows, n_bins if 1 <= n_bins <= _lib.SCALED_MAX_BINS else 1), dtype=np.int64)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
-                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), *head,
-                  n_bins, int(maxgap), _dev(device), out.ctypes.data))
+    _lib.check(fn(*lead, *head, n_bins, int(maxgap), _dev(device), out.ctypes.data))
     return out
 
 
@@ -358,17 +319,11 @@ def _take_runs(lib, handle, ss):
 def pileup_runs(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False, requiredF=0,
                 filteredF=-1, pe_mid=False, maxgap=16385, device=None):
     """bamProfile's signals as runs (bsig_pileup_runs): a RunSignals; the per-base cells stay on the GPU."""
-    _check_gr(gr)
+    head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
     h = C.c_void_p()
-    _lib.check(lib.bsig_pileup_runs(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
-                                    names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                    tf.ctypes.data, len(tf), int(mapqual), int(binsize), int(shift),
-                                    int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
-                                    int(maxgap), _dev(device), C.byref(h)))
+    _lib.check(lib.bsig_pileup_runs(*head, int(mapqual), int(binsize), int(shift), int(bool(ss)), int(requiredF), int(filteredF),
+                                    int(bool(pe_mid)), int(maxgap), _dev(device), C.byref(h)))
     return _take_runs(lib, h, ss)
 
 
@@ -376,17 +331,12 @@ def coverage_runs(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1
                   maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
     """bamCoverage's signals as runs (bsig_coverage_runs): a RunSignals; the per-base cells stay on the GPU.
     ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_runs_resized)."""
-    _check_gr(gr)
+    head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
     h = C.c_void_p()
     fn, rule = _coverage_rule(lib, "runs", tspan, frag_len)
-    _lib.check(fn(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
-                  start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf),
-                  int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap),
-                  _dev(device), int(binsize), int(bool(ss)), C.byref(h)))
+    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
+                  int(bool(ss)), C.byref(h)))
     return _take_runs(lib, h, ss)
 
 
@@ -400,24 +350,19 @@ def coverage_core(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1
     """The native entry point behind bamCoverage (ref: R/RcppExports.R:16-18).  ``binsize`` / ``ss``:
     per-base coverage summed over bins / split into sense and antisense rows (bsig_coverage_core_ex).
     ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_core_resized, whatever the bins)."""
-    _check_gr(gr)
+    head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
     n = len(gr)
     ex = _is_ex(binsize, ss) or bool(frag_len)
     off = np.empty(n + 1, dtype=np.int64)
-    cells = lib.bsig_layout(n, width.ctypes.data, int(binsize) if ex else 1, int(bool(ss)) if ex else 0, off.ctypes.data)
+    cells = lib.bsig_layout(n, head.width.ctypes.data, int(binsize) if ex else 1, int(bool(ss)) if ex else 0, off.ctypes.data)
     out = np.zeros(cells, dtype=np.int32)
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    head = (os.path.expanduser(str(bampath)).encode(), n, codes.ctypes.data, len(levels), names, start.ctypes.data,
-            width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual), int(requiredF),
-            int(filteredF))
+    flt = (int(mapqual), int(requiredF), int(filteredF))
     if ex:
         fn, rule = _coverage_rule(lib, "core_ex", tspan, frag_len)
-        _lib.check(fn(*head, rule, int(maxgap), _dev(device), int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
+        _lib.check(fn(*head, *flt, rule, int(maxgap), _dev(device), int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
     else:
-        _lib.check(lib.bsig_coverage_core(*head, int(bool(tspan)), int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
+        _lib.check(lib.bsig_coverage_core(*head, *flt, int(bool(tspan)), int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
     return _split(out, off, ex and bool(ss))
 
 
@@ -441,37 +386,25 @@ def pileup_core_into(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss
                      filteredF=-1, pe_mid=False, maxgap=16385, device=None):
     """pileup_core with the result delivered in place (bsig_pileup_core_into, what the R shim binds): the
     per-range arrays are allocated first, as allocateList does, and the native side writes straight into them."""
-    _check_gr(gr)
-    lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
-    out, vs = _alloc_signals(width, int(binsize), bool(ss))
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    _lib.check(lib.bsig_pileup_core_into(os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels),
-                                         names, start.ctypes.data, width.ctypes.data, strand.ctypes.data,
-                                         tf.ctypes.data, len(tf), int(mapqual), int(binsize), int(shift),
-                                         int(bool(ss)), int(requiredF), int(filteredF), int(bool(pe_mid)),
-                                         int(maxgap), _dev(device), _dest_pointers(vs)))
+    head = _head(bampath, gr, tlen_filter)
+    out, vs = _alloc_signals(head.width, int(binsize), bool(ss))
+    _lib.check(_lib.load().bsig_pileup_core_into(*head, int(mapqual), int(binsize), int(shift), int(bool(ss)), int(requiredF),
+                                                 int(filteredF), int(bool(pe_mid)), int(maxgap), _dev(device), _dest_pointers(vs)))
     return out
 
 
 def coverage_core_into(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
                        maxgap=16385, device=None, *, binsize=1, ss=False):
     """coverage_core with the result delivered in place (bsig_coverage_core_into / bsig_coverage_core_ex_into)."""
-    _check_gr(gr)
+    head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
-    levels, codes, start, width, strand = gr.flatten()
     ex = _is_ex(binsize, ss)
-    out, vs = _alloc_signals(width, max(int(binsize), 1) if ex else 1, ex and bool(ss))
-    tf = np.asarray([int(x) for x in tlen_filter], dtype=np.int32)
-    names = (C.c_char_p * max(len(levels), 1))(*[s.encode() for s in levels])
-    head = (os.path.expanduser(str(bampath)).encode(), len(gr), codes.ctypes.data, len(levels), names,
-            start.ctypes.data, width.ctypes.data, strand.ctypes.data, tf.ctypes.data, len(tf), int(mapqual),
-            int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap), _dev(device))
+    out, vs = _alloc_signals(head.width, max(int(binsize), 1) if ex else 1, ex and bool(ss))
+    rest = (int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(maxgap), _dev(device))
     if ex:
-        _lib.check(lib.bsig_coverage_core_ex_into(*head, int(binsize), int(bool(ss)), _dest_pointers(vs)))
+        _lib.check(lib.bsig_coverage_core_ex_into(*head, *rest, int(binsize), int(bool(ss)), _dest_pointers(vs)))
     else:
-        _lib.check(lib.bsig_coverage_core_into(*head, _dest_pointers(vs)))
+        _lib.check(lib.bsig_coverage_core_into(*head, *rest, _dest_pointers(vs)))
     return out
 
 

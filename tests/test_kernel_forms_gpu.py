@@ -1,4 +1,4 @@
-"""GPU: every pileup and sum-tiles kernel form that launch_mode and with_sum_kernel (csrc/kernels.hip) can launch, run
+"""GPU: every pileup and sum-tiles kernel form that launch_mode and sum_form (csrc/kernels.hip) can launch, run
 on tests/forms_deck.py's reads and ranges and compared with the C oracle cell by cell, exactly.  A case sets the tuning
 knobs (bsig_debug_set_knob) and call parameters that select one form, turns the launch log on (bsig_debug_launch_log),
 makes a plan, runs it twice -- the first run looks its windows up in the kernel, the second takes the form for resolved

@@ -464,6 +464,72 @@ def test_fewer_ranges_than_slots(synth_bam, gather, monkeypatch):
         _lib.load().bsig_cache_clear()
 
 
+def test_reductions_and_runs_with_few_and_uneven_blocks(synth_bam, monkeypatch):
+    """The dealer of the reductions and of the runs over four slots where a dealer goes wrong: no range, one and three
+    (slots with an empty block), five (blocks of 1, 1, 1 and 2) -- widths mixed, one of them 0, not in (rid, loc) order.
+    An adding kind (bamDepthHist), the two placing kinds (bamScaled, bamSummary) and bamCoverage(runs=True): four slots
+    give exactly what one gives, which for the sets with ranges is what the C oracle's cells give by the kinds'
+    definitions (tests/depthhist_expected.py, scaled_expected.py, summary_expected.py, runs_expected.py)."""
+    import depthhist_expected as de
+    import runs_expected as rx
+    import scaled_expected as se
+    import summary_expected as sme
+    from bamsignals_amd import GRanges, _lib, bamCoverage, bamDepthHist, bamScaled, bamSummary
+    from bamsignals_amd.wrappers import last_call_route
+    from oracle import oracle_c
+    bam, names, ref_len, cols, _, _ = synth_bam
+    orc = _oracle(cols)
+    rows = [(2, 500_000, 1500, 1), (0, 300_000, 700, -1), (4, 10_000, 0, 0), (0, 100_000, 2300, 0), (1, 5_000, 64, 1)]
+    sets = []
+    for n in (0, 1, 3, 5):
+        rid, loc, width, strand = (np.asarray([r[k] for r in rows[:n]], np.int32) for k in range(4))
+        gr = GRanges([names[r] for r in rid], loc + 1, width=width, strand=[{1: "+", -1: "-", 0: "*"}[int(s)] for s in strand])
+        sets.append((gr, dict(rid=rid, loc=loc, len=width, strand=strand)))
+    V, N, T = 8, 4, (1,)
+    kinds = {
+        "hist": (lambda gr: bamDepthHist(bam, gr, maxdepth=V, signal="ends", ss=True, verbose=False),
+                 lambda r: np.concatenate([r.counts, [r.n, r.total]]),
+                 lambda rg: de.expected(orc, rg, "ends", True, V), "sum of 4 blocks of ranges, added on the host"),
+        "scaled": (lambda gr: bamScaled(bam, gr, nbins=N, verbose=False), lambda r: r.sums,
+                   lambda rg: se.expected(orc, rg, "coverage", False, N)[:, 0, :], "scaled of 4 blocks of ranges, rows placed on the host"),
+        "summary": (lambda gr: bamSummary(bam, gr, thresholds=T, signal="ends", ss=True, verbose=False),
+                    lambda r: np.concatenate([np.stack([r.sum, r.max, r.summit], axis=-1), r.covered], axis=-1),
+                    lambda rg: sme.expected(orc, rg, "ends", True, T), "summary of 4 blocks of ranges, rows placed on the host"),
+        "runs": (lambda gr: bamCoverage(bam, gr, runs=True, verbose=False), lambda r: (r.seg_off, r.values, r.lengths),
+                 lambda rg: rx.encode_flat(*oracle_c.coverage_core(orc, rg), False), "block(s) of ranges, put in order on the host"),
+    }
+    monkeypatch.setenv("BAMSIGNALS_DECODE", "all")
+    monkeypatch.setenv("BAMSIGNALS_SHARD_MIN_BLOCKS", "2")
+    _lib.load().bsig_cache_clear()
+    try:
+        got = {}
+        for devices in ("0", "0,0,0,0"):
+            monkeypatch.setenv("BAMSIGNALS_DEVICES", devices)
+            for name, (call, flat, _, phrase) in kinds.items():
+                for k, (gr, _) in enumerate(sets):
+                    got[devices, name, k] = flat(call(gr))
+                    route = last_call_route()
+                    assert route.startswith("%d GPU slot(s)" % len(devices.split(","))), route
+                    if devices != "0":
+                        assert phrase in route, (name, k, route)
+                    elif name != "runs":        # (one slot runs through the runs' dealer too: one block)
+                        assert "blocks of ranges" not in route, (name, k, route)
+        for name, (_, _, want, _) in kinds.items():
+            for k, (gr, rg) in enumerate(sets):
+                one, four = got["0", name, k], got["0,0,0,0", name, k]
+                if name == "runs":
+                    rx.same_runs(four, one)
+                    if len(gr):
+                        rx.same_runs(one, want(rg))
+                else:
+                    assert one.dtype == np.int64 and np.array_equal(four, one), (name, k)
+                    if len(gr):
+                        assert np.array_equal(one, want(rg)), (name, k)
+                        assert one.any(), (name, k)
+    finally:
+        _lib.load().bsig_cache_clear()
+
+
 def test_concurrent_host_threads_on_the_multi_gpu_route(synth_bam, monkeypatch):
     """Several host threads inside the multi-GPU route at once (slots "0,0" and the forced one-rank RCCL
     exchange): the runs take turns on the slots' cached buffers and on the exchange (RCCL forbids

@@ -1,5 +1,5 @@
-"""GPU: every form of the five reductions' tile kernels that with_xcorr_kernel, with_frag_kernel, with_hist_kernel,
-with_summary_kernel and with_scaled_kernel (csrc/kernels.hip) can launch -- 9 + 12 + 30 + 15 + 24 = 90 instantiations -- run
+"""GPU: every form of the five reductions' tile kernels that xcorr_form, frag_form, hist_form,
+summary_form and scaled_form (csrc/kernels.hip) can launch -- 9 + 12 + 30 + 15 + 24 = 90 instantiations -- run
 on tests/forms_deck.py's reads and ranges and compared with the C oracle's per-base cells reduced in numpy
 (forms_deck.expected_xcorr / _frag / _hist / _summary / _scaled), exactly, in int64.  A case is
 test_kernel_forms_gpu.py's: the call parameters and environment that select one form are set, the launch log is turned on
@@ -380,7 +380,7 @@ def test_scaled(gpu, nt, layout, signal, word, ss, tile, heavy, n_bins, seg, run
 # the whole list
 # ---------------------------------------------------------------------------------------------------------------
 def test_the_occupancy_queries_log_nothing(gpu):
-    """making a plan asks *_blocks_per_cu, which goes through the same dispatchers: only a run's launches are logged"""
+    """making a plan asks tile_blocks_per_cu, which goes through the same selectors: only a run's launches are logged"""
     from bamsignals_amd.device import HistPlan
     from test_kernel_forms_gpu import _selected
     ctx, reads = gpu
