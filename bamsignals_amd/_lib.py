@@ -161,6 +161,17 @@ def load():
     lib.bsig_runs_free.argtypes = [C.c_void_p]
     lib.bsig_runs_free.restype = None
     lib.bsig_plan_runs_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.bsig_views_create.argtypes = lib.bsig_runs_create.argtypes
+    lib.bsig_views_n_seg.argtypes = [C.c_void_p]
+    lib.bsig_views_n_seg.restype = C.c_int64
+    lib.bsig_views_cells.argtypes = [C.c_void_p]
+    lib.bsig_views_cells.restype = C.c_int64
+    lib.bsig_views_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    lib.bsig_views_device.argtypes = [C.c_void_p, C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 6
+    lib.bsig_views_fetch.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+    lib.bsig_views_free.argtypes = [C.c_void_p]
+    lib.bsig_views_free.restype = None
+    lib.bsig_plan_views_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.bsig_pileup_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
     lib.bsig_bam_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -220,6 +231,17 @@ def load():
     lib.bsig_runs_result_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bsig_runs_result_free.argtypes = [C.c_void_p]
     lib.bsig_runs_result_free.restype = None
+    # the views calls: the runs calls' arguments, then lower and upper
+    lib.bsig_pileup_views.argtypes = core_head + [C.c_int32] * 11 + [C.POINTER(C.c_void_p)]
+    lib.bsig_coverage_views.argtypes = core_head + [C.c_int32] * 10 + [C.POINTER(C.c_void_p)]
+    lib.bsig_coverage_views_resized.argtypes = lib.bsig_coverage_views.argtypes
+    lib.bsig_views_result_n_seg.argtypes = [C.c_void_p]
+    lib.bsig_views_result_n_seg.restype = C.c_int64
+    lib.bsig_views_result_n_views.argtypes = [C.c_void_p]
+    lib.bsig_views_result_n_views.restype = C.c_int64
+    lib.bsig_views_result_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+    lib.bsig_views_result_free.argtypes = [C.c_void_p]
+    lib.bsig_views_result_free.restype = None
     lib.bsig_write_sam_as_bam_and_index.argtypes = [C.c_char_p, C.c_char_p]
     lib.bsig_write_columns_as_bam.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(Columns),
                                               C.c_int32]

@@ -722,13 +722,67 @@ int reduced_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t 
 }
 
 }  // namespace
-// the host-side result of bsig_pileup_runs / bsig_coverage_runs: the runs in the caller's range order
-struct bsig_runs_result {
+// the host-side result of an encoded file-level call, in the caller's range order: segment k owns entries seg_off[k] ..
+// seg_off[k + 1] of every value column (runs: values, lengths; views: start, width, sum, max, summit)
+namespace bsig {
+struct EncodedColumns {
+    static constexpr int kMaxCols = 5;
     int64_t n_seg = 0;
     std::vector<int64_t> seg_off;
-    std::vector<int32_t> values, lengths;
+    std::vector<uint8_t> col[kMaxCols];
+    int64_t entries() const { return seg_off.empty() ? 0 : seg_off.back(); }
 };
+}  // namespace bsig
+struct bsig_runs_result : bsig::EncodedColumns {};
+struct bsig_views_result : bsig::EncodedColumns {};
 namespace {
+using bsig::EncodedColumns;
+
+// which encoder a call's blocks go through (runs.hip / views.hip), and the bytes of an entry of each value column
+enum class EncoderKind { runs, views };
+struct Encoder {
+    EncoderKind kind;
+    const char *noun;                   // the route's word
+    int n_cols;
+    size_t elem[EncodedColumns::kMaxCols];
+    int32_t lower = 0, upper = 0;       // views: the thresholds
+};
+Encoder runs_encoder() { return Encoder{EncoderKind::runs, "runs", 2, {4, 4, 0, 0, 0}}; }
+Encoder views_encoder(int32_t lower, int32_t upper) { return Encoder{EncoderKind::views, "views", 5, {4, 4, 8, 4, 4}, lower, upper}; }
+
+// a block's result in `buf` encoded on its device (*t_encoded: when that was done); the seg_off and the value columns of
+// the block to the host
+int encode_block(const Encoder &enc, bsig_plan *plan, const int32_t *buf, EncodedColumns &B, double *t_encoded)
+{
+    int64_t n = 0;
+    int rc;
+    auto size_cols = [&] {
+        for (int c = 0; c < enc.n_cols; ++c) B.col[c].resize((size_t)n * enc.elem[c]);
+    };
+    if (enc.kind == EncoderKind::views) {
+        bsig_views *v = nullptr;
+        rc = bsig_plan_views_create(plan, &v);
+        if (rc == BSIG_OK) rc = bsig_views_encode(v, buf, enc.lower, enc.upper, &n);
+        *t_encoded = now_s();
+        if (rc == BSIG_OK) {
+            size_cols();
+            rc = bsig_views_fetch(v, B.seg_off.data(), (int32_t *)B.col[0].data(), (int32_t *)B.col[1].data(), (int64_t *)B.col[2].data(),
+                                  (int32_t *)B.col[3].data(), (int32_t *)B.col[4].data());
+        }
+        if (v) bsig_views_free(v);
+    } else {
+        bsig_runs *r = nullptr;
+        rc = bsig_plan_runs_create(plan, &r);
+        if (rc == BSIG_OK) rc = bsig_runs_encode(r, buf, &n);
+        *t_encoded = now_s();
+        if (rc == BSIG_OK) {
+            size_cols();
+            rc = bsig_runs_fetch(r, B.seg_off.data(), (int32_t *)B.col[0].data(), (int32_t *)B.col[1].data());
+        }
+        if (r) bsig_runs_free(r);
+    }
+    return rc;
+}
 
 // cells per block of ranges whose per-base result is in HBM at one time (bsig_pileup_runs / bsig_coverage_runs)
 int64_t runs_block_cells()
@@ -740,13 +794,14 @@ int64_t runs_block_cells()
     return (int64_t)1 << 31;
 }
 
-// The per-range result as runs (bsig_pileup_runs / bsig_coverage_runs).  Each GPU takes a contiguous share of the
-// (rid, loc)-sorted ranges (slot_block), and cuts it into blocks of at most runs_block_cells() cells (a
-// single larger range is a block of its own): a block's plan runs into a device buffer, the overflow flag is checked,
-// the buffer is encoded (runs.hip) and only the runs are downloaded.  The host puts the segments in the caller's order.
-int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
+// The per-range result as runs or views (bsig_pileup_runs / bsig_coverage_runs, bsig_pileup_views / bsig_coverage_views).
+// Each GPU takes a contiguous share of the (rid, loc)-sorted ranges (slot_block), and cuts it into blocks of at most
+// runs_block_cells() cells (a single larger range is a block of its own): a block's plan runs into a device buffer, the
+// overflow flag is checked, the buffer is encoded (runs.hip / views.hip) and only the encoder's result is downloaded.  The
+// host puts the segments in the caller's order.
+int encoded_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, const int32_t *rid, const int32_t *loc,
                   const int32_t *width, const int32_t *strand, const bsig_params &prm, int32_t frag_len, const bsig::PlanRule &rule,
-                  bsig_runs_result &out, double *X, std::string &route)
+                  const Encoder &enc, EncodedColumns &out, double *X, std::string &route)
 {
     const size_t nd = reads.size();
     const int64_t S = rule.ss ? 2 : 1;
@@ -757,11 +812,9 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
         const int32_t w = width[order[(size_t)i]];
         return w > 0 ? S * (((int64_t)w + rule.binsize - 1) / rule.binsize) : 0;
     };
-    struct Block {
+    struct Block : EncodedColumns {
         int64_t a = 0, b = 0, cells = 0;      // ranges order[a .. b)
         size_t slot = 0;
-        std::vector<int64_t> seg_off;
-        std::vector<int32_t> values, lengths;
     };
     std::vector<Block> blocks;
     for (size_t k = 0; k < nd; ++k) {
@@ -797,7 +850,6 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
             const RangeBlock G(order, B.a, B.b, rid, loc, width, strand);
             const double t0 = now_s();
             bsig_plan *plan = nullptr;
-            bsig_runs *enc = nullptr;
             rk = plain_plan(sl.ctx[k], reads[k], (int64_t)m, G.rid.data(), G.loc.data(), G.width.data(), G.strand.data(), prm, frag_len, &plan);
             if (rk == BSIG_OK && bsig_plan_cells(plan) != B.cells) rk = fail(BSIG_ERR_ARG, "a block's cells do not match its plan's");
             const double t1 = now_s();
@@ -805,18 +857,12 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
             if (rk == BSIG_OK) rk = bsig_ctx_sync(sl.ctx[k]);
             // (a bin past INT32_MAX fails the call before anything is encoded)
             if (rk == BSIG_OK) rk = bsig::plan_check_overflow(plan);
-            if (rk == BSIG_OK) rk = bsig_plan_runs_create(plan, &enc);
-            int64_t n_runs = 0;
-            if (rk == BSIG_OK) rk = bsig_runs_encode(enc, (const int32_t *)buf, &n_runs);
-            const double t2 = now_s();
+            double t2 = now_s();
             if (rk == BSIG_OK) {
                 B.seg_off.resize(m * (size_t)S + 1);
-                B.values.resize((size_t)n_runs);
-                B.lengths.resize((size_t)n_runs);
-                rk = bsig_runs_fetch(enc, B.seg_off.data(), B.values.data(), B.lengths.data());
+                rk = encode_block(enc, plan, (const int32_t *)buf, B, &t2);
             }
             if (nd == 1) { X[3] += t1 - t0; X[4] += t2 - t1; X[5] += now_s() - t2; }
-            if (enc) bsig_runs_free(enc);
             if (plan) bsig_plan_free(plan);
         }
         if (buf) bsig::block_free(sl.ctx[k]->device, buf, got);
@@ -831,19 +877,16 @@ int runs_on_slots(Slots &sl, const std::vector<bsig_reads *> &reads, int64_t n, 
             for (int64_t a = 0; a < S; ++a)
                 out.seg_off[(size_t)(order[(size_t)(B.a + t)] * S + a) + 1] = B.seg_off[(size_t)(t * S + a) + 1] - B.seg_off[(size_t)(t * S + a)];
     for (int64_t k = 0; k < n * S; ++k) out.seg_off[(size_t)k + 1] += out.seg_off[(size_t)k];
-    out.values.resize((size_t)out.seg_off.back());
-    out.lengths.resize((size_t)out.seg_off.back());
+    for (int c = 0; c < enc.n_cols; ++c) out.col[c].resize((size_t)out.seg_off.back() * enc.elem[c]);
     for (const Block &B : blocks)
         for (int64_t t = 0; t < B.b - B.a; ++t) {
             // (a range's segments are neighbours on both sides)
             const int64_t from = B.seg_off[(size_t)(t * S)], cnt = B.seg_off[(size_t)((t + 1) * S)] - from;
             const int64_t to = out.seg_off[(size_t)(order[(size_t)(B.a + t)] * S)];
-            if (cnt) {
-                memcpy(out.values.data() + to, B.values.data() + from, (size_t)cnt * sizeof(int32_t));
-                memcpy(out.lengths.data() + to, B.lengths.data() + from, (size_t)cnt * sizeof(int32_t));
-            }
+            for (int c = 0; cnt && c < enc.n_cols; ++c)
+                memcpy(out.col[c].data() + (size_t)to * enc.elem[c], B.col[c].data() + (size_t)from * enc.elem[c], (size_t)cnt * enc.elem[c]);
         }
-    route = "runs of " + std::to_string(blocks.size()) + " block(s) of ranges, put in order on the host";
+    route = std::string(enc.noun) + " of " + std::to_string(blocks.size()) + " block(s) of ranges, put in order on the host";
     return BSIG_OK;
 }
 
@@ -859,7 +902,8 @@ struct FileDest {
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
     int32_t arg = 0;                // xcorr: max_lag; frag: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins
     const int32_t *thresholds = nullptr;    // summary: arg of them
-    bsig_runs_result *runs = nullptr;   // the per-range result as runs, in the caller's range order
+    EncodedColumns *runs = nullptr;            // the per-range result as runs or views (enc says which), in the caller's range order
+    Encoder enc = runs_encoder();
     static FileDest reduce(Reduce kind, int64_t *cells, int32_t arg = 0)
     {
         FileDest to;
@@ -898,7 +942,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         switch (to.kind) {
         case Reduce::none:
             if (!to.runs) break;
-            if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
+            if (prm.mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no %s: one cell per range", to.enc.noun);
             rc = bsig::check_params(prm, n, width, &early, frag_len);
             break;
         case Reduce::sum:
@@ -1243,7 +1287,7 @@ int file_level(const char *bampath, int64_t n, const int32_t *seq_code, int32_t 
         rc = reduced_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, cells, row, to.reduced, X, gather, make_plan,
                               to.kind == Reduce::scaled ? "scaled" : to.kind == Reduce::summary ? "summary" : "sum");
     } else if (to.runs) {
-        rc = runs_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, frag_len, rule, *to.runs, X, gather);
+        rc = encoded_on_slots(*slots, res->reads, n, rid.data(), loc.data(), width, strand, prm, frag_len, rule, to.enc, *to.runs, X, gather);
     } else if (!many) {
         // plan (ranges -> tiles in HBM), kernels, download -- timed apart
         bsig_plan *plan = nullptr;
@@ -1696,17 +1740,17 @@ int bsig_coverage_runs(const char *bampath, int64_t n, const int32_t *seq_code, 
 
 int64_t bsig_runs_result_n_seg(const bsig_runs_result *r) { return r ? r->n_seg : 0; }
 
-int64_t bsig_runs_result_n_runs(const bsig_runs_result *r) { return r && !r->seg_off.empty() ? r->seg_off.back() : 0; }
+int64_t bsig_runs_result_n_runs(const bsig_runs_result *r) { return r ? r->entries() : 0; }
 
 int bsig_runs_result_copy(const bsig_runs_result *r, int64_t *seg_off, int32_t *values, int32_t *lengths)
 {
     if (!r || !seg_off) return fail(BSIG_ERR_ARG, "NULL argument");
-    const size_t n_runs = (size_t)bsig_runs_result_n_runs(r);
+    const size_t n_runs = (size_t)r->entries();
     if (n_runs && (!values || !lengths)) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     memcpy(seg_off, r->seg_off.data(), r->seg_off.size() * sizeof(int64_t));
     if (n_runs) {
-        memcpy(values, r->values.data(), n_runs * sizeof(int32_t));
-        memcpy(lengths, r->lengths.data(), n_runs * sizeof(int32_t));
+        memcpy(values, r->col[0].data(), n_runs * sizeof(int32_t));
+        memcpy(lengths, r->col[1].data(), n_runs * sizeof(int32_t));
     }
     return BSIG_OK;
 }
@@ -1776,6 +1820,89 @@ int bsig_coverage_runs_resized(const char *bampath, int64_t n, const int32_t *se
     if (rc == BSIG_OK) *result = res.release();
     return rc;
 }
+
+// The three runs calls with the thresholds of the views behind their arguments: the same dispatcher, the same route, the
+// views encoder in the blocks' loop.  The thresholds are judged here, before file_level opens the BAM.
+static int views_call(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels, const char *const *levels,
+                      const int32_t *start, const int32_t *width, const int32_t *strand, const bsig_params &p, int32_t device,
+                      int32_t frag_len, int32_t lower, int32_t upper, bsig_views_result **result)
+{
+    std::unique_ptr<bsig_views_result> res(new bsig_views_result);
+    FileDest to;
+    to.runs = res.get();
+    to.enc = views_encoder(lower, upper);
+    const int rc = file_level(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, to, frag_len);
+    if (rc == BSIG_OK) *result = res.release();
+    return rc;
+}
+
+static int views_thresholds(int32_t lower, int32_t upper, bsig_views_result **result)
+{
+    if (!result) return fail(BSIG_ERR_ARG, "result is NULL");
+    *result = nullptr;
+    if (lower > upper) return fail(BSIG_ERR_ARG, "lower (%d) is above upper (%d)", (int)lower, (int)upper);
+    return BSIG_OK;
+}
+
+int bsig_pileup_views(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                      const char *const *levels, const int32_t *start, const int32_t *width,
+                      const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss, int32_t requiredF,
+                      int32_t filteredF, int32_t pe_mid, int32_t maxgap, int32_t device, int32_t lower, int32_t upper,
+                      bsig_views_result **result)
+{
+    (void)maxgap;
+    if (const int rc = views_thresholds(lower, upper, result)) return rc;
+    return views_call(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device, 0,
+                      lower, upper, result);
+}
+
+int bsig_coverage_views(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                        const char *const *levels, const int32_t *start, const int32_t *width,
+                        const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                        int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                        int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t lower, int32_t upper,
+                        bsig_views_result **result)
+{
+    (void)maxgap;
+    if (const int rc = views_thresholds(lower, upper, result)) return rc;
+    return views_call(bampath, n, seq_code, n_levels, levels, start, width, strand,
+                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device, 0,
+                      lower, upper, result);
+}
+
+int bsig_coverage_views_resized(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                                const char *const *levels, const int32_t *start, const int32_t *width,
+                                const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                                int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                                int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t lower, int32_t upper,
+                                bsig_views_result **result)
+{
+    (void)maxgap;
+    if (const int rc = views_thresholds(lower, upper, result)) return rc;
+    const bsig_params p = coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss);
+    if (const int rc = bsig::resized_rule(p, frag_len)) return rc;
+    return views_call(bampath, n, seq_code, n_levels, levels, start, width, strand, p, device, frag_len, lower, upper, result);
+}
+
+int64_t bsig_views_result_n_seg(const bsig_views_result *r) { return r ? r->n_seg : 0; }
+
+int64_t bsig_views_result_n_views(const bsig_views_result *r) { return r ? r->entries() : 0; }
+
+int bsig_views_result_copy(const bsig_views_result *r, int64_t *seg_off, int32_t *start, int32_t *width, int64_t *sum, int32_t *max,
+                           int32_t *summit)
+{
+    if (!r || !seg_off) return fail(BSIG_ERR_ARG, "NULL argument");
+    const size_t n = (size_t)r->entries();
+    if (n && (!start || !width || !sum || !max || !summit)) return fail(BSIG_ERR_ARG, "output buffer is NULL");
+    memcpy(seg_off, r->seg_off.data(), r->seg_off.size() * sizeof(int64_t));
+    void *const dst[EncodedColumns::kMaxCols] = {start, width, sum, max, summit};
+    for (int c = 0; n && c < EncodedColumns::kMaxCols; ++c) memcpy(dst[c], r->col[c].data(), r->col[c].size());
+    return BSIG_OK;
+}
+
+void bsig_views_result_free(bsig_views_result *r) { delete r; }
 
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath)
 {

@@ -11,7 +11,8 @@
 // them (no workgroup ever waits for another one):
 //   1. k_runs_walk<false>  counts the run starts of every stretch (a cell is a start iff it is first in its segment or
 //                          differs from its predecessor): one __ballot and one population count per 64 cells
-//   2. k_runs_scan         one workgroup: exclusive scan of the stretch counts in 64 bits, and the total
+//   2. k_runs_scan         one workgroup: exclusive scan of the stretch counts in 64 bits, and the total (encode_common.h,
+//                          with the segment table, seg_of and k_runs_fill_empty: shared with views.hip)
 //      -- the host reads the total and allocates values / lengths / positions at their exact size --
 //   3. k_runs_walk<true>   the same walk: every start stores its value and its flattened position at its scanned slot;
 //                          the first cell of a segment also stores its slot as the segment's run offset
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../../include/bamsignals_abi.h"
+#include "encode_common.h"
 #include "host_util.h"
 #include "runtime_internal.h"
 
@@ -35,22 +37,7 @@ using bsig::fail;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kUnroll = 4;                   // rounds of 64 cells whose loads are issued together
-constexpr int kScanThreads = 1024;
-constexpr int kFlatThreads = 256;            // the per-run and per-segment passes
-constexpr int32_t kDefaultChunk = 2048;      // cells per stretch (env BAMSIGNALS_RUNS_CHUNK_CELLS)
-
-// the segment of flattened cell c: the largest s in [lo, hi] with cell0[s] <= c (cell0[lo] <= c; empty segments share
-// their cell0 with the next segment, so the largest one is the segment that holds the cell)
-__device__ __forceinline__ int64_t seg_of(const int64_t *__restrict__ cell0, int64_t lo, int64_t hi, int64_t c)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (cell0[mid] <= c) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // EMIT = false: counts[stretch] = run starts of the stretch.  EMIT = true: st_base[stretch] = runs before the stretch;
 // every start stores values / pos at its slot, a segment's first cell stores seg_off.
@@ -126,34 +113,6 @@ __global__ __launch_bounds__(kWave) void k_runs_walk(const int32_t *__restrict__
     if (!EMIT && lane == 0) counts[blockIdx.x] = n_starts;
 }
 
-// Exclusive scan of the stretch counts in 64 bits, and the total.  One workgroup, as k_chunk_scan (kernels.hip): every
-// thread sums a slab of consecutive stretches, the slab sums are scanned in LDS, every thread writes its slab's bases.
-__global__ __launch_bounds__(kScanThreads) void k_runs_scan(int64_t n, const uint32_t *__restrict__ counts,
-                                                            int64_t *__restrict__ st_base, int64_t *__restrict__ total)
-{
-    __shared__ int64_t slab[kScanThreads];
-    const int tid = threadIdx.x;
-    const int64_t per = (n + kScanThreads - 1) / kScanThreads;
-    const int64_t k0 = (int64_t)tid * per < n ? (int64_t)tid * per : n, k1 = k0 + per < n ? k0 + per : n;
-    int64_t sum = 0;
-    for (int64_t k = k0; k < k1; ++k) sum += counts[k];
-    slab[tid] = sum;
-    __syncthreads();
-    // inclusive scan over the slabs, in place (Hillis-Steele: ten steps)
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const int64_t add = tid >= d ? slab[tid - d] : 0;
-        __syncthreads();
-        slab[tid] += add;
-        __syncthreads();
-    }
-    int64_t run = slab[tid] - sum;
-    for (int64_t k = k0; k < k1; ++k) {
-        st_base[k] = run;
-        run += counts[k];
-    }
-    if (tid == kScanThreads - 1) *total = slab[tid];
-}
-
 // length[r] = the distance to the next start (pos holds the low 32 bits of the flattened positions: a run is shorter
 // than 2^31 cells, so the difference is exact)
 __global__ __launch_bounds__(kFlatThreads) void k_runs_lengths(int64_t n_runs, const uint32_t *__restrict__ pos, uint32_t total_lo,
@@ -165,33 +124,10 @@ __global__ __launch_bounds__(kFlatThreads) void k_runs_lengths(int64_t n_runs, c
     lengths[r] = (int32_t)(next - pos[r]);
 }
 
-// seg_off of the zero-length segments and seg_off[n_seg]: a zero-length segment has the offset of the next segment
-// that holds a cell (which k_runs_walk<true> stored), or the total
-__global__ __launch_bounds__(kFlatThreads) void k_runs_fill_empty(int64_t n_seg, const int64_t *__restrict__ cell0, int64_t total,
-                                                                  int64_t n_runs, int64_t *__restrict__ seg_off)
-{
-    const int64_t k = (int64_t)blockIdx.x * kFlatThreads + threadIdx.x;
-    if (k > n_seg) return;
-    if (k == n_seg) { seg_off[k] = n_runs; return; }
-    const int64_t c = cell0[k];
-    if (cell0[k + 1] != c) return;
-    seg_off[k] = c >= total ? n_runs : seg_off[seg_of(cell0, k, n_seg - 1, c)];
-}
-
 }  // namespace
 
-struct bsig_runs {
-    bsig_ctx *ctx = nullptr;
-    int64_t n_seg = 0, total = 0, n_st = 0;
-    int32_t stride = 1, chunk = kDefaultChunk;
-    bool has_empty = false;
-    DevPool pool;                        // the tables and the scan's arrays: as long as the object
-    int64_t *cell0 = nullptr;            // n_seg + 1
-    int64_t *base = nullptr;             // n_seg
-    uint32_t *counts = nullptr;          // n_st
-    int64_t *st_base = nullptr;          // n_st
-    int64_t *d_total = nullptr;
-    int64_t *seg_off = nullptr;          // n_seg + 1
+// (the segment table and the scan's arrays: encode_common.h)
+struct bsig_runs : SegTable {
     std::unique_ptr<DevPool> res;        // values, lengths and positions of the last encode, at their exact size
     int64_t n_runs = -1;                 // of the last encode (-1: none yet)
     int32_t *values = nullptr, *lengths = nullptr;
@@ -203,47 +139,8 @@ int bsig_runs_create(bsig_ctx *ctx, int64_t n_seg, const int64_t *base, const in
 {
     if (!ctx || !out) return fail(BSIG_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (n_seg < 0) return fail(BSIG_ERR_ARG, "negative number of segments");
-    if (n_seg > 0 && (!base || !len)) return fail(BSIG_ERR_ARG, "segment table missing");
-    if (stride != 1 && stride != 2) return fail(BSIG_ERR_ARG, "stride must be 1 or 2");
-    std::vector<int64_t> cell0((size_t)n_seg + 1);
-    bool has_empty = false;
-    int64_t acc = 0;
-    for (int64_t k = 0; k < n_seg; ++k) {
-        if (len[k] < 0) return fail(BSIG_ERR_ARG, "segment %lld has a negative length", (long long)k);
-        if (base[k] < 0) return fail(BSIG_ERR_ARG, "segment %lld has a negative base", (long long)k);
-        cell0[(size_t)k] = acc;
-        acc += len[k];
-        has_empty = has_empty || len[k] == 0;
-    }
-    cell0[(size_t)n_seg] = acc;
     std::unique_ptr<bsig_runs> R(new bsig_runs);
-    R->ctx = ctx;
-    R->n_seg = n_seg;
-    R->total = acc;
-    R->stride = stride;
-    R->has_empty = has_empty;
-    if (const char *e = getenv("BAMSIGNALS_RUNS_CHUNK_CELLS")) {      // (testing: seams everywhere)
-        const long long v = atoll(e);
-        if (v >= kWave && v <= (1 << 24)) R->chunk = (int32_t)v;
-    }
-    R->n_st = (acc + R->chunk - 1) / R->chunk;
-    if (R->n_st > INT32_MAX) return fail(BSIG_ERR_ARG, "too many cells for one encoder: %lld", (long long)acc);
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(R->pool.alloc(&R->cell0, (size_t)n_seg + 1));
-    HIP_TRY(R->pool.alloc(&R->seg_off, (size_t)n_seg + 1));
-    HIP_TRY(R->pool.alloc(&R->d_total, 1));
-    HIP_TRY(hipMemcpyAsync(R->cell0, cell0.data(), ((size_t)n_seg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (n_seg) {
-        HIP_TRY(R->pool.alloc(&R->base, (size_t)n_seg));
-        HIP_TRY(hipMemcpyAsync(R->base, base, (size_t)n_seg * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    }
-    if (R->n_st) {
-        HIP_TRY(R->pool.alloc(&R->counts, (size_t)R->n_st));
-        HIP_TRY(R->pool.alloc(&R->st_base, (size_t)R->n_st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));      // (the host tables go away)
+    if (const int rc = R->build(ctx, n_seg, base, len, stride, "BAMSIGNALS_RUNS_CHUNK_CELLS")) return rc;
     *out = R.release();
     return BSIG_OK;
 }

@@ -2832,24 +2832,45 @@ int bsig_plan_run_summary_host(bsig_plan *p, int64_t *host) { return run_reduced
 int bsig_plan_run_scaled_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kScaled, host); }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
-// The run-length encoder (runs.hip) of a plan's own layout: range i's cells off[i] .. off[i + 1] are one segment, or with
-// strands the two rows of the 2 * bin + antisense cells (stride 2)
-int bsig_plan_runs_create(const bsig_plan *p, bsig_runs **out)
+// The segment table of a plan's own layout, for the encoders of a per-range result (runs.hip, views.hip): range i's cells
+// off[i] .. off[i + 1] are one segment, or with strands the two rows of the 2 * bin + antisense cells (stride 2)
+static int plan_segments(const bsig_plan *p, const char *what, std::vector<int64_t> &base, std::vector<int32_t> &len, int *stride)
 {
-    if (!p || !out) return fail(BSIG_ERR_ARG, "NULL argument");
-    *out = nullptr;
     if (p->kind != kPlain)      // (the kind's noun without its article)
         return fail(BSIG_ERR_ARG, "a %s plan has no per-range result to encode", strchr(kKinds[p->kind].a, ' ') + 1);
-    if (p->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no runs: one cell per range");
+    if (p->mode == BSIG_MODE_COUNT) return fail(BSIG_ERR_ARG, "bamCount has no %s: one cell per range", what);
     const int S = p->kp.ss ? 2 : 1;
-    std::vector<int64_t> base((size_t)(p->n_ranges * S));
-    std::vector<int32_t> len((size_t)(p->n_ranges * S));
+    base.resize((size_t)(p->n_ranges * S));
+    len.resize((size_t)(p->n_ranges * S));
     for (int64_t i = 0; i < p->n_ranges; ++i)
         for (int a = 0; a < S; ++a) {
             base[(size_t)(i * S + a)] = p->off[(size_t)i] + a;
             len[(size_t)(i * S + a)] = (int32_t)((p->off[(size_t)i + 1] - p->off[(size_t)i]) / S);
         }
+    *stride = S;
+    return BSIG_OK;
+}
+
+int bsig_plan_runs_create(const bsig_plan *p, bsig_runs **out)
+{
+    if (!p || !out) return fail(BSIG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    std::vector<int64_t> base;
+    std::vector<int32_t> len;
+    int S = 1;
+    if (const int rc = plan_segments(p, "runs", base, len, &S)) return rc;
     return bsig_runs_create(p->ctx, p->n_ranges * S, base.data(), len.data(), S, out);
+}
+
+int bsig_plan_views_create(const bsig_plan *p, bsig_views **out)
+{
+    if (!p || !out) return fail(BSIG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    std::vector<int64_t> base;
+    std::vector<int32_t> len;
+    int S = 1;
+    if (const int rc = plan_segments(p, "views", base, len, &S)) return rc;
+    return bsig_views_create(p->ctx, p->n_ranges * S, base.data(), len.data(), S, out);
 }
 
 int bsig_debug_new_layout_gen(bsig_reads *reads)

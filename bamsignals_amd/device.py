@@ -327,6 +327,13 @@ class Plan(_PlanBase):
         _lib.check(self._lib.bsig_plan_runs_create(self._h, C.byref(h)))
         return RunEncoder._adopt(self.ctx, h)
 
+    def views(self):
+        """The views encoder of this plan's result layout (bsig_plan_views_create): the segments of ``runs()``;
+        ``encode`` what ``run_device`` wrote, at any thresholds.  Not for a bamCount plan."""
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_plan_views_create(self._h, C.byref(h)))
+        return ViewEncoder._adopt(self.ctx, h)
+
 
 class _ReducedPlan(_PlanBase):
     """A plan that reduces all its ranges to ``cells`` int64 (bsig_plan_create_<_KIND>, bsig_plan_run_<_KIND>[_host])."""
@@ -521,6 +528,74 @@ class RunEncoder:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.bsig_runs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class ViewEncoder:
+    """Views of int32 device buffers (bsig_views_*): the segments are ``RunEncoder``'s.  ``encode(src_ptr, lower, upper)``
+    finds the maximal stretches of consecutive cells with ``lower <= v <= upper`` (signed) of every segment on the device
+    and returns their number; ``fetch()`` copies them to the host -- ``seg_off`` (segment k owns views ``seg_off[k] ..
+    seg_off[k + 1]``), ``start`` and ``width`` in cells of the segment, ``sum`` (int64), ``max`` and ``summit`` (the first
+    cell of the segment that holds the max) -- ``device_pointers()`` leaves them in HBM.  An object encodes any number of
+    buffers at any thresholds."""
+
+    NAMES = ("seg_off", "start", "width", "sum", "max", "summit")
+    DTYPES = (np.int64, np.int32, np.int32, np.int64, np.int32, np.int32)
+
+    def __init__(self, ctx, base, length, stride=1):
+        self._lib = _lib.load()
+        base = np.ascontiguousarray(base, dtype=np.int64)
+        length = _i32(length)
+        if len(base) != len(length):
+            raise ValueError("base and length differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_views_create(ctx._h, len(base), _ptr(base), _ptr(length), int(stride), C.byref(h)))
+        self.ctx, self._h = ctx, h
+        self.n_seg = len(base)
+        self.cells = int(self._lib.bsig_views_cells(h))
+        self.n_views = None
+
+    @classmethod
+    def _adopt(cls, ctx, h):
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        self.ctx, self._h = ctx, h
+        self.n_seg = int(self._lib.bsig_views_n_seg(h))
+        self.cells = int(self._lib.bsig_views_cells(h))
+        self.n_views = None
+        return self
+
+    def encode(self, src_ptr, lower, upper=2**31 - 1):
+        """Find the views of the int32 device buffer at ``src_ptr`` (synchronises); returns their number."""
+        n = C.c_int64(0)
+        self.n_views = None
+        _lib.check(self._lib.bsig_views_encode(self._h, C.c_void_p(src_ptr), int(lower), int(upper), C.byref(n)))
+        self.n_views = int(n.value)
+        return self.n_views
+
+    def device_pointers(self):
+        """(n_views, seg_off, start, width, sum, max, summit): device addresses of the last encode's result (valid until
+        the next; the five value addresses are None when there is no view)."""
+        n = C.c_int64(0)
+        ps = [C.c_void_p() for _ in range(6)]
+        _lib.check(self._lib.bsig_views_device(self._h, C.byref(n), *[C.byref(p) for p in ps]))
+        return (int(n.value),) + tuple(p.value for p in ps)
+
+    def fetch(self):
+        """(seg_off int64[n_seg + 1], start, width int32[n_views], sum int64[n_views], max, summit int32[n_views]) of the
+        last encode, in host memory."""
+        if self.n_views is None:
+            raise ValueError("nothing has been encoded yet")
+        out = [np.empty(self.n_seg + 1 if k == 0 else self.n_views, dtype=dt) for k, dt in enumerate(self.DTYPES)]
+        _lib.check(self._lib.bsig_views_fetch(self._h, *[_ptr(a) if a.size else None for a in out]))
+        return tuple(out)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bsig_views_free(self._h)
             self._h = None
 
     def __del__(self):

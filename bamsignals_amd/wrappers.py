@@ -194,7 +194,7 @@ def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1,
 
 
 def _coverage_rule(lib, what, tspan, frag_len):
-    """The file-level coverage call of a kind (``core_ex`` / ``sum`` / ``runs``) and the int32 that travels in its
+    """The file-level coverage call of a kind (``core_ex`` / ``sum`` / ``runs`` / ``views``) and the int32 that travels in its
     interval-rule slot: ``tspan``, or with ``frag_len`` the resized call (bsig_coverage_<what>_resized) and the length."""
     if frag_len:
         if tspan:
@@ -338,6 +338,43 @@ def coverage_runs(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1
     _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
                   int(bool(ss)), C.byref(h)))
     return _take_runs(lib, h, ss)
+
+
+def _take_views(lib, handle, ss):
+    """a bsig_views_result handle -> SignalViews (the arrays are allocated once the handle says how large they are)"""
+    from .views import SignalViews
+    try:
+        n_seg, n = int(lib.bsig_views_result_n_seg(handle)), int(lib.bsig_views_result_n_views(handle))
+        out = [np.empty(n_seg + 1, dtype=np.int64)] + [np.empty(n, dtype=dt) for dt in (np.int32, np.int32, np.int64, np.int32, np.int32)]
+        _lib.check(lib.bsig_views_result_copy(handle, *[a.ctypes.data if a.size else None for a in out]))
+    finally:
+        lib.bsig_views_result_free(handle)
+    return SignalViews(*out, bool(ss))
+
+
+def pileup_views(bampath, gr, tlen_filter, lower, upper, mapqual=0, binsize=1, shift=0, ss=False, requiredF=0,
+                 filteredF=-1, pe_mid=False, maxgap=16385, device=None):
+    """The views of bamProfile's signals (bsig_pileup_views): a SignalViews of the stretches with ``lower <= v <= upper``;
+    the per-base cells stay on the GPU."""
+    head = _head(bampath, gr, tlen_filter)
+    lib = _lib.load()
+    h = C.c_void_p()
+    _lib.check(lib.bsig_pileup_views(*head, int(mapqual), int(binsize), int(shift), int(bool(ss)), int(requiredF), int(filteredF),
+                                     int(bool(pe_mid)), int(maxgap), _dev(device), int(lower), int(upper), C.byref(h)))
+    return _take_views(lib, h, ss)
+
+
+def coverage_views(bampath, gr, tlen_filter, lower, upper, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
+                   maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+    """The views of bamCoverage's signals (bsig_coverage_views): a SignalViews, as ``pileup_views``.
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_views_resized)."""
+    head = _head(bampath, gr, tlen_filter)
+    lib = _lib.load()
+    h = C.c_void_p()
+    fn, rule = _coverage_rule(lib, "views", tspan, frag_len)
+    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
+                  int(bool(ss)), int(lower), int(upper), C.byref(h)))
+    return _take_views(lib, h, ss)
 
 
 def _is_ex(binsize, ss):

@@ -448,6 +448,36 @@ void bsig_runs_free(bsig_runs *runs);
  * fail with BSIG_ERR_ARG. */
 int bsig_plan_runs_create(const bsig_plan *plan, bsig_runs **runs);
 
+/* Views on the device: the stretches of a per-range result that lie in a band of values, each with its sum, its max and
+ * its summit (IRanges' slice() with viewSums / viewMaxs / viewWhichMaxs; callable regions; candidate peaks).  The input is
+ * bsig_runs_create's, with its refusals: any int32 device buffer plus a table of segments, stride 1 or 2.  A cell is IN
+ * iff lower <= v <= upper, compared as signed 32-bit; a VIEW is a maximal stretch of consecutive in-cells of one segment: a
+ * segment boundary always ends a view, a zero-length segment has none, a segment with cells may have none.  The result is
+ * six device arrays:
+ *   seg_off  int64, n_seg + 1 : segment k owns views seg_off[k] .. seg_off[k + 1]
+ *   start    int32  0-based cell index inside the segment of the view's first cell      width   int32, >= 1
+ *   sum      int64  of the view's cells                                                  max     int32
+ *   summit   int32  cell index inside the segment of the FIRST cell that holds the max (bsig_plan_create_summary's tie rule)
+ * The thresholds belong to the encode, not to the object: one resident buffer can be asked at several depths.
+ * bsig_views_encode counts the views, allocates the five value arrays at their exact size, writes them and synchronises;
+ * lower > upper is BSIG_ERR_ARG; each encode replaces the result of the one before.  No view at all is a legal result: the
+ * value pointers of bsig_views_device are then NULL, and bsig_views_fetch accepts NULL for them.  The result is exact,
+ * does not depend on the stretch, and is the same on every run (integer atomics only where a view crosses stretches).
+ * env BAMSIGNALS_VIEWS_CHUNK_CELLS (read by bsig_views_create; 64 .. 2^24, default 2,048): the cells of the flattened
+ * segments that one workgroup walks (testing).                                                                         */
+typedef struct bsig_views bsig_views;
+int bsig_views_create(bsig_ctx *ctx, int64_t n_seg, const int64_t *base, const int32_t *len, int32_t stride, bsig_views **views);
+int64_t bsig_views_n_seg(const bsig_views *views);
+int64_t bsig_views_cells(const bsig_views *views);               /* the sum of len                              */
+int bsig_views_encode(bsig_views *views, const int32_t *src_dev, int32_t lower, int32_t upper, int64_t *n_views);
+int bsig_views_device(const bsig_views *views, int64_t *n_views, const int64_t **seg_off, const int32_t **start,
+                      const int32_t **width, const int64_t **sum, const int32_t **max, const int32_t **summit);
+int bsig_views_fetch(bsig_views *views, int64_t *seg_off, int32_t *start, int32_t *width, int64_t *sum, int32_t *max,
+                     int32_t *summit);
+void bsig_views_free(bsig_views *views);
+/* The views encoder of a plan's own result layout: the segments and the refusals of bsig_plan_runs_create. */
+int bsig_plan_views_create(const bsig_plan *plan, bsig_views **views);
+
 /* one-shot: columns already in HBM -> host result (upload ranges, run, download)               */
 int bsig_pileup_columns(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges,
                         const int32_t *rid, const int32_t *loc, const int32_t *len,
@@ -728,6 +758,40 @@ int64_t bsig_runs_result_n_seg(const bsig_runs_result *result);
 int64_t bsig_runs_result_n_runs(const bsig_runs_result *result);
 int bsig_runs_result_copy(const bsig_runs_result *result, int64_t *seg_off, int32_t *values, int32_t *lengths);
 void bsig_runs_result_free(bsig_runs_result *result);
+/* The file-level calls with the result as VIEWS (bsig_views_*, where a view is defined): the arguments of bsig_pileup_runs,
+ * bsig_coverage_runs and bsig_coverage_runs_resized plus the thresholds lower <= upper, on the same route -- blocks of at
+ * most env BAMSIGNALS_RUNS_BLOCK_CELLS cells of the (rid, loc)-sorted ranges, each GPU a contiguous share, only the views
+ * downloaded, the segments put in the caller's range order on the host.  binsize <= 0 fails with BSIG_ERR_ARG; all
+ * parameters, lower <= upper included, are checked before the BAM is opened.  The result is a host-side handle: ask it for
+ * n_seg and n_views, copy it out (seg_off: n_seg + 1 int64; start, width, max, summit: n_views int32 each; sum: n_views
+ * int64; the value pointers may be NULL when there is no view) and free it.  bsig_last_call_route() says "views".      */
+typedef struct bsig_views_result bsig_views_result;
+int bsig_pileup_views(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                      int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                      const int32_t *width, const int32_t *strand,
+                      const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss,
+                      int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t maxgap,
+                      int32_t device, int32_t lower, int32_t upper, bsig_views_result **result);
+int bsig_coverage_views(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                        int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                        const int32_t *width, const int32_t *strand,
+                        const int32_t *tlen_filter, int32_t n_tlen_filter,
+                        int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
+                        int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+                        int32_t lower, int32_t upper, bsig_views_result **result);
+int bsig_coverage_views_resized(const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+                                int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+                                const int32_t *width, const int32_t *strand,
+                                const int32_t *tlen_filter, int32_t n_tlen_filter,
+                                int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
+                                int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+                                int32_t lower, int32_t upper, bsig_views_result **result);
+int64_t bsig_views_result_n_seg(const bsig_views_result *result);
+int64_t bsig_views_result_n_views(const bsig_views_result *result);
+int bsig_views_result_copy(const bsig_views_result *result, int64_t *seg_off, int32_t *start, int32_t *width, int64_t *sum,
+                           int32_t *max, int32_t *summit);
+void bsig_views_result_free(bsig_views_result *result);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
