@@ -1,7 +1,7 @@
 # Diagnostic: the north star's and the real-shaped file's decode under k_inflate's register budgets.
 # Needs builds without the three-waves-per-SIMD request:
 #   for w in 2 1; do (cd bamsignals_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-kernarg-preload-count=8 \
-#      -DBSIG_INFLATE_WAVES=$w -shared -o ../libbamsignals_hip_w$w.so kernels.hip runtime.hip devdecode.hip collect.hip bamio.cpp fileapi.cpp -lz -lpthread -ldl); done
+#      -DBSIG_INFLATE_WAVES=$w -shared -o ../libbamsignals_hip_w$w.so kernels.hip runtime.hip devdecode.hip collect.hip bamio.cpp fileapi.cpp filecall.cpp -lz -lpthread -ldl); done
 mkdir -p gpurun_out
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 export BSIG_KEEP_BAM=1

@@ -2,7 +2,7 @@
 """Diagnostic: where a lane of k_inflate spends its time.  Needs the profiling build
   (cd bamsignals_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-kernarg-preload-count=8 \
      -DBSIG_INFLATE_PROF -shared -o ../libbamsignals_hip_prof.so kernels.hip runtime.hip devdecode.hip collect.hip \
-     bamio.cpp fileapi.cpp -lz -lpthread -ldl)
+     bamio.cpp fileapi.cpp filecall.cpp -lz -lpthread -ldl)
 which counts per lane: turns of the symbol loop, turns that carried literals / a slice of a match, symbols that
 missed the first-level table, deflate blocks (= code tables built) and the shader-clock cycles between a deflate
 block's first bit and its first symbol.  Lanes of a wave run in lockstep, so a lane's cycles include what it
