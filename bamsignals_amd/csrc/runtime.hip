@@ -326,7 +326,7 @@ struct bsig_plan {
     DevPool pool;
     BsigWorkItem *items = nullptr;
     int32_t *d_out = nullptr;      // device result buffer of bsig_plan_run_host, kept between calls
-    // slices of heavy tiles (tiles whose read windows hold more than kHeavyReads reads): the same
+    // slices of heavy tiles (tiles whose read windows hold more reads than probe_windows' heavy_reads): the same
     // kernels run a second time over these items with fixed windows and accumulate = 1
     BsigWorkItem *heavy_items = nullptr;
     void *heavy_windows = nullptr;
@@ -1684,378 +1684,267 @@ struct PlanRequest {
         const bsig::ScaledShape *scaled;
     };
 };
-// the reads in tile t's windows (win: BSIG_MAX_CLASSES index ranges a tile, k_resolve_tiles' output)
-static int64_t tile_reads(const std::vector<uint2> &win, size_t t)
+// (planmath.h's pairs go to the device as uint2, byte for byte)
+static_assert(sizeof(bsig::Pair32) == sizeof(uint2) && offsetof(bsig::Pair32, x) == offsetof(uint2, x) && offsetof(bsig::Pair32, y) == offsetof(uint2, y),
+              "Pair32 must be laid out as uint2");
+static bsig::KindFacts kind_facts(const PlanRequest &rq)
 {
-    int64_t total = 0;
-    for (int c = 0; c < BSIG_MAX_CLASSES; ++c) total += (int64_t)win[t * BSIG_MAX_CLASSES + c].y - win[t * BSIG_MAX_CLASSES + c].x;
-    return total;
+    bsig::KindFacts kf;
+    switch (rq.kind) {
+    case kPlain: break;
+    case kSum: kf.sum = true; break;
+    case kXcorr: kf.xcorr = true; kf.xcorr_body = rq.xcorr->body; kf.max_lag = rq.xcorr->max_lag; break;
+    case kFrag: kf.frag = true; kf.len_bin = rq.frag->len_bin; break;
+    // the kinds that walk their tiles whole: the caller's tile (16 .. 2,048 cells, checked by the kind's *_shape)
+    case kHist: kf.own_tile_cells = rq.hist->tiles.tile_cells; break;
+    case kSummary: kf.own_tile_cells = rq.summary->tiles.tile_cells; kf.row_tiles = true; break;
+    case kScaled: kf.own_tile_cells = rq.scaled->tiles.tile_cells; kf.row_tiles = true; break;
+    }
+    return kf;
 }
+// What plan_create_impl's stages hand on: the caller's arguments, the plan being made, and the host side of its tiles
+struct PlanWork {
+    bsig_ctx *ctx;
+    const bsig_reads *reads;
+    int64_t n;
+    const int32_t *rid, *loc, *len, *strand;
+    const bsig_params *prm;
+    const PlanRequest &rq;
+    bsig::PlanRule r{};
+    bsig::KindFacts kf;
+    bsig::TileSize ts{};
+    std::unique_ptr<bsig_plan> plan;
+    std::vector<BsigWorkItem> items;
+    // probe_windows: the tiles' windows on the device; on the host (with the reads they hold, tile by tile) only when
+    // somebody reads them
+    DevPool tmp;
+    uint2 *d_win = nullptr;
+    bool any_heavy = false;
+    std::vector<bsig::Pair32> win;
+    std::vector<int64_t> reads_of_tile;
+    int64_t heavy_reads = 0, slice_reads = 0;
+    bsig::HeavySplit heavy;
+    PlanWork(bsig_ctx *ctx_, const bsig_reads *reads_, int64_t n_, const int32_t *rid_, const int32_t *loc_, const int32_t *len_,
+             const int32_t *strand_, const bsig_params *prm_, const PlanRequest &rq_)
+        : ctx(ctx_), reads(reads_), n(n_), rid(rid_), loc(loc_), len(len_), strand(strand_), prm(prm_), rq(rq_) {}
+    // a tile of these kinds is walked whole: a cell's value must be complete before it is counted or compared
+    bool whole_tiles() const { return rq.kind == kHist || kf.row_tiles; }
+};
+// every HIP error of plan creation is the one refusal
+static int upload_failed(hipError_t e)
+{
+    return fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "plan upload failed: %s", hipGetErrorString(e));
+}
+#define PLAN_TRY(expr)                                      \
+    do {                                                    \
+        const hipError_t e_ = (expr);                       \
+        if (e_ != hipSuccess) return upload_failed(e_);     \
+    } while (0)
+
+// stage 1: the arguments, the parameters (check_params), the chromosome ids
+static int check_request(PlanWork &W, bsig_plan **out)
+{
+    if (!W.ctx || !W.reads || !W.prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
+    *out = nullptr;
+    if (W.n < 0 || (W.n > 0 && (!W.rid || !W.loc || !W.len || !W.strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
+    if (const int rc = bsig::check_params(*W.prm, W.n, W.len, &W.r, W.rq.frag_len)) return rc;
+    for (int64_t i = 0; i < W.n; ++i)
+        if (W.rid[i] < 0 || W.rid[i] >= W.reads->n_ref)
+            return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", W.rid[i]);
+    return BSIG_OK;
+}
+// stage 2: the plan with its tile size and its kernels' parameters (planmath.h: tile_cells_for, fill_kparams)
+static void shape_plan(PlanWork &W)
+{
+    const bsig_reads *reads = W.reads;
+    W.plan.reset(new bsig_plan);
+    bsig_plan *P = W.plan.get();
+    P->ctx = W.ctx; P->reads = reads; P->mode = W.r.mode; P->n_ranges = W.n;
+    P->made_for_gen = reads->layout_gen;
+    P->threads = W.r.threads;
+    W.kf = kind_facts(W.rq);
+    W.ts = bsig::tile_cells_for(W.r, W.prm->tile_cells, W.n, W.len, W.kf);
+    P->tile_cells = W.ts.cells;
+    bsig::LayoutFacts L{};
+    const uint16_t *packed = reads->dev.cls[BSIG_CLASS_PACKED].p5h;
+    for (int c = 0; c < BSIG_MAX_CLASSES; ++c) {
+        const BsigClassCols &C = reads->dev.cls[c];
+        L.cls[c] = bsig::ClassFacts{C.n, C.maxspan, C.kshift, C.p5h != nullptr, C.p5h && packed ? (uint32_t)(C.p5h - packed) : 0u};
+    }
+    L.codes = reads->fmtab.data();
+    L.n_codes = reads->dev.n_codes;
+    const char *quad = getenv("BAMSIGNALS_OVERLAP_QUAD");
+    bsig::fill_kparams(P->kp, *W.prm, W.r, P->tile_cells, L, W.kf, quad && !strcmp(quad, "0"));
+}
+// stage 3: the result's layout, the ranges in genomic order (ref: std::sort by (rid, loc), src/bamsignals.cpp:222-226,246)
+// and their tiles (planmath.h: cut_tiles)
+static int cut_plan(PlanWork &W)
+{
+    bsig_plan *P = W.plan.get();
+    P->off.resize(W.n + 1);
+    bsig_layout(W.n, W.len, W.r.lay_binsize, P->kp.ss, P->off.data());
+    std::vector<int64_t> order;
+    bsig::sort_ranges(W.n, W.rid, W.loc, order);
+    bsig::Tiles T = bsig::cut_tiles(order, W.rid, W.loc, W.len, W.strand, P->off.data(), W.reads->ref_unit0.data(),
+                                    W.reads->ref_units.data(), W.r, W.prm->tile_cells, W.ts, W.kf);
+    W.items = std::move(T.items);
+    P->needs_zero = T.needs_zero;
+    P->kernel_mode = T.kernel_mode;
+    P->n_items = (int64_t)W.items.size();
+    if (P->n_items >= (1ll << 31)) return fail(BSIG_ERR_ARG, "too many tiles for one launch");
+    return BSIG_OK;
+}
+// stage 4: the tiles and the packed class's filter table for these parameters (kernels.hip: k_make_ptab) on the device
+static int upload_tiles(PlanWork &W)
+{
+    bsig_plan *P = W.plan.get();
+    hipStream_t st = W.ctx->stream;
+    PLAN_TRY(hipSetDevice(W.ctx->device));
+    PLAN_TRY(P->pool.alloc(&P->items, std::max<size_t>(W.items.size(), 1)));
+    PLAN_TRY(P->pool.alloc(&P->ptab, (size_t)BSIG_PACK_CODES));
+    PLAN_TRY(bsig::launch_make_ptab(W.reads->dev, P->kp, P->ptab, st));
+    P->kp.ptab = P->ptab;
+    if (!W.items.empty()) PLAN_TRY(hipMemcpyAsync(P->items, W.items.data(), W.items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, st));
+    PLAN_TRY(hipStreamSynchronize(st));
+    return BSIG_OK;
+}
+// stage 5: One wave streams a tile's reads; a tile on a read hotspot (chrM, rDNA, an amplicon) can hold millions and would
+// keep the whole launch waiting.  The window sizes are probed once per plan; the windows themselves are only fetched when
+// there is something to slice (a frag plan cuts its runs by them, the kinds that walk their tiles whole prove their sums
+// by them).
+static int probe_windows(PlanWork &W)
+{
+    bsig_plan *P = W.plan.get();
+    hipStream_t st = W.ctx->stream;
+    W.heavy_reads = 32768; W.slice_reads = 8192;
+    // (k_profile's 16-bit tile image relies on the 32,768 ceiling: the environment may only lower it)
+    if (const char *v = getenv("BAMSIGNALS_HEAVY_READS")) {
+        W.heavy_reads = std::min<long long>(32768, std::max<long long>(4, atoll(v)));
+        W.slice_reads = std::max<int64_t>(4, W.heavy_reads / 4);
+    }
+    // (k_coverage's cells are SIGNED 16-bit: +32,768 starts on one cell would not fit; k_coverage_bins' int32 cells
+    // need the same ceiling: 32,767 reads adding at most 65,536 each stay below 2^31)
+    if (P->kernel_mode == BSIG_MODE_COVERAGE) W.heavy_reads = std::min<int64_t>(W.heavy_reads, 32767);
+    if (W.items.empty()) return BSIG_OK;
+    unsigned long long *d_heavy = nullptr, n_heavy_dev = 0;
+    PLAN_TRY(W.tmp.alloc(&W.d_win, W.items.size() * BSIG_MAX_CLASSES));
+    PLAN_TRY(W.tmp.alloc(&d_heavy, 1));
+    PLAN_TRY(hipMemsetAsync(d_heavy, 0, sizeof(unsigned long long), st));
+    PLAN_TRY(bsig::launch_resolve(W.reads->dev, P->kp, P->kernel_mode, P->items, P->n_items, W.d_win, st));
+    PLAN_TRY(bsig::launch_count_heavy(W.d_win, P->n_items, W.heavy_reads, d_heavy, st));
+    PLAN_TRY(hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, st));
+    PLAN_TRY(hipStreamSynchronize(st));
+    // a tile of a fragment-length histogram has no image that its reads could overflow: none is heavy, none is sliced
+    W.any_heavy = n_heavy_dev != 0 && W.rq.kind != kFrag;
+    if (!n_heavy_dev && W.rq.kind != kFrag && !W.whole_tiles()) return BSIG_OK;
+    W.win.resize(W.items.size() * BSIG_MAX_CLASSES);
+    PLAN_TRY(hipMemcpyAsync(W.win.data(), W.d_win, W.win.size() * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    PLAN_TRY(hipStreamSynchronize(st));
+    W.reads_of_tile = bsig::reads_of_tiles(W.win);
+    return BSIG_OK;
+}
+// stage 6: the proofs that no 64-bit sum of a plan whose tiles are walked whole wraps (planmath.h: depth_bound) -- the depth
+// histogram's over all tiles, the summaries' range by range (a range's tiles are consecutive, and out_off is its row)
+static int check_depth_bounds(const PlanWork &W)
+{
+    if (W.reads_of_tile.empty() || !W.whole_tiles()) return BSIG_OK;
+    const std::vector<BsigWorkItem> &items = W.items;
+    const bool coverage = W.r.mode == BSIG_MODE_COVERAGE;
+    if (!W.kf.row_tiles) {
+        const long double bound = bsig::depth_bound(items, W.reads_of_tile, 0, items.size(), coverage);
+        if (bound >= bsig::kTwo63)
+            return fail(BSIG_ERR_ARG, "the summed depth of these ranges could exceed 2^63 - 1 (the reads of their tiles add up "
+                                      "to %.3Lg): take fewer ranges per call", bound);
+        return BSIG_OK;
+    }
+    for (size_t t = 0, u = 0; t < items.size(); t = u) {
+        while (u < items.size() && items[u].out_off == items[t].out_off) ++u;
+        const long double bound = bsig::depth_bound(items, W.reads_of_tile, t, u, coverage);
+        if (bound >= bsig::kTwo63)
+            return fail(BSIG_ERR_ARG, "the summed depth of range %lld could exceed 2^63 - 1 (the reads of its tiles add up "
+                                      "to %.3Lg): cut the range", (long long)(items[t].out_off / (W.r.ss ? 2 : 1)), bound);
+    }
+    return BSIG_OK;
+}
+// stage 7: the heavy tiles cut into slices or marked to be walked whole (planmath.h: split_heavy), their items and windows
+// uploaded, the main items once more with their heavy flags
+static int upload_heavy(PlanWork &W)
+{
+    bsig_plan *P = W.plan.get();
+    if (!W.any_heavy) return BSIG_OK;
+    const bsig::HeavyPolicy policy = W.whole_tiles() || W.rq.kind == kXcorr ? bsig::kWalkWhole : bsig::kSlice;
+    W.heavy = bsig::split_heavy(W.items, W.win, W.reads_of_tile, W.heavy_reads, W.slice_reads, policy, P->kernel_mode == BSIG_MODE_COUNT);
+    const std::vector<BsigWorkItem> &hitems = W.heavy.hitems;
+    const std::vector<bsig::Pair32> &hwin = W.heavy.hwin;
+    P->n_heavy_tiles = W.heavy.n_heavy_tiles;
+    if (hitems.empty()) return BSIG_OK;
+    hipStream_t st = W.ctx->stream;
+    P->n_heavy_slices = (int64_t)hitems.size();
+    uint2 *hw = nullptr;
+    PLAN_TRY(P->pool.alloc(&P->heavy_items, hitems.size()));
+    if (!hwin.empty()) PLAN_TRY(P->pool.alloc(&hw, hwin.size()));
+    P->heavy_windows = hw;
+    PLAN_TRY(hipMemcpyAsync(P->heavy_items, hitems.data(), hitems.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, st));
+    if (hw) PLAN_TRY(hipMemcpyAsync(hw, hwin.data(), hwin.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+    // the heavy flags of the main items
+    PLAN_TRY(hipMemcpyAsync(P->items, W.items.data(), W.items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, st));
+    // binned coverage: the slices' atomic adds are the only ones that can take a bin past INT32_MAX
+    if (W.r.cov_ex) {
+        PLAN_TRY(P->pool.alloc(&P->overflow, 1));
+        PLAN_TRY(hipMemsetAsync(P->overflow, 0, sizeof(int32_t), st));
+    }
+    P->kp.overflow = P->overflow;
+    PLAN_TRY(hipStreamSynchronize(st));
+    return BSIG_OK;
+}
+// ... and the cross-correlation's proof that no 64-bit sum wraps (planmath.h: xcorr_bound), which counts the heavy tiles
+static int check_xcorr_bound(const PlanWork &W)
+{
+    if (W.rq.kind != kXcorr || W.items.empty()) return BSIG_OK;
+    const long double bound = bsig::xcorr_bound(W.plan->n_items, W.plan->n_heavy_tiles, W.heavy.heavy_sq);
+    if (bound >= bsig::kTwo63)
+        return fail(BSIG_ERR_ARG, "the cross-correlation of these ranges could exceed 2^63 - 1 (the squared read counts "
+                                  "of their tiles add up to %.3Lg): correlate fewer ranges per call", bound);
+    return BSIG_OK;
+}
+// stage 8: what the plan's kind keeps beside its tiles
+static int setup_kind(PlanWork &W)
+{
+    bsig_plan *P = W.plan.get();
+    const PlanRequest &rq = W.rq;
+    P->kind = rq.kind;
+    if (rq.kind != kPlain) P->red.reset(new Reduced);
+    int64_t widths = 0;             // (moments[0] of an xcorr plan; with strands twice that many cells for a hist plan's)
+    for (int64_t i = 0; i < W.n; ++i) widths += W.len[i];
+    const int64_t n_wide = (int64_t)W.heavy.hitems.size();
+    switch (rq.kind) {
+    case kPlain: break;
+    case kSum: return sum_setup(P, *rq.sum, W.items, W.heavy.hitems);
+    case kXcorr: return xcorr_setup(P, *rq.xcorr, W.ts.xbody, n_wide, widths);
+    case kFrag: return frag_setup(P, *rq.frag, W.reads_of_tile);
+    case kHist: return hist_setup(P, *rq.hist, W.items, n_wide, widths * (W.r.ss ? 2 : 1));
+    case kSummary: return summary_setup(P, *rq.summary, W.items, n_wide);
+    case kScaled: return scaled_setup(P, *rq.scaled, W.items, n_wide);
+    }
+    return BSIG_OK;
+}
+// Every plan is made here, in these stages; their order is the order in which refusals win.
 static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
                             const int32_t *loc, const int32_t *len, const int32_t *strand,
                             const bsig_params *prm, const PlanRequest &rq, bsig_plan **out)
 {
-    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create");
-    *out = nullptr;
-    if (n < 0 || (n > 0 && (!rid || !loc || !len || !strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
-    bsig::PlanRule r;
-    if (const int rc = bsig::check_params(*prm, n, len, &r, rq.frag_len)) return rc;
-    for (int64_t i = 0; i < n; ++i)
-        if (rid[i] < 0 || rid[i] >= reads->n_ref) return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", rid[i]);
-    const int mode = r.mode;
-
-    std::unique_ptr<bsig_plan> owner(new bsig_plan);
-    bsig_plan *P = owner.get();
-    P->ctx = ctx; P->reads = reads; P->mode = mode; P->n_ranges = n;
-    P->made_for_gen = reads->layout_gen;
-    // default tile: the widest range if it fits 2048 cells (less LDS per workgroup = more
-    // workgroups per CU), else 2048-cell tiles
-    int64_t widest = 64;
-    // (binned profiles and binned / strand-split coverage size their tiles by one rule)
-    const bool binned = mode == BSIG_MODE_PROFILE || r.cov_ex;
-    const bool split_ss = binned && r.ss;
-    for (int64_t i = 0; i < n && mode != BSIG_MODE_COUNT; ++i)
-        widest = std::max<int64_t>(widest, ((int64_t)len[i] + r.binsize - 1) / r.binsize);
-    // (strand-split images hold two values per cell: keep the image at 8 KiB there too, otherwise
-    // only 10 workgroups fit a CU and the launch is occupancy-bound: 0.62 -> 0.55 ms on config 4)
-    const int64_t cap_cells = split_ss ? 1024 : 2048;
-    P->tile_cells = prm->tile_cells > 0 ? prm->tile_cells : (int)std::min<int64_t>(widest, cap_cells);
-    int min_cells = 64;
-    if (binned && r.binsize > 1 && prm->tile_cells <= 0) {
-        // wide bins: a tile of 2048 cells would span megabases and one wave would stream all of
-        // its reads; keep a tile to about 16 kbp so that genome-wide binning still fills the chip
-        const int64_t by_span = std::max<int64_t>(4, (16384 + r.binsize - 1) / r.binsize);
-        P->tile_cells = (int)std::min<int64_t>(P->tile_cells, by_span);
-        min_cells = 4;
-    }
-    // a tile image is at most 32 KiB of LDS
-    P->tile_cells = std::min(std::max(P->tile_cells, min_cells), split_ss ? 4096 : 8192);
-    P->tile_cells = (P->tile_cells + 3) & ~3;
-    // cross-correlation: a body no wider than the widest range, and an image of the body and a halo of max_lag cells
-    const int xbody = rq.kind == kXcorr ? (int)std::min<int64_t>(rq.xcorr->body, widest) : 0;
-    if (rq.kind == kXcorr) P->tile_cells = (xbody + rq.xcorr->max_lag + 3) & ~3;
-    // depth histogram: the caller's tile (16 .. 2,048 cells, checked by hist_shape), whatever the widest range
-    if (rq.kind == kHist) P->tile_cells = (rq.hist->tiles.tile_cells + 3) & ~3;
-    if (rq.kind == kSummary) P->tile_cells = (rq.summary->tiles.tile_cells + 3) & ~3;
-    if (rq.kind == kScaled) P->tile_cells = (rq.scaled->tiles.tile_cells + 3) & ~3;
-    // a summary or scaled tile writes no cell: it carries its range's first result row
-    const bool row_tiles = rq.kind == kSummary || rq.kind == kScaled;
-    // a tile of these kinds is walked whole: a cell's value must be complete before it is counted or compared
-    const bool whole_tiles = rq.kind == kHist || row_tiles;
-    P->threads = r.threads;
-    BsigKParams &K = P->kp;
-    K.mapqual = prm->mapqual;
-    K.requiredF = (uint32_t)prm->requiredF;
-    K.filteredF = (uint32_t)prm->filteredF;
-    K.has_tlen_filter = prm->n_tlen_filter == 2;
-    K.tf0 = prm->tlen_filter[0]; K.tf1 = prm->tlen_filter[1];
-    K.shift = mode == BSIG_MODE_COVERAGE ? 0 : prm->shift;
-    K.midpoint = r.mid; K.tspan = r.tspan;
-    K.frag_len = r.frag_len;        // (no tlen column for it: use_tlen below stays the filter's)
-    K.minoverlap = r.minoverlap; K.within = r.overlap == 2;
-    if (const char *v = getenv("BAMSIGNALS_OVERLAP_QUAD")) K.overlap_wide = r.overlap && !strcmp(v, "0");
-    K.use_tlen = K.has_tlen_filter || r.mid || r.tspan;
-    K.ss = r.ss;
-    K.binsize = r.binsize;
-    K.ext = (int32_t)r.ext;
-    K.tile_cells = P->tile_cells;
-    // The packed class's read bodies (SmallOne::four, CountOne::quad) take a read's offset from its chunk in signed
-    // 24-bit multiplies (v_mad_i32_i24: the low 24 bits of each operand, sign-extended), exact for operands in
-    // [-2^23, 2^23).  The operand is at most d + span - 1 + 2 |shift| + h in magnitude: d < 2^15 the position in the
-    // chunk, span - 1 < 256, h = |tlen| >> 1 <= tlen_filter[1] / 2 under the midpoint rule (a read outside the filter is
-    // forced out of every tile whatever its offset).  Wider shifts or template lengths take the full-width body.
-    {
-        const int64_t h_max = r.mid ? std::max<int64_t>(0, prm->tlen_filter[1]) / 2 : 0;
-        K.rel24 = 2 * std::llabs((long long)K.shift) + h_max + (1 << BSIG_PACK_POS_BITS) + 256 < (1ll << 23);
-    }
-    // The packed class's 16-bit 5'-end column (kernels.hip: ProfileOne::oct) serves a plan that reads nothing else of
-    // a packed read: bins of one base, no template-length rule, and a flag/mapq filter that rejects none of the file's
-    // codes (fm_rejected, evaluated here on the pair table).  The half-word keeps 15 bits of the 5' end, so every
-    // tile's packed window must also lie in one chunk with room for a reverse read's span behind it: tile bases +
-    // 2 ext + maxspan + two buckets of rounding <= 2^15 - 256.  Then base + ((h - base) & 0x7FFF) is the 5' end, and
-    // no window has a second chunk (packed_later_chunks).  Anything else reads the 4-byte words.
-    {
-        const BsigClassCols &C = reads->dev.cls[BSIG_CLASS_PACKED];
-        bool half = mode == BSIG_MODE_PROFILE && K.binsize == 1 && !K.use_tlen && C.p5h != nullptr;
-        for (int c = 0; half && c < reads->dev.n_codes; ++c) {
-            const uint32_t fm = reads->fmtab[(size_t)c];
-            const uint32_t nf = ~(fm & 0xFFFFu);
-            const bool rej = (int)((fm >> 16) & 0xFFu) < K.mapqual || (K.requiredF & nf) != 0u || (K.filteredF & nf) == 0u;
-            half = !rej;
-        }
-        half = half && (int64_t)K.tile_cells + 2 * r.ext + C.maxspan + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
-        K.packed_half = half ? 1 : 0;
-    }
-    // Span classes 0 and 1 from their own 16-bit columns (kernels.hip: for_each_read under P.short_half).  Their reads'
-    // (flag, mapq) pairs are not the pair table's, so the filter must be one that rejects no read by its parameters
-    // alone: no mapq bound, no required flag, and a filtered-flag bit above the 16 a flag has (then filteredF & ~flag is
-    // never 0).  The window of class c for a tile holds pos in [wlo, whi) rounded outwards to buckets, wlo = tile start
-    // - ext - (maxspan - 1), whi = tile end + ext: at most tile bases + 2 ext + (maxspan - 1) + two buckets wide from its
-    // base, the rounded wlo (ProfileOne::short_base).  A reverse read's 5' end lies up to maxspan - 1 behind its pos -- or
-    // 255 behind it where class 0's 8-bit span field holds a span below 1, which the 256 spare bases cover.  So with
-    // tile bases + 2 ext + 2 (maxspan - 1) + two buckets <= 2^15 - 256 every 5' end is less than 2^15 from the base
-    // and base + ((h - base) & 0x7FFF) is the 5' end.  Anything else reads pos and fm as before.
-    {
-        bool sh = K.packed_half && K.mapqual <= 0 && K.requiredF == 0u && (K.filteredF >> 16) != 0u;
-        for (int c = 0; sh && c < 2; ++c) {
-            const BsigClassCols &C = reads->dev.cls[c];
-            if (C.n == 0) continue;
-            sh = C.p5h != nullptr &&
-                 (int64_t)K.tile_cells + 2 * r.ext + 2 * ((int64_t)C.maxspan - 1) + 2 * ((int64_t)1 << C.kshift) <= (1 << BSIG_PACK_POS_BITS) - 256;
-        }
-        K.short_half = sh ? 1 : 0;
-        // what the kernels read: where a class's column begins behind the packed class's, and ext + maxspan - 1 with
-        // the bucket's log2 (never 0: short_win[1] != 0 is the kernels' form of short_half)
-        for (int c = 0; c < 2; ++c) {
-            const BsigClassCols &C = reads->dev.cls[c];
-            K.short_off[c] = sh && C.p5h ? (uint32_t)(C.p5h - reads->dev.cls[BSIG_CLASS_PACKED].p5h) : 0u;
-            K.short_win[c] = sh ? (int32_t)((uint32_t)(r.ext + (C.n ? C.maxspan - 1 : 0)) << 5 | (uint32_t)(C.n ? C.kshift : 4)) : 0;
-        }
-    }
-    // (a frag plan's tiles are count tiles, which divide by no binsize: the multiplier is its row width's)
-    bsig::magic_u31(rq.kind == kFrag ? rq.frag->len_bin : K.binsize, &K.div_magic, &K.div_shift);
-    K.div_m15 = 0; K.div_s15 = 0;
-    if (K.binsize >= 2 && K.binsize <= 8192) {
-        // s = 15 + ceil(log2 b), m = ceil(2^s / b): n * m / 2^s = n / b + n * e / (b * 2^s) with e < b, and the second
-        // term stays below 2^-ceil(log2 b) <= 1 / b for n < 2^15, so the floor is exact; n * m < 2^32, m < 2^17
-        int L = 0;
-        while ((1 << L) < K.binsize) ++L;
-        K.div_s15 = 15 + L;
-        K.div_m15 = (uint32_t)((((uint64_t)1 << K.div_s15) + (uint64_t)K.binsize - 1) / (uint64_t)K.binsize);
-    }
-
-    P->off.resize(n + 1);
-    bsig_layout(n, len, r.lay_binsize, K.ss, P->off.data());
-
-    // tiles in genomic order (ref: std::sort by (rid, loc), src/bamsignals.cpp:222-226,246):
-    // neighbouring workgroups then stream neighbouring reads
-    std::vector<int64_t> order;
-    bsig::sort_ranges(n, rid, loc, order);
-    std::vector<BsigWorkItem> items;
-    items.reserve(n);
-    const int64_t mult = K.ss ? 2 : 1;
-    // count mode: bases per workgroup (with the window's reach on both sides still one chunk of the packed
-    // class's position bits: one index lookup per tile)
-    // (a frag plan's and an overlap plan's tile_cells: bases per tile, for tests of the tiles' seams)
-    const int count_split = (rq.kind == kFrag || r.overlap) && prm->tile_cells > 0 ? std::min(std::max(prm->tile_cells, 16), 1 << (BSIG_PACK_POS_BITS - 1))
-                                                      : 1 << (BSIG_PACK_POS_BITS - 1);
-    // bins wider than a workgroup should stream on its own: every bin becomes bamCount-style
-    // sub-intervals that add into the (zeroed) result with integer atomics
-    const bool wide_bins = mode == BSIG_MODE_PROFILE && prm->tile_cells <= 0 && K.binsize > count_split / 2;
-    P->kernel_mode = wide_bins ? BSIG_MODE_COUNT : mode;
-    for (int64_t k = 0; k < n; ++k) {
-        const int64_t i = order[k];
-        if (len[i] <= 0) {
-            if (P->off[i + 1] > P->off[i]) P->needs_zero = true;      // bamCount of a zero-width range: 0
-            continue;
-        }
-        BsigWorkItem w{};
-        w.loc = loc[i]; w.len = len[i];
-        w.ref_unit0 = reads->ref_unit0[rid[i]];
-        w.units_strand = reads->ref_units[rid[i]] | (strand[i] < 0 ? BSIG_ITEM_NEG : 0u);
-        if (wide_bins) {
-            const int64_t cells = (P->off[i + 1] - P->off[i]) / mult;
-            for (int64_t c = 0; c < cells; ++c) {
-                // cell c covers [c*bs, (c+1)*bs) in range orientation (ref: src/bamsignals.cpp:356-362)
-                const int64_t ra = c * (int64_t)K.binsize, rb = std::min<int64_t>(len[i], ra + K.binsize);
-                const int64_t g0 = strand[i] < 0 ? len[i] - rb : ra, g1 = strand[i] < 0 ? len[i] - ra : rb;
-                for (int64_t a = g0; a < g1; a += count_split) {
-                    w.c0 = (int32_t)a;
-                    w.nc = (int32_t)std::min<int64_t>(count_split, g1 - a);
-                    w.out_off = P->off[i] + c * mult;
-                    w.units_strand |= BSIG_ITEM_ATOMIC;
-                    P->needs_zero = true;
-                    items.push_back(w);
-                }
-            }
-        } else if (mode == BSIG_MODE_COUNT) {
-            const bool split = len[i] > count_split;
-            for (int64_t a = 0; a < len[i]; a += count_split) {
-                w.c0 = (int32_t)a;
-                w.nc = (int32_t)std::min<int64_t>(count_split, len[i] - a);
-                w.out_off = P->off[i];
-                if (split) { w.units_strand |= BSIG_ITEM_ATOMIC; P->needs_zero = true; }
-                items.push_back(w);
-            }
-        } else if (rq.kind == kXcorr) {
-            // a body of the range's cells and, behind it, as much of max_lag cells as the range still has: the tile is
-            // piled up over body + halo (nc) and correlated over the body, whose length rides in out_off
-            for (int64_t c0 = 0; c0 < len[i]; c0 += xbody) {
-                const int64_t nb = std::min<int64_t>(xbody, len[i] - c0);
-                w.c0 = (int32_t)c0;
-                w.nc = (int32_t)(nb + std::min<int64_t>(rq.xcorr->max_lag, len[i] - c0 - nb));
-                w.out_off = nb;
-                items.push_back(w);
-            }
-        } else {
-            const int64_t cells = (P->off[i + 1] - P->off[i]) / mult;
-            for (int64_t c0 = 0; c0 < cells; c0 += P->tile_cells) {
-                w.c0 = (int32_t)c0;
-                w.nc = (int32_t)std::min<int64_t>(P->tile_cells, cells - c0);
-                w.out_off = row_tiles ? i * mult : P->off[i] + c0 * mult;
-                items.push_back(w);
-            }
-        }
-    }
-    // a sum plan adds up all tiles of one c0 (every range has the same width, so also the same nc): consecutive
-    if (rq.kind == kSum) std::stable_sort(items.begin(), items.end(), [](const BsigWorkItem &a, const BsigWorkItem &b) { return a.c0 < b.c0; });
-    P->n_items = (int64_t)items.size();
-    if (P->n_items >= (1ll << 31)) return fail(BSIG_ERR_ARG, "too many tiles for one launch");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = P->pool.alloc(&P->items, std::max<size_t>(items.size(), 1));
-    // the packed class's filter table for these parameters (kernels.hip: k_make_ptab)
-    if (e == hipSuccess) e = P->pool.alloc(&P->ptab, (size_t)BSIG_PACK_CODES);
-    if (e == hipSuccess) e = bsig::launch_make_ptab(reads->dev, K, P->ptab, ctx->stream);
-    K.ptab = P->ptab;
-    if (e == hipSuccess && !items.empty())
-        e = hipMemcpyAsync(P->items, items.data(), items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-
-    // ---- heavy tiles --------------------------------------------------------------------------
-    // One wave streams a tile's reads; a tile on a read hotspot (chrM, rDNA, an amplicon) can hold
-    // millions and would keep the whole launch waiting.  Probe the window sizes once per plan and
-    // cut the windows of heavy tiles into slices that separate workgroups add up with atomics.
-    int64_t heavy_reads = 32768, slice_reads = 8192;
-    // (k_profile's 16-bit tile image relies on the 32,768 ceiling: the environment may only lower it)
-    if (const char *v = getenv("BAMSIGNALS_HEAVY_READS")) { heavy_reads = std::min<long long>(32768, std::max<long long>(4, atoll(v))); slice_reads = std::max<int64_t>(4, heavy_reads / 4); }
-    // (k_coverage's cells are SIGNED 16-bit: +32,768 starts on one cell would not fit; k_coverage_bins' int32 cells
-    // need the same ceiling: 32,767 reads adding at most 65,536 each stay below 2^31)
-    if (P->kernel_mode == BSIG_MODE_COVERAGE) heavy_reads = std::min<int64_t>(heavy_reads, 32767);
-    std::vector<BsigWorkItem> hitems;
-    std::vector<int64_t> frag_reads;        // a frag plan: the reads in every tile's windows
-    if (e == hipSuccess && !items.empty()) {
-        DevPool tmp;
-        uint2 *d_win = nullptr;
-        e = tmp.alloc(&d_win, items.size() * BSIG_MAX_CLASSES);
-        std::vector<uint2> win;
-        unsigned long long *d_heavy = nullptr, n_heavy_dev = 0;
-        if (e == hipSuccess) e = tmp.alloc(&d_heavy, 1);
-        if (e == hipSuccess) e = hipMemsetAsync(d_heavy, 0, sizeof(unsigned long long), ctx->stream);
-        if (e == hipSuccess) e = bsig::launch_resolve(reads->dev, K, P->kernel_mode, P->items, P->n_items, d_win, ctx->stream);
-        if (e == hipSuccess) e = bsig::launch_count_heavy(d_win, P->n_items, heavy_reads, d_heavy, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        // the windows themselves are only fetched when there is something to slice (a frag plan cuts its runs by them)
-        if (e == hipSuccess && (n_heavy_dev || rq.kind == kFrag || whole_tiles)) {
-            win.resize(items.size() * BSIG_MAX_CLASSES);
-            e = hipMemcpyAsync(win.data(), d_win, win.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        }
-        std::vector<uint2> hwin;
-        long double xc_heavy_sq = 0;
-        if (e == hipSuccess && rq.kind == kFrag) {
-            // a tile of a histogram has no image that its reads could overflow: none is heavy, none is sliced
-            frag_reads.resize(items.size());
-            for (size_t t = 0; t < items.size(); ++t) frag_reads[t] = tile_reads(win, t);
-        }
-        if (e == hipSuccess && rq.kind == kHist) {
-            // The depth histogram's proof that its sum moment stays below 2^63: a read in a tile's windows adds at most 1 to
-            // one cell of the tile (5' ends) or to each of its cells (coverage)
-            long double bound = 0;
-            for (size_t t = 0; t < items.size(); ++t) {
-                const int64_t total = tile_reads(win, t);
-                bound += mode == BSIG_MODE_COVERAGE ? (long double)total * (long double)items[t].nc : (long double)total;
-            }
-            if (bound >= 9223372036854775808.0L) {
-                return fail(BSIG_ERR_ARG, "the summed depth of these ranges could exceed 2^63 - 1 (the reads of their tiles add up "
-                                          "to %.3Lg): take fewer ranges per call", bound);
-            }
-        }
-        if (e == hipSuccess && row_tiles) {
-            // The summaries' proof, range by range, that a sum stays below 2^63: the depth histogram's bound over the
-            // range's own tiles (they are consecutive, and out_off is the range's row)
-            for (size_t t = 0; t < items.size();) {
-                long double bound = 0;
-                size_t u = t;
-                for (; u < items.size() && items[u].out_off == items[t].out_off; ++u) {
-                    const int64_t total = tile_reads(win, u);
-                    bound += mode == BSIG_MODE_COVERAGE ? (long double)total * (long double)items[u].nc : (long double)total;
-                }
-                if (bound >= 9223372036854775808.0L) {
-                    return fail(BSIG_ERR_ARG, "the summed depth of range %lld could exceed 2^63 - 1 (the reads of its tiles add up "
-                                              "to %.3Lg): cut the range", (long long)(items[t].out_off / mult), bound);
-                }
-                t = u;
-            }
-        }
-        if (e == hipSuccess && n_heavy_dev && rq.kind != kFrag) {
-            for (size_t t = 0; t < items.size(); ++t) {
-                const int64_t total = tile_reads(win, t);
-                if (total <= heavy_reads) continue;
-                ++P->n_heavy_tiles;
-                if (whole_tiles) {
-                    // a cell's value must be complete before it is counted (and a max is not linear in slices of the
-                    // reads): such a tile is walked whole, by one workgroup of the second launch, into an image of 32-bit cells
-                    hitems.push_back(items[t]);
-                    items[t].units_strand |= BSIG_ITEM_HEAVY;
-                    continue;
-                }
-                if (rq.kind == kXcorr) {
-                    // a product of two counts is not linear in slices of the reads: such a tile is walked whole, by one
-                    // workgroup of the second launch, into an image of 32-bit cells
-                    hitems.push_back(items[t]);
-                    xc_heavy_sq += (long double)total * (long double)total;
-                    items[t].units_strand |= BSIG_ITEM_HEAVY;
-                    continue;
-                }
-                BsigWorkItem sl = items[t];
-                if (P->kernel_mode == BSIG_MODE_COUNT) sl.units_strand |= BSIG_ITEM_ATOMIC;
-                for (int c = 0; c < BSIG_MAX_CLASSES; ++c) {
-                    const uint2 wc = win[t * BSIG_MAX_CLASSES + c];
-                    for (int64_t j0 = wc.x; j0 < (int64_t)wc.y; j0 += slice_reads) {
-                        hitems.push_back(sl);
-                        for (int k = 0; k < BSIG_MAX_CLASSES; ++k)
-                            hwin.push_back(k == c ? make_uint2((uint32_t)j0, (uint32_t)std::min<int64_t>(j0 + slice_reads, wc.y)) : make_uint2(0u, 0u));
-                    }
-                }
-                items[t].units_strand |= BSIG_ITEM_HEAVY;
-            }
-        }
-        if (e == hipSuccess && !hitems.empty()) {
-            P->n_heavy_slices = (int64_t)hitems.size();
-            uint2 *hw = nullptr;
-            e = P->pool.alloc(&P->heavy_items, hitems.size());
-            if (e == hipSuccess && !hwin.empty()) e = P->pool.alloc(&hw, hwin.size());
-            P->heavy_windows = hw;
-            if (e == hipSuccess) e = hipMemcpyAsync(P->heavy_items, hitems.data(), hitems.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess && hw) e = hipMemcpyAsync(hw, hwin.data(), hwin.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
-            // the heavy flags of the main items
-            if (e == hipSuccess) e = hipMemcpyAsync(P->items, items.data(), items.size() * sizeof(BsigWorkItem), hipMemcpyHostToDevice, ctx->stream);
-            // binned coverage: the slices' atomic adds are the only ones that can take a bin past INT32_MAX
-            if (e == hipSuccess && r.cov_ex) e = P->pool.alloc(&P->overflow, 1);
-            if (e == hipSuccess && P->overflow) e = hipMemsetAsync(P->overflow, 0, sizeof(int32_t), ctx->stream);
-            K.overflow = P->overflow;
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        }
-        // The cross-correlation's proof that no 64-bit sum wraps.  A tile with n reads in its windows counts each of
-        // them in at most one cell, so sum(S) + sum(A) <= n and every sum the tile adds to -- a lag's S[x] A[x + d], a
-        // strand's squares -- is at most n^2.  The tiles that are not heavy have n <= 2^15; the heavy ones' n is known.
-        if (e == hipSuccess && rq.kind == kXcorr) {
-            const long double bound = (long double)(P->n_items - P->n_heavy_tiles) * 1073741824.0L + xc_heavy_sq;
-            if (bound >= 9223372036854775808.0L) {
-                return fail(BSIG_ERR_ARG, "the cross-correlation of these ranges could exceed 2^63 - 1 (the squared read counts "
-                                          "of their tiles add up to %.3Lg): correlate fewer ranges per call", bound);
-            }
-        }
-    }
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "plan upload failed: %s", hipGetErrorString(e));
-    P->kind = rq.kind;
-    if (rq.kind != kPlain) P->red.reset(new Reduced);
-    int64_t widths = 0;             // (moments[0] of an xcorr plan; with strands twice that many cells for a hist plan's)
-    for (int64_t i = 0; i < n; ++i) widths += len[i];
-    int rc = BSIG_OK;
-    switch (rq.kind) {
-    case kPlain: break;
-    case kSum: rc = sum_setup(P, *rq.sum, items, hitems); break;
-    case kXcorr: rc = xcorr_setup(P, *rq.xcorr, xbody, (int64_t)hitems.size(), widths); break;
-    case kFrag: rc = frag_setup(P, *rq.frag, frag_reads); break;
-    case kHist: rc = hist_setup(P, *rq.hist, items, (int64_t)hitems.size(), widths * mult); break;
-    case kSummary: rc = summary_setup(P, *rq.summary, items, (int64_t)hitems.size()); break;
-    case kScaled: rc = scaled_setup(P, *rq.scaled, items, (int64_t)hitems.size()); break;
-    }
-    if (rc != BSIG_OK) return rc;
-    *out = owner.release();
+    PlanWork W(ctx, reads, n, rid, loc, len, strand, prm, rq);
+    if (const int rc = check_request(W, out)) return rc;
+    shape_plan(W);
+    if (const int rc = cut_plan(W)) return rc;
+    if (const int rc = upload_tiles(W)) return rc;
+    if (const int rc = probe_windows(W)) return rc;
+    if (const int rc = check_depth_bounds(W)) return rc;
+    if (const int rc = upload_heavy(W)) return rc;
+    if (const int rc = check_xcorr_bound(W)) return rc;
+    W.tmp.release();                // (the probe's windows: not held while the kind allocates its own)
+    if (const int rc = setup_kind(W)) return rc;
+    *out = W.plan.release();
     return BSIG_OK;
 }
 // ---- what the six *_setup functions share ------------------------------------------------------------------------
@@ -2078,28 +1967,8 @@ static int64_t tiles_per_run(const bsig_plan *P, int n_cu, int per_cu, int64_t l
     const int64_t resident = (int64_t)std::max(n_cu, 1) * per_cu;
     return std::max<int64_t>(least, (P->n_items + resident - 1) / resident);
 }
-// The plan's tiles, in their order, cut into runs of at most `per` tiles whose weights add up to `ceiling` at most (a tile
-// heavier than the ceiling makes a run of its own)
-template <typename Weight>
-static void cut_runs(int64_t n_items, int64_t per, int64_t ceiling, Weight &&weight, std::vector<uint2> &runs)
-{
-    int64_t a = 0, in_run = 0;
-    for (int64_t t = 0; t < n_items; ++t) {
-        const int64_t w = weight(t);
-        if (t > a && (t - a >= per || in_run + w > ceiling)) {
-            runs.push_back(make_uint2((uint32_t)a, (uint32_t)t));
-            a = t; in_run = 0;
-        }
-        in_run += w;
-    }
-    if (a < n_items) runs.push_back(make_uint2((uint32_t)a, (uint32_t)n_items));
-}
-// the wide tiles (32-bit image) follow the main runs as runs of one tile each: they are few and long
-static void append_wide_runs(int64_t n_wide, std::vector<uint2> &runs)
-{
-    for (int64_t k = 0; k < n_wide; ++k) runs.push_back(make_uint2((uint32_t)k, (uint32_t)k + 1u));
-}
-static int upload_runs(bsig_plan *P, const std::vector<uint2> &runs)
+// (the cutters themselves -- cut_runs, append_wide_runs, cut_sum_runs -- are planmath.h's)
+static int upload_runs(bsig_plan *P, const std::vector<bsig::Pair32> &runs)
 {
     if (runs.empty()) return BSIG_OK;
     hipStream_t st = P->ctx->stream;
@@ -2127,10 +1996,10 @@ static int setup_runs(bsig_plan *P, size_t lds, Refuse &&refuse, const bsig::Til
     if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
     if (lds > (size_t)lds_max) return refuse(lds_max);
     const int64_t per = tiles_per_run(P, n_cu, bsig::tile_blocks_per_cu(form), 1, run_tiles);
-    std::vector<uint2> runs;
-    cut_runs(P->n_items, per, ceiling, weight, runs);
+    std::vector<bsig::Pair32> runs;
+    bsig::cut_runs(P->n_items, per, ceiling, weight, runs);
     P->red->n_runs_main = (int64_t)runs.size();
-    append_wide_runs(n_wide, runs);
+    bsig::append_wide_runs(n_wide, runs);
     P->red->n_runs_extra = n_wide;
     return upload_runs(P, runs);
 }
@@ -2141,7 +2010,7 @@ static int setup_runs(bsig_plan *P, size_t lds, Refuse &&refuse, const bsig::Til
 // every slab exact in 32 bits (k_sum_tiles).
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems)
 {
-    constexpr int64_t kSumChunkSlots = 32, kMaxRunTiles = 65536;
+    constexpr int64_t kMaxRunTiles = 65536;
     Reduced &R = *P->red;
     auto &Q = R.sum;
     R.cells = shape.cells;
@@ -2162,29 +2031,11 @@ static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vecto
         return fail(BSIG_ERR_ARG, "tile_cells %d needs %zu bytes of LDS per workgroup, the device has %d", P->tile_cells, form().lds, lds_max);
     // (BAMSIGNALS_SUM_RUN_TILES: shorter or longer runs, never past the cap that keeps a slab exact)
     const int64_t per = std::min<int64_t>(kMaxRunTiles, tiles_per_run(P, n_cu, bsig::tile_blocks_per_cu(form()), nw, "BAMSIGNALS_SUM_RUN_TILES"));
-    std::vector<uint2> runs;
+    std::vector<bsig::Pair32> runs;
     std::vector<BsigSumChunk> chunks;
-    auto cut = [&](const std::vector<BsigWorkItem> &it) {
-        int64_t chunk_c0 = -1;
-        for (size_t a = 0; a < it.size();) {
-            size_t b = a;
-            while (b < it.size() && it[b].c0 == it[a].c0) ++b;             // the tiles of one c0: [a, b)
-            for (size_t r = a; r < b; r += (size_t)per) {
-                const uint32_t slot = (uint32_t)runs.size();
-                runs.push_back(make_uint2((uint32_t)r, (uint32_t)std::min<size_t>(b, r + (size_t)per)));
-                if (chunk_c0 != it[a].c0 || chunks.back().slot_hi - chunks.back().slot_lo >= kSumChunkSlots) {
-                    chunks.push_back(BsigSumChunk{slot, slot, it[a].c0 * Q.S, it[a].nc * Q.S});
-                    chunk_c0 = it[a].c0;
-                }
-                chunks.back().slot_hi = slot + 1;
-                Q.max_nvals = std::max(Q.max_nvals, it[a].nc * Q.S);
-            }
-            a = b;
-        }
-    };
-    cut(items);
+    Q.max_nvals = std::max(Q.max_nvals, bsig::cut_sum_runs(items, per, Q.S, runs, chunks));
     R.n_runs_main = (int64_t)runs.size();
-    cut(hitems);
+    Q.max_nvals = std::max(Q.max_nvals, bsig::cut_sum_runs(hitems, per, Q.S, runs, chunks));
     R.n_runs_extra = (int64_t)runs.size() - R.n_runs_main;
     Q.n_chunks = (int64_t)chunks.size();
     hipStream_t st = P->ctx->stream;
@@ -2213,7 +2064,7 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
         return fail(BSIG_ERR_ARG, "a tile of %d + %d cells needs %zu bytes of LDS per workgroup, the device has %d", body,
                     shape.max_lag, lds, lds_max);
     };
-    // (no counter of a run can wrap: plan_create_impl's proof)
+    // (no counter of a run can wrap: check_xcorr_bound's proof)
     return setup_runs(P, lds, refuse, form(false), "BAMSIGNALS_XCORR_RUN_TILES", 0, [](int64_t) { return (int64_t)0; }, n_wide);
 }
 

@@ -14,6 +14,7 @@
 #include "../../include/bamsignals_abi.h"
 #include "bsig_types.h"
 #include "host_util.h"
+#include "planmath.h"
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -239,21 +240,7 @@ int plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async = false, doub
 // ... and a reduction plan's (sum, xcorr, frag, hist, summary, scaled): its kind's device run call into the plan's own int64 buffer (made
 // at the first call), then the download; timed as above.  A sum plan without cells has nothing to run
 int plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
-// bsig_params as every entry point reads them (runtime.hip: check_params)
-struct PlanRule {
-    int mode;               // the kernel family: BSIG_MODE_COVERAGE_EX is BSIG_MODE_COVERAGE with bins and / or strands
-    bool cov_ex;            // ... that coverage (binned tiles; heavy slices watch its bins for overflow)
-    int32_t binsize;        // the result's bins: profile's and coverage_ex's; 1 for coverage and count
-    bool ss;                // strand-split result (profile, count, coverage_ex)
-    bool mid, tspan;        // paired-end midpoint (profile, count) / extend (coverage, overlap)
-    int32_t frag_len;       // a resized plan (coverage): bases every read covers from its 5' end; 0: off
-    int64_t ext;            // how far beyond a range a read can count: |shift| + midpoint's tlen_filter[1], or extend's; a
-                            // resized plan's frag_len - 1
-    int32_t lay_binsize;    // bsig_layout's binsize (-1: count)
-    int overlap;            // bamOverlaps (mode is then the count family's): 0 no, 1 type "any", 2 type "within"
-    int32_t minoverlap;     // ... bases a read must share with its range (the caller's binsize field); 0 otherwise
-    int threads;            // per workgroup
-};
+// (PlanRule, bsig_params as every entry point reads them: planmath.h)
 // frag_len: what a resized plan's creator was given (resized_rule has judged it), 0 for every other plan
 int check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out, int32_t frag_len = 0);
 // what only a resized plan asks, ahead of check_params (runtime.hip: resized_rule): a coverage mode, no paired-end
