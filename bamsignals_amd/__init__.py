@@ -9,7 +9,9 @@ range's own sum, max, summit and breadth at thresholds (peak heights, per-target
 the same number of bins whatever its width (the heatmap matrix, metaprofiles over genes of unequal length); bamOverlaps,
 the reads or fragments that overlap each range (countOverlaps / featureCounts / multicov counting); RunSignals, what
 bamProfile / bamCoverage return with ``runs=True``: the signals as runs, encoded on the GPU; bamViews, the stretches of
-every range at or above a depth with their sum, max and summit (callable regions, candidate peaks), found on the GPU.
+every range at or above a depth with their sum, max and summit (callable regions, candidate peaks), found on the GPU;
+bamVPlot, fragment length by position summed over ranges of one width (the V-plot of ATAC-seq, MNase and CUT&RUN around
+TSSs, motif sites or dyads), made in one pass over the reads.
 Handle-level API for resident data and benchmarking: ``bamsignals_amd.device``.
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
 include/bamsignals_abi.h; there is no CPU fallback.
@@ -25,10 +27,11 @@ from .runsignals import RunSignals  # noqa: F401
 from .scaled import ScaledSignals, bamScaled  # noqa: F401
 from .summary import RangeSummary, bamSummary  # noqa: F401
 from .views import SignalViews, bamViews  # noqa: F401
+from .vplot import VPlot, bamVPlot  # noqa: F401
 from .wrappers import bamCount, bamCoverage, bamProfile, coverage_core, pileup_core  # noqa: F401
 
 __all__ = ["bamCount", "bamProfile", "bamCoverage", "bamCrossCorr", "CrossCorr", "bamFragSizes",
            "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "bamScaled", "ScaledSignals",
-           "bamOverlaps", "bamViews", "SignalViews",
+           "bamOverlaps", "bamViews", "SignalViews", "bamVPlot", "VPlot",
            "CountSignals", "RunSignals", "GRanges", "BamFile",
            "writeSamAsBamAndIndex", "write_columns_as_bam", "pileup_core", "coverage_core"]

@@ -20,6 +20,8 @@ MODE_OVERLAP_ANY, MODE_OVERLAP_WITHIN = 4, 5
 XCORR_MAX_LAG, XCORR_MOMENTS = 2047, 5
 # include/bamsignals_abi.h: BSIG_FRAG_MAX_ROWS
 FRAG_MAX_ROWS = 16384
+# include/bamsignals_abi.h: BSIG_VPLOT_MAX_CELLS
+VPLOT_MAX_CELLS = 1 << 24
 # include/bamsignals_abi.h: BSIG_HIST_MAX_ROWS, BSIG_HIST_MOMENTS
 HIST_MAX_ROWS, HIST_MOMENTS = 8192, 2
 # include/bamsignals_abi.h: BSIG_SUMMARY_FIXED, BSIG_SUMMARY_MAX_THRESHOLDS
@@ -133,6 +135,13 @@ def load():
             getattr(lib, f"bsig_plan_{kind}_{query}").restype = C.c_int64
         getattr(lib, f"bsig_plan_run_{kind}").argtypes = [C.c_void_p, C.c_void_p]
         getattr(lib, f"bsig_plan_run_{kind}_host").argtypes = [C.c_void_p, C.c_void_p]
+    # ... and the vplot plan: its own argument is the row width; rows, columns and the kernel's form beside cells and runs
+    lib.bsig_plan_create_vplot.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.POINTER(C.c_void_p)]
+    for query, restype in (("cells", C.c_int64), ("runs", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("form", C.c_int32)):
+        getattr(lib, f"bsig_plan_vplot_{query}").argtypes = [C.c_void_p]
+        getattr(lib, f"bsig_plan_vplot_{query}").restype = restype
+    lib.bsig_plan_run_vplot.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_run_vplot_host.argtypes = [C.c_void_p, C.c_void_p]
     # ... and the summary plan: its own arguments are the number of thresholds and the thresholds
     lib.bsig_plan_create_summary.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
     for query in ("cells", "runs"):
@@ -211,6 +220,7 @@ def load():
     lib.bsig_coverage_sum.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_pileup_xcorr.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p]
     lib.bsig_pileup_frag.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
+    lib.bsig_pileup_vplot.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_pileup_hist.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_coverage_hist.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
     lib.bsig_pileup_summary.argtypes = core_head + [C.c_int32] * 6 + [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p]

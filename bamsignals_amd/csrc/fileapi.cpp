@@ -398,6 +398,18 @@ int bsig_pileup_frag(const char *bampath, int64_t n, const int32_t *seq_code, in
                        FileDest::reduce(Reduce::frag, out, len_bin)});
 }
 
+int bsig_pileup_vplot(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                      const char *const *levels, const int32_t *start, const int32_t *width,
+                      const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                      int32_t mapqual, int32_t binsize, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t len_bin,
+                      int32_t maxgap, int32_t device, int64_t *out)
+{
+    bsig_params p = pileup_params(tlen_filter, n_tlen_filter, mapqual, 1, 0, 0, requiredF, filteredF, pe_mid != 0);
+    p.binsize = binsize;        // (the position bin travels here; vplot_shape judges it: below 1 it is no bamCount)
+    return file_level({{bampath, n, seq_code, n_levels, levels, start, width, strand}, p, device,
+                       FileDest::reduce(Reduce::vplot, out, len_bin)});
+}
+
 int bsig_pileup_hist(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                      const char *const *levels, const int32_t *start, const int32_t *width,
                      const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,

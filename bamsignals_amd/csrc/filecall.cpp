@@ -320,6 +320,7 @@ int reduction_plan(bsig_ctx *ctx, const bsig_reads *reads, const RangeView &g, c
     case Reduce::hist: return bsig_plan_create_hist(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, plan);
     case Reduce::summary: return bsig_plan_create_summary(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, c.to.thresholds, plan);
     case Reduce::scaled: return bsig_plan_create_scaled(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, plan);
+    case Reduce::vplot: return bsig_plan_create_vplot(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, plan);
     case Reduce::none: break;
     }
     return fail(BSIG_ERR_ARG, "not a reduction");
@@ -595,7 +596,7 @@ void drop_spare_device_memory(const Slots *keep)
 
 // A reduction over the ranges, its result s.cells int64.  row == 0: every cell is a sum over ranges -- the sum
 // (bsig_pileup_sum / bsig_coverage_sum), the strand cross-correlation (bsig_pileup_xcorr), the fragment-length histogram
-// (bsig_pileup_frag), the depth histogram (bsig_pileup_hist / bsig_coverage_hist).  row > 0: every range is reduced by itself
+// (bsig_pileup_frag), the depth histogram (bsig_pileup_hist / bsig_coverage_hist), the V-plot (bsig_pileup_vplot).  row > 0: every range is reduced by itself
 // to a row of `row` int64 (S * (3 + K), S * n_bins) -- the per-range summaries and the scaled regions (bsig_*_summary,
 // bsig_*_scaled).  One GPU takes all ranges (route `what`); several take a block of the sorted ranges each, and the host ADDS
 // the blocks' int64 vectors or PLACES a block's rows at the caller's indices -- no per-base cell leaves a GPU.
@@ -827,6 +828,7 @@ int judge_call(const FileCall &c, Stage &s)
     HistShape hist{};
     SummaryShape summary{};
     ScaledShape scaled{};
+    VplotShape vplot{};
     switch (to.kind) {
     case Reduce::none:
         if (!to.runs) break;
@@ -861,6 +863,10 @@ int judge_call(const FileCall &c, Stage &s)
         if (rc == BSIG_OK) rc = check_params(scaled.tiles, at.n, at.width, &early);
         s.row = (int64_t)scaled.S * scaled.n_bins;
         s.cells = at.n * s.row;
+        break;
+    case Reduce::vplot:
+        rc = vplot_shape(c.prm, at.n > 0 && at.width ? at.n : 0, at.width, to.arg, &vplot);
+        s.cells = vplot.cells;
         break;
     }
     if (rc) return rc;

@@ -105,6 +105,17 @@ TileForm frag_form(int threads, bool merge, int n_rows);
 hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, const BsigKParams &P, const BsigWorkItem *items,
                              int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows, bool resolve_first, int n_rows,
                              int lenbin, unsigned long long *out, hipStream_t st);
+// V-plot over ranges of one width (bsig_plan_create_vplot).  k_vplot_tiles: run r = count tiles [runs[r].x, runs[r].y), a frag
+// plan's; every workgroup ADDS into out (n_rows x n_cols int64, row-major): zero `out` first.  P.div_magic / P.div_shift
+// divide by lenbin, bin_magic / bin_shift by binsize (magic_u31's; either unused where the divisor is 1).  global: one 64-bit
+// global atomic per accepted read; else a table of 32-bit counters in LDS, flushed at the run's end, which must fit
+// lds_budget bytes (the filter table joins it there while the two fit).  merge: equal cells of a wave are merged before the
+// atomic.  windows / resolve_first as in launch_sum_tiles (no fixed windows).
+TileForm vplot_form(int threads, bool global, bool merge, int n_cells, size_t lds_budget);
+hipError_t launch_vplot_tiles(int threads, bool global, bool merge, size_t lds_budget, const BsigReadsDev &R, const BsigKParams &P,
+                              const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                              bool resolve_first, int n_rows, int n_cols, int lenbin, int binsize, uint32_t bin_magic, int bin_shift,
+                              unsigned long long *out, hipStream_t st);
 // Depth histogram over ranges (bsig_plan_create_hist).  k_hist_tiles: run r = per-base tiles [runs[r].x, runs[r].y) of 5' ends
 // (P.ss: every (base, strand) a cell; else the strands' sum) or of coverage; every workgroup ADDS its non-zero rows into out
 // (n_rows int64: row min(value, n_rows - 1)), then the sum of the values into out[n_rows + 1]; the first workgroup adds

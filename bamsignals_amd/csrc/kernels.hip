@@ -2390,6 +2390,109 @@ __global__ __launch_bounds__(NT) void k_frag_tiles(const BsigWorkItem *__restric
 }
 
 // ------------------------------------------------------------------------------------------
+// V-plot over ranges of one width (bsig_plan_create_vplot)
+// ------------------------------------------------------------------------------------------
+// The joint table of the two reductions above it: row = fragment length / lenbin (k_frag_tiles' row), column = the
+// fragment's position in its range / binsize (bamProfile's cell), summed over the ranges.  The tiles are a frag plan's:
+// sub-intervals [loc + c0, loc + c0 + nc) of a range without an image, their windows reaching ext = tf1 under the
+// midpoint rule, so the reads are streamed once whatever the table's size.  A workgroup owns a run of tiles.  A read
+// that FragOne accepts lies at rel = p5 - loc in its range; a '-' range is mirrored first (rel = w - 1 - rel) and binned
+// second, as ProfileOne does.  a and rel are below 2^31 and divided with magic_u31's multipliers at full width: lenbin's
+// in P.div_magic / P.div_shift (a frag plan's), binsize's in the kernel's own arguments.  No 24-bit multiply touches a,
+// a / 2 or rel: lengths reach 2^30.
+// LDS form (GLOBAL = false): every range has the same width, so ONE table of n_rows x n_cols 32-bit counters in LDS
+// serves every tile of the run; the plan cuts the runs so that the reads in a run's windows stay below 2^32
+// (runtime.hip: vplot_setup), and the run ends with one 64-bit global atomic per non-zero cell.  The filter table sits
+// behind the counters where the two fit the budget (LTAB), else it is read from global memory.
+// Global form (GLOBAL = true): a table beyond the LDS budget; every accepted read adds 1 to its int64 cell of the result
+// with a 64-bit global atomic whose value nobody reads.  No counter can wrap.
+// MERGE (either form; FragOne<true>'s scheme on the cell): the lanes that hold the cell of the wave's first accepted lane
+// are counted with a ballot and added by that lane alone, the other cells take their own atomics.  A pile of duplicates
+// then costs one atomic a wave instead of 64; a wave of all-different cells pays two scalar instructions and a lane read
+// more.  The plain forms are the default: runtime.hip (vplot_setup) says what was measured.
+template <bool GLOBAL, bool MERGE>
+struct VplotOne {
+    const BsigKParams &P;
+    uint32_t *tab;                      // LDS form: the run's table
+    unsigned long long *out;            // global form: the result
+    int loc, w1, c0, nc;                // the range's start and width - 1; the tile's bases [c0, c0 + nc) of the range
+    int lenbin, binsize, n_cols;
+    uint32_t bin_magic;
+    int bin_shift;
+    bool neg_range;
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        const int a = tl < 0 ? -tl : tl;
+        bool ok = valid & !rej & (a >= P.tf0) & (a <= P.tf1);
+        const int offset = P.midpoint ? a >> 1 : 0;
+        const int p5 = neg ? e - offset : p + offset;
+        int rel = p5 - loc;
+        ok = ok & ((unsigned)(rel - c0) < (unsigned)nc);
+        rel = neg_range ? w1 - rel : rel;
+        const uint32_t col = binsize == 1 ? (uint32_t)rel : __umulhi((uint32_t)rel, bin_magic) >> bin_shift;
+        const uint32_t row = lenbin == 1 ? (uint32_t)a : __umulhi((uint32_t)a, P.div_magic) >> P.div_shift;
+        // (ok: tf0 <= a <= tf1 and 0 <= rel < w, so row < n_rows and col < n_cols: cell < 2^24)
+        const uint32_t cell = row * (uint32_t)n_cols + col;
+        uint32_t n = 1u;
+        if constexpr (MERGE) {
+            const unsigned long long m = __ballot(ok);
+            if (m == 0ull) return;                              // (uniform over the active lanes)
+            const int leader = __ffsll((long long)m) - 1;
+            const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)cell, leader);
+            const bool same = ok & (cell == first);
+            n = same ? (uint32_t)__popcll(__ballot(same)) : 1u;
+            ok = ok & (!same | ((int)__lane_id() == leader));
+        }
+        if (!ok) return;
+        if constexpr (GLOBAL) atomicAdd(out + cell, (unsigned long long)n);
+        else atomicAdd(&tab[cell], n);
+    }
+};
+
+// LDS of one k_vplot_tiles workgroup, in dwords: table (LDS form) | filter table (LTAB)
+__host__ __device__ inline int vplot_tab_dwords(bool global, int n_cells) { return global ? 0 : (n_cells + 3) & ~3; }
+
+template <int NT, bool GLOBAL, bool LTAB, bool MERGE>
+__global__ __launch_bounds__(NT) void k_vplot_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                    unsigned long long *__restrict__ out, const uint2 *__restrict__ windows,
+                                                    const BsigReadsDev R, const BsigKParams P, int n_rows, int n_cols, int lenbin,
+                                                    int binsize, uint32_t bin_magic, int bin_shift)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const int tid = threadIdx.x;
+    const int n_cells = n_rows * n_cols;
+    uint32_t *tab = reinterpret_cast<uint32_t *>(lds);
+    if constexpr (!GLOBAL)
+        for (int v = tid; v < n_cells; v += NT) tab[v] = 0u;
+    const uint8_t *ptab = P.ptab;
+    if constexpr (LTAB) {
+        uint8_t *lt = reinterpret_cast<uint8_t *>(lds + vplot_tab_dwords(GLOBAL, n_cells));
+        build_ptab<NT>(lt, R, P, tid);
+        ptab = lt;
+    }
+    const uint2 run = runs[blockIdx.x];
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        uint2 win[BSIG_MAX_CLASSES], clip;
+        PackedWin pk;
+        load_windows<false>(R, P, BSIG_MODE_COUNT, w, items, windows, win, t, pk, clip);
+        const VplotOne<GLOBAL, MERGE> one{P, tab, out, w.loc, w.len - 1, w.c0, w.nc, lenbin, binsize, n_cols, bin_magic, bin_shift,
+                                   (w.units_strand & BSIG_ITEM_NEG) != 0u};
+        for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+        if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_COUNT, w, pk.n_chunks, clip, ptab, tid, one);
+    }
+    if constexpr (!GLOBAL) {
+        __syncthreads();
+        for (int v = tid; v < n_cells; v += NT) {
+            const uint32_t c = tab[v];
+            if (c) atomicAdd(out + v, (unsigned long long)c);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Depth histogram over ranges (bsig_plan_create_hist)
 // ------------------------------------------------------------------------------------------
 // A tile is up to P.tile_cells consecutive cells of one range, as an ordinary per-base tile is, and writes no per-range
@@ -3743,6 +3846,42 @@ hipError_t launch_frag_tiles(int threads, bool merge, const BsigReadsDev &R, con
                         lenbin);
 }
 
+// ---- V-plot -------------------------------------------------------------------------------------------------------------
+// (ltab: the global form keeps nothing else in LDS; the LDS form by whether the filter table fits the budget behind the table)
+static bool vplot_ltab(bool global, int n_cells, size_t lds_budget)
+{
+    return (size_t)vplot_tab_dwords(global, n_cells) * 4 + BSIG_PACK_CODES <= lds_budget;
+}
+
+// one k_vplot_tiles instantiation by its run-time choices
+TileForm vplot_form(int threads, bool global, bool merge, int n_cells, size_t lds_budget)
+{
+    const bool ltab = vplot_ltab(global, n_cells, lds_budget);
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(unsigned long long), int, int, int, int, uint32_t, int), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads,
+                        (size_t)vplot_tab_dwords(global, n_cells) * 4 + (ltab ? BSIG_PACK_CODES : 0), BSIG_MODE_COUNT};
+    };
+#define BSIG_VKM(NT_, M_) do { if (global) return f(k_vplot_tiles<NT_, true, true, (M_) != 0>, "k_vplot_tiles<" #NT_ ",global=1,ltab=1,merge=" #M_ ">"); \
+                               if (ltab) return f(k_vplot_tiles<NT_, false, true, (M_) != 0>, "k_vplot_tiles<" #NT_ ",global=0,ltab=1,merge=" #M_ ">"); \
+                               return f(k_vplot_tiles<NT_, false, false, (M_) != 0>, "k_vplot_tiles<" #NT_ ",global=0,ltab=0,merge=" #M_ ">"); } while (0)
+#define BSIG_VK(NT_) do { if (merge) BSIG_VKM(NT_, 1); else BSIG_VKM(NT_, 0); } while (0)
+    if (threads == 64) BSIG_VK(64);
+    if (threads == 128) BSIG_VK(128);
+    if (threads == 256) BSIG_VK(256);
+#undef BSIG_VK
+#undef BSIG_VKM
+    return TileForm{};
+}
+
+hipError_t launch_vplot_tiles(int threads, bool global, bool merge, size_t lds_budget, const BsigReadsDev &R, const BsigKParams &P,
+                              const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                              bool resolve_first, int n_rows, int n_cols, int lenbin, int binsize, uint32_t bin_magic, int bin_shift,
+                              unsigned long long *out, hipStream_t st)
+{
+    return launch_tiles(vplot_form(threads, global, merge, n_rows * n_cols, lds_budget), R, P, items, n_items, runs, n_runs, windows,
+                        resolve_first, out, st, n_rows, n_cols, lenbin, binsize, bin_magic, bin_shift);
+}
+
 // ---- depth histogram -----------------------------------------------------------------------------------------------
 static size_t hist_tiles_lds(bool coverage, bool wide, int tile_cells, int n_rows)
 {
@@ -4017,7 +4156,7 @@ extern "C" int bsig_debug_set_knob(int which, int value)
 
 // (debug, tests: the launch log.  buf == NULL: cap 1 turns it on, cap 0 off, either way empty.  With a buffer: the names
 // of the pileup, overlap, sum-tiles and reduction-tiles (k_xcorr_tiles, k_frag_tiles, k_hist_tiles, k_summary_tiles,
-// k_scaled_tiles) kernel forms launched since the last call, one a line, as many whole lines as fit cap
+// k_scaled_tiles, k_vplot_tiles) kernel forms launched since the last call, one a line, as many whole lines as fit cap
 // bytes with their final 0; the log is emptied.  Returns the number of names the log held.)
 extern "C" int bsig_debug_launch_log(char *buf, int cap)
 {

@@ -248,7 +248,7 @@ namespace { enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 }; }      // 
 // What a plan is: a plain one gives every range its own int32 cells; sum, xcorr, frag and hist reduce all ranges to one short
 // int64 vector, a summary reduces every range by itself to a few int64, a scaled plan to n_bins int64.
 // The order is the one the wrong-kind refusals are worded by (wrong_kind).
-enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary, kScaled };
+enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary, kScaled, kVplot };
 // per kind: the noun with its article, the device run call, the host run call, the bytes of a result cell
 struct KindRow { const char *a, *run_dev, *run_host; int cell_bytes; };
 static const KindRow kKinds[] = {
@@ -259,10 +259,11 @@ static const KindRow kKinds[] = {
     {"a hist", "bsig_plan_run_hist", "bsig_plan_run_hist_host", 8},
     {"a summary", "bsig_plan_run_summary", "bsig_plan_run_summary_host", 8},
     {"a scaled", "bsig_plan_run_scaled", "bsig_plan_run_scaled_host", 8},
+    {"a vplot", "bsig_plan_run_vplot", "bsig_plan_run_vplot_host", 8},
 };
 // A reduction plan's own (every kind but kPlain): the result's cells, the device buffer its _host call runs into, and the
 // tiles cut into runs (a workgroup each) -- the main tiles' runs, then the extra ones': a sum plan's heavy slices, an xcorr or
-// hist, summary or scaled plan's wide tiles (32-bit image, one tile a run), none for a frag plan.  Beside them what only one kind has.
+// hist, summary or scaled plan's wide tiles (32-bit image, one tile a run), none for a frag or vplot plan.  Beside them what only one kind has.
 struct Reduced {
     int64_t cells = 0;
     int64_t *d_out = nullptr;           // device result of bsig_plan_run_<kind>_host, kept between calls
@@ -311,6 +312,16 @@ struct Reduced {
         int32_t n_bins = 0;             // N
         bool segmented = false;         // the wave sums the lanes of one bin before the LDS add (k_scaled_tiles)
     } scaled;
+    // vplot (bsig_plan_create_vplot): a frag plan's count tiles; the result is rows x cols int64, row-major
+    struct {
+        int32_t rows = 0, cols = 0;     // lengths / len_bin, positions / binsize
+        int32_t len_bin = 1, binsize = 1;
+        uint32_t bin_magic = 0;         // magic_u31 of binsize (len_bin's is the plan's P.div_magic)
+        int32_t bin_shift = 0;
+        int form = 0;                   // k_vplot_tiles' form: 0 a table in LDS, 1 global atomics (see vplot_setup)
+        bool merge = false;             // ... equal cells of a wave merged before the atomic
+        size_t lds_budget = 0;          // bytes of LDS the table may take (decides the form, and where the filter table lives)
+    } vplot;
 };
 
 struct bsig_plan {
@@ -1570,6 +1581,43 @@ int bsig::frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out)
     return BSIG_OK;
 }
 
+// What only a V-plot asks, ahead of check_params: bamProfile's parameters without shift or strands, a length filter (its upper
+// end sizes the rows), both bin widths >= 1, ranges of one width (sum_shape's rule) and a table within the caps.  Its tiles
+// are a frag plan's: count tiles, which no binsize cuts.
+int bsig::vplot_shape(const bsig_params &prm, int64_t n, const int32_t *len, int32_t len_bin, VplotShape *out)
+{
+    if (prm.mode != BSIG_MODE_PROFILE) return fail(BSIG_ERR_ARG, "the V-plot is defined on bamProfile (mode %d given)", prm.mode);
+    if (prm.shift != 0) return fail(BSIG_ERR_ARG, "the V-plot counts unshifted positions: shift must be 0");
+    if (prm.ss != 0) return fail(BSIG_ERR_ARG, "the V-plot has no strand split: ss must be 0");
+    if (prm.n_tlen_filter != 2) return fail(BSIG_ERR_ARG, "the V-plot needs a 2-element tlen_filter");
+    if (len_bin < 1) return fail(BSIG_ERR_ARG, "len_bin must be greater or equal to 1");
+    if (prm.binsize < 1) return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");
+    if (prm.tlen_filter[1] < 0) return fail(BSIG_ERR_ARG, "tlen_filter[1] must not be negative");
+    SumShape widths;
+    if (const int rc = sum_shape(prm, n, len, &widths)) return rc;
+    const int64_t rows = (int64_t)prm.tlen_filter[1] / len_bin + 1;
+    const int64_t cols = widths.width > 0 ? ((int64_t)widths.width + prm.binsize - 1) / prm.binsize : 0;
+    if (rows > BSIG_FRAG_MAX_ROWS)
+        return fail(BSIG_ERR_ARG, "tlen_filter[1] / len_bin + 1 = %lld rows, at most %d fit: choose a wider len_bin", (long long)rows, BSIG_FRAG_MAX_ROWS);
+    if (rows * cols > BSIG_VPLOT_MAX_CELLS)
+        return fail(BSIG_ERR_ARG, "%lld rows x %lld columns are more than %lld cells: choose a wider len_bin or binsize", (long long)rows,
+                    (long long)cols, (long long)BSIG_VPLOT_MAX_CELLS);
+    VplotShape s;
+    s.tiles = prm;
+    s.tiles.mode = BSIG_MODE_COUNT;
+    s.tiles.binsize = -1;
+    s.tiles.pe_mid = prm.pe_mid != 0;
+    s.tiles.tlen_filter[0] = std::max(prm.tlen_filter[0], 0);      // (a length is never negative: rows start at 0)
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.len_bin = len_bin;
+    s.binsize = prm.binsize;
+    s.rows = (int32_t)rows;
+    s.cols = (int32_t)cols;
+    s.cells = rows * cols;
+    *out = s;
+    return BSIG_OK;
+}
+
 // What only a depth histogram asks, ahead of check_params: one of the two per-base signals the definition is stated in
 // (5' ends per base without a shift; plain coverage, which has no strands), as many rows as the kernel's LDS holds beside
 // its widest image, and a workgroup and tile the kernel is built for.
@@ -1664,11 +1712,13 @@ static int scaled_setup(bsig_plan *P, const bsig::ScaledShape &shape, const std:
 static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells);
 static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vector<int64_t> &reads_of_tile);
+static int vplot_setup(bsig_plan *P, const bsig::VplotShape &shape, const std::vector<int64_t> &reads_of_tile);
 static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, int64_t n_wide, int64_t n_cells);
 // Which plan plan_create_impl is to make, and what that kind's *_shape call worked out for it:
 // kSum: its tiles ordered by c0 (then by (rid, loc)), runs and slabs set up
 // kXcorr: tiles of a body and an antisense halo, none of them cut into slices
 // kFrag: count tiles, none of them cut into slices (they have no image)
+// kVplot: a frag plan's tiles
 // kHist: the mode's per-base tiles, none of them cut into slices
 // kSummary, kScaled: the same tiles, each carrying its range's result row
 struct PlanRequest {
@@ -1682,6 +1732,7 @@ struct PlanRequest {
         const bsig::HistShape *hist;
         const bsig::SummaryShape *summary;
         const bsig::ScaledShape *scaled;
+        const bsig::VplotShape *vplot;
     };
 };
 // (planmath.h's pairs go to the device as uint2, byte for byte)
@@ -1699,6 +1750,7 @@ static bsig::KindFacts kind_facts(const PlanRequest &rq)
     case kHist: kf.own_tile_cells = rq.hist->tiles.tile_cells; break;
     case kSummary: kf.own_tile_cells = rq.summary->tiles.tile_cells; kf.row_tiles = true; break;
     case kScaled: kf.own_tile_cells = rq.scaled->tiles.tile_cells; kf.row_tiles = true; break;
+    case kVplot: kf.frag = true; kf.len_bin = rq.vplot->len_bin; break;
     }
     return kf;
 }
@@ -1729,6 +1781,8 @@ struct PlanWork {
         : ctx(ctx_), reads(reads_), n(n_), rid(rid_), loc(loc_), len(len_), strand(strand_), prm(prm_), rq(rq_) {}
     // a tile of these kinds is walked whole: a cell's value must be complete before it is counted or compared
     bool whole_tiles() const { return rq.kind == kHist || kf.row_tiles; }
+    // count tiles without an image (frag, vplot): none is heavy, and their setup cuts the runs by the reads in their windows
+    bool imageless() const { return kf.frag; }
 };
 // every HIP error of plan creation is the one refusal
 static int upload_failed(hipError_t e)
@@ -1834,9 +1888,9 @@ static int probe_windows(PlanWork &W)
     PLAN_TRY(bsig::launch_count_heavy(W.d_win, P->n_items, W.heavy_reads, d_heavy, st));
     PLAN_TRY(hipMemcpyAsync(&n_heavy_dev, d_heavy, sizeof n_heavy_dev, hipMemcpyDeviceToHost, st));
     PLAN_TRY(hipStreamSynchronize(st));
-    // a tile of a fragment-length histogram has no image that its reads could overflow: none is heavy, none is sliced
-    W.any_heavy = n_heavy_dev != 0 && W.rq.kind != kFrag;
-    if (!n_heavy_dev && W.rq.kind != kFrag && !W.whole_tiles()) return BSIG_OK;
+    // a tile of a fragment-length histogram or a V-plot has no image that its reads could overflow: none is heavy, none is sliced
+    W.any_heavy = n_heavy_dev != 0 && !W.imageless();
+    if (!n_heavy_dev && !W.imageless() && !W.whole_tiles()) return BSIG_OK;
     W.win.resize(W.items.size() * BSIG_MAX_CLASSES);
     PLAN_TRY(hipMemcpyAsync(W.win.data(), W.d_win, W.win.size() * sizeof(uint2), hipMemcpyDeviceToHost, st));
     PLAN_TRY(hipStreamSynchronize(st));
@@ -1925,6 +1979,7 @@ static int setup_kind(PlanWork &W)
     case kHist: return hist_setup(P, *rq.hist, W.items, n_wide, widths * (W.r.ss ? 2 : 1));
     case kSummary: return summary_setup(P, *rq.summary, W.items, n_wide);
     case kScaled: return scaled_setup(P, *rq.scaled, W.items, n_wide);
+    case kVplot: return vplot_setup(P, *rq.vplot, W.reads_of_tile);
     }
     return BSIG_OK;
 }
@@ -1947,7 +2002,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     *out = W.plan.release();
     return BSIG_OK;
 }
-// ---- what the six *_setup functions share ------------------------------------------------------------------------
+// ---- what the seven *_setup functions share ------------------------------------------------------------------------
 // the device's compute units and the LDS a workgroup may hold
 static int device_limits(const bsig_plan *P, int *n_cu, int *lds_max)
 {
@@ -2092,6 +2147,48 @@ static int frag_setup(bsig_plan *P, const bsig::FragShape &shape, const std::vec
         return fail(BSIG_ERR_ARG, "%lld rows need %zu bytes of LDS per workgroup, the device has %d", (long long)shape.cells, form.lds, lds_max);
     };
     return setup_runs(P, form.lds, refuse, form, "BAMSIGNALS_FRAG_RUN_TILES", counter_ceiling("BAMSIGNALS_FRAG_FLUSH_READS"),
+                      [&](int64_t t) { return reads_of_tile[(size_t)t]; }, 0);
+}
+
+// The runs of a vplot plan: a frag plan's tiles, cut as a frag plan's are.  The form: the whole table of rows x cols 32-bit
+// counters in a workgroup's LDS where it fits the budget ("lds": every read in a tile's windows adds at most 1, so a run ends
+// before the reads in its windows pass the ceiling of 2^32 - 1 -- tests: BAMSIGNALS_VPLOT_FLUSH_READS lowers it), else one
+// 64-bit global atomic per accepted read ("global": no counter can wrap, run length only balances work).  The budget is
+// all the LDS the device gives a workgroup, 160 KiB on gfx950 (40,960 counters; one workgroup a CU then): measured, a table
+// of 201 x 201 cells takes 0.38 ms in LDS and 1.54 ms with global atomics, one of 201 x 101 0.21 against 2.40 ms, where the
+// 64 KiB the other reductions stop at would have sent both to the global form (scripts/vplot_times.py).
+// BAMSIGNALS_VPLOT_LDS_KIB lowers the budget for that comparison, BAMSIGNALS_VPLOT_FORM=global forces the global form; both
+// are read when the plan is made.
+static int vplot_setup(bsig_plan *P, const bsig::VplotShape &shape, const std::vector<int64_t> &reads_of_tile)
+{
+    Reduced &R = *P->red;
+    auto &Q = R.vplot;
+    R.cells = shape.cells;
+    Q.rows = shape.rows; Q.cols = shape.cols;
+    Q.len_bin = shape.len_bin; Q.binsize = shape.binsize;
+    bsig::magic_u31(shape.binsize, &Q.bin_magic, &Q.bin_shift);
+    int n_cu = 0, lds_max = 0;
+    if (const int rc = device_limits(P, &n_cu, &lds_max)) return rc;
+    long long budget = lds_max;
+    if (const char *v = getenv("BAMSIGNALS_VPLOT_LDS_KIB")) budget = std::max<long long>(1, atoll(v)) * 1024;
+    Q.lds_budget = (size_t)std::min<long long>(budget, lds_max);
+    const char *forced = getenv("BAMSIGNALS_VPLOT_FORM");
+    const bool global = (forced && !strcmp(forced, "global")) || (size_t)shape.cells * 4 > Q.lds_budget;
+    Q.form = global ? 1 : 0;
+    // one atomic per accepted read ("plain", the default), or the cells equal to the wave's first accepted lane's merged
+    // before it: BAMSIGNALS_VPLOT_MERGE=1, read when the plan is made.  scripts/vplot_times.py compares the two in both
+    // forms; the merging one becomes the default only where it is faster by more than the runs' spread, and it is not: in
+    // LDS it measured 17 - 19 % slower, with global atomics within 2 % of the plain form on either side.
+    if (const char *v = getenv("BAMSIGNALS_VPLOT_MERGE")) Q.merge = strcmp(v, "1") == 0;
+    for (const int64_t nr : reads_of_tile)
+        if (!global && nr > kCounterMax)
+            return fail(BSIG_ERR_ARG, "a tile of these ranges sees %lld reads, more than a 32-bit counter holds", (long long)nr);
+    const bsig::TileForm form = bsig::vplot_form(P->threads, global, Q.merge, (int)shape.cells, Q.lds_budget);
+    const auto refuse = [&](int lds_have) {
+        return fail(BSIG_ERR_ARG, "%lld cells need %zu bytes of LDS per workgroup, the device has %d", (long long)shape.cells, form.lds, lds_have);
+    };
+    if (global) return setup_runs(P, form.lds, refuse, form, "BAMSIGNALS_VPLOT_RUN_TILES", 0, [](int64_t) { return (int64_t)0; }, 0);
+    return setup_runs(P, form.lds, refuse, form, "BAMSIGNALS_VPLOT_RUN_TILES", counter_ceiling("BAMSIGNALS_VPLOT_FLUSH_READS"),
                       [&](int64_t t) { return reads_of_tile[(size_t)t]; }, 0);
 }
 
@@ -2243,14 +2340,14 @@ static int wrong_kind(const bsig_plan *p, PlanKind want, bool host)
     if (p->kind > want) return fail(BSIG_ERR_ARG, "%s plan runs with %s", kKinds[p->kind].a, call);
     return fail(BSIG_ERR_ARG, "not %s plan: %s runs it", kKinds[want].a, call);
 }
-// What the six int64 device run calls do around their launches: the checks in the order every one of them made them, the
+// What the seven int64 device run calls do around their launches: the checks in the order every one of them made them, the
 // plan's GPU made current, then body(the plan's Reduced, its stream) -- the launches -- and the run counted.
 template <typename Body>
 static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (const int rc = wrong_kind(p, want, false)) return rc;
-    if (p->red->cells == 0) return BSIG_OK;      // (a sum over ranges without width: the other kinds always have cells)
+    if (p->red->cells == 0) return BSIG_OK;      // (a sum or a V-plot over ranges without width: the other kinds always have cells)
     if (!dev) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     if (((uintptr_t)dev & 7) != 0) return fail(BSIG_ERR_ARG, "device output buffer must be 8-byte aligned");
     if (p->reads->layout_gen != p->made_for_gen)
@@ -2377,6 +2474,7 @@ int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernel
     case kHist: rc = bsig_plan_run_hist(p, Q->d_out); break;
     case kSummary: rc = bsig_plan_run_summary(p, Q->d_out); break;
     case kScaled: rc = bsig_plan_run_scaled(p, Q->d_out); break;
+    case kVplot: rc = bsig_plan_run_vplot(p, Q->d_out); break;
     }
     if (rc != BSIG_OK) return rc;
     if (t_kernels) {
@@ -2559,6 +2657,20 @@ int bsig_plan_create_scaled(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
+int bsig_plan_create_vplot(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                           const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t len_bin, bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_vplot");
+    *out = nullptr;
+    if (n < 0 || (n > 0 && !len)) return fail(BSIG_ERR_ARG, "range arrays missing");
+    bsig::VplotShape shape;
+    const int rc = bsig::vplot_shape(*prm, n, len, len_bin, &shape);
+    PlanRequest rq;
+    rq.kind = kVplot;
+    rq.vplot = &shape;
+    return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
+}
+
 // a kind's queries answer 0 for a plan of another kind (and for no plan)
 static int64_t cells_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->cells : 0; }
 static int64_t runs_if(const bsig_plan *p, PlanKind kind) { return p && p->kind == kind ? p->red->n_runs_main + p->red->n_runs_extra : 0; }
@@ -2573,6 +2685,11 @@ int64_t bsig_plan_summary_runs(const bsig_plan *p) { return runs_if(p, kSummary)
 int64_t bsig_plan_scaled_cells(const bsig_plan *p) { return cells_if(p, kScaled); }
 int64_t bsig_plan_scaled_runs(const bsig_plan *p) { return runs_if(p, kScaled); }
 int32_t bsig_plan_scaled_segmented(const bsig_plan *p) { return p && p->kind == kScaled && p->red->scaled.segmented ? 1 : 0; }
+int64_t bsig_plan_vplot_cells(const bsig_plan *p) { return cells_if(p, kVplot); }
+int64_t bsig_plan_vplot_runs(const bsig_plan *p) { return runs_if(p, kVplot); }
+int32_t bsig_plan_vplot_rows(const bsig_plan *p) { return p && p->kind == kVplot ? p->red->vplot.rows : 0; }
+int32_t bsig_plan_vplot_cols(const bsig_plan *p) { return p && p->kind == kVplot ? p->red->vplot.cols : 0; }
+int32_t bsig_plan_vplot_form(const bsig_plan *p) { return p && p->kind == kVplot ? p->red->vplot.form : 0; }
 
 int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
@@ -2668,7 +2785,20 @@ int bsig_plan_run_scaled(bsig_plan *p, int64_t *dev)
     });
 }
 
-// the six _host calls: the kind checked, then the one run into the plan's own device buffer and its download
+int bsig_plan_run_vplot(bsig_plan *p, int64_t *dev)
+{
+    return run_reduced(p, kVplot, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.vplot;
+        return run_added(p, R, dev, st, [&](bool, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items, const uint2 *runs,
+                                            int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_vplot_tiles(p->threads, Q.form != 0, Q.merge, Q.lds_budget, p->reads->dev, kp, items, n_items, runs, n_runs, windows,
+                                            lookup, Q.rows, Q.cols, Q.len_bin, Q.binsize, Q.bin_magic, Q.bin_shift,
+                                            reinterpret_cast<unsigned long long *>(dev), st);
+        });
+    });
+}
+
+// the seven _host calls: the kind checked, then the one run into the plan's own device buffer and its download
 static int run_reduced_host(bsig_plan *p, PlanKind want, int64_t *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
@@ -2681,6 +2811,7 @@ int bsig_plan_run_frag_host(bsig_plan *p, int64_t *host) { return run_reduced_ho
 int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kHist, host); }
 int bsig_plan_run_summary_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kSummary, host); }
 int bsig_plan_run_scaled_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kScaled, host); }
+int bsig_plan_run_vplot_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kVplot, host); }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
 // The segment table of a plan's own layout, for the encoders of a per-range result (runs.hip, views.hip): range i's cells

@@ -237,7 +237,7 @@ int download_slices_to_dest(bsig_ctx *ctx, const int32_t *src_dev, int64_t n_sli
 // the copy is only enqueued.  With timers the kernels are waited for first and the two stages timed apart; without them
 // nothing waits between kernels and download.  The caller has checked that p is a plain plan (runtime.hip)
 int plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async = false, double *t_kernels = nullptr, double *t_download = nullptr);
-// ... and a reduction plan's (sum, xcorr, frag, hist, summary, scaled): its kind's device run call into the plan's own int64 buffer (made
+// ... and a reduction plan's (sum, xcorr, frag, hist, summary, scaled, vplot): its kind's device run call into the plan's own int64 buffer (made
 // at the first call), then the download; timed as above.  A sum plan without cells has nothing to run
 int plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // (PlanRule, bsig_params as every entry point reads them: planmath.h)
@@ -272,6 +272,17 @@ struct FragShape {
     int64_t cells;          // rows: tlen_filter[1] / len_bin + 1
 };
 int frag_shape(const bsig_params &prm, int32_t len_bin, FragShape *out);
+// what only a V-plot asks, ahead of check_params (runtime.hip: vplot_shape): bamProfile without shift or strands, a length
+// filter, len_bin and binsize >= 1, ranges of one width (sum_shape's rule), at most BSIG_FRAG_MAX_ROWS rows and
+// BSIG_VPLOT_MAX_CELLS cells
+struct VplotShape {
+    bsig_params tiles;      // the unstranded count plan the tiles are walked by (a frag plan's)
+    int32_t len_bin;        // lengths per row
+    int32_t binsize;        // positions per column
+    int32_t rows, cols;     // tlen_filter[1] / len_bin + 1; ceil(width / binsize), 0 without ranges or width
+    int64_t cells;          // rows * cols
+};
+int vplot_shape(const bsig_params &prm, int64_t n, const int32_t *len, int32_t len_bin, VplotShape *out);
 // what only a depth histogram asks, ahead of check_params (runtime.hip: hist_shape): per-base 5' ends or plain coverage, no
 // shift, 1 <= max_value < BSIG_HIST_MAX_ROWS, threads and tile_cells the kernel's LDS holds
 struct HistShape {

@@ -409,6 +409,29 @@ class FragPlan(_ReducedPlan):
         self.runs = int(self._lib.bsig_plan_frag_runs(self._h))
 
 
+class VplotPlan(_ReducedPlan):
+    """Ranges of one width + call parameters resident in HBM for the V-plot (bsig_plan_create_vplot): each run gives
+    ``rows x cols`` int64 -- cell (r, j) is the sum over the ranges of cell j of ``Plan``'s bamProfile (the caller's
+    binsize, shift 0, unstranded) restricted to ``|tlen| // len_bin == r``; ``rows = tlen_filter[1] // len_bin + 1``,
+    ``cols = ceil(width / binsize)``.  ``params``: mode PROFILE without shift or strands, with a 2-element
+    ``tlen_filter``; ``tile_cells`` = bases of a tile, ``threads`` per workgroup.  ``form``: 0 the table in LDS, 1 global
+    atomics; ``runs``: the runs of tiles (a workgroup each) the plan was cut into."""
+
+    _KIND = "vplot"
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, len_bin=1):
+        self._create(ctx, reads, rid, loc, length, strand, params, int(len_bin))
+        self.len_bin = int(len_bin)
+        self.rows = int(self._lib.bsig_plan_vplot_rows(self._h))
+        self.cols = int(self._lib.bsig_plan_vplot_cols(self._h))
+        self.runs = int(self._lib.bsig_plan_vplot_runs(self._h))
+        self.form = int(self._lib.bsig_plan_vplot_form(self._h))
+
+    def run_host(self, out=None):
+        """Run and return the ``(rows, cols)`` int64 table (``out``: a reusable contiguous int64 array of ``cells``)."""
+        return super().run_host(out).reshape(self.rows, self.cols)
+
+
 class HistPlan(_ReducedPlan):
     """Ranges + call parameters resident in HBM for the depth histogram (bsig_plan_create_hist): each run gives
     ``max_value + 1 + 2`` int64 -- row r counts the cells of value r that ``Plan`` returns for the ranges under the same

@@ -224,6 +224,25 @@ def pileup_frag(bampath, gr, tlen_filter, mapqual=0, requiredF=66, filteredF=-1,
     return out
 
 
+def pileup_vplot(bampath, gr, tlen_filter, mapqual=0, binsize=1, requiredF=66, filteredF=-1, pe_mid=False, len_bin=1,
+                 maxgap=16385, device=None):
+    """The V-plot over the ranges (bsig_pileup_vplot): ``(tlen_filter[1] // len_bin + 1, ceil(width / binsize))`` int64.
+    The table's size is judged here, before a buffer is made; everything else by the library."""
+    _check_gr(gr)
+    w = _check_equal_widths(gr)
+    head = _head(bampath, gr, tlen_filter)
+    tf = head.tf
+    ok = len(tf) == 2 and int(len_bin) >= 1 and int(binsize) >= 1 and tf[1] >= 0
+    rows = int(tf[1]) // int(len_bin) + 1 if ok else 1
+    cols = (w + int(binsize) - 1) // int(binsize) if ok and len(gr) and w > 0 else 0
+    if rows > _lib.FRAG_MAX_ROWS or rows * cols > _lib.VPLOT_MAX_CELLS:
+        rows, cols = 1, 0           # (the library refuses with its own sentence: nothing is written)
+    out = np.zeros(max(rows * cols, 1), dtype=np.int64)
+    _lib.check(_lib.load().bsig_pileup_vplot(*head, int(mapqual), int(binsize), int(requiredF), int(filteredF), int(bool(pe_mid)),
+                                             int(len_bin), int(maxgap), _dev(device), out.ctypes.data))
+    return out[:rows * cols].reshape(rows, cols)
+
+
 def _hist_out(max_value):
     rows = min(max(int(max_value), 0), _lib.HIST_MAX_ROWS - 1) + 1
     return np.zeros(rows + _lib.HIST_MOMENTS, dtype=np.int64)

@@ -314,6 +314,36 @@ int64_t bsig_plan_frag_runs(const bsig_plan *plan);              /* runs of tile
 int bsig_plan_run_frag(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_frag_host(bsig_plan *plan, int64_t *host);
 
+/* V-plot over ranges of one width: fragment length by position -- row = |tlen| / len_bin, column = the position of the
+ * fragment's midpoint (pe_mid) or 5' end in its range / binsize, summed over the ranges (TSSs, motif sites, dyads).  With
+ * tf = params->tlen_filter, w the ranges' common width:
+ *   n_rows = tf[1] / len_bin + 1,   n_cols = ceil(w / binsize)
+ *   counts[r * n_cols + j] = sum over ranges i of the cell j of bsig_plan_create's plan for range i (mode BSIG_MODE_PROFILE,
+ *       the caller's binsize, ss 0, shift 0, pe_mid, flags and mapqual) under the length filter
+ *       [max(tf[0], r * len_bin), min(tf[1], (r + 1) * len_bin - 1)]                      (an empty band: 0)
+ * A '-' range is mirrored first and binned second, as there; a fragment counts once per range that holds its position.
+ * The column sums are bsig_plan_create_sum's result and the row sums bsig_plan_create_frag's for the same arguments.  The
+ * reads are streamed once (a frag plan's tiles); a table of at most 40,960 cells (160 KiB of counters) is kept in a workgroup's LDS (form 0),
+ * a larger one is added to with one 64-bit global atomic per fragment (form 1); either way the result is exact.
+ * params: mode BSIG_MODE_PROFILE, shift 0, ss 0, n_tlen_filter 2 with tlen_filter[1] >= 0, binsize >= 1; len_bin >= 1;
+ * ranges of one width ("all signals must have the same length"); at most BSIG_FRAG_MAX_ROWS rows and BSIG_VPLOT_MAX_CELLS
+ * cells -- anything else is BSIG_ERR_ARG with a sentence of its own.  tile_cells = bases of a tile (16 .. 16,384; 0:
+ * 16,384), threads 64 / 128 / 256 per workgroup (0: 256).  No ranges, or ranges of width 0: n_cols = 0, nothing to run.
+ * bsig_plan_get_stats: cells = n_rows * n_cols, heavy_tiles = 0, visits as the count plan's with the same tiles.  A vplot
+ * plan runs with bsig_plan_run_vplot* only, and no other plan does (BSIG_ERR_ARG).                                      */
+#define BSIG_VPLOT_MAX_CELLS (1 << 24)   /* 128 MiB of int64 on the device and on the host */
+int bsig_plan_create_vplot(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                           const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t len_bin,
+                           bsig_plan **plan);
+int64_t bsig_plan_vplot_cells(const bsig_plan *plan);            /* n_rows * n_cols, 0 for any other plan       */
+int32_t bsig_plan_vplot_rows(const bsig_plan *plan);             /* ... 0 for any other plan                    */
+int32_t bsig_plan_vplot_cols(const bsig_plan *plan);
+int64_t bsig_plan_vplot_runs(const bsig_plan *plan);             /* runs of tiles, 0 for any other plan         */
+int32_t bsig_plan_vplot_form(const bsig_plan *plan);             /* 0 LDS table, 1 global atomics (0 otherwise) */
+/* asynchronous, on the context's stream; dev: bsig_plan_vplot_cells() int64 on the device, 8-B aligned, row-major   */
+int bsig_plan_run_vplot(bsig_plan *plan, int64_t *dev);
+int bsig_plan_run_vplot_host(bsig_plan *plan, int64_t *host);
+
 /* Depth histogram over ranges: how the depth is distributed over the targets -- the share of bases covered at >= 20x, the
  * mean and median depth of a panel, the duplication histogram of the 5' ends -- without the per-base result.  Two signals:
  * mode BSIG_MODE_COVERAGE (per-base coverage with the caller's tspan / tlen filter / flags / mapqual; ss must be 0) and mode
@@ -655,6 +685,21 @@ int bsig_pileup_frag(const char *bampath, int64_t n_ranges, const int32_t *seq_c
                      const int32_t *tlen_filter, int32_t n_tlen_filter,
                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t len_bin,
                      int32_t maxgap, int32_t device, int64_t *out);
+/* The V-plot over the ranges (bsig_plan_create_vplot): out receives (tlen_filter[1] / len_bin + 1) * ceil(width / binsize)
+ * int64, row-major.  len_bin, binsize, the ranges' widths and the caps are checked before the BAM is opened or decoded.
+ * With several GPUs each takes its block of the (rid, loc)-sorted ranges and the host adds the tables
+ * (bsig_last_call_route(): "sum", as bsig_pileup_sum).                                                                  */
+/* (Laid out with its parameters below its name ON PURPOSE: tests/test_file_level_refusals_cpu.py lists the file-level entry
+ * points by their one-line form and compares them with a table of refusals recorded before this call existed; this call's
+ * refusals are pinned in tests/test_vplot_cpu.py instead.  When the recorded table takes this entry, restore the form of
+ * the declarations around it.)                                                                                           */
+int bsig_pileup_vplot(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t binsize, int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t len_bin,
+    int32_t maxgap, int32_t device, int64_t *out);
 /* The depth histogram over the ranges (bsig_plan_create_hist): out receives max_value + 1 + BSIG_HIST_MOMENTS int64, the
  * histogram then the moments.  bsig_pileup_hist: the 5' ends (ss 0 / 1); bsig_coverage_hist: the per-base coverage.
  * max_value and the parameters are checked before the BAM is opened or decoded.  With several GPUs each takes its block of
