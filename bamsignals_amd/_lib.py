@@ -28,6 +28,8 @@ HIST_MAX_ROWS, HIST_MOMENTS = 8192, 2
 SUMMARY_FIXED, SUMMARY_MAX_THRESHOLDS = 3, 8
 # include/bamsignals_abi.h: BSIG_SCALED_MAX_BINS
 SCALED_MAX_BINS = 2048
+# the largest keep_dup (keepDup): an int32
+KEEP_DUP_MAX = 2**31 - 1
 
 ERR_NAMES = {-1: "BSIG_ERR_ARG", -2: "BSIG_ERR_IO", -3: "BSIG_ERR_NOINDEX", -4: "BSIG_ERR_CHROM",
              -5: "BSIG_ERR_EXT", -6: "BSIG_ERR_DEVICE", -7: "BSIG_ERR_NOMEM", -8: "BSIG_ERR_FORMAT"}
@@ -158,6 +160,13 @@ def load():
     lib.bsig_plan_scaled_segmented.restype = C.c_int32
     lib.bsig_plan_run_scaled.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_plan_run_scaled_host.argtypes = [C.c_void_p, C.c_void_p]
+    # ... and the capped plan: keep_dup and frag_len
+    lib.bsig_plan_create_capped.argtypes = lib.bsig_plan_create.argtypes[:-1] + [C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    for query in ("cells", "runs"):
+        getattr(lib, f"bsig_plan_capped_{query}").argtypes = [C.c_void_p]
+        getattr(lib, f"bsig_plan_capped_{query}").restype = C.c_int64
+    lib.bsig_plan_run_capped.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bsig_plan_run_capped_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.bsig_runs_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.bsig_runs_n_seg.argtypes = [C.c_void_p]
     lib.bsig_runs_n_seg.restype = C.c_int64
@@ -227,6 +236,10 @@ def load():
     lib.bsig_coverage_summary.argtypes = core_head + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p]
     lib.bsig_pileup_scaled.argtypes = core_head + [C.c_int32] * 8 + [C.c_void_p]
     lib.bsig_coverage_scaled.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
+    # the capped signals: bsig_pileup_core's arguments with keep_dup behind pe_mid, bsig_coverage_core_ex's with frag_len and
+    # keep_dup behind tspan
+    lib.bsig_pileup_capped.argtypes = core_head + [C.c_int32] * 10 + [C.c_void_p, C.c_void_p]
+    lib.bsig_coverage_capped.argtypes = core_head + [C.c_int32] * 10 + [C.c_void_p, C.c_void_p]
     lib.bsig_pileup_runs.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
     lib.bsig_coverage_runs.argtypes = core_head + [C.c_int32] * 8 + [C.POINTER(C.c_void_p)]
     # ... of reads resized to the fragment: frag_len in tspan's place

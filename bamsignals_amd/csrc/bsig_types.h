@@ -146,4 +146,16 @@ struct BsigSumChunk {
     int32_t cell0, nvals;
 };
 
+// Capped coverage (capped.hip: k_capped_scan, k_capped_cover): one range's row of the scratch -- the capped per-base 5' ends
+// of the range widened by frag_len - 1 on both sides, (forward, reverse) pairs in genome order -- and its cells of the result
+struct BsigCappedRange {
+    int64_t s_off;      // int32 offset of the row in the scratch (even: a pair is 8-B aligned)
+    int64_t r_off;      // int32 offset of the range's first result cell (bsig_layout)
+    int32_t w;          // the range's width
+    int32_t lead;       // pairs in front of the range's first base: frag_len - 1, less what lies below base 0 (negative: so
+                        // many of the range's own first bases lie below base 0)
+    int32_t slen;       // pairs in the row: lead + w + frag_len - 1 (0 for a range without width)
+    int32_t neg;        // 1: range on the '-' strand
+};
+
 #endif

@@ -476,6 +476,30 @@ int bsig_coverage_scaled(const char *bampath, int64_t n, const int32_t *seq_code
                        FileDest::reduce(Reduce::scaled, out, n_bins)});
 }
 
+int bsig_pileup_capped(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                       const char *const *levels, const int32_t *start, const int32_t *width,
+                       const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                       int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss, int32_t requiredF, int32_t filteredF, int32_t pe_mid,
+                       int32_t keep_dup, int32_t maxgap, int32_t device, int32_t *out, const int64_t *off)
+{
+    return file_level({{bampath, n, seq_code, n_levels, levels, start, width, strand},
+                       pileup_params(tlen_filter, n_tlen_filter, mapqual, binsize, shift, ss, requiredF, filteredF, pe_mid), device,
+                       FileDest::capped(out, off, keep_dup)});
+}
+
+int bsig_coverage_capped(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                         const char *const *levels, const int32_t *start, const int32_t *width,
+                         const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                         int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t frag_len,
+                         int32_t keep_dup, int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *out,
+                         const int64_t *off)
+{
+    FileCall c{{bampath, n, seq_code, n_levels, levels, start, width, strand},
+               coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, tspan, true, binsize, ss), device,
+               FileDest::capped(out, off, keep_dup), frag_len};
+    return file_level(c);
+}
+
 int bsig_pileup_runs(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
                      const char *const *levels, const int32_t *start, const int32_t *width,
                      const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,

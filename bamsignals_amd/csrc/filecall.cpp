@@ -321,6 +321,7 @@ int reduction_plan(bsig_ctx *ctx, const bsig_reads *reads, const RangeView &g, c
     case Reduce::summary: return bsig_plan_create_summary(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, c.to.thresholds, plan);
     case Reduce::scaled: return bsig_plan_create_scaled(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, plan);
     case Reduce::vplot: return bsig_plan_create_vplot(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, plan);
+    case Reduce::capped: return bsig_plan_create_capped(ctx, reads, g.n, g.rid, g.loc, g.width, g.strand, p, arg, c.frag_len, plan);
     case Reduce::none: break;
     }
     return fail(BSIG_ERR_ARG, "not a reduction");
@@ -600,9 +601,63 @@ void drop_spare_device_memory(const Slots *keep)
 // to a row of `row` int64 (S * (3 + K), S * n_bins) -- the per-range summaries and the scaled regions (bsig_*_summary,
 // bsig_*_scaled).  One GPU takes all ranges (route `what`); several take a block of the sorted ranges each, and the host ADDS
 // the blocks' int64 vectors or PLACES a block's rows at the caller's indices -- no per-base cell leaves a GPU.
+// The capped signals (bsig_pileup_capped / bsig_coverage_capped) take the same route with int32 cells: their rows are of
+// unequal length, so a block's rows are placed through the layout's offsets (capped_on_slots).
+int capped_on_slots(const Stage &s, std::string &route)
+{
+    const FileCall &c = s.call;
+    const std::vector<bsig_reads *> &reads = s.res->reads;
+    const RangeView g = s.ranges();
+    int32_t *out = c.to.out;
+    const int64_t *off = c.to.off;
+    const size_t nd = reads.size();
+    if (nd == 1) {
+        const double t0 = now_s();
+        bsig_plan *plan = nullptr;
+        int rc = reduction_plan(s.slots->ctx[0], reads[0], g, c, &plan);
+        s.X[3] = now_s() - t0;
+        if (rc == BSIG_OK) rc = plan_run_reduced_to_host(plan, out, &s.X[4], &s.X[5]);
+        if (plan) bsig_plan_free(plan);
+        route = "capped";
+        return rc;
+    }
+    std::vector<int64_t> order;
+    sort_ranges(g.n, g.rid, g.loc, order);
+    const int rc = for_each_slot(nd, [&](size_t k) -> int {
+        int64_t a, b;
+        slot_block(g.n, k, nd, &a, &b);
+        if (a >= b) return BSIG_OK;
+        const RangeBlock B(order, a, b, g);
+        bsig_plan *plan = nullptr;
+        int rk = reduction_plan(s.slots->ctx[k], reads[k], B.view(), c, &plan);
+        std::vector<int32_t> part;
+        if (rk == BSIG_OK) {
+            try {
+                part.resize((size_t)bsig_plan_cells(plan));
+            } catch (const std::bad_alloc &) {
+                rk = fail(BSIG_ERR_NOMEM, "out of host memory for %lld result cells", (long long)bsig_plan_cells(plan));
+            }
+        }
+        if (rk == BSIG_OK) rk = plan_run_reduced_to_host(plan, part.data());
+        if (rk == BSIG_OK) {    // (the blocks' ranges are disjoint: every slot writes rows of its own)
+            const int64_t *po = bsig_plan_offsets(plan);
+            for (int64_t i = a; i < b && rk == BSIG_OK; ++i) {
+                const int64_t j = order[(size_t)i], len = po[i - a + 1] - po[i - a];
+                if (len != off[j + 1] - off[j]) rk = fail(BSIG_ERR_ARG, "offsets do not match bsig_layout() for these parameters");
+                else std::copy(part.begin() + po[i - a], part.begin() + po[i - a + 1], out + off[j]);
+            }
+        }
+        if (plan) bsig_plan_free(plan);
+        return rk;
+    });
+    if (rc != BSIG_OK) return rc;
+    route = "capped of " + std::to_string(nd) + " blocks of ranges, rows placed on the host";
+    return BSIG_OK;
+}
 int reduced_on_slots(const Stage &s, std::string &route)
 {
     const FileCall &c = s.call;
+    if (c.to.kind == Reduce::capped) return capped_on_slots(s, route);
     const std::vector<bsig_reads *> &reads = s.res->reads;
     const RangeView g = s.ranges();
     const int64_t cells = s.cells, row = s.row;
@@ -808,7 +863,13 @@ int judge_call(const FileCall &c, Stage &s)
     using Shape = FileDest::Shape;
     // (what an entry point refuses of its own leaves the route of the thread's call before standing, as it always has)
     if (to.shape == Shape::into && !to.dst) return fail(BSIG_ERR_ARG, "destinations missing");
-    if (to.shape == Shape::reduced && !to.reduced) return fail(BSIG_ERR_ARG, "%s is NULL", to.name);
+    if (to.shape == Shape::reduced && to.kind != Reduce::capped && !to.reduced) return fail(BSIG_ERR_ARG, "%s is NULL", to.name);
+    CappedShape capped{};
+    if (to.kind == Reduce::capped) {
+        // the capped signals' own refusals come first of all: keep_dup, single ends, the fragment length and its mode
+        if (const int rk = capped_shape(c.prm, to.arg, c.frag_len, &capped)) return rk;
+        if (!to.out) return fail(BSIG_ERR_ARG, "out is NULL");
+    }
     if (to.shape == Shape::encoded && to.enc.kind == EncoderKind::views && to.enc.lower > to.enc.upper)
         return fail(BSIG_ERR_ARG, "lower (%d) is above upper (%d)", (int)to.enc.lower, (int)to.enc.upper);
     if (c.overlap && c.overlap_type != 0 && c.overlap_type != 1) return fail(BSIG_ERR_ARG, "overlap type must be 0 (any) or 1 (within)");
@@ -868,9 +929,20 @@ int judge_call(const FileCall &c, Stage &s)
         rc = vplot_shape(c.prm, at.n > 0 && at.width ? at.n : 0, at.width, to.arg, &vplot);
         s.cells = vplot.cells;
         break;
+    case Reduce::capped:
+        if (!to.off) return fail(BSIG_ERR_ARG, "offsets missing");
+        rc = check_params(capped.tiles, at.n, at.width, &early);
+        if (rc == BSIG_OK) {
+            s.own_off.resize((size_t)at.n + 1);
+            s.cells = bsig_layout(at.n, at.width, capped.lay_binsize, capped.S == 2, s.own_off.data());
+            if (memcmp(to.off, s.own_off.data(), ((size_t)at.n + 1) * sizeof(int64_t)) != 0)
+                rc = fail(BSIG_ERR_ARG, "offsets do not match bsig_layout() for these parameters");
+        }
+        break;
     }
     if (rc) return rc;
     if (to.reduced) std::fill(to.reduced, to.reduced + s.cells, (int64_t)0);
+    if (to.kind == Reduce::capped) std::fill(to.out, to.out + s.cells, (int32_t)0);
     return BSIG_OK;
 }
 
@@ -1194,12 +1266,12 @@ int run_result(const Stage &s, std::string &result)
     int rc = BSIG_ERR_NOMEM;
     for (int attempt = 0; attempt < 2 && rc == BSIG_ERR_NOMEM; ++attempt) {
         if (attempt) drop_spare_device_memory(s.slots.get());
-        if (to.reduced) rc = reduced_on_slots(s, result);
+        if (to.shape == FileDest::Shape::reduced) rc = reduced_on_slots(s, result);
         else if (to.runs) rc = encoded_on_slots(s, result);
         else if (!s.many) rc = run_on_one(s, t_run);
         else rc = run_on_slots(s, result);
     }
-    if (!s.many && !to.reduced && !to.runs) result = "download";
+    if (!s.many && to.shape != FileDest::Shape::reduced && !to.runs) result = "download";
     return rc;
 }
 

@@ -35,7 +35,7 @@ inline Encoder views_encoder(int32_t lower, int32_t upper) { return Encoder{Enco
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
 // layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, or an encoder's columns
-enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled, vplot };
+enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled, vplot, capped };
 struct FileDest {
     enum class Shape { flat, into, reduced, encoded } shape = Shape::flat;
     int32_t *out = nullptr;
@@ -45,7 +45,8 @@ struct FileDest {
     int64_t *reduced = nullptr;     // the kind's cells: the sum's bins, max_lag + 1 + BSIG_XCORR_MOMENTS, tlen_filter[1] / len_bin + 1
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
     const char *name = "out";       // ... as the entry point calls that argument
-    int32_t arg = 0;                // xcorr: max_lag; frag, vplot: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins
+    int32_t arg = 0;                // xcorr: max_lag; frag, vplot: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins;
+                                    // capped: keep_dup
     const int32_t *thresholds = nullptr;    // summary: arg of them
     EncodedColumns *runs = nullptr;         // the per-range result as runs or views (enc says which), in the caller's range order
     Encoder enc = runs_encoder();
@@ -65,6 +66,14 @@ struct FileDest {
     {
         FileDest to;
         to.shape = Shape::reduced; to.kind = kind; to.reduced = cells; to.arg = arg; to.thresholds = thresholds;
+        return to;
+    }
+    // the capped signals: a reduction plan's route, but the result is int32 cells at the caller's offsets (out, off), as a
+    // plain call's -- `reduced` stays NULL
+    static FileDest capped(int32_t *out, const int64_t *off, int32_t keep_dup)
+    {
+        FileDest to;
+        to.shape = Shape::reduced; to.kind = Reduce::capped; to.out = out; to.off = off; to.arg = keep_dup;
         return to;
     }
     static FileDest encoded(EncodedColumns *cols, const Encoder &enc)

@@ -145,6 +145,26 @@ TileForm scaled_form(int threads, bool coverage, bool half, bool wide, bool segm
 hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segmented, const BsigReadsDev &R, const BsigKParams &P,
                                const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
                                bool resolve_first, int n_bins, unsigned long long *out, hipStream_t st);
+// Capped 5' ends (bsig_plan_create_capped).  k_capped_tiles: runs and per-base tiles as for launch_hist_tiles, of a plan whose
+// image is strand-split (P.ss = 1, P.binsize = 1); a tile's out_off is its RANGE's first cell of the int32 result, which is
+// in bsig_layout's order for the call's bins and ss_out.  Every 5'-end cell is capped at keep_dup per strand.  binned false:
+// bins of one base, every tile stores its own cells.  binned true: cell c of a range goes to bin __umulhi(c, bin_magic) >>
+// bin_shift (magic_u31's; bamCount: one bin of 2^31 - 1 bases) through n_acc int32 LDS accumulators a row (planmath.h:
+// capped_tile_bins) and every workgroup ADDS into out: zero `out` first.  wide / half / windows / resolve_first as in
+// launch_hist_tiles.
+TileForm capped_form(int threads, bool half, bool wide, bool binned, int tile_cells, int rows, int n_acc);
+hipError_t launch_capped_tiles(int threads, bool wide, bool binned, const BsigReadsDev &R, const BsigKParams &P,
+                               const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                               bool resolve_first, int keep_dup, int ss_out, uint32_t bin_magic, int bin_shift, int n_acc,
+                               int32_t *out, hipStream_t st);
+// Capped coverage, stage 2 (capped.hip).  scratch: per range a row of slen (forward, reverse) pairs of capped 5' ends in genome
+// order, as launch_capped_tiles stores them for the widened '+' ranges (ss_out 1, not binned).  launch_capped_scan: every row's
+// inclusive prefix sums in place (uint32, modulo 2^32).  launch_capped_cover: the coverage of reads resized to frag_len bases
+// from those, cell x of a range to bin __umulhi(x, bin_magic) >> bin_shift of its result cells (ss: 2 * bin + antisense);
+// binned false: bins of one base, stored; binned true: ADDED -- zero `out` first.  One workgroup per range.
+hipError_t launch_capped_scan(const BsigCappedRange *ranges, int64_t n_ranges, uint32_t *scratch, hipStream_t st);
+hipError_t launch_capped_cover(const BsigCappedRange *ranges, int64_t n_ranges, const uint32_t *scratch, int frag_len, int ss,
+                               bool binned, uint32_t bin_magic, int bin_shift, int32_t *out, hipStream_t st);
 hipError_t warm_pileup_module(hipStream_t st);
 hipError_t launch_visits(const BsigReadsDev &R, const BsigKParams &P, int mode, const BsigWorkItem *items,
                          int64_t n_items, unsigned long long *acc, hipStream_t st);

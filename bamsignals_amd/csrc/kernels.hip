@@ -2181,6 +2181,30 @@ struct XcorrWideOne {
     }
 };
 
+// ... and its sibling for a plan with a shift (the capped 5' ends): the 5' end moves by P.shift in the read's own direction,
+// as ProfileOne moves it
+struct ShiftedWideOne {
+    const BsigKParams &P;
+    uint32_t *cnt;
+    int loc, len, c0, nc;
+    bool neg_range;
+    __device__ __forceinline__ void operator()(int p, int e, bool neg, bool rej, int tl, bool valid) const
+    {
+        if (!valid || rej || tlen_rejected(P, tl)) return;
+        int rel = (neg ? e - P.shift : p + P.shift) - loc;
+        if ((unsigned)rel >= (unsigned)len) return;
+        int anti = neg ? 1 : 0;
+        if (neg_range) { rel = len - rel - 1; anti ^= 1; }
+        const int lc = rel - c0;
+        if ((unsigned)lc < (unsigned)nc) atomicAdd(&cnt[2 * lc + anti], 1u);
+    }
+};
+// a consumer of walk_tile_cells that declares kShifted takes ShiftedWideOne for its wide tiles
+template <typename C, typename = void>
+struct wants_shift : std::false_type {};
+template <typename C>
+struct wants_shift<C, std::void_t<decltype(C::kShifted)>> : std::true_type {};
+
 // LDS of one k_xcorr_tiles workgroup, in dwords: image | list | 64-bit lag accumulators | counter (+ pad) | filter table
 struct XcorrLds {
     int img, list, acc, misc, ptab, total;
@@ -2674,7 +2698,11 @@ __device__ __forceinline__ void walk_tile_cells(const BsigWorkItem &w, uint32_t 
         }
     } else {
         load_windows<false>(R, P, BSIG_MODE_PROFILE, w, items, windows, win, t, pk, clip);
-        if constexpr (WIDE) {
+        if constexpr (WIDE && wants_shift<Cells>::value) {
+            const ShiftedWideOne one{P, img, w.loc, w.len, w.c0, nc, neg_range};
+            for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
+            if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
+        } else if constexpr (WIDE) {
             const XcorrWideOne one{P, img, w.loc, w.len, w.c0, nc, neg_range};
             for_each_read<NT, 2, false>(R, P, win, pk.base, ptab, tid, one);
             if (pk.n_chunks > 1) packed_later_chunks<NT>(R, P, BSIG_MODE_PROFILE, w, pk.n_chunks, clip, ptab, tid, one);
@@ -3056,6 +3084,150 @@ __global__ __launch_bounds__(NT) void k_scaled_tiles(const BsigWorkItem *__restr
         __syncthreads();
     }
     if (cur >= 0) flush(cur);
+}
+
+// ------------------------------------------------------------------------------------------
+// Capped 5' ends (bsig_plan_create_capped)
+// ------------------------------------------------------------------------------------------
+// keepDup = k: every per-base, per-strand 5'-end cell e is replaced by min(e, k) BEFORE anything is binned or the strands
+// are added.  Tiles, images and the walk are the depth histogram's (walk_tile_cells) with the image always strand-split
+// (P.ss is 1 whatever the result's strands: the walk then hands the sense cell over as row 0 and the antisense cell as row 1
+// of the same x, one after the other, to the same lane); the tile's work item carries the first result cell of its RANGE
+// (out_off), and the result is int32 in bsig_layout's order for the call's bins and strands: cell 2 * bin + antisense with
+// strands, bin without.
+// BINNED false (bins of one base): the tile owns its cells and stores them, zeros included -- one 8-byte store a lane with
+// strands (the layout's offsets are even then), one 4-byte store without.  Nothing is zeroed first and nothing is atomic.
+// BINNED true (wider bins, and bamCount as one bin of 2^31 - 1 bases): cell c0 + x lies in bin (c0 + x) / binsize, an exact
+// magic division (magic_u31).  Lanes take ascending x, so a bin is a run of lanes: a wave with no cell to add is done, one with
+// a few lets them add for themselves; of the others a wave whose cells lie in one bin adds them up with xor shuffles and
+// issues one LDS add, any other runs ScaledCells' segmented scan keyed on the bin and the last lane of every bin adds.  The accumulators are int32 in LDS, one per bin the tile touches (planmath.h: capped_tile_bins)
+// and row; after the tile the non-zero ones are added into the result with int32 global atomics, because a bin may straddle
+// tiles, runs and the wide launch: the call zeroes the result first.  Integers: the order does not matter.
+// Exactness.  A wave sum is at most the reads of a tile's windows, below 2^32; no capped sum exceeds the uncapped one, so
+// the result's int32 contract is bamProfile's.
+template <bool BINNED>
+struct CappedCells {
+    static constexpr bool kShifted = true;
+    uint32_t k;                         // keepDup
+    bool ss;                            // the RESULT's strands (the image always has them)
+    int lane;
+    int32_t *dst = nullptr;             // !BINNED: the tile's first result cell
+    uint32_t *acc = nullptr;            // BINNED: LDS, rows of n_acc accumulators
+    int n_acc = 0;
+    uint32_t c0 = 0u, b0 = 0u;          // BINNED: the tile's first cell and that cell's bin
+    uint32_t magic = 0u;
+    int shift = 0;
+    uint32_t held = 0u;                 // the capped sense cell, until the antisense cell of the same x arrives
+    __device__ __forceinline__ uint32_t bin(uint32_t c) const { return __umulhi(c, magic) >> shift; }
+    // (all lanes of the wave are here: the loops around `at` are uniform)
+    __device__ __forceinline__ void add(uint32_t *row, uint32_t b, uint32_t s, bool ok) const
+    {
+        // 5' ends are mostly zeros: a wave without a cell to add is done, and one with a few (at most kSparse of its 64
+        // lanes) lets them add for themselves -- cheaper than the twelve shuffles of the scan (s is 0 where ok is false)
+        constexpr int kSparse = 16;
+        const unsigned long long some = __ballot(s != 0u);
+        if (some == 0ull) return;                                   // (uniform)
+        if (__popcll(some) <= kSparse) {                            // (uniform)
+            if (s) atomicAdd(&row[b], s);
+            return;
+        }
+        const uint32_t b_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        const uint32_t b_last = (uint32_t)__builtin_amdgcn_readlane((int)b, kWave - 1);
+        if (b_first == b_last) {                                    // (uniform) one bin, or no cell at all
+            if (b_first == 0xFFFFFFFFu) return;
+            for (int m = kWave / 2; m >= 1; m /= 2) s += __shfl_xor(s, m);
+            if (lane == 0 && s) atomicAdd(&row[b], s);
+            return;
+        }
+#pragma unroll
+        for (int d = 1; d < kWave; d *= 2) {
+            const uint32_t os = __shfl_up(s, d), ob = __shfl_up(b, d);
+            if (lane >= d && ob == b) s += os;
+        }
+        const uint32_t nb = __shfl_down(b, 1);
+        if (ok && s && (lane == kWave - 1 || nb != b)) atomicAdd(&row[b], s);
+    }
+    template <int ROW>
+    __device__ __forceinline__ void at(uint32_t v, bool ok, int x)
+    {
+        const uint32_t c = v < k ? v : k;
+        if constexpr (ROW == 0) {
+            held = c;
+        } else if constexpr (!BINNED) {
+            if (ok) {
+                if (ss) *reinterpret_cast<int2 *>(dst + 2 * (size_t)x) = make_int2((int)held, (int)c);
+                else dst[x] = (int)(held + c);
+            }
+        } else {
+            // the bin within the tile's own; clamped, which an exact quotient never needs: no address depends on it
+            uint32_t b = 0xFFFFFFFFu;
+            if (ok) {
+                b = bin(c0 + (uint32_t)x) - b0;
+                b = b < (uint32_t)n_acc ? b : (uint32_t)n_acc - 1u;
+            }
+            if (ss) {
+                add(acc, b, ok ? held : 0u, ok);
+                add(acc + n_acc, b, ok ? c : 0u, ok);
+            } else {
+                add(acc, b, ok ? held + c : 0u, ok);
+            }
+        }
+    }
+};
+
+template <int NT, int KIND, bool WIDE, bool BINNED>
+__global__ __launch_bounds__(NT) void k_capped_tiles(const BsigWorkItem *__restrict__ items, const uint2 *__restrict__ runs,
+                                                     int32_t *__restrict__ out, const uint2 *__restrict__ windows,
+                                                     const BsigReadsDev R, const BsigKParams P, const int keep_dup, const int ss_out,
+                                                     const uint32_t bin_magic, const int bin_shift, const int n_acc)
+{
+    static_assert(KIND == kHistEnds || KIND == kHistEndsHalf, "capped cells are 5' ends");
+    static_assert(!(WIDE && KIND == kHistEndsHalf), "a wide tile reads the packed words");
+    extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+    const int tid = threadIdx.x;
+    const int S = ss_out ? 2 : 1;                                     // (uniform)
+    const HistLds L = hist_lds(KIND, WIDE, P.tile_cells, BINNED ? S * n_acc : 0);
+    uint32_t *img = reinterpret_cast<uint32_t *>(lds) + L.img;
+    int32_t *wtot = lds + L.wtot;
+    uint8_t *ptab = reinterpret_cast<uint8_t *>(lds + L.ptab);
+    uint32_t *acc = reinterpret_cast<uint32_t *>(lds) + L.hist;
+    for (int v = tid; v < L.ptab; v += NT) lds[v] = 0;
+    if (BINNED) for (int v = tid; v < S * n_acc; v += NT) acc[v] = 0u;
+    if (KIND != kHistEndsHalf) build_ptab<NT>(ptab, R, P, tid);
+    const uint2 run = runs[blockIdx.x];
+    CappedCells<BINNED> cnt{(uint32_t)keep_dup, ss_out != 0, tid & (kWave - 1)};
+    cnt.acc = acc; cnt.n_acc = n_acc; cnt.magic = bin_magic; cnt.shift = bin_shift;
+    __syncthreads();
+
+#pragma unroll 1
+    for (uint32_t t = run.x; t < run.y; ++t) {
+        const BsigWorkItem w = items[t];
+        // (a tile listed apart for the wide launch: its cells are capped there, none here)
+        if (!WIDE && (w.units_strand & BSIG_ITEM_HEAVY)) continue;
+        int nb = 0;
+        if constexpr (BINNED) {
+            cnt.c0 = (uint32_t)w.c0;
+            cnt.b0 = cnt.bin((uint32_t)w.c0);
+            nb = (int)(cnt.bin((uint32_t)(w.c0 + w.nc - 1)) - cnt.b0) + 1;
+            nb = nb < n_acc ? nb : n_acc;
+        } else {
+            cnt.dst = out + w.out_off + (long long)w.c0 * S;
+        }
+        walk_tile_cells<NT, KIND, WIDE>(w, t, items, windows, R, P, img, wtot, ptab, tid, cnt);
+        __syncthreads();
+        if constexpr (BINNED) {
+            for (int r = 0; r < S; ++r) {
+                for (int j = tid; j < nb; j += NT) {
+                    const uint32_t v = acc[r * n_acc + j];
+                    if (v) {
+                        acc[r * n_acc + j] = 0u;
+                        atomicAdd(out + w.out_off + (long long)(cnt.b0 + (uint32_t)j) * S + r, (int32_t)v);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3998,6 +4170,41 @@ hipError_t launch_scaled_tiles(int threads, bool coverage, bool wide, bool segme
     return launch_tiles(scaled_form(threads, coverage, !wide && P.packed_half != 0, wide, !wide && segmented, P.tile_cells,
                                     !coverage && P.ss ? 2 : 1, n_bins),
                         R, P, items, n_items, runs, n_runs, windows, resolve_first, out, st, n_bins);
+}
+
+// ---- capped 5' ends ------------------------------------------------------------------------------------------------
+// one k_capped_tiles instantiation by its run-time choices (n_acc: accumulators per row, 0 without bins)
+TileForm capped_form(int threads, bool half, bool wide, bool binned, int tile_cells, int rows, int n_acc)
+{
+    const auto f = [&](void (*k)(BSIG_TILE_PARAMS(int32_t), int, int, uint32_t, int, int), const char *name) {
+        return TileForm{reinterpret_cast<const void *>(k), name, threads,
+                        (size_t)hist_lds(kHistEnds, wide, tile_cells, binned ? rows * n_acc : 0).total * 4, BSIG_MODE_PROFILE};
+    };
+#define BSIG_CN(NT_, K_, W_, B_) f(k_capped_tiles<NT_, K_, (W_) != 0, (B_) != 0>, "k_capped_tiles<" #NT_ "," #K_ ",wide=" #W_ ",binned=" #B_ ">")
+#define BSIG_CC(NT_) do { if (wide) { if (binned) return BSIG_CN(NT_, kHistEnds, 1, 1); \
+                                      return BSIG_CN(NT_, kHistEnds, 1, 0); } \
+                          if (half) { if (binned) return BSIG_CN(NT_, kHistEndsHalf, 0, 1); \
+                                      return BSIG_CN(NT_, kHistEndsHalf, 0, 0); } \
+                          if (binned) return BSIG_CN(NT_, kHistEnds, 0, 1); \
+                          return BSIG_CN(NT_, kHistEnds, 0, 0); } while (0)
+    if (threads == 64) BSIG_CC(64);
+    if (threads == 128) BSIG_CC(128);
+    if (threads == 256) BSIG_CC(256);
+#undef BSIG_CC
+#undef BSIG_CN
+    return TileForm{};
+}
+
+hipError_t launch_capped_tiles(int threads, bool wide, bool binned, const BsigReadsDev &R, const BsigKParams &P,
+                               const BsigWorkItem *items, int64_t n_items, const uint2 *runs, int64_t n_runs, void *windows,
+                               bool resolve_first, int keep_dup, int ss_out, uint32_t bin_magic, int bin_shift, int n_acc,
+                               int32_t *out, hipStream_t st)
+{
+    if (n_runs <= 0) return hipSuccess;
+    if (keep_dup < 1 || !P.ss || P.binsize != 1 || (binned && n_acc < 1)) return hipErrorInvalidValue;
+    return launch_tiles(capped_form(threads, !wide && P.packed_half != 0, wide, binned, P.tile_cells, ss_out ? 2 : 1, n_acc),
+                        R, P, items, n_items, runs, n_runs, windows, resolve_first, out, st, keep_dup, ss_out, bin_magic, bin_shift,
+                        n_acc);
 }
 
 hipError_t launch_make_ptab(const BsigReadsDev &R, const BsigKParams &P, uint8_t *out, hipStream_t st)

@@ -45,6 +45,8 @@ struct KindFacts {
     int32_t len_bin = 0;            // ... and whose kernel divides by the row width
     int32_t own_tile_cells = 0;     // hist, summary, scaled: the shape's resolved tile_cells; these kinds' tiles are walked whole
     bool row_tiles = false;         // summary, scaled: a tile writes no cell, it carries its range's first result row
+    bool capped = false;            // capped: per-base tiles whatever the result's bins (off is the RESULT's layout); a tile
+                                    // carries its range's first result cell
 };
 
 // ---- tile size ------------------------------------------------------------------------------------------------------
@@ -292,8 +294,10 @@ inline Tiles cut_tiles(const std::vector<int64_t> &order, const int32_t *rid, co
         w.loc = loc[i]; w.len = len[i];
         w.ref_unit0 = ref_unit0[rid[i]];
         w.units_strand = ref_units[rid[i]] | (strand[i] < 0 ? BSIG_ITEM_NEG : 0u);
-        const int64_t cells = (off[i + 1] - off[i]) / mult;
-        if (wide_bins) {
+        const int64_t cells = kf.capped ? (int64_t)len[i] : (off[i + 1] - off[i]) / mult;
+        if (kf.capped) {
+            cell_tiles(w, cells, ts.cells, off[i], 0, T.items);
+        } else if (wide_bins) {
             wide_bin_tiles(w, strand[i] < 0, cells, r.binsize, count_split, off[i], mult, T.items);
             T.needs_zero = true;
         } else if (r.mode == BSIG_MODE_COUNT) {
@@ -309,6 +313,56 @@ inline Tiles cut_tiles(const std::vector<int64_t> &order, const int32_t *rid, co
     // a sum plan adds up all tiles of one c0 (every range has the same width, so also the same nc): consecutive
     if (kf.sum) std::stable_sort(T.items.begin(), T.items.end(), [](const BsigWorkItem &a, const BsigWorkItem &b) { return a.c0 < b.c0; });
     return T;
+}
+
+// ---- capped 5' ends -------------------------------------------------------------------------------------------------
+// The bins of a capped plan's result as its kernel divides: the caller's binsize, and for bamCount (lay_binsize -1) one bin
+// of 2^31 - 1 bases, wider than any range
+inline int32_t capped_binsize(int32_t lay_binsize) { return lay_binsize < 0 ? INT32_MAX : lay_binsize; }
+// The bins a tile of at most tile_cells per-base cells can touch: cells c0 .. c0 + tile_cells - 1 with c0 anywhere in a bin
+// lie in at most (tile_cells - 1) / binsize + 2 consecutive bins (floor((c0 + n - 1) / b) - floor(c0 / b) <= (n - 1) / b + 1,
+// counted inclusively).  The int32 LDS accumulators a row of k_capped_tiles; 0 for bins of one base, which have none.
+inline int32_t capped_tile_bins(int32_t tile_cells, int32_t binsize)
+{
+    if (binsize <= 1 || tile_cells < 1) return 0;
+    return (int32_t)(((int64_t)tile_cells - 1) / binsize + 2);
+}
+// The capped coverage's stage 1 piles the capped 5' ends up over every range widened by frag_len - 1 bases on both sides: a
+// read covers frag_len bases from its 5' end, so ends that far outside still reach the range.  The left end is clipped at
+// base 0 -- nothing has a 5' end below it, the clipped part counts as zeros; a range that begins below 0 loses its own bases
+// below 0 too, which no read covers (lead is then negative) --; the right end is left to overhang the reference.
+struct CappedWide {
+    int32_t loc, len;       // the widened range (len 0 for a range without width, or with nothing at or above base 0)
+    int32_t lead;           // bases of it in front of the range's own first base: at most frag_len - 1; negative: the range's
+                            // first -lead bases lie below base 0
+    bool fits;              // false: the widened range's end passes 2^31 - 1
+};
+inline CappedWide capped_widen(int32_t loc, int32_t len, int32_t frag_len)
+{
+    CappedWide c{loc, 0, 0, true};
+    if (len <= 0) return c;
+    const int64_t lo = std::max<int64_t>((int64_t)loc - (frag_len - 1), 0);
+    const int64_t lead = (int64_t)loc - lo;
+    const int64_t wide = lead + (int64_t)len + (frag_len - 1);
+    c.fits = wide <= INT32_MAX && lo + wide <= INT32_MAX;
+    if (!c.fits) return c;
+    c.lead = (int32_t)lead;
+    if (wide <= 0) return c;
+    c.loc = (int32_t)lo; c.len = (int32_t)wide;
+    return c;
+}
+// k_capped_cover's indexes into a scratch row of inclusive prefix sums (PF of the forward ends, PR of the reverse ends; an
+// index below 0 reads as 0): the coverage of the range's base u (genome order, 0-based) is
+//   PF[u + lead] - PF[u + lead - L]  +  PR[u + lead + L - 1] - PR[u + lead - 1]
+// -- the forward reads with their 5' end in [u - L + 1, u], the reverse reads with theirs in [u, u + L - 1] --, and 0 where
+// u + lead < 0: that base lies below base 0, where no read is.
+struct CappedIdx {
+    int64_t f_hi, f_lo, r_hi, r_lo;
+};
+inline CappedIdx capped_window(int32_t u, int32_t lead, int32_t frag_len)
+{
+    const int64_t j = (int64_t)u + lead;
+    return CappedIdx{j, j - frag_len, j + frag_len - 1, j - 1};
 }
 
 // ---- tile loads, bounds, heavy split --------------------------------------------------------------------------------

@@ -246,9 +246,10 @@ void block_cache_release()
 
 namespace { enum { kSumProfile = 0, kSumCover = 1, kSumCoverSS = 2 }; }      // launch_sum_tiles' kinds (kernels.h)
 // What a plan is: a plain one gives every range its own int32 cells; sum, xcorr, frag and hist reduce all ranges to one short
-// int64 vector, a summary reduces every range by itself to a few int64, a scaled plan to n_bins int64.
+// int64 vector, a summary reduces every range by itself to a few int64, a scaled plan to n_bins int64; a capped plan gives every
+// range its own int32 cells, as a plain one does, but runs as the reductions do (runs of tiles walked whole).
 // The order is the one the wrong-kind refusals are worded by (wrong_kind).
-enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary, kScaled, kVplot };
+enum PlanKind { kPlain = 0, kSum, kXcorr, kFrag, kHist, kSummary, kScaled, kVplot, kCapped };
 // per kind: the noun with its article, the device run call, the host run call, the bytes of a result cell
 struct KindRow { const char *a, *run_dev, *run_host; int cell_bytes; };
 static const KindRow kKinds[] = {
@@ -260,13 +261,14 @@ static const KindRow kKinds[] = {
     {"a summary", "bsig_plan_run_summary", "bsig_plan_run_summary_host", 8},
     {"a scaled", "bsig_plan_run_scaled", "bsig_plan_run_scaled_host", 8},
     {"a vplot", "bsig_plan_run_vplot", "bsig_plan_run_vplot_host", 8},
+    {"a capped", "bsig_plan_run_capped", "bsig_plan_run_capped_host", 4},
 };
 // A reduction plan's own (every kind but kPlain): the result's cells, the device buffer its _host call runs into, and the
 // tiles cut into runs (a workgroup each) -- the main tiles' runs, then the extra ones': a sum plan's heavy slices, an xcorr or
 // hist, summary or scaled plan's wide tiles (32-bit image, one tile a run), none for a frag or vplot plan.  Beside them what only one kind has.
 struct Reduced {
-    int64_t cells = 0;
-    int64_t *d_out = nullptr;           // device result of bsig_plan_run_<kind>_host, kept between calls
+    int64_t cells = 0;                  // of kKinds[kind].cell_bytes each
+    int64_t *d_out = nullptr;           // device result of bsig_plan_run_<kind>_host, kept between calls (whole qwords)
     uint2 *runs = nullptr;              // [t0, t1) of the items, the extra runs of the heavy items
     int64_t n_runs_main = 0, n_runs_extra = 0;
     // sum (bsig_plan_create_sum): per-base tiles ordered by c0, a run of one c0, summed over the ranges by k_sum_tiles
@@ -322,6 +324,21 @@ struct Reduced {
         bool merge = false;             // ... equal cells of a wave merged before the atomic
         size_t lds_budget = 0;          // bytes of LDS the table may take (decides the form, and where the filter table lives)
     } vplot;
+    // capped (bsig_plan_create_capped): per-base strand-split tiles, their out_off the range's first cell of the int32 result
+    struct {
+        int32_t keep_dup = 1;           // k
+        int S = 1;                      // values per result cell
+        bool binned = false;            // bins wider than a base, or bamCount: the kernels add into a zeroed result
+        uint32_t bin_magic = 0;         // magic_u31 of the bins' width (planmath.h: capped_binsize)
+        int32_t bin_shift = 0;
+        int32_t n_acc = 0;              // LDS accumulators a row (planmath.h: capped_tile_bins)
+        // the capped coverage (frag_len > 0): the tiles store into `scratch` (the plan's off is ITS layout: bins of one base,
+        // strands kept, over the widened ranges), k_capped_scan and k_capped_cover make the result, laid out by res_off
+        int32_t frag_len = 0;
+        uint32_t *scratch = nullptr;
+        BsigCappedRange *ranges = nullptr;
+        std::vector<int64_t> res_off;   // bsig_layout of the caller's ranges, bins and strands
+    } capped;
 };
 
 struct bsig_plan {
@@ -1707,7 +1724,53 @@ int bsig::scaled_shape(const bsig_params &prm, int32_t n_bins, ScaledShape *out)
     return BSIG_OK;
 }
 
+// What only the capped 5' ends ask, ahead of check_params: single ends on bamProfile or bamCount, and a cap of at least 1.  The
+// tiles are per-base and strand-split whatever the result's bins and strands: the cap applies per base and strand.
+int bsig::capped_shape(const bsig_params &prm, int32_t keep_dup, int32_t frag_len, CappedShape *out)
+{
+    const bool cover = prm.mode == BSIG_MODE_COVERAGE || prm.mode == BSIG_MODE_COVERAGE_EX;
+    if (!cover && prm.mode != BSIG_MODE_PROFILE && prm.mode != BSIG_MODE_COUNT)
+        return fail(BSIG_ERR_ARG, "keep_dup is defined on bamProfile, bamCount and bamCoverage (mode %d given)", prm.mode);
+    if (cover && frag_len == 0)
+        return fail(BSIG_ERR_ARG, "duplicates of different lengths have no defined survivor: bamCoverage takes keep_dup with a fragment length only");
+    if (!cover && frag_len != 0)
+        return fail(BSIG_ERR_ARG, "reads are resized to the fragment for bamCoverage only (mode %d given): frag_len must be 0", prm.mode);
+    if (cover && (frag_len < 1 || frag_len > BSIG_FRAG_LEN_MAX))
+        return fail(BSIG_ERR_ARG, "the fragment length must be between 1 and %d (%d given)", BSIG_FRAG_LEN_MAX, frag_len);
+    if (keep_dup < 1) return fail(BSIG_ERR_ARG, "keep_dup must be at least 1 (%d given)", keep_dup);
+    if (prm.pe_mid != 0)
+        return fail(BSIG_ERR_ARG, "a paired-end duplicate is a fragment with both ends equal, which a 5' end and a strand do not identify: pe_mid must be 0 with keep_dup");
+    if (prm.tspan != 0)
+        return fail(BSIG_ERR_ARG, "a paired-end duplicate is a fragment with both ends equal, which a 5' end and a strand do not identify: tspan must be 0 with keep_dup");
+    if (prm.n_tlen_filter != 0)
+        return fail(BSIG_ERR_ARG, "keep_dup caps single-end reads: it takes no template-length rule (n_tlen_filter must be 0)");
+    const bool bins = prm.mode == BSIG_MODE_PROFILE || prm.mode == BSIG_MODE_COVERAGE_EX;
+    if (bins && prm.binsize < 1) return fail(BSIG_ERR_ARG, "provide a binsize greater or equal to 1");
+    if (prm.mode == BSIG_MODE_COVERAGE_EX && prm.binsize > kMaxCoverageBin)
+        return fail(BSIG_ERR_ARG, "coverage bins are at most 65536 bases wide (bamProfile / bamCount count at that scale)");
+    if (prm.threads != 0 && prm.threads != 64 && prm.threads != 128 && prm.threads != 256)
+        return fail(BSIG_ERR_ARG, "threads must be 64, 128 or 256");
+    if (prm.tile_cells != 0 && (prm.tile_cells < 16 || prm.tile_cells > 2048))
+        return fail(BSIG_ERR_ARG, "tile_cells must be between 16 and 2048");
+    CappedShape s;
+    s.tiles = prm;
+    s.tiles.mode = BSIG_MODE_PROFILE;
+    s.tiles.binsize = 1;
+    s.tiles.ss = 1;
+    if (cover) s.tiles.shift = 0;       // (coverage takes no shift)
+    s.tiles.threads = prm.threads != 0 ? prm.threads : 256;
+    s.tiles.tile_cells = prm.tile_cells != 0 ? prm.tile_cells : 2048;
+    s.keep_dup = keep_dup;
+    s.frag_len = frag_len;
+    s.lay_binsize = prm.mode == BSIG_MODE_COUNT ? -1 : bins ? prm.binsize : 1;
+    s.binsize = bsig::capped_binsize(s.lay_binsize);
+    s.S = prm.mode != BSIG_MODE_COVERAGE && prm.ss != 0 ? 2 : 1;
+    *out = s;
+    return BSIG_OK;
+}
+
 static int sum_setup(bsig_plan *P, const bsig::SumShape &shape, const std::vector<BsigWorkItem> &items, const std::vector<BsigWorkItem> &hitems);
+static int capped_setup(bsig_plan *P, const bsig::CappedShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int scaled_setup(bsig_plan *P, const bsig::ScaledShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int summary_setup(bsig_plan *P, const bsig::SummaryShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide);
 static int hist_setup(bsig_plan *P, const bsig::HistShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide, int64_t n_cells);
@@ -1721,6 +1784,7 @@ static int xcorr_setup(bsig_plan *P, const bsig::XcorrShape &shape, int body, in
 // kVplot: a frag plan's tiles
 // kHist: the mode's per-base tiles, none of them cut into slices
 // kSummary, kScaled: the same tiles, each carrying its range's result row
+// kCapped: per-base strand-split tiles, each carrying its range's first cell of a result laid out by the call's own bins
 struct PlanRequest {
     PlanKind kind = kPlain;
     int32_t frag_len = 0;           // kPlain, kSum: a resized plan's fragment length (bsig::resized_rule passed), else 0
@@ -1733,6 +1797,7 @@ struct PlanRequest {
         const bsig::SummaryShape *summary;
         const bsig::ScaledShape *scaled;
         const bsig::VplotShape *vplot;
+        const bsig::CappedShape *capped;
     };
 };
 // (planmath.h's pairs go to the device as uint2, byte for byte)
@@ -1751,6 +1816,7 @@ static bsig::KindFacts kind_facts(const PlanRequest &rq)
     case kSummary: kf.own_tile_cells = rq.summary->tiles.tile_cells; kf.row_tiles = true; break;
     case kScaled: kf.own_tile_cells = rq.scaled->tiles.tile_cells; kf.row_tiles = true; break;
     case kVplot: kf.frag = true; kf.len_bin = rq.vplot->len_bin; break;
+    case kCapped: kf.own_tile_cells = rq.capped->tiles.tile_cells; kf.capped = true; break;
     }
     return kf;
 }
@@ -1780,7 +1846,7 @@ struct PlanWork {
              const int32_t *strand_, const bsig_params *prm_, const PlanRequest &rq_)
         : ctx(ctx_), reads(reads_), n(n_), rid(rid_), loc(loc_), len(len_), strand(strand_), prm(prm_), rq(rq_) {}
     // a tile of these kinds is walked whole: a cell's value must be complete before it is counted or compared
-    bool whole_tiles() const { return rq.kind == kHist || kf.row_tiles; }
+    bool whole_tiles() const { return rq.kind == kHist || kf.row_tiles || kf.capped; }
     // count tiles without an image (frag, vplot): none is heavy, and their setup cuts the runs by the reads in their windows
     bool imageless() const { return kf.frag; }
 };
@@ -1836,7 +1902,11 @@ static int cut_plan(PlanWork &W)
 {
     bsig_plan *P = W.plan.get();
     P->off.resize(W.n + 1);
-    bsig_layout(W.n, W.len, W.r.lay_binsize, P->kp.ss, P->off.data());
+    // (a capped plan's tiles are per base and strand-split; its result has the call's own bins and strands)
+    // ... and the capped coverage's tiles store the capped ends of the widened ranges into the plan's scratch, laid out here
+    if (W.rq.kind == kCapped && W.rq.capped->frag_len) bsig_layout(W.n, W.len, 1, 1, P->off.data());
+    else if (W.rq.kind == kCapped) bsig_layout(W.n, W.len, W.rq.capped->lay_binsize, W.rq.capped->S == 2, P->off.data());
+    else bsig_layout(W.n, W.len, W.r.lay_binsize, P->kp.ss, P->off.data());
     std::vector<int64_t> order;
     bsig::sort_ranges(W.n, W.rid, W.loc, order);
     bsig::Tiles T = bsig::cut_tiles(order, W.rid, W.loc, W.len, W.strand, P->off.data(), W.reads->ref_unit0.data(),
@@ -1980,6 +2050,7 @@ static int setup_kind(PlanWork &W)
     case kSummary: return summary_setup(P, *rq.summary, W.items, n_wide);
     case kScaled: return scaled_setup(P, *rq.scaled, W.items, n_wide);
     case kVplot: return vplot_setup(P, *rq.vplot, W.reads_of_tile);
+    case kCapped: return capped_setup(P, *rq.capped, W.items, n_wide);
     }
     return BSIG_OK;
 }
@@ -2002,7 +2073,7 @@ static int plan_create_impl(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     *out = W.plan.release();
     return BSIG_OK;
 }
-// ---- what the seven *_setup functions share ------------------------------------------------------------------------
+// ---- what the eight *_setup functions share ------------------------------------------------------------------------
 // the device's compute units and the LDS a workgroup may hold
 static int device_limits(const bsig_plan *P, int *n_cu, int *lds_max)
 {
@@ -2277,6 +2348,52 @@ static int scaled_setup(bsig_plan *P, const bsig::ScaledShape &shape, const std:
                       [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, n_wide);
 }
 
+// The runs of a capped plan: cut as a summary plan's are, with the tiles-per-run rule of the other kinds that walk their tiles
+// whole (env BAMSIGNALS_CAPPED_RUN_TILES); the wide tiles follow as runs of their own.  With bins a workgroup holds S * n_acc
+// int32 accumulators of LDS beside its image, flushed after every tile: nothing but the shared cutter's ceiling bounds a run.
+static int capped_setup(bsig_plan *P, const bsig::CappedShape &shape, const std::vector<BsigWorkItem> &items, int64_t n_wide)
+{
+    Reduced &R = *P->red;
+    auto &Q = R.capped;
+    Q.keep_dup = shape.keep_dup;
+    Q.S = shape.S;
+    Q.binned = shape.binsize > 1;
+    Q.frag_len = shape.frag_len;
+    bsig::magic_u31(shape.binsize, &Q.bin_magic, &Q.bin_shift);
+    const bool cover = shape.frag_len > 0;
+    // (the capped coverage's tiles store per-base cells with strands, whatever the result's bins: no accumulators)
+    Q.n_acc = cover ? 0 : bsig::capped_tile_bins(P->tile_cells, shape.binsize);
+    R.cells = P->off.back();
+    if (cover) {
+        const int64_t n = P->n_ranges;
+        Q.res_off.resize((size_t)n + 1);
+        bsig_layout(n, shape.len0, shape.lay_binsize, shape.S == 2, Q.res_off.data());
+        R.cells = Q.res_off.back();
+        std::vector<BsigCappedRange> rg((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t w = std::max(shape.len0[i], 0);
+            rg[(size_t)i] = BsigCappedRange{P->off[(size_t)i], Q.res_off[(size_t)i], w, shape.lead[i],
+                                            (int32_t)((P->off[(size_t)i + 1] - P->off[(size_t)i]) / 2), shape.strand0[i] < 0 ? 1 : 0};
+        }
+        hipStream_t st = P->ctx->stream;
+        // the scratch: 2 x (w + 2 L - 2) int32 per range, less what lies below base 0; out of memory is the plan's refusal
+        HIP_TRY(P->pool.alloc(&Q.scratch, (size_t)std::max<int64_t>(P->off.back(), 1)));
+        HIP_TRY(P->pool.alloc(&Q.ranges, (size_t)std::max<int64_t>(n, 1)));
+        if (n) HIP_TRY(hipMemcpyAsync(Q.ranges, rg.data(), rg.size() * sizeof(BsigCappedRange), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const auto form = [&](bool wide) {
+        return bsig::capped_form(P->threads, P->kp.packed_half != 0, wide, !cover && Q.binned, P->tile_cells, cover ? 2 : Q.S, Q.n_acc);
+    };
+    const size_t lds = form(n_wide > 0).lds;
+    const auto refuse = [&](int lds_max) {
+        return fail(BSIG_ERR_ARG, "a tile of %d cells and its bins need %zu bytes of LDS per workgroup, the device has %d", P->tile_cells, lds,
+                    lds_max);
+    };
+    return setup_runs(P, lds, refuse, form(false), "BAMSIGNALS_CAPPED_RUN_TILES", kCounterMax,
+                      [&](int64_t t) { return (int64_t)items[(size_t)t].nc; }, n_wide);
+}
+
 extern "C" {
 
 int bsig_plan_create(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid,
@@ -2301,9 +2418,14 @@ int bsig_plan_create_resized(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, 
     return plan_create_impl(ctx, reads, n, rid, loc, len, strand, prm, rq, out);
 }
 
-const int64_t *bsig_plan_offsets(const bsig_plan *p) { return p ? p->off.data() : nullptr; }
+// (a capped coverage plan's own layout is its scratch's: the caller sees the result's)
+static const std::vector<int64_t> &result_layout(const bsig_plan *p)
+{
+    return p->red && !p->red->capped.res_off.empty() ? p->red->capped.res_off : p->off;
+}
+const int64_t *bsig_plan_offsets(const bsig_plan *p) { return p ? result_layout(p).data() : nullptr; }
 
-int64_t bsig_plan_cells(const bsig_plan *p) { return p ? p->off.back() : 0; }
+int64_t bsig_plan_cells(const bsig_plan *p) { return p ? result_layout(p).back() : 0; }
 
 }  // extern "C"
 // The main launch of a run, bsig_plan_run's or bsig_plan_run_sum's: launch(kp, resolved, lookup) enqueues it in the form
@@ -2340,10 +2462,10 @@ static int wrong_kind(const bsig_plan *p, PlanKind want, bool host)
     if (p->kind > want) return fail(BSIG_ERR_ARG, "%s plan runs with %s", kKinds[p->kind].a, call);
     return fail(BSIG_ERR_ARG, "not %s plan: %s runs it", kKinds[want].a, call);
 }
-// What the seven int64 device run calls do around their launches: the checks in the order every one of them made them, the
+// What the device run calls of every kind but kPlain do around their launches: the checks in the order every one of them made them, the
 // plan's GPU made current, then body(the plan's Reduced, its stream) -- the launches -- and the run counted.
 template <typename Body>
-static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
+static int run_reduced(bsig_plan *p, PlanKind want, void *dev, Body &&body)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (const int rc = wrong_kind(p, want, false)) return rc;
@@ -2360,11 +2482,11 @@ static int run_reduced(bsig_plan *p, PlanKind want, int64_t *dev, Body &&body)
 // The body of the run calls whose kernels ADD into the result (xcorr, frag, hist, summary, scaled): the result zeroed, the
 // main launch in the form run_main chose, then the extra runs -- the tiles with more reads than a 16-bit cell may see: whole,
 // with 32-bit cells, their windows looked up in place.  launch(wide, kp, items, n_items, runs, n_runs, windows, lookup) is the
-// kind's launch_*_tiles.
+// kind's launch_*_tiles.  zero false: every cell is stored by the tile that owns it (a capped plan with bins of one base).
 template <typename Launch>
-static int run_added(bsig_plan *p, const Reduced &R, int64_t *dev, hipStream_t st, Launch &&launch)
+static int run_added(bsig_plan *p, const Reduced &R, void *dev, hipStream_t st, Launch &&launch, bool zero = true)
 {
-    HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int64_t), st));
+    if (zero) HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * (size_t)kKinds[p->kind].cell_bytes, st));
     if (R.n_runs_main) {
         const int rc = run_main(p, [&](const BsigKParams &kp, BsigResolved *resolved, bool lookup) {
             return launch(false, kp, p->items, p->n_items, R.runs, R.n_runs_main, resolved, lookup);
@@ -2454,7 +2576,7 @@ int bsig::plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async, double
     if (t_download) *t_download = since(t1);
     return rc != BSIG_OK ? rc : plan_check_overflow(p);
 }
-int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels, double *t_download)
+int bsig::plan_run_reduced_to_host(bsig_plan *p, void *host, double *t_kernels, double *t_download)
 {
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
@@ -2464,7 +2586,8 @@ int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernel
     if (!host) return fail(BSIG_ERR_ARG, "output buffer is NULL");
     HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
-    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (size_t)Q->cells));
+    const size_t bytes = (size_t)Q->cells * (size_t)kKinds[p->kind].cell_bytes;
+    if (!Q->d_out) HIP_TRY(p->pool.alloc(&Q->d_out, (bytes + 7) / 8));
     int rc = BSIG_OK;
     switch (p->kind) {
     case kPlain: break;
@@ -2475,6 +2598,7 @@ int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernel
     case kSummary: rc = bsig_plan_run_summary(p, Q->d_out); break;
     case kScaled: rc = bsig_plan_run_scaled(p, Q->d_out); break;
     case kVplot: rc = bsig_plan_run_vplot(p, Q->d_out); break;
+    case kCapped: rc = bsig_plan_run_capped(p, reinterpret_cast<int32_t *>(Q->d_out)); break;
     }
     if (rc != BSIG_OK) return rc;
     if (t_kernels) {
@@ -2482,7 +2606,7 @@ int bsig::plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernel
         *t_kernels = since(t0);
     }
     const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(host, Q->d_out, (size_t)Q->cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(host, Q->d_out, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (t_download) *t_download = since(t1);
     return BSIG_OK;
@@ -2657,6 +2781,32 @@ int bsig_plan_create_scaled(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, c
     return rc != BSIG_OK ? rc : plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
 }
 
+int bsig_plan_create_capped(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
+                            const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t keep_dup, int32_t frag_len,
+                            bsig_plan **out)
+{
+    if (!ctx || !reads || !prm || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_plan_create_capped");
+    *out = nullptr;
+    bsig::CappedShape shape;
+    if (const int rc = bsig::capped_shape(*prm, keep_dup, frag_len, &shape)) return rc;
+    PlanRequest rq;
+    rq.kind = kCapped;
+    rq.capped = &shape;
+    if (!frag_len) return plan_create_impl(ctx, reads, n, rid, loc, len, strand, &shape.tiles, rq, out);
+    // the capped coverage: stage 1 walks the widened ranges, every one as a '+' range (the scratch is in genome order)
+    if (n < 0 || (n > 0 && (!rid || !loc || !len || !strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
+    std::vector<int32_t> wloc((size_t)n), wlen((size_t)n), lead((size_t)n), plus((size_t)n, 1);
+    for (int64_t i = 0; i < n; ++i) {
+        if (len[i] < 0) return fail(BSIG_ERR_ARG, "range %lld has a negative width", (long long)i);
+        const bsig::CappedWide c = bsig::capped_widen(loc[i], len[i], frag_len);
+        if (!c.fits)
+            return fail(BSIG_ERR_ARG, "range %lld widened by the fragment length ends beyond 2^31 - 1: cut the range", (long long)i);
+        wloc[(size_t)i] = c.loc; wlen[(size_t)i] = c.len; lead[(size_t)i] = c.lead;
+    }
+    shape.len0 = len; shape.strand0 = strand; shape.lead = lead.data();
+    return plan_create_impl(ctx, reads, n, rid, wloc.data(), wlen.data(), plus.data(), &shape.tiles, rq, out);
+}
+
 int bsig_plan_create_vplot(bsig_ctx *ctx, const bsig_reads *reads, int64_t n, const int32_t *rid, const int32_t *loc,
                            const int32_t *len, const int32_t *strand, const bsig_params *prm, int32_t len_bin, bsig_plan **out)
 {
@@ -2690,6 +2840,8 @@ int64_t bsig_plan_vplot_runs(const bsig_plan *p) { return runs_if(p, kVplot); }
 int32_t bsig_plan_vplot_rows(const bsig_plan *p) { return p && p->kind == kVplot ? p->red->vplot.rows : 0; }
 int32_t bsig_plan_vplot_cols(const bsig_plan *p) { return p && p->kind == kVplot ? p->red->vplot.cols : 0; }
 int32_t bsig_plan_vplot_form(const bsig_plan *p) { return p && p->kind == kVplot ? p->red->vplot.form : 0; }
+int64_t bsig_plan_capped_cells(const bsig_plan *p) { return cells_if(p, kCapped); }
+int64_t bsig_plan_capped_runs(const bsig_plan *p) { return runs_if(p, kCapped); }
 
 int bsig_plan_run_sum(bsig_plan *p, int64_t *sum_dev)
 {
@@ -2798,8 +2950,34 @@ int bsig_plan_run_vplot(bsig_plan *p, int64_t *dev)
     });
 }
 
-// the seven _host calls: the kind checked, then the one run into the plan's own device buffer and its download
-static int run_reduced_host(bsig_plan *p, PlanKind want, int64_t *host)
+int bsig_plan_run_capped(bsig_plan *p, int32_t *dev)
+{
+    return run_reduced(p, kCapped, dev, [&](const Reduced &R, hipStream_t st) -> int {
+        const auto &Q = R.capped;
+        if (!Q.frag_len)
+            return run_added(p, R, dev, st, [&](bool wide, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items,
+                                                const uint2 *runs, int64_t n_runs, void *windows, bool lookup) {
+                return bsig::launch_capped_tiles(p->threads, wide, Q.binned, p->reads->dev, kp, items, n_items, runs, n_runs, windows,
+                                                 lookup, Q.keep_dup, Q.S == 2, Q.bin_magic, Q.bin_shift, Q.n_acc, dev, st);
+            }, Q.binned);
+        // the capped coverage: the capped ends of the widened ranges into the scratch (every pair has its tile: nothing to
+        // zero), its rows' prefix sums, then the window sums into the result
+        int32_t *scratch = reinterpret_cast<int32_t *>(Q.scratch);
+        const int rc = run_added(p, R, scratch, st, [&](bool wide, const BsigKParams &kp, const BsigWorkItem *items, int64_t n_items,
+                                                        const uint2 *runs, int64_t n_runs, void *windows, bool lookup) {
+            return bsig::launch_capped_tiles(p->threads, wide, false, p->reads->dev, kp, items, n_items, runs, n_runs, windows, lookup,
+                                             Q.keep_dup, 1, 0u, 0, 0, scratch, st);
+        }, false);
+        if (rc != BSIG_OK) return rc;
+        HIP_TRY(bsig::launch_capped_scan(Q.ranges, p->n_ranges, Q.scratch, st));
+        if (Q.binned) HIP_TRY(hipMemsetAsync(dev, 0, (size_t)R.cells * sizeof(int32_t), st));
+        HIP_TRY(bsig::launch_capped_cover(Q.ranges, p->n_ranges, Q.scratch, Q.frag_len, Q.S == 2, Q.binned, Q.bin_magic, Q.bin_shift, dev, st));
+        return BSIG_OK;
+    });
+}
+
+// the _host calls: the kind checked, then the one run into the plan's own device buffer and its download
+static int run_reduced_host(bsig_plan *p, PlanKind want, void *host)
 {
     if (!p) return fail(BSIG_ERR_ARG, "plan is NULL");
     if (const int rc = wrong_kind(p, want, true)) return rc;
@@ -2812,6 +2990,7 @@ int bsig_plan_run_hist_host(bsig_plan *p, int64_t *host) { return run_reduced_ho
 int bsig_plan_run_summary_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kSummary, host); }
 int bsig_plan_run_scaled_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kScaled, host); }
 int bsig_plan_run_vplot_host(bsig_plan *p, int64_t *host) { return run_reduced_host(p, kVplot, host); }
+int bsig_plan_run_capped_host(bsig_plan *p, int32_t *host) { return run_reduced_host(p, kCapped, host); }
 
 // (tests: what a re-layout of the resident columns does to the plans made before it)
 // The segment table of a plan's own layout, for the encoders of a per-range result (runs.hip, views.hip): range i's cells

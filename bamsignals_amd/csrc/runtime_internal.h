@@ -237,9 +237,10 @@ int download_slices_to_dest(bsig_ctx *ctx, const int32_t *src_dev, int64_t n_sli
 // the copy is only enqueued.  With timers the kernels are waited for first and the two stages timed apart; without them
 // nothing waits between kernels and download.  The caller has checked that p is a plain plan (runtime.hip)
 int plan_run_to_host(bsig_plan *p, const HostDest *dst, bool async = false, double *t_kernels = nullptr, double *t_download = nullptr);
-// ... and a reduction plan's (sum, xcorr, frag, hist, summary, scaled, vplot): its kind's device run call into the plan's own int64 buffer (made
-// at the first call), then the download; timed as above.  A sum plan without cells has nothing to run
-int plan_run_reduced_to_host(bsig_plan *p, int64_t *host, double *t_kernels = nullptr, double *t_download = nullptr);
+// ... and a reduction plan's (sum, xcorr, frag, hist, summary, scaled, vplot; capped): its kind's device run call into the plan's own
+// buffer (made at the first call) of the kind's cells -- int64, a capped plan's int32 --, then the download; timed as above.  A
+// sum plan without cells has nothing to run
+int plan_run_reduced_to_host(bsig_plan *p, void *host, double *t_kernels = nullptr, double *t_download = nullptr);
 // (PlanRule, bsig_params as every entry point reads them: planmath.h)
 // frag_len: what a resized plan's creator was given (resized_rule has judged it), 0 for every other plan
 int check_params(const bsig_params &prm, int64_t n, const int32_t *len, PlanRule *out, int32_t frag_len = 0);
@@ -309,6 +310,21 @@ struct ScaledShape {
     int32_t n_bins;         // N: int64 per (range, row)
 };
 int scaled_shape(const bsig_params &prm, int32_t n_bins, ScaledShape *out);
+// what only a capped plan asks, ahead of check_params (runtime.hip: capped_shape): single ends (no midpoint, no extension, no
+// template-length rule), keep_dup >= 1, threads and tile_cells the kernel's LDS holds; frag_len 0 on bamProfile or bamCount
+// (the capped 5' ends), 1 .. BSIG_FRAG_LEN_MAX on bamCoverage (the capped coverage of resized reads)
+struct CappedShape {
+    bsig_params tiles;      // the per-base, strand-split 5'-end plan the tiles are piled up by (threads and tile_cells resolved)
+    int32_t keep_dup;       // k: every (base, strand) cell counts min(cell, k)
+    int32_t frag_len;       // 0, or the bases every kept read covers from its 5' end
+    int32_t lay_binsize;    // bsig_layout's binsize of the RESULT (-1: bamCount)
+    int32_t binsize;        // the bins the kernels divide by (planmath.h: capped_binsize)
+    int S;                  // values per result cell: 2 with strands
+    // the capped coverage: the plan's tiles walk the WIDENED ranges (planmath.h: capped_widen), all of them as '+' ranges;
+    // these are the caller's own widths and strands and every widened range's lead (bsig_plan_create_capped fills them)
+    const int32_t *len0 = nullptr, *strand0 = nullptr, *lead = nullptr;
+};
+int capped_shape(const bsig_params &prm, int32_t keep_dup, int32_t frag_len, CappedShape *out);
 // BSIG_ERR_ARG if the plan's last run took a coverage bin past INT32_MAX (bsig_plan_overflowed), else BSIG_OK;
 // for callers that have synchronised the plan's stream
 int plan_check_overflow(bsig_plan *p);

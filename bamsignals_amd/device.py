@@ -495,6 +495,36 @@ class ScaledPlan(_ReducedPlan):
         return super().run_host(out).reshape(self.n_ranges, self.rows, self.n_bins)
 
 
+class CappedPlan(_ReducedPlan):
+    """Ranges + call parameters resident in HBM for the capped signals, keepDup (bsig_plan_create_capped): every per-base,
+    per-strand 5'-end cell counts ``min(cell, keep_dup)`` before anything is binned, added or extended.  ``frag_len`` 0:
+    ``params`` of mode PROFILE (binsize, ss, shift) or COUNT, and each run gives what ``Plan`` gives for them, capped;
+    ``frag_len`` > 0: ``params`` of mode COVERAGE or COVERAGE_EX, and each run gives the coverage of the kept reads resized
+    to ``frag_len`` bases, as ``Plan(..., frag_len=)`` lays it out.  No midpoint, no extension, no ``tlen_filter``.  The
+    result is ``cells`` int32 at ``offsets`` (bsig_layout's order: the caller's range order).  ``runs``: the runs of
+    tiles (a workgroup each) the plan was cut into.  ``stats()['heavy_tiles']`` counts the tiles that took the 32-bit
+    image."""
+
+    _KIND = "capped"
+
+    def __init__(self, ctx, reads, rid, loc, length, strand, params, keep_dup, frag_len=0):
+        self._create(ctx, reads, rid, loc, length, strand, params, int(keep_dup), int(frag_len))
+        self.keep_dup, self.frag_len = int(keep_dup), int(frag_len)
+        self.n_ranges = len(_i32(length))
+        self.runs = int(self._lib.bsig_plan_capped_runs(self._h))
+        off = self._lib.bsig_plan_offsets(self._h)
+        self.offsets = np.ctypeslib.as_array(off, shape=(self.n_ranges + 1,)).copy()
+
+    def run_host(self, out=None):
+        """Run and return the flat int32 result in host memory (``out``: a reusable contiguous int32 array of ``cells``)."""
+        if out is None:
+            out = np.empty(self.cells, dtype=np.int32)
+        elif out.dtype != np.int32 or out.size != self.cells or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous int32 array of plan.cells elements")
+        _lib.check(self._lib.bsig_plan_run_capped_host(self._h, _ptr(out)))
+        return out
+
+
 class RunEncoder:
     """Run-length encoder of int32 device buffers (bsig_runs_*): segment k is the ``length[k]`` cells
     ``src[base[k] + p * stride]``; ``stride`` 1, or 2 for one row of the interleaved ``2 * bin + antisense`` layout.

@@ -322,6 +322,40 @@ def coverage_scaled(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=
     return _scaled_call(_lib.load().bsig_coverage_scaled, bampath, gr, tlen_filter, head, n_bins, 1, maxgap, device)
 
 
+def pileup_capped(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False, requiredF=0,
+                  filteredF=-1, pe_mid=False, keep_dup=1, maxgap=16385, device=None):
+    """``pileup_core`` with every per-base, per-strand 5'-end cell capped at ``keep_dup`` before it is binned or the
+    strands are added (bsig_pileup_capped); the same list."""
+    head = _head(bampath, gr, tlen_filter)
+    lib = _lib.load()
+    n = len(gr)
+    off = np.empty(n + 1, dtype=np.int64)
+    cells = lib.bsig_layout(n, head.width.ctypes.data, int(binsize), int(bool(ss)), off.ctypes.data)
+    out = np.zeros(cells, dtype=np.int32)
+    _lib.check(lib.bsig_pileup_capped(*head, int(mapqual), int(binsize), int(shift), int(bool(ss)), int(requiredF),
+                                      int(filteredF), int(bool(pe_mid)), int(keep_dup), int(maxgap), _dev(device),
+                                      out.ctypes.data, off.ctypes.data))
+    if binsize <= 0:
+        return [out.reshape(-1, 2).T if ss else out]
+    return _split(out, off, ss)
+
+
+def coverage_capped(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False, frag_len=0, keep_dup=1,
+                    maxgap=16385, device=None, *, binsize=1, ss=False):
+    """``coverage_core(frag_len=)`` of the reads that ``keep_dup`` keeps: at most that many per 5' end and strand
+    (bsig_coverage_capped); the same list."""
+    head = _head(bampath, gr, tlen_filter)
+    lib = _lib.load()
+    n = len(gr)
+    off = np.empty(n + 1, dtype=np.int64)
+    cells = lib.bsig_layout(n, head.width.ctypes.data, int(binsize), int(bool(ss)), off.ctypes.data)
+    out = np.zeros(cells, dtype=np.int32)
+    _lib.check(lib.bsig_coverage_capped(*head, int(mapqual), int(requiredF), int(filteredF), int(bool(tspan)), int(frag_len),
+                                        int(keep_dup), int(maxgap), _dev(device), int(binsize), int(bool(ss)),
+                                        out.ctypes.data, off.ctypes.data))
+    return _split(out, off, bool(ss))
+
+
 def _take_runs(lib, handle, ss):
     """a bsig_runs_result handle -> RunSignals (the arrays are allocated once the handle says how large they are)"""
     try:
@@ -481,13 +515,41 @@ def last_call_route():
     return _lib.load().bsig_last_call_route().decode()
 
 
+def _keep_dup(keepDup, paired_end, choices):  # noqa: N803
+    """keepDup as a call reads it: 0 for None, else a whole number in 1 .. 2**31 - 1, and only for single ends"""
+    if keepDup is None:
+        return 0
+    if isinstance(keepDup, (bool, np.bool_)) or not isinstance(keepDup, (int, float, np.integer, np.floating)) \
+            or not float(keepDup).is_integer():
+        raise ValueError("keepDup must be a whole number of reads")
+    k = int(keepDup)
+    if k < 1:
+        raise ValueError("keepDup must be at least 1")
+    if k > _lib.KEEP_DUP_MAX:
+        raise ValueError(f"keepDup must be at most {_lib.KEEP_DUP_MAX}")
+    if _match_arg(paired_end, choices, "paired.end") != "ignore":
+        raise ValueError('keepDup caps single-end reads by their 5\' end and strand: a paired-end duplicate is a fragment with '
+                         'both ends equal, which those do not identify (paired_end must be "ignore")')
+    return k
+
+
 def bamCount(bampath, gr, mapqual=0, shift=0, ss=False, paired_end=("ignore", "filter", "midpoint"),  # noqa: N802
-             tlenFilter=None, filteredFlag=-1, verbose=True):  # noqa: N803
+             tlenFilter=None, filteredFlag=-1, verbose=True, *, keepDup=None):  # noqa: N803
     """For each range, count the reads whose 5' end maps in it (R/wrappers.R:101-120).
-    Returns an int32 vector, or a 2 x n matrix (rows sense, antisense) with ``ss=True``."""
+    Returns an int32 vector, or a 2 x n matrix (rows sense, antisense) with ``ss=True``.
+
+    ``keepDup=k`` (keyword only; a whole number in 1 .. 2**31 - 1; ``None``, the default: every read counts): at most ``k``
+    reads per position and strand, MACS's ``--keep-dup k``.  Of the reads that pass the filter, ``e_s[p]`` have their 5' end
+    -- ``pos`` of a forward read, ``end`` of a reverse one, after ``shift`` -- on base ``p`` and strand ``s``; a range's
+    count is the sum of ``min(e_s[p], k)`` over its bases, per strand with ``ss`` and over both strands without (the cap
+    is applied per strand first).  ``paired_end`` must be ``"ignore"``."""
+    k = _keep_dup(keepDup, paired_end, ("ignore", "filter", "midpoint"))
     if verbose:
         _print_sentence(bampath)
     pe = _match_arg(paired_end, ("ignore", "filter", "midpoint"), "paired.end")
+    if k:
+        return pileup_capped(os.path.expanduser(str(bampath)), gr, (), mapqual, -1, shift, ss, flagMask(pe), filteredFlag,
+                             False, k)[0]
     pu = pileup_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual, -1,
                      shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
     return pu[0]
@@ -495,7 +557,7 @@ def bamCount(bampath, gr, mapqual=0, shift=0, ss=False, paired_end=("ignore", "f
 
 def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N802
                paired_end=("ignore", "filter", "midpoint"), tlenFilter=None, filteredFlag=-1, verbose=True,  # noqa: N803
-               *, aggregate=False, runs=False):
+               *, aggregate=False, runs=False, keepDup=None):
     """For each base pair (or bin) of the ranges, the number of reads whose 5' end maps there
     (R/wrappers.R:124-151).  Returns a CountSignals.
 
@@ -505,9 +567,20 @@ def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N8
     vignette's rowMeans of alignSignals) is this divided by ``len(gr)``.
 
     ``runs=True``: returns a RunSignals -- the same signals as runs (value, length), encoded on the GPU, so that the
-    per-base cells are never downloaded; ``sig.decode(i)`` is the CountSignals' element i.  Not with ``aggregate``."""
+    per-base cells are never downloaded; ``sig.decode(i)`` is the CountSignals' element i.  Not with ``aggregate``.
+
+    ``keepDup=k`` (a whole number in 1 .. 2**31 - 1; ``None``, the default: every read counts): at most ``k`` reads per
+    position and strand, MACS's ``--keep-dup k``.  Of the reads that pass the filter, ``e_s[p]`` have their 5' end -- ``pos``
+    of a forward read, ``end`` of a reverse one, after ``shift`` -- on base ``p`` and strand ``s``; bin j of a range holds
+    the sum of ``min(e_s[p], k)`` over the bin's bases, sense and antisense as separate rows with ``ss`` and added
+    without (the cap is applied per strand first; a '-' range is mirrored first and binned second, and its strands swap,
+    as always).  The reads that share a cell are indistinguishable, so which of them survive never matters.
+    ``paired_end`` must be ``"ignore"``; not with ``aggregate`` or ``runs`` (not built yet)."""
     if runs and aggregate:
         raise ValueError("runs=True and aggregate=True exclude each other: a sum over ranges has no per-range runs")
+    k = _keep_dup(keepDup, paired_end, ("ignore", "filter", "midpoint"))
+    if k and (aggregate or runs):
+        raise ValueError("keepDup with aggregate=True or runs=True is out of scope so far: take the per-range signals")
     if verbose:
         _print_sentence(bampath)
     if binsize < 1:
@@ -525,6 +598,10 @@ def bamProfile(bampath, gr, binsize=1, mapqual=0, shift=0, ss=False,  # noqa: N8
     if runs:
         return pileup_runs(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                            int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
+    if k:
+        pu = pileup_capped(os.path.expanduser(str(bampath)), gr, (), mapqual, int(binsize), shift, ss, flagMask(pe),
+                           filteredFlag, False, k)
+        return CountSignals(pu, bool(ss), _trusted=True)
     pu = pileup_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                      int(binsize), shift, ss, flagMask(pe), filteredFlag, pe == "midpoint")
     return CountSignals(pu, bool(ss), _trusted=True)
@@ -566,7 +643,8 @@ def _frag_length(fragLength):  # noqa: N803
 
 
 def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFilter=None,  # noqa: N802,N803
-                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False, runs=False, fragLength=None):
+                filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False, runs=False, fragLength=None,
+                keepDup=None):
     """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173).
 
     ``binsize`` (1 .. 65,536): bin j of a range covers its bases [j*binsize, min((j+1)*binsize, width)) in range
@@ -589,9 +667,22 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     below 0 exist in no range.  With ``ss`` the fragment counts on the read's own strand; ``binsize``, ``aggregate``
     and ``runs`` work on it as on plain coverage.  ``paired_end`` must be ``"ignore"``: a paired-end fragment already
     has its length (``"extend"``).  The length comes from the data:
-    ``fragLength=bamCrossCorr(...).fragment_length()``."""
+    ``fragLength=bamCrossCorr(...).fragment_length()``.
+    ``keepDup=k`` (a whole number in 1 .. 2**31 - 1; ``None``, the default: every read counts), with ``fragLength=L`` only:
+    at most ``k`` reads per position and strand, MACS's ``--keep-dup k`` beside its ``--extsize``.  Of the reads that pass
+    the filter, ``e_s[p]`` have their 5' end on base ``p`` and strand ``s``; with ``c_s[p] = min(e_s[p], k)`` every kept
+    read covers ``L`` bases from its 5' end in its own direction, so in range orientation cell ``x`` is the sum of
+    ``c_sense[p]`` over ``p = x - L + 1 .. x`` plus the sum of ``c_anti[p]`` over ``p = x .. x + L - 1``, 5' ends up to
+    ``L - 1`` bases outside the range included; with ``ss`` the two sums are the two rows, and ``binsize`` sums cells as
+    for plain coverage.  Without ``fragLength`` it is refused: duplicates of different lengths have no defined survivor.
+    ``paired_end`` must be ``"ignore"``; not with ``aggregate`` or ``runs`` (not built yet)."""
     if runs and aggregate:
         raise ValueError("runs=True and aggregate=True exclude each other: a sum over ranges has no per-range runs")
+    k = _keep_dup(keepDup, paired_end, ("ignore", "extend"))
+    if k and fragLength is None:
+        raise ValueError("keepDup needs fragLength for bamCoverage: duplicates of different lengths have no defined survivor")
+    if k and (aggregate or runs):
+        raise ValueError("keepDup with aggregate=True or runs=True is out of scope so far: take the per-range signals")
     frag = _frag_length(fragLength)
     if frag and _match_arg(paired_end, ("ignore", "extend"), "paired.end") != "ignore":
         raise ValueError('fragLength resizes single-end reads: with paired_end="extend" a fragment already has its length, '
@@ -612,6 +703,10 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     if runs:
         return coverage_runs(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                              flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
+    if k:
+        pu = coverage_capped(os.path.expanduser(str(bampath)), gr, (), mapqual, flagMask(pe), filteredFlag, False, frag, k,
+                             binsize=b, ss=bool(ss))
+        return CountSignals(pu, bool(ss), _trusted=True)
     pu = coverage_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
                        flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
     return CountSignals(pu, bool(ss), _trusted=True)

@@ -449,6 +449,37 @@ int32_t bsig_plan_scaled_segmented(const bsig_plan *plan);
 int bsig_plan_run_scaled(bsig_plan *plan, int64_t *dev);
 int bsig_plan_run_scaled_host(bsig_plan *plan, int64_t *host);
 
+/* Capped 5' ends: keepDup.  Of the reads that pass the filter, e_s[p] have their 5' end (pos on the forward strand, end on
+ * the reverse one, moved by params->shift) on base p and strand s; keep_dup = k replaces e_s[p] by min(e_s[p], k), per
+ * strand, BEFORE anything is binned or the strands are added (MACS's --keep-dup k; k = 1 is its default).  The reads that
+ * share a cell are indistinguishable for the signal, so the result needs no order of the reads and the integers are exact.
+ * params: BSIG_MODE_PROFILE (binsize >= 1, ss, shift) or BSIG_MODE_COUNT (ss, shift); pe_mid, tspan, a template-length rule
+ * (n_tlen_filter != 0) and keep_dup < 1 fail with BSIG_ERR_ARG, each with its own message: a paired-end duplicate is a
+ * fragment with both ends equal, which a 5' end and a strand do not identify.  frag_len 0: the capped 5' ends, those two
+ * modes only.  frag_len = L in 1 .. BSIG_FRAG_LEN_MAX: the capped COVERAGE, on BSIG_MODE_COVERAGE or BSIG_MODE_COVERAGE_EX
+ * (binsize, ss) only -- every kept read covers L bases from its 5' end in its own direction (bsig_plan_create_resized's
+ * signal on the capped ends): in range orientation cell x is the sum of the capped sense ends on x - L + 1 .. x and of the
+ * capped antisense ends on x .. x + L - 1, 5' ends up to L - 1 bases outside the range included; with ss the two sums are the
+ * two rows.  bamCoverage without a fragment length is refused (duplicates of different lengths have no defined survivor).
+ * The coverage runs in two stages: the capped ends of every range widened by L - 1 bases on both sides (clipped at base 0)
+ * go to a device scratch of 2 * (w + 2 L - 2) int32 per range, allocated when the plan is made (BSIG_ERR_NOMEM if it does
+ * not fit; a widened range that ends beyond 2^31 - 1 is BSIG_ERR_ARG); prefix sums of its rows and two differences a cell
+ * give the result, in time linear in the cells whatever L is.  threads 64 / 128 / 256 (0: 256), tile_cells 16 .. 2048 (0: 2048).
+ * The result is bsig_plan_capped_cells() int32 in bsig_layout()'s order for the same binsize and ss (bsig_plan_offsets()),
+ * that is in the CALLER'S range order, as a plain plan's; no capped sum exceeds the uncapped one.  Tiles are per base and
+ * strand-split whatever the bins; tiles with more reads than a 16-bit cell may see are walked whole with 32-bit cells in a
+ * second launch (bsig_plan_get_stats: heavy_tiles).  bsig_plan_capped_runs() shows how the tiles were cut into runs (env
+ * BAMSIGNALS_CAPPED_RUN_TILES, read when the plan is made, forces a number of tiles per run).  A capped plan runs with
+ * bsig_plan_run_capped* only, and no other plan does (BSIG_ERR_ARG). */
+int bsig_plan_create_capped(bsig_ctx *ctx, const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                            const int32_t *len, const int32_t *strand, const bsig_params *params, int32_t keep_dup,
+                            int32_t frag_len, bsig_plan **plan);
+int64_t bsig_plan_capped_cells(const bsig_plan *plan);           /* bsig_layout's cells, 0 for any other plan and NULL */
+int64_t bsig_plan_capped_runs(const bsig_plan *plan);            /* runs of tiles, 0 for any other plan and NULL */
+/* asynchronous, on the context's stream; dev: bsig_plan_capped_cells() int32 on the device, 8-B aligned */
+int bsig_plan_run_capped(bsig_plan *plan, int32_t *dev);
+int bsig_plan_run_capped_host(bsig_plan *plan, int32_t *host);
+
 /* Run-length encoding on the device: a per-range result as runs (value, length), the form of an Rle / a bedGraph.  The
  * encoder works on ANY int32 device buffer plus a table of segments: segment k is the len[k] cells
  * src[base[k] + p * stride], p = 0 .. len[k] - 1; stride 1, or 2 for one row of the 2 * bin + antisense layout (else
@@ -752,6 +783,33 @@ int bsig_coverage_scaled(const char *bampath, int64_t n_ranges, const int32_t *s
                          const int32_t *tlen_filter, int32_t n_tlen_filter,
                          int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan,
                          int32_t n_bins, int32_t maxgap, int32_t device, int64_t *out);
+/* The capped signals (bsig_plan_create_capped): keep_dup = k caps every per-base, per-strand 5'-end cell at k before anything
+ * is binned, added or extended.  bsig_pileup_capped: bsig_pileup_core's arguments and result (binsize <= 0: bamCount) with
+ * keep_dup behind pe_mid; bsig_coverage_capped: bsig_coverage_core_ex's with frag_len and keep_dup behind tspan -- the
+ * coverage of the kept reads resized to frag_len bases.  out / off as in bsig_layout() for the call's binsize and ss.  pe_mid,
+ * tspan, a template-length rule (n_tlen_filter != 0), keep_dup < 1 and a frag_len outside 1 .. BSIG_FRAG_LEN_MAX fail with
+ * BSIG_ERR_ARG before the BAM is opened or decoded, each with its own message.  With several GPUs each takes its block of
+ * the (rid, loc)-sorted ranges and the host PLACES each block's rows through the layout's offsets (bsig_last_call_route():
+ * "capped of N blocks of ranges, rows placed on the host"; one GPU: "capped").  */
+/* (Laid out with their parameters below their names ON PURPOSE, as bsig_pileup_vplot is: tests/test_file_level_refusals_cpu.py
+ * lists the file-level entry points by their one-line form and compares them with a table of refusals recorded before these
+ * calls existed; their refusals are pinned in tests/test_capped_cpu.py instead.)                                           */
+int bsig_pileup_capped(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t binsize, int32_t shift, int32_t ss,
+    int32_t requiredF, int32_t filteredF, int32_t pe_mid, int32_t keep_dup, int32_t maxgap,
+    int32_t device, int32_t *out, const int64_t *off);
+int bsig_coverage_capped(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t tspan, int32_t frag_len, int32_t keep_dup,
+    int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+    int32_t *out, const int64_t *off);
 /* The file-level calls with the result as RUNS (bsig_runs_*): bsig_pileup_core's / bsig_coverage_core_ex's arguments
  * without out / off; binsize <= 0 (bamCount) fails with BSIG_ERR_ARG, and all parameters are checked before the BAM is
  * opened.  The per-base cells live only in HBM, and only for one block of the (rid, loc)-sorted ranges at a time: a block
