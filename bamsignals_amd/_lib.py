@@ -104,6 +104,12 @@ def load():
     lib.bsig_host_free.restype = None
     lib.bsig_reads_upload.argtypes = [C.c_void_p, C.POINTER(Columns), C.POINTER(C.c_void_p)]
     lib.bsig_reads_get_info.argtypes = [C.c_void_p, C.POINTER(ReadsInfo)]
+    # spliced reads (rows = aligned blocks): made from CIGAR columns or from a BAM, told apart by bsig_reads_is_spliced
+    # (BSIG_LIB_PATH may name a build from before them, as for bsig_overlap_core below)
+    if hasattr(lib, "bsig_reads_upload_spliced"):
+        lib.bsig_reads_upload_spliced.argtypes = lib.bsig_reads_upload.argtypes
+        lib.bsig_reads_is_spliced.argtypes = [C.c_void_p]
+        lib.bsig_reads_is_spliced.restype = C.c_int32
     lib.bsig_reads_clone.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.bsig_reads_free.argtypes = [C.c_void_p]
     lib.bsig_reads_free.restype = None
@@ -202,6 +208,9 @@ def load():
                                               C.POINTER(C.c_int32)]
     lib.bsig_reads_from_bam_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int32, C.POINTER(C.c_void_p)]
+    if hasattr(lib, "bsig_reads_from_bam_spliced"):
+        lib.bsig_reads_from_bam_spliced.argtypes = lib.bsig_reads_from_bam.argtypes
+        lib.bsig_reads_from_bam_regions_spliced.argtypes = lib.bsig_reads_from_bam_regions.argtypes
     lib.bsig_device_decode_timing.argtypes = [C.POINTER(C.c_double)]
     lib.bsig_device_decode_timing.restype = None
     lib.bsig_bam_n_ref.argtypes = [C.c_void_p]
@@ -258,6 +267,12 @@ def load():
     lib.bsig_pileup_views.argtypes = core_head + [C.c_int32] * 11 + [C.POINTER(C.c_void_p)]
     lib.bsig_coverage_views.argtypes = core_head + [C.c_int32] * 10 + [C.POINTER(C.c_void_p)]
     lib.bsig_coverage_views_resized.argtypes = lib.bsig_coverage_views.argtypes
+    # ... and of spliced reads: the same calls without tspan
+    if hasattr(lib, "bsig_coverage_core_spliced"):
+        lib.bsig_coverage_core_spliced.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p]
+        lib.bsig_coverage_sum_spliced.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
+        lib.bsig_coverage_runs_spliced.argtypes = core_head + [C.c_int32] * 7 + [C.POINTER(C.c_void_p)]
+        lib.bsig_coverage_views_spliced.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
     lib.bsig_views_result_n_seg.argtypes = [C.c_void_p]
     lib.bsig_views_result_n_seg.restype = C.c_int64
     lib.bsig_views_result_n_views.argtypes = [C.c_void_p]

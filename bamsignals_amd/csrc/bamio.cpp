@@ -1880,7 +1880,21 @@ int BamWriter::write(const BamRecord &r)
     std::vector<uint8_t> b;
     const size_t l_name = r.name.size() + 1;
     if (l_name > 255) return fail(BSIG_ERR_FORMAT, "read name longer than 254 characters");
-    if (r.cigar.size() > 65535) return fail(BSIG_ERR_FORMAT, "more than 65535 CIGAR operations are not supported by the writer");
+    if (r.cigar.size() > 65535) {
+        // a record's n_cigar_op is 16 bits: the real operations go to a CG:B,I tag behind the placeholder
+        // "<l_seq>S<reference length>N" (SAM spec 4.2.2), which readers -- this library's included -- follow
+        if (r.flag & 0x4) return fail(BSIG_ERR_FORMAT, "more than 65535 CIGAR operations on an unmapped read");
+        BamRecord q = r;
+        const int64_t rlen = cigar_rlen(r.cigar.data(), (int)r.cigar.size(), r.flag);
+        if (r.seq.size() >= (1u << 28) || rlen >= (1ll << 28)) return fail(BSIG_ERR_FORMAT, "record too large");
+        q.cigar = {(uint32_t)r.seq.size() << 4 | 4u, (uint32_t)rlen << 4 | 3u};
+        const uint32_t n_ops = (uint32_t)r.cigar.size();
+        const uint8_t head[4] = {'C', 'G', 'B', 'I'};
+        q.aux.insert(q.aux.end(), head, head + 4);
+        q.aux.insert(q.aux.end(), (const uint8_t *)&n_ops, (const uint8_t *)&n_ops + 4);
+        q.aux.insert(q.aux.end(), (const uint8_t *)r.cigar.data(), (const uint8_t *)(r.cigar.data() + n_ops));
+        return write(q);
+    }
     const size_t l_seq = r.seq.size();
     const size_t bs = 32 + l_name + 4 * r.cigar.size() + (l_seq + 1) / 2 + l_seq + r.aux.size();
     const int64_t endpos = (int64_t)r.pos + cigar_rlen(r.cigar.data(), (int)r.cigar.size(), r.flag);

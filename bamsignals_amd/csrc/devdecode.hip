@@ -44,6 +44,7 @@
 #include "collect.h"
 #include "inflate_lane.h"
 #include "runtime_internal.h"
+#include "splice.h"
 
 using bsig::fail;
 
@@ -278,6 +279,88 @@ __global__ __launch_bounds__(kExtractThreads) void k_bam_extract(
         const int32_t up = __shfl_up(rid, 1);
         const int32_t prev = (threadIdx.x & 63u) ? up : k ? (int32_t)ld32(seg + offs[k - 1] + 4) : seg_prev_rid[s];
         for (int32_t q = prev + 1; q <= rid; ++q) ref_first[q] = index0 + i;     // each q is written once
+    }
+}
+
+// ---- spliced decodes: the gaps of a chunk's records, while its stream is still resident ---------
+// A record's CIGAR as k_bam_extract finds it: behind the read name, or -- for the placeholder of an alignment
+// with more than 65,535 operations -- in the CG:B,I tag.  *c receives where the operations begin.
+__device__ __forceinline__ uint32_t record_cigar(const uint8_t *__restrict__ r, const uint8_t **c)
+{
+    const uint32_t l_name = ld32(r + 12) & 0xFFu, n_cig = ld32(r + 16) & 0xFFFFu;
+    *c = r + 36 + l_name;
+    if (n_cig != 2) return n_cig;
+    const uint32_t c0 = ld32(*c), c1 = ld32(*c + 4);
+    const int32_t l_seq = (int32_t)ld32(r + 20);
+    if ((c0 & 0xFu) == 4u && (int32_t)(c0 >> 4) == l_seq && (c1 & 0xFu) == 3u) {
+        uint32_t cnt = 0;
+        const uint32_t at = find_cg_tag(r, 4u + ld32(r), l_name, (uint32_t)l_seq, &cnt);
+        if (at) { *c = r + at; return cnt; }
+    }
+    return n_cig;
+}
+
+// k_bam_extract's segments and launch shape: per record its number of gaps (splice_walk.h) at the record's place in
+// the chunk, per segment their sum
+__global__ __launch_bounds__(kExtractThreads) void k_bam_gap_count(
+    const uint8_t *__restrict__ stream, const uint64_t *__restrict__ seg_start, const uint16_t *__restrict__ off16,
+    const uint32_t *__restrict__ seg_n, const int64_t *__restrict__ seg_base, uint32_t *__restrict__ read_gaps,
+    uint32_t *__restrict__ seg_gaps)
+{
+    __shared__ uint32_t scratch[kExtractThreads];
+    const int64_t s = blockIdx.x;
+    const uint32_t n = seg_n[s];
+    uint32_t mine = 0;
+    if (n) {
+        const uint8_t *seg = stream + seg_start[s];
+        const uint16_t *offs = off16 + s * kMaxRecPerSeg;
+        const int64_t base = seg_base[s];
+        for (uint32_t k = threadIdx.x; k < n; k += kExtractThreads) {
+            const uint8_t *r = seg + offs[k];
+            const uint8_t *c;
+            const uint32_t n_ops = record_cigar(r, &c);
+            const uint32_t g = bsig::walk_gaps((int32_t)ld32(r + 8), ld32(r + 16) >> 16, n_ops, [&](uint32_t q) { return ld32(c + 4 * q); },
+                                               [](uint32_t, int32_t, int32_t) {});
+            read_gaps[base + k] = g;
+            mine += g;
+        }
+    }
+    uint32_t total;
+    bsig::block_exclusive_scan<kExtractThreads>(mine, scratch, &total);
+    if (threadIdx.x == 0) seg_gaps[s] = total;
+}
+
+// ... and the rows, in record order: the segment's records in rounds of one per thread, each round's gaps behind the
+// round before.  index0: the share-local index of the chunk's first record
+__global__ __launch_bounds__(kExtractThreads) void k_bam_gap_emit(
+    const uint8_t *__restrict__ stream, const uint64_t *__restrict__ seg_start, const uint16_t *__restrict__ off16,
+    const uint32_t *__restrict__ seg_n, const int64_t *__restrict__ seg_base, const uint32_t *__restrict__ read_gaps,
+    const int64_t *__restrict__ seg_gap_base, bsig::GapRow *__restrict__ rows, int64_t n_rows, int64_t index0)
+{
+    __shared__ uint32_t scratch[kExtractThreads];
+    const int64_t s = blockIdx.x;
+    const uint32_t n = seg_n[s];
+    if (n == 0) return;                                   // (the whole workgroup)
+    const uint8_t *seg = stream + seg_start[s];
+    const uint16_t *offs = off16 + s * kMaxRecPerSeg;
+    const int64_t base = seg_base[s];
+    int64_t at = seg_gap_base[s];
+    for (uint32_t k0 = 0; k0 < n; k0 += kExtractThreads) {
+        const uint32_t k = k0 + threadIdx.x;
+        const uint32_t g = k < n ? read_gaps[base + k] : 0u;
+        uint32_t total;
+        const uint32_t before = bsig::block_exclusive_scan<kExtractThreads>(g, scratch, &total);
+        if (g) {
+            const uint8_t *r = seg + offs[k];
+            const uint8_t *c;
+            const uint32_t n_ops = record_cigar(r, &c);
+            const int64_t to = at + before, read = index0 + base + k;
+            bsig::walk_gaps((int32_t)ld32(r + 8), ld32(r + 16) >> 16, n_ops, [&](uint32_t q) { return ld32(c + 4 * q); },
+                            [&](uint32_t j, int32_t a, int32_t b) {
+                                if (j < g && to + j < n_rows) rows[to + j] = bsig::GapRow{read, a, b};
+                            });
+        }
+        at += total;
     }
 }
 
@@ -1186,7 +1269,7 @@ struct Reservation {
 // in *out or an error; t_gpu_join receives the time before the layout, t_layout the layout's.
 int finish_reads(bsig_ctx *ctx, hipStream_t st, ScratchPool &tmp, std::vector<std::unique_ptr<Piece>> &pieces, int64_t n_reads,
                  const BamHeader &hdr, const long long *d_ref_first, double &t_gpu_join, double &t_layout, bsig_reads **out,
-                 Reservation *reserved)
+                 Reservation *reserved, const std::vector<GapTable> *gaps = nullptr)
 {
     const double t_join = now_s();
     const int32_t n_ref = (int32_t)hdr.names.size();
@@ -1196,6 +1279,7 @@ int finish_reads(bsig_ctx *ctx, hipStream_t st, ScratchPool &tmp, std::vector<st
     std::vector<int64_t> ref_off((size_t)n_ref + 1, n_reads);
     auto bail = [&](int code) { (void)hipStreamSynchronize(st); delete R; return code; };
     if (n_reads == 0 || n_ref == 0) {
+        R->spliced = gaps != nullptr;
         const int rc = layout_from_device(ctx, R, 0, n_ref, hdr.lens.data(), ref_off.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
         if (rc) return bail(rc);
         *out = R;
@@ -1240,8 +1324,31 @@ int finish_reads(bsig_ctx *ctx, hipStream_t st, ScratchPool &tmp, std::vector<st
     t_gpu_join = now_s() - t_join;
     diag_mark("join of the column pieces");
     const double t_lay = now_s();
-    const int rc = layout_from_device(ctx, R, n_reads, n_ref, hdr.lens.data(), ref_off.data(), cols->pos, cols->end, cols->flag,
-                                      cols->mapq, cols->tlen);
+    int rc;
+    if (gaps) {
+        // a spliced decode: the chunks' gap pieces joined (their reads are numbered from the decode's first read already),
+        // then the split stage in front of the layout (splice.hip)
+        GapTable all;
+        if (gaps->size() == 1) all = (*gaps)[0];
+        else if (gaps->size() > 1) {
+            for (const GapTable &g : *gaps) all.n += g.n;
+            GapRow *d_rows = nullptr;
+            e = tmp.alloc(&d_rows, (size_t)all.n);
+            int64_t at = 0;
+            for (const GapTable &g : *gaps) {
+                if (e == hipSuccess) e = hipMemcpyAsync(d_rows + at, g.rows, (size_t)g.n * sizeof(GapRow), hipMemcpyDeviceToDevice, st);
+                at += g.n;
+            }
+            if (e != hipSuccess)
+                return bail(fail(e == hipErrorOutOfMemory ? BSIG_ERR_NOMEM : BSIG_ERR_DEVICE, "joining the gap pieces failed: %s", hipGetErrorString(e)));
+            all.rows = d_rows;
+        }
+        rc = spliced_layout(ctx, R, n_reads, n_ref, hdr.lens.data(), ref_off.data(), cols->pos, cols->end, cols->flag, cols->mapq,
+                            cols->tlen, all);
+    } else {
+        rc = layout_from_device(ctx, R, n_reads, n_ref, hdr.lens.data(), ref_off.data(), cols->pos, cols->end, cols->flag,
+                                cols->mapq, cols->tlen);
+    }
     if (rc) return bail(rc);
     t_layout = now_s() - t_lay;
     diag_mark("resident layout");
@@ -1275,8 +1382,50 @@ struct ShareOut {
     uint64_t chain_first = 0, chain_end = 0;          // absolute offsets in the uncompressed stream
     int32_t first_rid = -1, first_pos = -1, last_rid = -1, last_pos = -1;
     double t_inflate = 0, t_wait = 0, t_gpu = 0;
+    // a spliced decode (set by the caller): every chunk also leaves the gaps of its records, one piece of the gap table
+    // each, the reads numbered share-locally
+    bool want_gaps = false;
+    std::vector<GapTable> gaps;
 };
 constexpr size_t kOverlapBlocks = 4;
+
+// The gap piece of one chunk, launched right behind its k_bam_extract with the same segment arguments while the chunk's
+// stream is still resident: count per record and segment, scan on the device, ONE host read to size the piece, emit.
+hipError_t chunk_gaps(ScratchPool &tmp, hipStream_t st, const uint8_t *d_stream, const uint64_t *d_seg_start, const uint16_t *d_off16,
+                      const uint32_t *d_seg_n, const int64_t *d_seg_base, int64_t n_seg, int64_t n_chunk, int64_t index0, ShareOut &R)
+{
+    uint32_t *d_read_gaps = nullptr, *d_seg_gaps = nullptr;
+    int64_t *d_seg_gap_base = nullptr, *d_total = nullptr;
+    hipError_t e = tmp.alloc(&d_read_gaps, (size_t)n_chunk);
+    if (e == hipSuccess) e = tmp.alloc(&d_seg_gaps, (size_t)n_seg);
+    if (e == hipSuccess) e = tmp.alloc(&d_seg_gap_base, (size_t)n_seg);
+    if (e == hipSuccess) e = tmp.alloc(&d_total, 1);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bam_gap_count, dim3((unsigned)n_seg), dim3(kExtractThreads), 0, st, d_stream, d_seg_start, d_off16, d_seg_n,
+                       d_seg_base, d_read_gaps, d_seg_gaps);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = launch_gap_scan(n_seg, d_seg_gaps, d_seg_gap_base, d_total, st);
+    int64_t total = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && total > 0) {
+        GapRow *d_rows = nullptr;
+        e = tmp.alloc(&d_rows, (size_t)total);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_bam_gap_emit, dim3((unsigned)n_seg), dim3(kExtractThreads), 0, st, d_stream, d_seg_start, d_off16, d_seg_n,
+                           d_seg_base, d_read_gaps, d_seg_gap_base, d_rows, total, index0);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);      // (the counts go back below)
+        GapTable piece;
+        piece.rows = d_rows;
+        piece.n = total;
+        R.gaps.push_back(piece);
+    }
+    tmp.give_back(d_read_gaps);
+    tmp.give_back(d_seg_gaps);
+    tmp.give_back(d_seg_gap_base);
+    return e;
+}
 
 // Returns BSIG_OK, kNeedsCpuPath (this file / this split cannot be proven on the device), or an error.
 // more_follow: f.blocks() is only the head of the file's table (BgzfFile::open_progressive): the share cannot be
@@ -1741,6 +1890,7 @@ int decode_share(bsig_ctx *ctx, const BgzfFile &f, const BamHeader &hdr, const s
             hipLaunchKernelGGL(k_bam_extract, dim3((unsigned)n_seg), dim3(kExtractThreads), 0, st, d_stream, d_seg_start, d_off16,
                                d_seg_n, d_seg_base, d_seg_prev, pc.pos, pc.flag, pc.mapq, pc.tlen, pc.end, R.d_ref_first, R.n_reads);
             DD_TRY(hipGetLastError());
+            if (R.want_gaps) DD_TRY(chunk_gaps(tmp, st, d_stream, d_seg_start, d_off16, d_seg_n, d_seg_base, n_seg, n_chunk, R.n_reads, R));
             R.n_reads += n_chunk;
         }
         // the cut-off record moves in front of the next chunk (source and destination do not overlap:
@@ -2084,14 +2234,16 @@ int reads_from_bam_streamed(bsig_ctx *ctx, const std::string &path, int threads,
 // the rest of the table is built by the host (327,000 small reads for the north star's file: 0.04-0.06 s that
 // the call used to spend before its first launch).  The two shares are then joined like the shares of several
 // GPUs: the chains must meet, the reads must stay in order.
-int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, bsig_reads **out)
+// spliced: the reads split at their N gaps (splice.hip).  Such a decode takes neither the streamed form nor the two-step
+// scan nor the reservation: one share, chunk by chunk, every chunk leaving its gap piece.
+int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, bsig_reads **out, bool spliced = false)
 {
     double *T = g_dev_decode_timing;
     for (int k = 0; k < 6; ++k) T[k] = 0;
     const double t_begin = now_s();
     *out = nullptr;
     diag_mark(nullptr);
-    {
+    if (!spliced) {
         // large files: the file streamed into HBM once, decoded round by round behind the stream
         bool taken = false;
         const int rs = reads_from_bam_streamed(ctx, path, threads, out, taken, T);
@@ -2112,6 +2264,7 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
     diag_mark("map + block table (head)");
     T[0] = now_s() - t_begin;
     ShareOut S, S2;
+    S.want_gaps = spliced;
     bool two = false;
     // the resident columns are reserved while the file is still being inflated (Reservation above): the first pass
     // says how many reads a byte of stream holds; 8 bytes per read (a packed word and the template length) plus the
@@ -2141,7 +2294,7 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
         const double est_blocks = (double)hb.size() * (double)F.f.size() / (double)std::max<uint64_t>(seen, 1);
         double min_blocks = 150000.0;
         if (const char *e = getenv("BAMSIGNALS_TWO_STEP_MIN_BLOCKS")) min_blocks = atof(e);
-        if (F.gpu_inflate && hb.size() > 4 * kOverlapBlocks && est_blocks >= min_blocks) {
+        if (!spliced && F.gpu_inflate && hb.size() > 4 * kOverlapBlocks && est_blocks >= min_blocks) {
             // the head share ends kOverlapBlocks before the end of what is tabulated: its last record may run on
             // ... and holds whole rounds of inflate lanes (the blocks behind them go with the rest)
             size_t Bh = F.f.blocks().size() - kOverlapBlocks;
@@ -2170,7 +2323,7 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
         }
     }
     if (!two) {
-        rc = decode_share(ctx, F.f, F.hdr, F.uoff, 0, F.f.blocks().size(), threads, F.gpu_inflate, S, false, false, &reserve);
+        rc = decode_share(ctx, F.f, F.hdr, F.uoff, 0, F.f.blocks().size(), threads, F.gpu_inflate, S, false, false, spliced ? nullptr : &reserve);
         if (rc) return rc;
     }
     diag_mark("decode_share (all passes)");
@@ -2196,7 +2349,8 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
         for (auto &pp : S2.pieces) pieces.push_back(std::move(pp));
         rc = finish_reads(ctx, ctx->stream, *S2.tmp, pieces, S.n_reads + S2.n_reads, F.hdr, S2.d_ref_first, t_join, t_layout, out, &reserved);
     } else {
-        rc = finish_reads(ctx, ctx->stream, *S.tmp, S.pieces, S.n_reads, F.hdr, S.d_ref_first, t_join, t_layout, out, &reserved);
+        rc = finish_reads(ctx, ctx->stream, *S.tmp, S.pieces, S.n_reads, F.hdr, S.d_ref_first, t_join, t_layout, out, &reserved,
+                          spliced ? &S.gaps : nullptr);
     }
     g_reserve_wait = reserved.t_wait;
     if (rc) return rc;
@@ -2728,6 +2882,7 @@ int decode_islands(bsig_ctx *ctx, const BgzfFile &f, const BamHeader &hdr, const
             hipLaunchKernelGGL(k_bam_extract, dim3((unsigned)n_seg), dim3(kExtractThreads), 0, st, d_view, d_seg_start, d_off16,
                                d_seg_n, d_seg_base, d_seg_prev, pc.pos, pc.flag, pc.mapq, pc.tlen, pc.end, d_ref_first, n_reads);
             DR_TRY(hipGetLastError());
+            if (R.want_gaps) DR_TRY(chunk_gaps(tmp, st, d_view, d_seg_start, d_off16, d_seg_n, d_seg_base, n_seg, n_chunk, n_reads, R));
             n_reads += n_chunk;
         }
         DR_TRY(hipStreamSynchronize(st));
@@ -2759,7 +2914,7 @@ bool islands_gpu_inflate(const std::vector<Island> &isl, int threads)
 // for.  A superset of the overlapping records, each at most once, in file order -- exactly what the CPU
 // region decode (bamio.cpp: bam_decode_regions) returns.
 int reads_from_regions_device(bsig_ctx *ctx, const std::string &path, const BaiIndex &idx,
-                              const std::vector<Region> &regions, int threads, bsig_reads **out)
+                              const std::vector<Region> &regions, int threads, bsig_reads **out, bool spliced = false)
 {
     double *T = g_dev_decode_timing;
     for (int k = 0; k < 6; ++k) T[k] = 0;
@@ -2775,6 +2930,7 @@ int reads_from_regions_device(bsig_ctx *ctx, const std::string &path, const BaiI
     if (rc) return rc;
     T[0] = now_s() - t_begin;
     ShareOut S;
+    S.want_gaps = spliced;
     rc = decode_islands(ctx, f, hdr, isl, 0, isl.size(), threads, islands_gpu_inflate(isl, threads), S);
     if (rc) return rc;
     T[1] = S.t_inflate;
@@ -2783,7 +2939,8 @@ int reads_from_regions_device(bsig_ctx *ctx, const std::string &path, const BaiI
     if (!S.tmp) S.tmp.reset(new ScratchPool(ctx->device, ctx->stream));
     // ---- join the pieces, first read of every reference, resident layout ---------------------------
     double t_join = 0, t_layout = 0;
-    rc = finish_reads(ctx, ctx->stream, *S.tmp, S.pieces, S.n_reads, hdr, S.d_ref_first, t_join, t_layout, out, nullptr);
+    rc = finish_reads(ctx, ctx->stream, *S.tmp, S.pieces, S.n_reads, hdr, S.d_ref_first, t_join, t_layout, out, nullptr,
+                      spliced ? &S.gaps : nullptr);
     if (rc) return rc;
     T[3] = S.t_gpu + t_join;
     T[5] = t_layout;
@@ -2874,14 +3031,13 @@ hipError_t warm_decode_module(hipStream_t st)
 
 extern "C" {
 
-int bsig_reads_from_bam(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads)
+static int reads_from_bam_impl(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads, bool spliced)
 {
-    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam");
     *reads = nullptr;
     const char *path = bsig_bam_path(bam);
     const char *mode = getenv("BAMSIGNALS_DEVICE_DECODE");        // "0": always the CPU decode
     int rc = bsig::kNeedsCpuPath;
-    if (!(mode && !strcmp(mode, "0"))) rc = bsig::reads_from_bam_device(ctx, path, threads, reads);
+    if (!(mode && !strcmp(mode, "0"))) rc = bsig::reads_from_bam_device(ctx, path, threads, reads, spliced);
     if (rc != bsig::kNeedsCpuPath) return rc;
     if (mode && !strcmp(mode, "require"))                          // testing: no silent change of path
         return fail(BSIG_ERR_FORMAT, "%s needs the CPU decode path (BAMSIGNALS_DEVICE_DECODE=require)", path);
@@ -2889,7 +3045,20 @@ int bsig_reads_from_bam(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_read
     rc = bsig_bam_decode(bam, -1, nullptr, nullptr, nullptr, threads, &cols);
     if (rc) return rc;
     for (int k = 0; k < 6; ++k) g_dev_decode_timing[k] = 0;
-    return bsig_reads_upload(ctx, &cols, reads);
+    // (the CPU decode's columns hold the CIGARs: the gap table comes from them)
+    return spliced ? bsig_reads_upload_spliced(ctx, &cols, reads) : bsig_reads_upload(ctx, &cols, reads);
+}
+
+int bsig_reads_from_bam(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads)
+{
+    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam");
+    return reads_from_bam_impl(ctx, bam, threads, reads, false);
+}
+
+int bsig_reads_from_bam_spliced(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads)
+{
+    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_spliced");
+    return reads_from_bam_impl(ctx, bam, threads, reads, true);
 }
 
 int bsig_reads_from_bam_multi(bsig_ctx *const *ctxs, int32_t n, bsig_bam *bam, int32_t threads, bsig_reads **reads,
@@ -2925,10 +3094,10 @@ int bsig_reads_from_bam_multi(bsig_ctx *const *ctxs, int32_t n, bsig_bam *bam, i
     return rc;
 }
 
-int bsig_reads_from_bam_regions(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
-                                const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads)
+static int reads_from_regions_impl(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
+                                   const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads, bool spliced)
 {
-    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_regions");
+    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_regions%s", spliced ? "_spliced" : "");
     if (n_regions < 0 || (n_regions > 0 && (!rid || !beg || !end))) return fail(BSIG_ERR_ARG, "region arrays missing");
     *reads = nullptr;
     const char *mode = getenv("BAMSIGNALS_DEVICE_DECODE");
@@ -2936,7 +3105,7 @@ int bsig_reads_from_bam_regions(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions,
     if (!(mode && !strcmp(mode, "0"))) {
         std::vector<bsig::Region> rg((size_t)n_regions);
         for (int64_t i = 0; i < n_regions; ++i) rg[(size_t)i] = bsig::Region{rid[i], beg[i], end[i]};
-        rc = bsig::reads_from_regions_device(ctx, bsig_bam_path(bam), *bsig_bam_index(bam), rg, threads, reads);
+        rc = bsig::reads_from_regions_device(ctx, bsig_bam_path(bam), *bsig_bam_index(bam), rg, threads, reads, spliced);
     }
     if (rc != bsig::kNeedsCpuPath) return rc;
     if (mode && !strcmp(mode, "require"))
@@ -2945,7 +3114,19 @@ int bsig_reads_from_bam_regions(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions,
     rc = bsig_bam_decode(bam, n_regions, rid, beg, end, threads, &cols);
     if (rc) return rc;
     for (int k = 0; k < 6; ++k) g_dev_decode_timing[k] = 0;
-    return bsig_reads_upload(ctx, &cols, reads);
+    return spliced ? bsig_reads_upload_spliced(ctx, &cols, reads) : bsig_reads_upload(ctx, &cols, reads);
+}
+
+int bsig_reads_from_bam_regions(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
+                                const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads)
+{
+    return reads_from_regions_impl(ctx, bam, n_regions, rid, beg, end, threads, reads, false);
+}
+
+int bsig_reads_from_bam_regions_spliced(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
+                                        const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads)
+{
+    return reads_from_regions_impl(ctx, bam, n_regions, rid, beg, end, threads, reads, true);
 }
 
 // (debug, host only -- no GPU is touched: the block table as RawStream's header walk builds it, the file fed in chunks

@@ -249,6 +249,17 @@ FileCall resized_call(const bsig::RangeArgs &at, const bsig_params &p, int32_t d
     c.rule_first = rule_first;
     return c;
 }
+// bamCoverage(splice = TRUE): the binned, stranded coverage calls without tspan, on the file's spliced reads -- the same
+// dispatcher, the same routes; the dispatcher judges the flag -- with rule_first the rest of the parameters as well -- before
+// it opens the BAM, as for the resized calls.
+FileCall spliced_call(const bsig::RangeArgs &at, const bsig_params &p, int32_t device, const FileDest &to, bool rule_first)
+{
+    FileCall c{at, p, device, to};
+    c.spliced = true;
+    c.rule_first = rule_first;
+    return c;
+}
+
 // A call whose result is a host-side handle (runs, views): made here, filled by the dispatcher through the encoder `enc`,
 // and the caller's only if the call succeeds.
 template <typename Result>
@@ -592,6 +603,53 @@ int bsig_coverage_views_resized(const char *bampath, int64_t n, const int32_t *s
     return encoded_call(resized_call({bampath, n, seq_code, n_levels, levels, start, width, strand},
                                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss), device,
                                      {}, frag_len, false),
+                        bsig::views_encoder(lower, upper), result);
+}
+
+int bsig_coverage_core_spliced(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                               const char *const *levels, const int32_t *start, const int32_t *width,
+                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t *out, const int64_t *off)
+{
+    return file_level(spliced_call({bampath, n, seq_code, n_levels, levels, start, width, strand},
+                                   coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss), device,
+                                   FileDest::flat(out, off), true));
+}
+
+int bsig_coverage_sum_spliced(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                              const char *const *levels, const int32_t *start, const int32_t *width,
+                              const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                              int32_t mapqual, int32_t requiredF, int32_t filteredF,
+                              int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum)
+{
+    return file_level(spliced_call({bampath, n, seq_code, n_levels, levels, start, width, strand},
+                                   coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss), device,
+                                   sum_dest(sum), true));
+}
+
+int bsig_coverage_runs_spliced(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                               const char *const *levels, const int32_t *start, const int32_t *width,
+                               const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                               int32_t mapqual, int32_t requiredF, int32_t filteredF,
+                               int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result)
+{
+    return encoded_call(spliced_call({bampath, n, seq_code, n_levels, levels, start, width, strand},
+                                     coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss), device,
+                                     {}, false),
+                        bsig::runs_encoder(), result);
+}
+
+int bsig_coverage_views_spliced(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                                const char *const *levels, const int32_t *start, const int32_t *width,
+                                const int32_t *strand, const int32_t *tlen_filter, int32_t n_tlen_filter,
+                                int32_t mapqual, int32_t requiredF, int32_t filteredF,
+                                int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int32_t lower, int32_t upper,
+                                bsig_views_result **result)
+{
+    return encoded_call(spliced_call({bampath, n, seq_code, n_levels, levels, start, width, strand},
+                                     coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss), device,
+                                     {}, false),
                         bsig::views_encoder(lower, upper), result);
 }
 

@@ -874,6 +874,15 @@ int judge_call(const FileCall &c, Stage &s)
         return fail(BSIG_ERR_ARG, "lower (%d) is above upper (%d)", (int)to.enc.lower, (int)to.enc.upper);
     if (c.overlap && c.overlap_type != 0 && c.overlap_type != 1) return fail(BSIG_ERR_ARG, "overlap type must be 0 (any) or 1 (within)");
     if (c.filter_missing) return fail(BSIG_ERR_ARG, "tlen_filter missing");
+    if (c.spliced) {
+        // what bsig_plan_create would refuse on spliced reads, before any I/O: only the coverage of the blocks as they lie
+        if (c.prm.mode != BSIG_MODE_COVERAGE && c.prm.mode != BSIG_MODE_COVERAGE_EX)
+            return fail(BSIG_ERR_ARG, "spliced reads give coverage only: a block's start is not a read's 5' end");
+        if (c.prm.tspan) return fail(BSIG_ERR_ARG, "spliced reads: tspan would extend every block of a read to the whole fragment");
+        if (c.resized || c.frag_len) return fail(BSIG_ERR_ARG, "spliced reads: frag_len would resize every block of a read, not the read");
+        if (to.kind != Reduce::none && to.kind != Reduce::sum)
+            return fail(BSIG_ERR_ARG, "spliced reads: only the per-range coverage, its sum, its runs and its views are built");
+    }
     PlanRule early;
     int rc = c.resized ? resized_rule(c.prm, c.frag_len) : (int)BSIG_OK;
     if (rc == BSIG_OK && c.rule_first) rc = check_params(c.prm, at.n > 0 && at.width ? at.n : 0, at.width, &early, c.frag_len);
@@ -1012,6 +1021,7 @@ int slots_for(const std::vector<int> &devs, Stage &s)
 {
     s.rkey = s.bkey + "@";
     for (int d : devs) s.rkey += std::to_string(d) + ",";
+    if (s.call.spliced) s.rkey += "|spliced";      // (a file's plain and spliced reads are two resident sets)
     s.many = devs.size() > 1 || env_is("BAMSIGNALS_FORCE_SHARDED", "1");     // (=1: the multi-GPU route on one GPU, testing)
     std::lock_guard<std::mutex> lock(g_cache.mu);
     for (auto &sp : g_cache.slot_sets)
@@ -1068,12 +1078,13 @@ bool lookup_reads(Stage &s, const Wanted &w)
     if (s.key.empty()) return false;
     std::lock_guard<std::mutex> lock(g_cache.mu);
     s.res = Cache::touch(g_cache.resident, s.rkey);
-    s.how_decoded = "resident";
+    s.how_decoded = s.call.spliced ? "spliced, resident" : "resident";
     if (!s.res && !w.whole) {
         s.res = Cache::touch(g_cache.regional, s.rkey, [&](const Resident &R) {
             return regions_covered(R.cov, s.call.at.n, s.rid.data(), w.qbeg.data(), w.qend.data());
         });
-        s.how_decoded = "resident (index-driven decode of an earlier call)";
+        s.how_decoded = s.call.spliced ? "spliced, resident (index-driven decode of an earlier call)"
+                                       : "resident (index-driven decode of an earlier call)";
     }
     if (s.res) s.T[5] = 1;
     return s.res != nullptr;
@@ -1117,7 +1128,8 @@ int decode_whole(Stage &s, Sidecar &side, double *t6)
     const char *bampath = s.call.at.bampath;
     Resident &R = *s.res;
     const std::vector<bsig_ctx *> &ctx = s.slots->ctx;
-    const std::string path = s.key.empty() ? std::string() : sidecar_path(bampath);
+    // (spliced reads have no reads file: none is loaded, none is written)
+    const std::string path = s.key.empty() || s.call.spliced ? std::string() : sidecar_path(bampath);
     // (the reads file is tied to the CONTENT it was made from -- size and mtime of the BAM and of its
     // index files -- not to the spelling of the path it was reached by)
     side.stamp = file_stamp(bampath) + "#" + index_stamps(bampath);
@@ -1131,11 +1143,17 @@ int decode_whole(Stage &s, Sidecar &side, double *t6)
         R.free_reads();
     }
     const char *transport = nullptr;
+    const bool spliced = s.call.spliced;
+    // (a spliced set is decoded on the first GPU and cloned: the sharded route declines it)
     const int rc = decode_to_slots(s, t6, &transport,
-                                   [&](const char **over) { return reads_from_bam_sharded(ctx, bampath, 0, R.reads, over); },
-                                   [&] { return bsig_reads_from_bam(ctx[0], s.ob->bam, 0, &R.reads[0]); });
+                                   [&](const char **over) { return spliced ? (int)kNeedsCpuPath : reads_from_bam_sharded(ctx, bampath, 0, R.reads, over); },
+                                   [&] {
+                                       return spliced ? bsig_reads_from_bam_spliced(ctx[0], s.ob->bam, 0, &R.reads[0])
+                                                      : bsig_reads_from_bam(ctx[0], s.ob->bam, 0, &R.reads[0]);
+                                   });
     s.how_decoded = transport ? std::string("sharded decode, columns over ") + transport
                               : ctx.size() > 1 ? "decode on the first GPU + clones" : "decode";
+    if (spliced) s.how_decoded = "spliced " + s.how_decoded;
     if (rc == BSIG_OK) side.to_write = path;          // written after the decode lock is released (best effort)
     return rc;
 }
@@ -1150,13 +1168,21 @@ int decode_regions(Stage &s, const Wanted &w, double *t6)
     int rc = bam_index_wait(bam);                 // (parsed in the background since the open)
     if (rc) return rc;
     const char *transport = nullptr;
+    const bool spliced = s.call.spliced;
     rc = decode_to_slots(s, t6, &transport,
                          [&](const char **over) {
+                             if (spliced) return (int)kNeedsCpuPath;
                              return reads_from_regions_sharded(s.slots->ctx, s.call.at.bampath, *bsig_bam_index(bam), n, s.rid.data(),
                                                                w.qbeg.data(), w.qend.data(), 0, R.reads, over);
                          },
-                         [&] { return bsig_reads_from_bam_regions(s.slots->ctx[0], bam, n, s.rid.data(), w.qbeg.data(), w.qend.data(), 0, &R.reads[0]); });
+                         [&] {
+                             return spliced ? bsig_reads_from_bam_regions_spliced(s.slots->ctx[0], bam, n, s.rid.data(), w.qbeg.data(),
+                                                                                 w.qend.data(), 0, &R.reads[0])
+                                            : bsig_reads_from_bam_regions(s.slots->ctx[0], bam, n, s.rid.data(), w.qbeg.data(), w.qend.data(), 0,
+                                                                          &R.reads[0]);
+                         });
     s.how_decoded = transport ? std::string("index-driven decode, sharded, columns over ") + transport : "index-driven decode";
+    if (spliced) s.how_decoded = "spliced " + s.how_decoded;
     if (rc == BSIG_OK) set_coverage(R.cov, n, s.rid.data(), w.qbeg.data(), w.qend.data());
     return rc;
 }

@@ -107,6 +107,7 @@ struct FileCall {
     bool overlap = false;           // bamOverlaps: its type as given, and whether a tlen_filter was promised but not passed
     int32_t overlap_type = 0;
     bool filter_missing = false;
+    bool spliced = false;           // coverage that skips N gaps: the call runs on the file's spliced reads (splice.hip)
 };
 int file_level(const FileCall &call);
 

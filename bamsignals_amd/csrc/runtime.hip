@@ -767,6 +767,25 @@ int bsig::layout_from_device(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_
     return make_packed_half(R, st);
 }
 
+int bsig::check_columns(const bsig_columns *cols)
+{
+    const int64_t n = cols->n_reads;
+    if (n < 0 || cols->n_ref < 0) return fail(BSIG_ERR_ARG, "negative read or reference count");
+    if (cols->n_ref > 0 && (!cols->ref_len || !cols->ref_off)) return fail(BSIG_ERR_ARG, "ref_len/ref_off missing");
+    if (n > 0) {
+        if (!cols->pos || !cols->flag || !cols->mapq || !cols->tlen) return fail(BSIG_ERR_ARG, "read columns missing");
+        if (!cols->end && (!cols->cigar_off || !cols->cigar)) return fail(BSIG_ERR_ARG, "need either end or cigar_off+cigar");
+        if (cols->n_ref == 0) return fail(BSIG_ERR_ARG, "reads without references");
+    }
+    if (cols->n_ref > 0) {
+        if (cols->ref_off[0] != 0 || cols->ref_off[cols->n_ref] != n)
+            return fail(BSIG_ERR_ARG, "ref_off must run from 0 to n_reads");
+        for (int r = 0; r < cols->n_ref; ++r)
+            if (cols->ref_off[r] > cols->ref_off[r + 1]) return fail(BSIG_ERR_ARG, "ref_off must be non-decreasing");
+    }
+    return BSIG_OK;
+}
+
 extern "C" {
 
 static int upload_impl(bsig_ctx *ctx, const bsig_columns *cols, bsig_reads *R)
@@ -814,20 +833,7 @@ int bsig_reads_upload(bsig_ctx *ctx, const bsig_columns *cols, bsig_reads **out)
 {
     if (!ctx || !cols || !out) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_upload");
     *out = nullptr;
-    const int64_t n = cols->n_reads;
-    if (n < 0 || cols->n_ref < 0) return fail(BSIG_ERR_ARG, "negative read or reference count");
-    if (cols->n_ref > 0 && (!cols->ref_len || !cols->ref_off)) return fail(BSIG_ERR_ARG, "ref_len/ref_off missing");
-    if (n > 0) {
-        if (!cols->pos || !cols->flag || !cols->mapq || !cols->tlen) return fail(BSIG_ERR_ARG, "read columns missing");
-        if (!cols->end && (!cols->cigar_off || !cols->cigar)) return fail(BSIG_ERR_ARG, "need either end or cigar_off+cigar");
-        if (cols->n_ref == 0) return fail(BSIG_ERR_ARG, "reads without references");
-    }
-    if (cols->n_ref > 0) {
-        if (cols->ref_off[0] != 0 || cols->ref_off[cols->n_ref] != n)
-            return fail(BSIG_ERR_ARG, "ref_off must run from 0 to n_reads");
-        for (int r = 0; r < cols->n_ref; ++r)
-            if (cols->ref_off[r] > cols->ref_off[r + 1]) return fail(BSIG_ERR_ARG, "ref_off must be non-decreasing");
-    }
+    if (const int rc = bsig::check_columns(cols)) return rc;
     bsig_reads *R = new bsig_reads;
     R->ctx = ctx;
     const int rc = upload_impl(ctx, cols, R);
@@ -863,6 +869,7 @@ int bsig_reads_clone(const bsig_reads *src, bsig_ctx *dst_ctx, bsig_reads **out)
     bsig_reads *R = new bsig_reads;
     R->ctx = dst_ctx;
     R->info = src->info;
+    R->spliced = src->spliced;
     R->n_ref = src->n_ref;
     R->ref_unit0 = src->ref_unit0;
     R->ref_units = src->ref_units;
@@ -1214,6 +1221,9 @@ int layout_checksum(const bsig_reads *R, uint64_t *out)
 int bsig_reads_save(const bsig_reads *reads, const char *path, const char *stamp)
 {
     if (!reads || !path || !stamp) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_save");
+    if (reads->spliced)
+        return fail(BSIG_ERR_ARG, "spliced reads have no reads file: the format has no mark for rows that are aligned blocks, and a "
+                                  "loader would take them for reads");
     HIP_TRY(hipSetDevice(reads->ctx->device));
     SidecarHeader H;
     memset(&H, 0, sizeof H);
@@ -1861,6 +1871,26 @@ static int upload_failed(hipError_t e)
         if (e_ != hipSuccess) return upload_failed(e_);     \
     } while (0)
 
+// What a spliced set (rows = aligned blocks, splice.hip) may be asked: the coverage of the blocks as they lie.  A block's
+// start is no 5' end, a block is no fragment, and the blocks of one read would each be extended or resized: every other
+// signal would be silently wrong, so its creator refuses, in its own words.
+static int spliced_rule(const bsig_params &prm, const PlanRequest &rq)
+{
+    const bool coverage = prm.mode == BSIG_MODE_COVERAGE || prm.mode == BSIG_MODE_COVERAGE_EX;
+    switch (rq.kind) {
+    case kCapped: return fail(BSIG_ERR_ARG, "spliced reads: keep_dup caps reads by their 5' end, and a block's start is not one");
+    case kXcorr: return fail(BSIG_ERR_ARG, "spliced reads: the strand cross-correlation is of 5' ends, and a block's start is not one");
+    case kFrag: return fail(BSIG_ERR_ARG, "spliced reads: the fragment-length histogram counts reads, not their blocks");
+    case kVplot: return fail(BSIG_ERR_ARG, "spliced reads: the V-plot counts reads, not their blocks");
+    default: break;
+    }
+    if (rq.frag_len) return fail(BSIG_ERR_ARG, "spliced reads: frag_len would resize every block of a read, not the read");
+    if (prm.mode == BSIG_MODE_OVERLAP_ANY || prm.mode == BSIG_MODE_OVERLAP_WITHIN)
+        return fail(BSIG_ERR_ARG, "spliced reads: bamOverlaps would count a read once for each of its blocks");
+    if (!coverage) return fail(BSIG_ERR_ARG, "spliced reads give coverage only: a block's start is not a read's 5' end");
+    if (prm.tspan) return fail(BSIG_ERR_ARG, "spliced reads: tspan would extend every block of a read to the whole fragment");
+    return BSIG_OK;
+}
 // stage 1: the arguments, the parameters (check_params), the chromosome ids
 static int check_request(PlanWork &W, bsig_plan **out)
 {
@@ -1868,6 +1898,8 @@ static int check_request(PlanWork &W, bsig_plan **out)
     *out = nullptr;
     if (W.n < 0 || (W.n > 0 && (!W.rid || !W.loc || !W.len || !W.strand))) return fail(BSIG_ERR_ARG, "range arrays missing");
     if (const int rc = bsig::check_params(*W.prm, W.n, W.len, &W.r, W.rq.frag_len)) return rc;
+    if (W.reads->spliced)
+        if (const int rc = spliced_rule(*W.prm, W.rq)) return rc;
     for (int64_t i = 0; i < W.n; ++i)
         if (W.rid[i] < 0 || W.rid[i] >= W.reads->n_ref)
             return fail(BSIG_ERR_CHROM, "chromosome id %d not present in the bam file", W.rid[i]);

@@ -180,11 +180,15 @@ struct bsig_reads {
     // which layout this is: a number no other layout of the process has (next_layout_gen(), taken whenever the resident
     // columns and indexes are (re)built or loaded).  A plan's cached tile windows are valid for exactly one layout.
     uint64_t layout_gen = 0;
+    // the rows are aligned blocks of reads split at their N gaps (splice.hip), not reads: only plain coverage may be asked
+    bool spliced = false;
 };
 namespace bsig { uint64_t next_layout_gen(); }
 
 namespace bsig {
 struct BaiIndex;
+// what bsig_reads_upload and bsig_reads_upload_spliced ask of the caller's columns (runtime.hip)
+int check_columns(const bsig_columns *cols);
 // Builds the resident HBM layout of R (span classes + bucket indexes, bsig_types.h) from device
 // columns of n reads in BAM order; ref_off is a host array of n_ref + 1 entries.  The input
 // columns are only read.

@@ -77,9 +77,13 @@ class Reads:
 
     ``end`` may be omitted when ``cigar_off``/``cigar`` (packed ``len<<4|op``) are given: the GPU
     then derives ``bam_endpos - 1`` itself.
+
+    ``spliced=True`` (needs ``cigar_off``/``cigar``): the reads are split at their N gaps and the rows are their aligned
+    blocks, each with its read's flag, mapq and tlen (csrc/splice.hip); ``info()["n_reads"]`` then counts blocks.  Such
+    reads give plain coverage only: every other plan refuses them.
     """
 
-    def __init__(self, ctx, ref_len, ref_off, pos, flag, mapq, tlen, end=None, cigar_off=None, cigar=None):
+    def __init__(self, ctx, ref_len, ref_off, pos, flag, mapq, tlen, end=None, cigar_off=None, cigar=None, *, spliced=False):
         self._lib = _lib.load()
         self.ctx = ctx
         ref_len = _i32(ref_len)
@@ -98,13 +102,15 @@ class Reads:
         cols.ref_off = _ptr(ref_off).value
         cols.pos, cols.flag, cols.mapq, cols.tlen = (_ptr(a).value for a in (pos, flag, mapq, tlen))
         keep = [ref_len, ref_off, pos, flag, mapq, tlen]
-        if end is not None:
+        if spliced and (cigar_off is None or cigar is None):
+            raise ValueError("spliced reads need cigar_off + cigar: an end column does not say where the N gaps lie")
+        if end is not None and not spliced:
             end = _i32(end)
             if len(end) != n:
                 raise ValueError("end column differs in length")
             cols.end = _ptr(end).value
             keep.append(end)
-        else:
+        if end is None or spliced:
             if cigar_off is None or cigar is None:
                 raise ValueError("need either end or cigar_off + cigar")
             cigar_off = np.ascontiguousarray(cigar_off, dtype=np.int64)
@@ -115,20 +121,23 @@ class Reads:
             cols.cigar = _ptr(cigar).value
             keep += [cigar_off, cigar]
         h = C.c_void_p()
-        _lib.check(self._lib.bsig_reads_upload(ctx._h, C.byref(cols), C.byref(h)))
+        upload = self._lib.bsig_reads_upload_spliced if spliced else self._lib.bsig_reads_upload
+        _lib.check(upload(ctx._h, C.byref(cols), C.byref(h)))
         self._h = h
         self.n_reads = n
         self.n_ref = len(ref_len)
 
     @classmethod
-    def from_bam(cls, ctx, bam, threads=0):
+    def from_bam(cls, ctx, bam, threads=0, *, spliced=False):
         """The whole of an open ``bamio.BamFile`` decoded to HBM: BGZF inflate on the CPU thread pool,
-        records -> columns on the GPU (csrc/devdecode.hip; CPU decode where the file needs it)."""
+        records -> columns on the GPU (csrc/devdecode.hip; CPU decode where the file needs it).  ``spliced``: the reads
+        split at their N gaps, the gaps found on the GPU while the stream is resident."""
         self = cls.__new__(cls)
         self._lib = _lib.load()
         self.ctx = ctx
         h = C.c_void_p()
-        _lib.check(self._lib.bsig_reads_from_bam(ctx._h, bam._h, int(threads), C.byref(h)))
+        decode = self._lib.bsig_reads_from_bam_spliced if spliced else self._lib.bsig_reads_from_bam
+        _lib.check(decode(ctx._h, bam._h, int(threads), C.byref(h)))
         self._h = h
         self.n_ref = len(bam.ref_len)
         self.n_reads = self.info()["n_reads"]
@@ -156,7 +165,7 @@ class Reads:
         return out, bool(sharded.value)
 
     @classmethod
-    def from_bam_regions(cls, ctx, bam, rid, beg, end, threads=0):
+    def from_bam_regions(cls, ctx, bam, rid, beg, end, threads=0, *, spliced=False):
         """The records the BAI lists for the regions [beg, end) (0-based) decoded to HBM -- a superset
         of the overlapping records, each once, in file order (what ``BamFile.decode(rid, beg, end)``
         returns on the host)."""
@@ -169,8 +178,8 @@ class Reads:
         if not (len(rid) == len(beg) == len(end)):
             raise ValueError("region arrays differ in length")
         h = C.c_void_p()
-        _lib.check(self._lib.bsig_reads_from_bam_regions(ctx._h, bam._h, len(rid), _ptr(rid), _ptr(beg), _ptr(end),
-                                                         int(threads), C.byref(h)))
+        decode = self._lib.bsig_reads_from_bam_regions_spliced if spliced else self._lib.bsig_reads_from_bam_regions
+        _lib.check(decode(ctx._h, bam._h, len(rid), _ptr(rid), _ptr(beg), _ptr(end), int(threads), C.byref(h)))
         self._h = h
         self.n_ref = len(bam.ref_len)
         self.n_reads = self.info()["n_reads"]
@@ -203,6 +212,11 @@ class Reads:
         other._h = h
         other.n_ref, other.n_reads = self.n_ref, self.n_reads
         return other
+
+    @property
+    def spliced(self):
+        """Are the rows aligned blocks of reads split at their N gaps?"""
+        return bool(self._lib.bsig_reads_is_spliced(self._h))
 
     @staticmethod
     def device_decode_timing():

@@ -209,7 +209,7 @@ class SignalViews:
 
 
 def bamViews(bampath, gr, lower, upper=None, signal=("coverage", "ends"), mapqual=0, binsize=1, ss=False, shift=0,  # noqa: N802
-             paired_end="ignore", tlenFilter=None, filteredFlag=-1, fragLength=None, verbose=True):  # noqa: N803
+             paired_end="ignore", tlenFilter=None, filteredFlag=-1, fragLength=None, verbose=True, *, splice=False):  # noqa: N803
     """For each range, the stretches whose signal lies in ``[lower, upper]``, with their sum, max and summit: a SignalViews.
 
     ``lower`` / ``upper``: whole numbers in the int32 range, ``lower <= upper``; ``upper=None`` means 2^31 - 1, "at or
@@ -217,8 +217,9 @@ def bamViews(bampath, gr, lower, upper=None, signal=("coverage", "ends"), mapqua
     ``binsize``, ``ss``, ``paired_end`` ("ignore" or "extend"), ``tlenFilter``, ``filteredFlag`` and ``fragLength``;
     ``shift`` must be 0.  ``signal="ends"``: the cells of ``bamProfile`` -- the 5' ends -- with ``binsize``, ``ss``,
     ``shift`` and ``paired_end`` ("ignore", "filter" or "midpoint"); it takes no ``fragLength``.  With ``binsize`` a cell
-    is a bin and the thresholds are compared with the bin's sum.  The views are found on the GPU; only they are
-    downloaded."""
+    is a bin and the thresholds are compared with the bin's sum.  ``splice=True`` (``signal="coverage"`` only): the cells of
+    ``bamCoverage(..., splice=True)``, the coverage that skips the reads' ``N`` gaps.  The views are found on the GPU; only
+    they are downloaded."""
     lo, hi = _thresholds(lower, upper)
     sig = _w._match_arg(signal, ("coverage", "ends"), "signal")
     if isinstance(shift, (bool, np.bool_)) or not isinstance(shift, (int, np.integer)):
@@ -226,12 +227,17 @@ def bamViews(bampath, gr, lower, upper=None, signal=("coverage", "ends"), mapqua
     if sig == "coverage":
         if shift != 0:
             raise ValueError('signal="coverage" has no shift: a read covers the bases it covers')
+        sp = _w._splice(splice, paired_end, ("ignore", "extend"), fragLength)
         frag = _w._frag_length(fragLength)
         pe = _w._match_arg(paired_end, ("ignore", "extend"), "paired.end")
         if frag and pe != "ignore":
             raise ValueError('fragLength resizes single-end reads: with paired_end="extend" a fragment already has its length')
         b = _w._coverage_binsize(binsize)
     else:
+        if not isinstance(splice, (bool, np.bool_)):
+            raise ValueError("splice must be True or False")
+        if splice:
+            raise ValueError('splice with signal="ends": a block\'s start is not a read\'s 5\' end')
         if fragLength is not None:
             raise ValueError('signal="ends" takes no fragLength: a 5\' end is one base')
         pe = _w._match_arg(paired_end, ("ignore", "filter", "midpoint"), "paired.end")
@@ -247,5 +253,5 @@ def bamViews(bampath, gr, lower, upper=None, signal=("coverage", "ends"), mapqua
     path, tf = os.path.expanduser(str(bampath)), _w.tlenFilter(tlenFilter, pe)
     if sig == "coverage":
         return _w.coverage_views(path, gr, tf, lo, hi, mapqual, _w.flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss),
-                                 frag_len=frag)
+                                 frag_len=frag, **(dict(spliced=True) if sp else {}))
     return _w.pileup_views(path, gr, tf, lo, hi, mapqual, b, int(shift), bool(ss), _w.flagMask(pe), filteredFlag, pe == "midpoint")

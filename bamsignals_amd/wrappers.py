@@ -179,28 +179,35 @@ def pileup_sum(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=False
 
 
 def coverage_sum(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                 maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+                 maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0, spliced=False):
     """bamCoverage's signals summed over the ranges (bsig_coverage_sum): int64, ``(n_bins,)`` or ``(2, n_bins)``.
-    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_sum_resized)."""
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_sum_resized).  ``spliced``: of the
+    reads' aligned blocks (bsig_coverage_sum_spliced)."""
     _check_gr(gr)
     w = _check_equal_widths(gr)
     head = _head(bampath, gr, tlen_filter)
     n_bins = (w + int(binsize) - 1) // int(binsize) if len(gr) and w > 0 else 0
     out = np.zeros(n_bins * (2 if ss else 1), dtype=np.int64)
-    fn, rule = _coverage_rule(_lib.load(), "sum", tspan, frag_len)
-    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
+    fn, rule = _coverage_rule(_lib.load(), "sum", tspan, frag_len, spliced)
+    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), *rule, int(maxgap), _dev(device), int(binsize),
                   int(bool(ss)), out.ctypes.data))
     return _sum_shape(out, ss)
 
 
-def _coverage_rule(lib, what, tspan, frag_len):
-    """The file-level coverage call of a kind (``core_ex`` / ``sum`` / ``runs`` / ``views``) and the int32 that travels in its
-    interval-rule slot: ``tspan``, or with ``frag_len`` the resized call (bsig_coverage_<what>_resized) and the length."""
+def _coverage_rule(lib, what, tspan, frag_len, spliced=False):
+    """The file-level coverage call of a kind (``core_ex`` / ``sum`` / ``runs`` / ``views``) and the int32s that travel in its
+    interval-rule slot: ``(tspan,)``, or with ``frag_len`` the resized call (bsig_coverage_<what>_resized) and the length, or
+    with ``spliced`` the spliced call (bsig_coverage_<what>_spliced), which has no such slot."""
+    base = "bsig_coverage_" + ("core" if what == "core_ex" else what)
+    if spliced:
+        if tspan or frag_len:
+            raise ValueError("spliced coverage is of the reads' aligned blocks as they lie: no tspan, no frag_len")
+        return getattr(lib, base + "_spliced"), ()
     if frag_len:
         if tspan:
             raise ValueError("a paired-end fragment already has its length: frag_len excludes tspan")
-        return getattr(lib, "bsig_coverage_" + ("core" if what == "core_ex" else what) + "_resized"), int(frag_len)
-    return getattr(lib, "bsig_coverage_" + what), int(bool(tspan))
+        return getattr(lib, base + "_resized"), (int(frag_len),)
+    return getattr(lib, "bsig_coverage_" + what), (int(bool(tspan)),)
 
 
 def pileup_xcorr(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, max_lag=500, maxgap=16385, device=None):
@@ -381,14 +388,15 @@ def pileup_runs(bampath, gr, tlen_filter, mapqual=0, binsize=1, shift=0, ss=Fals
 
 
 def coverage_runs(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                  maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+                  maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0, spliced=False):
     """bamCoverage's signals as runs (bsig_coverage_runs): a RunSignals; the per-base cells stay on the GPU.
-    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_runs_resized)."""
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_runs_resized).  ``spliced``: of the
+    reads' aligned blocks (bsig_coverage_runs_spliced)."""
     head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
     h = C.c_void_p()
-    fn, rule = _coverage_rule(lib, "runs", tspan, frag_len)
-    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
+    fn, rule = _coverage_rule(lib, "runs", tspan, frag_len, spliced)
+    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), *rule, int(maxgap), _dev(device), int(binsize),
                   int(bool(ss)), C.byref(h)))
     return _take_runs(lib, h, ss)
 
@@ -418,14 +426,15 @@ def pileup_views(bampath, gr, tlen_filter, lower, upper, mapqual=0, binsize=1, s
 
 
 def coverage_views(bampath, gr, tlen_filter, lower, upper, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                   maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+                   maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0, spliced=False):
     """The views of bamCoverage's signals (bsig_coverage_views): a SignalViews, as ``pileup_views``.
-    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_views_resized)."""
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_views_resized).  ``spliced``: of the
+    reads' aligned blocks (bsig_coverage_views_spliced)."""
     head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
     h = C.c_void_p()
-    fn, rule = _coverage_rule(lib, "views", tspan, frag_len)
-    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), rule, int(maxgap), _dev(device), int(binsize),
+    fn, rule = _coverage_rule(lib, "views", tspan, frag_len, spliced)
+    _lib.check(fn(*head, int(mapqual), int(requiredF), int(filteredF), *rule, int(maxgap), _dev(device), int(binsize),
                   int(bool(ss)), int(lower), int(upper), C.byref(h)))
     return _take_views(lib, h, ss)
 
@@ -436,21 +445,22 @@ def _is_ex(binsize, ss):
 
 
 def coverage_core(bampath, gr, tlen_filter, mapqual=0, requiredF=0, filteredF=-1, tspan=False,
-                  maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0):
+                  maxgap=16385, device=None, *, binsize=1, ss=False, frag_len=0, spliced=False):
     """The native entry point behind bamCoverage (ref: R/RcppExports.R:16-18).  ``binsize`` / ``ss``:
     per-base coverage summed over bins / split into sense and antisense rows (bsig_coverage_core_ex).
-    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_core_resized, whatever the bins)."""
+    ``frag_len`` (not with ``tspan``): of reads resized to the fragment (bsig_coverage_core_resized, whatever the bins).
+    ``spliced``: of the reads' aligned blocks (bsig_coverage_core_spliced, whatever the bins)."""
     head = _head(bampath, gr, tlen_filter)
     lib = _lib.load()
     n = len(gr)
-    ex = _is_ex(binsize, ss) or bool(frag_len)
+    ex = _is_ex(binsize, ss) or bool(frag_len) or bool(spliced)
     off = np.empty(n + 1, dtype=np.int64)
     cells = lib.bsig_layout(n, head.width.ctypes.data, int(binsize) if ex else 1, int(bool(ss)) if ex else 0, off.ctypes.data)
     out = np.zeros(cells, dtype=np.int32)
     flt = (int(mapqual), int(requiredF), int(filteredF))
     if ex:
-        fn, rule = _coverage_rule(lib, "core_ex", tspan, frag_len)
-        _lib.check(fn(*head, *flt, rule, int(maxgap), _dev(device), int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
+        fn, rule = _coverage_rule(lib, "core_ex", tspan, frag_len, spliced)
+        _lib.check(fn(*head, *flt, *rule, int(maxgap), _dev(device), int(binsize), int(bool(ss)), out.ctypes.data, off.ctypes.data))
     else:
         _lib.check(lib.bsig_coverage_core(*head, *flt, int(bool(tspan)), int(maxgap), _dev(device), out.ctypes.data, off.ctypes.data))
     return _split(out, off, ex and bool(ss))
@@ -642,9 +652,25 @@ def _frag_length(fragLength):  # noqa: N803
     return f
 
 
+def _splice(splice, paired_end, choices, fragLength=None, keepDup=None):  # noqa: N803
+    """splice as a call reads it: a bool, and only for the reads as they lie"""
+    if not isinstance(splice, (bool, np.bool_)):
+        raise ValueError("splice must be True or False")
+    if not splice:
+        return False
+    if fragLength is not None:
+        raise ValueError("splice with fragLength: every aligned block of a read would be resized, not the read")
+    if keepDup is not None:
+        raise ValueError("splice with keepDup: reads are capped by their 5' end, and a block's start is not one")
+    if _match_arg(paired_end, choices, "paired.end") != "ignore":
+        raise ValueError('splice with paired_end="extend": every aligned block of a read would be extended to the whole '
+                         'fragment, introns included (paired_end must be "ignore")')
+    return True
+
+
 def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFilter=None,  # noqa: N802,N803
                 filteredFlag=-1, verbose=True, *, binsize=1, ss=False, aggregate=False, runs=False, fragLength=None,
-                keepDup=None):
+                keepDup=None, splice=False):
     """For each base pair of the ranges, the number of reads covering it (R/wrappers.R:154-173).
 
     ``binsize`` (1 .. 65,536): bin j of a range covers its bases [j*binsize, min((j+1)*binsize, width)) in range
@@ -675,9 +701,19 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
     ``c_sense[p]`` over ``p = x - L + 1 .. x`` plus the sum of ``c_anti[p]`` over ``p = x .. x + L - 1``, 5' ends up to
     ``L - 1`` bases outside the range included; with ``ss`` the two sums are the two rows, and ``binsize`` sums cells as
     for plain coverage.  Without ``fragLength`` it is refused: duplicates of different lengths have no defined survivor.
-    ``paired_end`` must be ``"ignore"``; not with ``aggregate`` or ``runs`` (not built yet)."""
+    ``paired_end`` must be ``"ignore"``; not with ``aggregate`` or ``runs`` (not built yet).
+    ``splice=True`` (a bool; ``False``, the default, is the reference's call): coverage that skips the reads' ``N`` gaps, as
+    ``GenomicAlignments::coverage()``, deepTools ``bamCoverage`` and ``bedtools genomecov -split`` do -- what RNA-seq needs,
+    where a read ``40M2000N60M`` otherwise fills its intron.  Walk the CIGAR from ``pos``: ``M D = X`` advance and are
+    covered, ``N`` advances and is not, ``I S H P`` advance nothing; a read covers its aligned blocks, the stretches between
+    its gaps (neighbouring ``N``, and ``N`` separated only by ``I S H P``, are one gap; ``D`` stays covered).  ``mapqual``
+    and ``filteredFlag`` act on a read's blocks as on the read.  ``binsize``, ``ss``, ``aggregate`` and ``runs`` work on it
+    as on plain coverage; ``bamCoverage(splice=True) <= bamCoverage()`` cell by cell, and on a file without ``N`` they are
+    equal.  Not with ``paired_end="extend"``, ``fragLength`` or ``keepDup``.  The file's spliced reads are a resident set of
+    their own beside its plain ones."""
     if runs and aggregate:
         raise ValueError("runs=True and aggregate=True exclude each other: a sum over ranges has no per-range runs")
+    sp = _splice(splice, paired_end, ("ignore", "extend"), fragLength, keepDup)
     k = _keep_dup(keepDup, paired_end, ("ignore", "extend"))
     if k and fragLength is None:
         raise ValueError("keepDup needs fragLength for bamCoverage: duplicates of different lengths have no defined survivor")
@@ -697,16 +733,17 @@ def bamCoverage(bampath, gr, mapqual=0, paired_end=("ignore", "extend"), tlenFil
         warnings.warn("some ranges' widths are not a multiple of the selected\n"
                       "             binsize, some bins will correspond to less than binsize basepairs")
     pe = _match_arg(paired_end, ("ignore", "extend"), "paired.end")
+    sp_kw = dict(spliced=True) if sp else {}        # (the plain calls stay exactly the calls they were)
     if aggregate:
         return coverage_sum(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                            flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
+                            flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag, **sp_kw)
     if runs:
         return coverage_runs(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                             flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
+                             flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag, **sp_kw)
     if k:
         pu = coverage_capped(os.path.expanduser(str(bampath)), gr, (), mapqual, flagMask(pe), filteredFlag, False, frag, k,
                              binsize=b, ss=bool(ss))
         return CountSignals(pu, bool(ss), _trusted=True)
     pu = coverage_core(os.path.expanduser(str(bampath)), gr, globals()["tlenFilter"](tlenFilter, pe), mapqual,
-                       flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag)
+                       flagMask(pe), filteredFlag, pe == "extend", binsize=b, ss=bool(ss), frag_len=frag, **sp_kw)
     return CountSignals(pu, bool(ss), _trusted=True)

@@ -140,6 +140,23 @@ typedef struct {
 } bsig_reads_info;
 
 int bsig_reads_upload(bsig_ctx *ctx, const bsig_columns *cols, bsig_reads **reads);
+/* SPLICED reads: coverage that skips N gaps (RNA-seq; GenomicAlignments::coverage(), deepTools bamCoverage, bedtools genomecov
+ * -split).  Walk a read's CIGAR with a cursor that starts at pos: M D = X (ops 0, 2, 7, 8) advance it and are covered, N (op
+ * 3) advances it and is not, I S H P advance nothing (D stays covered: drop.D.ranges = FALSE and bam_endpos' own rule).  A GAP is
+ * a maximal stretch of the read's span [pos, end] that comes from N operations -- neighbouring Ns, and Ns separated only by
+ * I / S / H / P, make one gap --, the read's BLOCKS are the non-empty stretches between its gaps.  A read without N has one
+ * block, [pos, end]; a read with flag 0x4 or without a reference-consuming operation keeps its single row [pos, pos]; a read
+ * whose reference-consuming operations are all N has no block; a leading or trailing N yields no empty block.
+ * The object is an ORDINARY bsig_reads whose rows are the blocks, each with its read's flag, mapq and tlen, stably sorted by
+ * (reference, block start) -- ties keep BAM order, then block order within the read -- in the ordinary resident layout:
+ * bsig_reads_get_info counts blocks, bsig_reads_clone keeps the mark, bsig_reads_is_spliced tells it.  It needs cigar_off +
+ * cigar (cols->end is not read; end alone is BSIG_ERR_ARG) and holds fewer than 2^32 reads and blocks.  bsig_reads_save of a
+ * spliced object fails with BSIG_ERR_ARG (the file format has no mark for it).  Every plan creator refuses a spliced object
+ * with BSIG_ERR_ARG and a sentence of its own for anything but BSIG_MODE_COVERAGE / _COVERAGE_EX with tspan == 0 and no
+ * frag_len: a block's start is no 5' end and a block is no fragment.  mapqual, the flag masks and a tlen_filter act on blocks
+ * exactly as on reads.                                                                                               */
+int bsig_reads_upload_spliced(bsig_ctx *ctx, const bsig_columns *cols, bsig_reads **reads);
+int32_t bsig_reads_is_spliced(const bsig_reads *reads);          /* 1 / 0; 0 for NULL                            */
 int bsig_reads_get_info(const bsig_reads *reads, bsig_reads_info *info);
 void bsig_reads_free(bsig_reads *reads);
 /* a copy of resident reads on another GPU (device-to-device over xGMI where peer access exists):
@@ -598,6 +615,14 @@ int bsig_reads_from_bam_multi(bsig_ctx *const *ctxs, int32_t n, bsig_bam *bam, i
 int bsig_reads_from_bam_regions(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
                                 const int64_t *beg, const int64_t *end, int32_t threads,
                                 bsig_reads **reads);
+/* bsig_reads_from_bam / _regions with the reads split at their N gaps (bsig_reads_upload_spliced above).  The gaps are found
+ * on the GPU while a chunk's inflated stream is still resident, right behind the record extraction (one host read per chunk
+ * sizes the chunk's piece of the gap table); a CG:B,I CIGAR is followed as there.  Where the file takes the CPU decode, its
+ * CIGAR columns go through bsig_reads_upload_spliced: same result.  BAMSIGNALS_DEVICE_DECODE as above.              */
+int bsig_reads_from_bam_spliced(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads);
+int bsig_reads_from_bam_regions_spliced(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
+                                        const int64_t *beg, const int64_t *end, int32_t threads,
+                                        bsig_reads **reads);
 /* stage seconds of the calling thread's last device-side decode: block scan, CPU inflate, waiting
  * for the copies, record walk + extraction kernels, total, HBM layout (all 0 after a CPU decode) */
 void bsig_device_decode_timing(double *t6);
@@ -890,6 +915,43 @@ int bsig_coverage_views_resized(const char *bampath, int64_t n_ranges, const int
                                 int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t frag_len,
                                 int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
                                 int32_t lower, int32_t upper, bsig_views_result **result);
+/* bamCoverage(splice = TRUE) at file level: bsig_coverage_core_ex, bsig_coverage_sum, bsig_coverage_runs and
+ * bsig_coverage_views WITHOUT tspan, on the file's spliced reads (bsig_reads_from_bam_spliced), through the same dispatcher.
+ * The flag is judged with the other parameters before the BAM is opened.  A file's plain and spliced reads are two resident
+ * sets of the cache (a second set only when one file is asked both ways); a spliced set has no reads file (none is loaded,
+ * none is written); with several GPUs it is decoded on the first and cloned.  bsig_last_call_route() says "spliced".
+ * (Laid out with their parameters below their names ON PURPOSE, as bsig_pileup_vplot is; their refusals are pinned in
+ * tests/test_spliced_cpu.py.)                                                                                        */
+int bsig_coverage_core_spliced(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF,
+    int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+    int32_t *out, const int64_t *off);
+int bsig_coverage_sum_spliced(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF,
+    int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, int64_t *sum);
+int bsig_coverage_runs_spliced(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF,
+    int32_t maxgap, int32_t device, int32_t binsize, int32_t ss, bsig_runs_result **result);
+int bsig_coverage_views_spliced(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    const int32_t *tlen_filter, int32_t n_tlen_filter,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF,
+    int32_t maxgap, int32_t device, int32_t binsize, int32_t ss,
+    int32_t lower, int32_t upper, bsig_views_result **result);
 int64_t bsig_views_result_n_seg(const bsig_views_result *result);
 int64_t bsig_views_result_n_views(const bsig_views_result *result);
 int bsig_views_result_copy(const bsig_views_result *result, int64_t *seg_off, int32_t *start, int32_t *width, int64_t *sum,
