@@ -3660,7 +3660,7 @@ static int knob(int k)
 }
 
 // The launch log (bsig_debug_launch_log, for the tests): the name of every pileup, overlap, sum-tiles and reduction-tiles
-// (xcorr, frag, hist, summary, scaled) kernel form launched while it is on -- the kernel template, its arguments and the
+// (xcorr, frag, hist, summary, scaled, vplot, capped) kernel form launched while it is on -- the kernel template, its arguments and the
 // run-time choices that change the code path.  The names are made in the dispatch macros below from the macros' own
 // arguments, so a new branch reports itself; the occupancy query (tile_blocks_per_cu) shares the selectors and logs
 // nothing.  Host code only; off, a launch pays one load and one branch.  Multi-slot calls launch from several threads: a
@@ -4363,8 +4363,8 @@ extern "C" int bsig_debug_set_knob(int which, int value)
 
 // (debug, tests: the launch log.  buf == NULL: cap 1 turns it on, cap 0 off, either way empty.  With a buffer: the names
 // of the pileup, overlap, sum-tiles and reduction-tiles (k_xcorr_tiles, k_frag_tiles, k_hist_tiles, k_summary_tiles,
-// k_scaled_tiles, k_vplot_tiles) kernel forms launched since the last call, one a line, as many whole lines as fit cap
-// bytes with their final 0; the log is emptied.  Returns the number of names the log held.)
+// k_scaled_tiles, k_vplot_tiles, k_capped_tiles) kernel forms launched since the last call, one a line, as many whole lines
+// as fit cap bytes with their final 0; the log is emptied.  Returns the number of names the log held.)
 extern "C" int bsig_debug_launch_log(char *buf, int cap)
 {
     std::lock_guard<std::mutex> lock(bsig::g_log_mu);

@@ -455,3 +455,96 @@ def expected_summary(signal, ss, thresholds, mapqual=0):
 def expected_scaled(signal, ss, n_bins, mapqual=0):
     import scaled_expected as sc
     return _frozen(sc.from_cells(reduction_cells(signal, ss, mapqual), ranges(), ss, n_bins))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the later forms (tests/test_later_forms_gpu.py): keepDup's capped cells, the V-plot and the resized coverage -- the
+# oracle's cells put together by the kinds' own expected sides (tests/*_expected.py), once per parameter set; never a GPU plan
+# ---------------------------------------------------------------------------------------------------------------
+# the V-plot's shapes on sum_ranges() (tlen_filter, len_bin, binsize) -> rows x cols = tf1 // len_bin + 1 by ceil(2,048 /
+# binsize) cells: a small table, one of exactly the 40,960 counters a gfx950 workgroup may declare (160 KiB), one row
+# fewer and one row more.  No template of the deck is longer than 600.
+VPLOT_SHAPES = {"small": ((0, 600), 7, 50), "budget": ((100, 399), 20, 1), "below": ((100, 379), 20, 1), "above": ((100, 419), 20, 1)}
+VPLOT_CELLS = {"small": 86 * 41, "budget": 20 * 2048, "below": 19 * 2048, "above": 21 * 2048}
+
+
+@functools.lru_cache(maxsize=None)
+def capped_cells(shift=0, mapqual=0):
+    """per range of the deck the (2, w) int64 matrix of its per-base 5'-end cells, rows sense and antisense, uncapped"""
+    import capped_expected as ce
+    return tuple(_frozen(c) for c in ce.stranded_cells(oracle_reads(), ranges(), shift=shift, mapqual=mapqual))
+
+
+@functools.lru_cache(maxsize=None)
+def expected_capped(k, binsize, ss, shift=0, mapqual=0):
+    """(flat int64 cells, offsets) of keepDup = k over ranges(): capped first, binned second (binsize -1: bamCount), the
+    strands added last"""
+    import capped_expected as ce
+    flat, off = ce.ends_from_cells(capped_cells(shift, mapqual), k, binsize, ss)
+    return _frozen(flat), _frozen(off)
+
+
+@functools.lru_cache(maxsize=None)
+def expected_capped_cover(k, L, binsize, ss, mapqual=0):
+    """(flat int64 cells, offsets) over ranges() of the coverage of the kept reads resized to L bases"""
+    import capped_expected as ce
+    flat, off = ce.coverage(oracle_reads(), ranges(), k, L, binsize, ss, mapqual=mapqual)
+    return _frozen(flat), _frozen(off)
+
+
+def capped_cover_rows(L):
+    """the pairs in every range's scratch row of a capped coverage plan: the range widened by L - 1 bases on both sides,
+    less what lies below base 0 (csrc/planmath.h: capped_widen; 0 for a range without width)"""
+    rg = ranges()
+    loc, w = rg["loc"].astype(np.int64), rg["len"].astype(np.int64)
+    lo = np.maximum(loc - (L - 1), 0)
+    return np.where(w > 0, np.maximum(loc - lo + w + L - 1, 0), 0)
+
+
+def _some_sum_ranges(which):
+    rg = sum_ranges()
+    if which == "all":
+        return rg
+    c = reads()
+    keep = np.isin(rg["rid"], c[{"c0": "c0_refs", "paired": "pair_refs"}[which]])
+    return {k: v[keep] for k, v in rg.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def expected_vplot(tlen_filter, len_bin, binsize, midpoint, mapqual=0, which="all"):
+    """the (rows, cols) int64 V-plot of sum_ranges() (which: all, or the class-0 / the paired islands' ranges alone): one
+    oracle bamProfile per non-empty row band, summed over the ranges"""
+    import vplot_expected as ve
+    assert tlen_filter[1] <= 600
+    return _frozen(ve.expected(oracle_reads(), _some_sum_ranges(which), tlen_filter, len_bin, binsize, midpoint, mapqual=mapqual))
+
+
+@functools.lru_cache(maxsize=None)
+def resized_columns(L):
+    """the deck's read columns with every read resized to L bases from its 5' end (tests/resized_expected.py)"""
+    import resized_expected as rx
+    return rx.resize_columns(reads(), L)
+
+
+@functools.lru_cache(maxsize=None)
+def expected_resized(L, pset):
+    """(flat int32 result, offsets) of the coverage parameter set PARAM_SETS[pset] on the whole deck with the reads
+    resized to L bases: the oracle's coverage of the resized columns"""
+    import resized_expected as rx
+    entry, args = PARAM_SETS[pset]
+    assert entry == "coverage"
+    out, off = rx.coverage(resized_columns(L), ranges(), args["binsize"], args["ss"])
+    assert out.max(initial=0) < 2 ** 31
+    out = out.astype(np.int32)
+    out.setflags(write=False)
+    return out, off
+
+
+@functools.lru_cache(maxsize=None)
+def expected_resized_sum(L, ss):
+    """the int64 sum over sum_ranges() of the per-base coverage of the reads resized to L bases (cell 2 * base + antisense
+    with strands)"""
+    import resized_expected as rx
+    rg = sum_ranges()
+    per_range, _ = rx.coverage(resized_columns(L), rg, 1, ss)
+    return _frozen(per_range.reshape(len(rg["len"]), -1).sum(axis=0).astype(np.int64))

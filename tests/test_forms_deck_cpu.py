@@ -2,7 +2,9 @@
 counts they name, their windows start at every residue modulo 8 in every class they are there for (the class-0 islands in
 class 0 of both layouts, the paired islands in the packed class), the ranges meet every
 value of out_off & 3 at every width, the cuts leave the tile counts they promise, every parameter set of the matrix
-counts something, and no cell leaves the 16-bit tile images' range without the heavy-tile knob."""
+counts something, and no cell leaves the 16-bit tile images' range without the heavy-tile knob.  For the later forms
+(tests/test_later_forms_gpu.py): cells on both sides of every cap, every branch of the capped bins' adder, scratch rows
+around the capped scan's rounds, the V-plot's shapes and the resized coverage."""
 import hashlib
 
 import numpy as np
@@ -185,3 +187,156 @@ def test_every_parameter_set_counts_something_within_16_bits():
     for name in deck.SUM_SETS:
         s = deck.expected_sum(name)
         assert s.dtype == np.int64 and s.any(), name
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the later forms (tests/test_later_forms_gpu.py, whose case tables are read here): conditions on the input, so that no
+# GPU case is vacuous
+# ---------------------------------------------------------------------------------------------------------------
+def _capped_cell_sets():
+    """the (shift, mapqual) of every capped case: a word form on a packed layout comes from mapqual 10"""
+    import test_later_forms_gpu as lf
+    return sorted({(c[6], 10 if c[1] else 0) for c in lf.CAPPED})
+
+
+def test_capped_cells_lie_on_both_sides_of_every_cap():
+    import test_later_forms_gpu as lf
+    assert _capped_cell_sets() == [(0, 0), (0, 10), (75, 0), (75, 10)]
+    n_ranges = len(deck.ranges()["len"])
+    for shift, mapqual in _capped_cell_sets():
+        cells = deck.capped_cells(shift, mapqual)
+        assert len(cells) == n_ranges and all(c.dtype == np.int64 and c.shape == (2, w) for c, w in zip(cells, deck.ranges()["len"]))
+        for row in (0, 1):
+            v = np.concatenate([c[row] for c in cells])
+            for k in lf.CAPPED_KS:
+                assert (v > k).any() and ((v >= 1) & (v <= k)).any(), (shift, mapqual, row, k)
+            assert v.max() <= 11                                 # (a cap of 11 would bite nowhere: the claim can fail)
+    # the island ranges without a filter or a shift: cells up to 11, most of the non-zero ones 1, some above every cap
+    isl = np.concatenate([c.reshape(-1) for c in deck.capped_cells(0, 0)[deck.N_BULK_RANGES:]])
+    assert (int(isl.max()), int((isl == 1).sum()), int((isl > 5).sum())) == (11, 64_104, 781)
+    # a coverage case's mapqual filter and cap too
+    for c in lf.CAPPED_COVER:
+        want, off = deck.expected_capped_cover(c[6], c[2], c[3], c[4], 10 if c[1] else 0)
+        assert want.dtype == np.int64 and want.any() and off[-1] == want.size, c
+        if c[2] == 1 and c[3] == 1:                              # a fragment of one base: the capped cells themselves
+            flat = deck.expected_capped(c[6], 1, c[4], 0, 10 if c[1] else 0)[0]
+            assert np.array_equal(want, flat) and c[6] <= want.max() <= (1 if c[4] else 2) * c[6], c
+
+
+def add_classes(cells, tile_cells, binsize, ss):
+    """Which branches of CappedCells::add (csrc/kernels.hip) the deck's ranges reach, restated: a range of w per-base cells
+    is cut into tiles of tile_cells (rounded up to whole fours), a wave walks the cells [64 j, 64 j + 64) of a tile -- the
+    lanes behind the tile's last cell hold nothing --, and what it adds is the sense row, then the antisense row (with
+    strands) or their sum (without).  A stretch with
+      a: 1 .. 16 non-zero cells lets them add for themselves;
+      b: more, every lane a cell and all in one bin, takes the xor reduction;
+      c: more, every lane a cell, in two or more bins, takes the segmented scan;
+      d: more, in a tile's last, partial stretch (the lanes behind it differ from every bin), takes the scan too.
+    A capped cell is zero exactly where the uncapped one is."""
+    tile = (tile_cells + 3) & ~3
+    met = set()
+    for c in cells:
+        w = c.shape[1]
+        rows = (c[0], c[1]) if ss else (c[0] + c[1],)
+        for c0 in range(0, w, tile):
+            nc = min(tile, w - c0)
+            for j in range(0, nc, 64):
+                n = min(64, nc - j)
+                first, last = ((c0 + j) // binsize, (c0 + j + n - 1) // binsize) if binsize > 0 else (0, 0)
+                for r in rows:
+                    nz = int(np.count_nonzero(r[c0 + j:c0 + j + n]))
+                    if nz:
+                        met.add("a" if nz <= 16 else "d" if n < 64 else "b" if first == last else "c")
+    return met
+
+
+def test_capped_cases_reach_every_branch_of_add():
+    import test_later_forms_gpu as lf
+    shapes = sorted({(c[4], c[2], c[3], c[6], 10 if c[1] else 0) for c in lf.CAPPED if c[2] != 1})
+    assert {(t, b) for t, b, _, _, _ in shapes} == {(t, b) for t in lf.CAPPED_TILES for b in (7, 274, -1)}
+    union = {False: set(), True: set()}
+    for tile, binsize, ss, shift, mapqual in shapes:
+        met = add_classes(deck.capped_cells(shift, mapqual), tile, binsize, ss)
+        union[ss] |= met
+        what = (tile, binsize, ss, shift, mapqual, sorted(met))
+        assert "a" in met, what
+        if tile == 16:                       # at most 16 cells a stretch: nothing but the lanes' own adds
+            assert met == {"a"}, what
+        elif tile == 18:                     # 20 cells, one partial stretch a tile: the densest islands fill more than 16
+            assert met == {"a", "d"}, what
+        elif binsize < 0:                    # bamCount: one bin
+            assert "b" in met and "c" not in met, what
+        elif binsize == 274:                 # a bin of at least a tile: a stretch lies in one or straddles two
+            assert {"b", "c"} <= met, what
+        else:                                # bins of 7: nine or ten a stretch
+            assert "c" in met and "b" not in met, what
+    assert union[False] == union[True] == set("abcd")
+    # (the aligned 64-cell stretches of the island ranges, strands apart: both sides of the 16 non-zero lanes)
+    nz = np.concatenate([np.count_nonzero(c.reshape(2, -1, 64), axis=2).reshape(-1) for c in deck.capped_cells(0, 0)[deck.N_BULK_RANGES:]])
+    assert (int(((nz >= 1) & (nz <= 16)).sum()), int((nz > 16).sum())) == (3842, 2222)
+    # a bin size that leaves a class empty is seen
+    assert "c" not in add_classes(deck.capped_cells(0, 0), 256, 8192, False)
+
+
+def test_capped_coverage_rows_straddle_the_scans_rounds():
+    """k_capped_scan carries from one round of 256 pairs to the next: rows of 256 k - 1, 256 k and 256 k + 1 pairs for the
+    first round's end and the eighth's, among the scratch rows of the capped coverage cases"""
+    import test_later_forms_gpu as lf
+    lengths = {c[2] for c in lf.CAPPED_COVER}
+    rows = np.concatenate([deck.capped_cover_rows(L) for L in lengths])
+    for n in (255, 256, 257, 2047, 2048, 2049):
+        assert (rows == n).any(), n
+    rg = deck.ranges()
+    # a fragment of one base widens nothing: a row is its range, less the bases of the ranges that begin at -3
+    assert np.array_equal(deck.capped_cover_rows(1), np.where(rg["len"] > 0, rg["len"] + np.minimum(rg["loc"], 0), 0))
+    assert int(np.sum(rg["loc"] < 0)) == 3
+    # widened by L - 1 on both sides, less what lies below base 0
+    w36 = deck.capped_cover_rows(36)
+    assert np.all(w36[rg["len"] > 0] <= rg["len"][rg["len"] > 0] + 70) and np.any(w36[rg["len"] > 0] < rg["len"][rg["len"] > 0] + 70)
+    assert not w36[rg["len"] == 0].any()
+
+
+def test_vplot_shapes_count_both_island_groups_and_their_edges():
+    import test_later_forms_gpu as lf
+    srg = deck.sum_ranges()
+    assert len(srg["len"]) == 198 and set(srg["len"].tolist()) == {deck.SUM_WIDTH} and set(srg["strand"].tolist()) == {1, -1, 0}
+    assert deck.VPLOT_CELLS == {"small": 3526, "budget": 40_960, "below": 38_912, "above": 43_008}
+    shapes = {(lf.VPLOT_WHICH[c[1]][0], c[3], c[6]) for c in lf.VPLOT}
+    assert {s for s, _, _ in shapes} == set(deck.VPLOT_SHAPES)
+    for shape, midpoint, mapqual in sorted(shapes):
+        tf, len_bin, binsize = deck.VPLOT_SHAPES[shape]
+        assert tf[1] <= 600
+        whole = deck.expected_vplot(tf, len_bin, binsize, midpoint, mapqual)
+        assert whole.dtype == np.int64 and whole.shape == (tf[1] // len_bin + 1, -(-deck.SUM_WIDTH // binsize))
+        assert whole.size == deck.VPLOT_CELLS[shape]
+        assert whole.max() >= 2 and whole[:, 0].any() and whole[:, -1].any(), (shape, midpoint, mapqual)
+        assert not whole[:tf[0] // len_bin].any()
+        for which in ("c0", "paired"):
+            part = deck.expected_vplot(tf, len_bin, binsize, midpoint, mapqual, which)
+            assert part.any() and np.all(part <= whole), (shape, midpoint, mapqual, which)
+    # the budget shapes are one table of exactly 160 KiB of 32-bit counters, one row fewer and one row more
+    assert 4 * deck.VPLOT_CELLS["budget"] == 160 * 1024
+    assert deck.VPLOT_CELLS["budget"] - deck.VPLOT_CELLS["below"] == deck.VPLOT_CELLS["above"] - deck.VPLOT_CELLS["budget"] == 2048
+    # the small shape under 14 KiB: the counters fit, the filter table's 512 bytes behind them do not
+    assert 4 * deck.VPLOT_CELLS["small"] <= 14 * 1024 < 4 * ((deck.VPLOT_CELLS["small"] + 3) & ~3) + 512
+    # the mapqual filter of the word-form case drops something
+    small = deck.VPLOT_SHAPES["small"]
+    assert deck.expected_vplot(*small, True, 10).sum() < deck.expected_vplot(*small, True).sum()
+
+
+def test_resized_sets_count_something_within_16_bits():
+    import test_later_forms_gpu as lf
+    psets = {"cover", "bins2_ss0", "bins2_ss1"} | {p for p, _, _, _ in lf.COV_BINS}
+    for L in lf.RESIZED_L:
+        for pset in sorted(psets):
+            want, off = deck.expected_resized(L, pset)
+            assert want.dtype == np.int32 and want.any() and off[-1] == want.size, (L, pset)
+        # per base: the tile images' signed 16-bit cells hold it without the heavy-tile knob
+        cover = deck.expected_resized(L, "cover")[0]
+        assert 0 <= cover.min() and cover.max() <= 32_767, (L, int(cover.max()))
+        for ss in (False, True):
+            s = deck.expected_resized_sum(L, ss)
+            assert s.dtype == np.int64 and s.any() and s.size == deck.SUM_WIDTH * (2 if ss else 1)
+        assert deck.expected_resized_sum(L, False).sum() == deck.expected_resized_sum(L, True).sum()
+    # a longer fragment covers more
+    assert deck.expected_resized(36, "cover")[0].sum() < deck.expected_resized(5000, "cover")[0].sum()

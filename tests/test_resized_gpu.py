@@ -5,7 +5,6 @@ edge of a tile's window, the identities with bamProfile and with paired.end = "e
 because its window was widened, the longest fragment the ABI takes, the sums and runs, the file-level calls, and what
 the resized creators refuse."""
 import ctypes as C
-import functools
 import os
 
 import numpy as np
@@ -83,20 +82,8 @@ def cov_params(binsize=1, ss=False, **kw):
 
 
 # ---- 1. the forms deck -----------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def deck_resized(L):
-    return rx.resize_columns(deck.reads(), L)
-
-
-@functools.lru_cache(maxsize=None)
-def deck_expected(L, pset):
-    entry, args = deck.PARAM_SETS[pset]
-    assert entry == "coverage"
-    out, off = rx.coverage(deck_resized(L), deck.ranges(), args["binsize"], args["ss"])
-    assert out.max(initial=0) < 2 ** 31
-    out = out.astype(np.int32)
-    out.setflags(write=False)
-    return out, off
+deck_resized = deck.resized_columns      # (the deck holds them: tests/test_later_forms_gpu.py compares with the same)
+deck_expected = deck.expected_resized
 
 
 @pytest.mark.parametrize("threads", [64, 128, 256])
