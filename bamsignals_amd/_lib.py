@@ -273,6 +273,20 @@ def load():
         lib.bsig_coverage_sum_spliced.argtypes = core_head + [C.c_int32] * 7 + [C.c_void_p]
         lib.bsig_coverage_runs_spliced.argtypes = core_head + [C.c_int32] * 7 + [C.POINTER(C.c_void_p)]
         lib.bsig_coverage_views_spliced.argtypes = core_head + [C.c_int32] * 9 + [C.POINTER(C.c_void_p)]
+    # the junctions of spliced reads: the table's size, the query at handle level and at file level, the result handle
+    # (BSIG_LIB_PATH may name a build from before them -- the yardstick of scripts/junctions_times.py)
+    if hasattr(lib, "bsig_reads_junctions"):
+        lib.bsig_reads_n_junction_rows.argtypes = [C.c_void_p]
+        lib.bsig_reads_n_junction_rows.restype = C.c_int64
+        lib.bsig_reads_junctions.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.POINTER(C.c_void_p)]
+        lib.bsig_junctions.argtypes = core_head[:8] + [C.c_int32] * 6 + [C.POINTER(C.c_void_p)]
+        lib.bsig_junctions_result_n_seg.argtypes = [C.c_void_p]
+        lib.bsig_junctions_result_n_seg.restype = C.c_int64
+        lib.bsig_junctions_result_n_junctions.argtypes = [C.c_void_p]
+        lib.bsig_junctions_result_n_junctions.restype = C.c_int64
+        lib.bsig_junctions_result_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+        lib.bsig_junctions_result_free.argtypes = [C.c_void_p]
+        lib.bsig_junctions_result_free.restype = None
     lib.bsig_views_result_n_seg.argtypes = [C.c_void_p]
     lib.bsig_views_result_n_seg.restype = C.c_int64
     lib.bsig_views_result_n_views.argtypes = [C.c_void_p]

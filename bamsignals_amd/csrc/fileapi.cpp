@@ -19,6 +19,7 @@
 #include "collect.h"
 #include "filecall.h"
 #include "host_util.h"
+#include "junctions.h"
 #include "runtime_internal.h"
 
 using bsig::EncodedColumns;
@@ -651,6 +652,25 @@ int bsig_coverage_views_spliced(const char *bampath, int64_t n, const int32_t *s
                                      coverage_params(tlen_filter, n_tlen_filter, mapqual, requiredF, filteredF, 0, true, binsize, ss), device,
                                      {}, false),
                         bsig::views_encoder(lower, upper), result);
+}
+
+// bamJunctions: the junctions of the ranges from the file's spliced reads.  A spliced call with a coverage call's parameters
+// (the dispatcher's stages judge and decode as for bamCoverage(splice = TRUE): the same resident set) and a destination of
+// its own; min_anchor is judged with the rest before the BAM is opened
+int bsig_junctions(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                   const char *const *levels, const int32_t *start, const int32_t *width,
+                   const int32_t *strand, int32_t mapqual, int32_t requiredF, int32_t filteredF,
+                   int32_t min_anchor, int32_t ss, int32_t device, bsig_junctions_result **result)
+{
+    if (!result) return fail(BSIG_ERR_ARG, "result is NULL");
+    *result = nullptr;
+    std::unique_ptr<bsig_junctions_result> res(new bsig_junctions_result);
+    res->ss = ss != 0;
+    const int rc = file_level(spliced_call({bampath, n, seq_code, n_levels, levels, start, width, strand},
+                                           coverage_params(nullptr, 0, mapqual, requiredF, filteredF, 0, true, 1, ss), device,
+                                           FileDest::junction_table(res.get(), min_anchor), true));
+    if (rc == BSIG_OK) *result = res.release();
+    return rc;
 }
 
 int64_t bsig_runs_result_n_seg(const bsig_runs_result *r) { return r ? r->n_seg : 0; }

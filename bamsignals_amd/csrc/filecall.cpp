@@ -21,6 +21,7 @@
 
 #include "collect.h"
 #include "host_util.h"
+#include "junctions.h"
 #include "rangemath.h"
 
 namespace bsig {
@@ -874,6 +875,10 @@ int judge_call(const FileCall &c, Stage &s)
         return fail(BSIG_ERR_ARG, "lower (%d) is above upper (%d)", (int)to.enc.lower, (int)to.enc.upper);
     if (c.overlap && c.overlap_type != 0 && c.overlap_type != 1) return fail(BSIG_ERR_ARG, "overlap type must be 0 (any) or 1 (within)");
     if (c.filter_missing) return fail(BSIG_ERR_ARG, "tlen_filter missing");
+    if (to.shape == Shape::junctions) {
+        if (!to.junctions) return fail(BSIG_ERR_ARG, "result is NULL");
+        if (const int rk = junctions_rule(to.arg)) return rk;
+    }
     if (c.spliced) {
         // what bsig_plan_create would refuse on spliced reads, before any I/O: only the coverage of the blocks as they lie
         if (c.prm.mode != BSIG_MODE_COVERAGE && c.prm.mode != BSIG_MODE_COVERAGE_EX)
@@ -1269,6 +1274,18 @@ int acquire_reads(Stage &s)
     return BSIG_OK;
 }
 
+// The junctions of the ranges (bsig_junctions): the query of junctions.hip on the first slot's spliced set -- the table is
+// the same on every slot, and only the distinct junctions come back
+int junctions_on_first(const Stage &s, std::string &route)
+{
+    const FileCall &c = s.call;
+    const RangeView g = s.ranges();
+    const int rc = junctions_query(s.res->reads[0], g.n, g.rid, g.loc, g.width, g.strand, c.prm.mapqual, c.prm.requiredF, c.prm.filteredF,
+                                   c.to.arg, c.prm.ss, c.to.junctions);
+    route = "junctions of " + std::to_string(g.n) + " range(s), counted on the first GPU";
+    return rc;
+}
+
 // one GPU, the per-range result: plan (ranges -> tiles in HBM), kernels, download -- timed apart
 int run_on_one(const Stage &s, double t_run)
 {
@@ -1292,12 +1309,13 @@ int run_result(const Stage &s, std::string &result)
     int rc = BSIG_ERR_NOMEM;
     for (int attempt = 0; attempt < 2 && rc == BSIG_ERR_NOMEM; ++attempt) {
         if (attempt) drop_spare_device_memory(s.slots.get());
-        if (to.shape == FileDest::Shape::reduced) rc = reduced_on_slots(s, result);
+        if (to.shape == FileDest::Shape::junctions) rc = junctions_on_first(s, result);
+        else if (to.shape == FileDest::Shape::reduced) rc = reduced_on_slots(s, result);
         else if (to.runs) rc = encoded_on_slots(s, result);
         else if (!s.many) rc = run_on_one(s, t_run);
         else rc = run_on_slots(s, result);
     }
-    if (!s.many && to.shape != FileDest::Shape::reduced && !to.runs) result = "download";
+    if (!s.many && to.shape != FileDest::Shape::reduced && to.shape != FileDest::Shape::junctions && !to.runs) result = "download";
     return rc;
 }
 

@@ -34,10 +34,11 @@ inline Encoder runs_encoder() { return Encoder{EncoderKind::runs, "runs", 2, {4,
 inline Encoder views_encoder(int32_t lower, int32_t upper) { return Encoder{EncoderKind::views, "views", 5, {4, 4, 8, 4, 4}, lower, upper}; }
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
-// layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, or an encoder's columns
+// layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, an encoder's columns, or the columns of
+// a junction query (junctions.hip)
 enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled, vplot, capped };
 struct FileDest {
-    enum class Shape { flat, into, reduced, encoded } shape = Shape::flat;
+    enum class Shape { flat, into, reduced, encoded, junctions } shape = Shape::flat;
     int32_t *out = nullptr;
     const int64_t *off = nullptr;
     int32_t *const *dst = nullptr;
@@ -46,10 +47,11 @@ struct FileDest {
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
     const char *name = "out";       // ... as the entry point calls that argument
     int32_t arg = 0;                // xcorr: max_lag; frag, vplot: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins;
-                                    // capped: keep_dup
+                                    // capped: keep_dup; junctions: min_anchor
     const int32_t *thresholds = nullptr;    // summary: arg of them
     EncodedColumns *runs = nullptr;         // the per-range result as runs or views (enc says which), in the caller's range order
     Encoder enc = runs_encoder();
+    EncodedColumns *junctions = nullptr;    // the ranges' distinct junctions with their counts: start, end, count, max_anchor
     static FileDest flat(int32_t *out, const int64_t *off)
     {
         FileDest to;
@@ -82,6 +84,12 @@ struct FileDest {
         to.shape = Shape::encoded; to.runs = cols; to.enc = enc;
         return to;
     }
+    static FileDest junction_table(EncodedColumns *cols, int32_t min_anchor)
+    {
+        FileDest to;
+        to.shape = Shape::junctions; to.junctions = cols; to.arg = min_anchor;
+        return to;
+    }
 };
 
 // the GRanges slots as the shim flattens them: the eight arguments every file-level entry point begins with
@@ -107,7 +115,7 @@ struct FileCall {
     bool overlap = false;           // bamOverlaps: its type as given, and whether a tlen_filter was promised but not passed
     int32_t overlap_type = 0;
     bool filter_missing = false;
-    bool spliced = false;           // coverage that skips N gaps: the call runs on the file's spliced reads (splice.hip)
+    bool spliced = false;           // coverage that skips N gaps, or the junctions: the call runs on the file's spliced reads (splice.hip)
 };
 int file_level(const FileCall &call);
 

@@ -906,6 +906,19 @@ int bsig_reads_clone(const bsig_reads *src, bsig_ctx *dst_ctx, bsig_reads **out)
         copy(src->dev.fmtab, BSIG_PACK_CODES * sizeof(uint32_t), &p);
         R->dev.fmtab = (const uint32_t *)p;
     }
+    if (src->junc.n > 0) {      // a spliced set's junction table (junctions.hip)
+        const bsig_reads::Junctions &S = src->junc;
+        bsig_reads::Junctions &D = R->junc;
+        const size_t rows = (size_t)S.n;
+        void *p;
+        copy(S.start, rows * sizeof(int32_t), &p); D.start = (const int32_t *)p;
+        copy(S.end, rows * sizeof(int32_t), &p); D.end = (const int32_t *)p;
+        copy(S.fm, rows * sizeof(uint32_t), &p); D.fm = (const uint32_t *)p;
+        copy(S.anchor, rows * sizeof(int32_t), &p); D.anchor = (const int32_t *)p;
+        copy(S.ref_off, ((size_t)src->n_ref + 1) * sizeof(int64_t), &p); D.ref_off = (const int64_t *)p;
+        D.n = S.n;
+    }
+    R->junc.h_ref_off = src->junc.h_ref_off;
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         delete R;

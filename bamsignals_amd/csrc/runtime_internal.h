@@ -182,6 +182,16 @@ struct bsig_reads {
     uint64_t layout_gen = 0;
     // the rows are aligned blocks of reads split at their N gaps (splice.hip), not reads: only plain coverage may be asked
     bool spliced = false;
+    // a spliced set's junction table (junctions.hip): one row per gap of a read, stably sorted by (reference, start, end);
+    // the columns live in `pool`.  A plain set has none
+    struct Junctions {
+        int64_t n = 0;                                   // rows
+        const int32_t *start = nullptr, *end = nullptr;  // first and last base of the gap
+        const uint32_t *fm = nullptr;                    // the read's flag | mapq << 16
+        const int32_t *anchor = nullptr;                 // min(aligned bases left of the gap, right of it)
+        const int64_t *ref_off = nullptr;                // device: the first row of every reference, n_ref + 1 entries
+        std::vector<int64_t> h_ref_off;                  // ... on the host
+    } junc;
 };
 namespace bsig { uint64_t next_layout_gen(); }
 

@@ -11,6 +11,7 @@
 //   order       rocPRIM's device radix sort of (key, row): stable, so ties keep BAM order and then block order;
 //   gather      k_block_gather: the five columns of the sorted rows; ref_off' follows from the scan (the rows of one
 //               reference stay contiguous), and layout_from_device does the rest.
+// The gap table is not thrown away behind the split: junctions.hip keeps it with the set, sorted, as its junction table.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -18,6 +19,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "junctions.h"
 #include "kernels.h"
 #include "splice.h"
 
@@ -260,8 +262,10 @@ int spliced_layout(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_ref, const
     hipStream_t st = ctx->stream;
     HIP_TRY(hipSetDevice(ctx->device));
     R->spliced = true;
-    if (n <= 0 || n_ref <= 0)
+    if (n <= 0 || n_ref <= 0) {
+        if (const int rc = junctions_build(ctx, R, 0, n_ref, nullptr, nullptr, nullptr, nullptr, nullptr, GapTable{})) return rc;
         return layout_from_device(ctx, R, 0, n_ref, ref_len, ref_off, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }
     if (n >= ((int64_t)1 << 32) - 8) return fail(BSIG_ERR_ARG, "more than 2^32 reads in a spliced set");
     DevPool tmp(2.0);
     // ---- blocks per read, their scan ------------------------------------------------------------------------------
@@ -277,6 +281,8 @@ int spliced_layout(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_ref, const
     HIP_TRY(tmp.alloc(&d_ref_row, (size_t)n_ref + 1));
     HIP_TRY(hipMemcpyAsync(d_ref_off, ref_off, ((size_t)n_ref + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_ref_row, 0xFF, ((size_t)n_ref + 1) * sizeof(long long), st));
+    // the gaps themselves stay with the set as its junction table (junctions.hip), in the set's own pool
+    if (const int rc = junctions_build(ctx, R, n, n_ref, d_ref_off, d_pos, d_end, d_flag, d_mapq, gaps)) return rc;
     hipLaunchKernelGGL(k_block_count, dim3((unsigned)n_groups), dim3(kSpliceThreads), 0, st, n, d_pos, d_end, gaps.rows, gaps.n,
                        d_read_blocks, d_group_blocks);
     HIP_TRY(hipGetLastError());

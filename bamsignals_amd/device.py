@@ -218,6 +218,27 @@ class Reads:
         """Are the rows aligned blocks of reads split at their N gaps?"""
         return bool(self._lib.bsig_reads_is_spliced(self._h))
 
+    @property
+    def n_junction_rows(self):
+        """Rows of a spliced set's junction table: one per N gap of a read (0 for a plain set)."""
+        return int(self._lib.bsig_reads_n_junction_rows(self._h))
+
+    def junctions(self, rid, loc, length, strand, mapqual=0, requiredF=0, filteredF=-1, min_anchor=0, ss=False):
+        """The distinct junctions of every range with their supporting reads (csrc/junctions.hip), counted on the GPU from
+        the set's junction table: ``(seg_off, start, end, count, max_anchor)`` -- range i owns entries ``seg_off[i] ..
+        seg_off[i + 1]``, ``start`` / ``end`` are the gap's first and last base (0-based), ``count`` is uint32 of shape
+        ``(n,)`` or, with ``ss``, ``(n, 2)`` (sense, antisense).  A junction belongs to a range that contains it whole; a
+        row counts if it passes ``mapqual`` / ``requiredF`` / ``filteredF`` and its anchor is at least ``min_anchor``.
+        Only a spliced set has a table."""
+        rid, loc, length, strand = (_i32(a) for a in (rid, loc, length, strand))
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_reads_junctions(self._h, n, _ptr(rid), _ptr(loc), _ptr(length), _ptr(strand), int(mapqual),
+                                                  int(requiredF), int(filteredF), int(min_anchor), int(bool(ss)), C.byref(h)))
+        return take_junctions(self._lib, h, ss)
+
     @staticmethod
     def device_decode_timing():
         """Stage seconds of this thread's last ``from_bam`` (all 0 when it took the CPU decode)."""
@@ -241,6 +262,18 @@ class Reads:
 
     def __del__(self):
         self.close()
+
+
+def take_junctions(lib, handle, ss):
+    """a bsig_junctions_result handle -> (seg_off, start, end, count, max_anchor); the handle is freed"""
+    try:
+        n_seg, n = int(lib.bsig_junctions_result_n_seg(handle)), int(lib.bsig_junctions_result_n_junctions(handle))
+        out = [np.empty(n_seg + 1, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32),
+               np.empty((n, 2) if ss else (n,), dtype=np.uint32), np.empty(n, dtype=np.int32)]
+        _lib.check(lib.bsig_junctions_result_copy(handle, *[a.ctypes.data if a.size else None for a in out]))
+    finally:
+        lib.bsig_junctions_result_free(handle)
+    return tuple(out)
 
 
 def make_params(mode, tlen_filter=(), mapqual=0, binsize=1, shift=0, ss=False, requiredF=0,

@@ -957,6 +957,45 @@ int64_t bsig_views_result_n_views(const bsig_views_result *result);
 int bsig_views_result_copy(const bsig_views_result *result, int64_t *seg_off, int32_t *start, int32_t *width, int64_t *sum,
                            int32_t *max, int32_t *summit);
 void bsig_views_result_free(bsig_views_result *result);
+/* ------------------------------------------------------------------------------------------
+ * Splice junctions with read counts (GenomicAlignments::summarizeJunctions' score / plus_score / minus_score, STAR's
+ * SJ.out.tab columns 7 and 9, regtools' anchor filter), found on the GPU (csrc/junctions.hip).
+ * A spliced bsig_reads keeps its gap table as a JUNCTION TABLE: every gap of every read (the gaps defined above
+ * bsig_reads_upload_spliced) is one row with its reference, its first and last base (0-based), its read's flag and mapq and
+ * its ANCHOR = min(left, right): the reference bases of the aligned block that ends right before the gap and of the one
+ * that begins right behind it (back to the read's previous gap or its pos, forward to its next gap or its end; D counts, I
+ * does not; a side without an aligned base is 0).  The rows are stably sorted by (reference, start, end) and live in the
+ * object's own device memory (bsig_reads_info.hbm_bytes counts them, bsig_reads_clone copies them); fewer than 2^32 - 8
+ * rows.  A plain object has no table: bsig_reads_n_junction_rows is 0, bsig_reads_junctions is BSIG_ERR_ARG.
+ * The query: a row belongs to range i iff it is on the range's reference, start >= loc and end <= loc + len - 1 (the junction
+ * lies within the range), it passes mapqual / requiredF / filteredF exactly as a read passes them in every other call, and
+ * anchor >= min_anchor (>= 0).  Range i's result is the distinct (start, end) among its rows, ascending by start, then end,
+ * each with count = the number of rows -- with ss two values, (sense, antisense): sense iff the row's 0x10 bit agrees with the
+ * range's strand, '*' counted as '+' -- and max_anchor = the largest anchor among them.  Ranges are independent (overlapping
+ * ranges each report a shared junction); a range of width 0 or without rows owns nothing.  seg_off has n + 1 entries in the
+ * caller's range order.  More than 2^32 - 8 (range, row) pairs in one query is BSIG_ERR_ARG.  All integer work: the result
+ * does not depend on the order in which the GPU runs it.
+ * bsig_junctions is the file-level call: the eight range arguments of every file-level call, on the file's spliced reads
+ * (the same resident set bsig_coverage_*_spliced use, whole-file or index-driven as the ranges ask); its parameters are
+ * judged before the BAM is opened; bsig_last_call_route() says "junctions".  With several GPUs the first one answers.
+ * The result handle: start, end, max_anchor hold one int32 per junction, count one uint32 -- two with ss.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct bsig_junctions_result bsig_junctions_result;
+int64_t bsig_reads_n_junction_rows(const bsig_reads *reads);     /* 0 for NULL and for a plain object                 */
+int bsig_reads_junctions(const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc, const int32_t *len,
+                         const int32_t *strand, int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_anchor,
+                         int32_t ss, bsig_junctions_result **result);
+int bsig_junctions(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_anchor, int32_t ss,
+    int32_t device, bsig_junctions_result **result);
+int64_t bsig_junctions_result_n_seg(const bsig_junctions_result *result);
+int64_t bsig_junctions_result_n_junctions(const bsig_junctions_result *result);
+int bsig_junctions_result_copy(const bsig_junctions_result *result, int64_t *seg_off, int32_t *start, int32_t *end,
+                               uint32_t *count, int32_t *max_anchor);
+void bsig_junctions_result_free(bsig_junctions_result *result);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
