@@ -287,6 +287,21 @@ def load():
         lib.bsig_junctions_result_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         lib.bsig_junctions_result_free.argtypes = [C.c_void_p]
         lib.bsig_junctions_result_free.restype = None
+    # reads per gene: the host-side gene model, the read table's size, the query at handle level and at file level
+    # (BSIG_LIB_PATH may name a build from before them -- the yardstick of scripts/genecounts_times.py)
+    if hasattr(lib, "bsig_reads_gene_counts"):
+        lib.bsig_gene_model_create.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int32] * 2 + [C.POINTER(C.c_void_p)]
+        lib.bsig_gene_model_free.argtypes = [C.c_void_p]
+        lib.bsig_gene_model_free.restype = None
+        lib.bsig_gene_model_n_genes.argtypes = [C.c_void_p]
+        lib.bsig_gene_model_n_ref.argtypes = [C.c_void_p]
+        lib.bsig_gene_model_n_segments.argtypes = [C.c_void_p, C.c_int32]
+        lib.bsig_gene_model_n_segments.restype = C.c_int64
+        lib.bsig_gene_model_copy_segments.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+        lib.bsig_reads_n_source_reads.argtypes = [C.c_void_p]
+        lib.bsig_reads_n_source_reads.restype = C.c_int64
+        lib.bsig_reads_gene_counts.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 2
+        lib.bsig_gene_counts.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)] + [C.c_int32] * 5 + [C.c_void_p] * 2
     lib.bsig_views_result_n_seg.argtypes = [C.c_void_p]
     lib.bsig_views_result_n_seg.restype = C.c_int64
     lib.bsig_views_result_n_views.argtypes = [C.c_void_p]

@@ -18,6 +18,7 @@
 #include "bamio.h"
 #include "collect.h"
 #include "filecall.h"
+#include "genecounts.h"
 #include "host_util.h"
 #include "junctions.h"
 #include "runtime_internal.h"
@@ -671,6 +672,19 @@ int bsig_junctions(const char *bampath, int64_t n, const int32_t *seq_code, int3
                                            FileDest::junction_table(res.get(), min_anchor), true));
     if (rc == BSIG_OK) *result = res.release();
     return rc;
+}
+
+// bamGeneCounts: every read of the file's spliced reads against a gene model.  A spliced call without ranges (the model's
+// references are the names in seq_levels) on the whole file's resident set, with a destination of its own; the parameters are
+// judged before the BAM is opened
+int bsig_gene_counts(const char *bampath, const bsig_gene_model *model, int32_t n_levels, const char *const *levels, int32_t mapqual,
+                     int32_t requiredF, int32_t filteredF, int32_t strandedness, int32_t device, int64_t *counts, int64_t *summary)
+{
+    FileCall c = spliced_call({bampath, 0, nullptr, n_levels, levels, nullptr, nullptr, nullptr},
+                              coverage_params(nullptr, 0, mapqual, requiredF, filteredF, 0, true, 1, 0), device,
+                              FileDest::gene_table(model, strandedness, counts, summary), true);
+    c.whole_file = true;
+    return file_level(c);
 }
 
 int64_t bsig_runs_result_n_seg(const bsig_runs_result *r) { return r ? r->n_seg : 0; }

@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "collect.h"
+#include "genecounts.h"
 #include "host_util.h"
 #include "junctions.h"
 #include "rangemath.h"
@@ -342,6 +343,7 @@ struct Stage {
     std::shared_ptr<Slots> slots;           // slots_for: the GPUs, whether the multi-GPU routes are taken, the reads' cache key
     bool many = false;
     std::string rkey;
+    std::vector<int32_t> ref_map;           // resolve_gene_references: for every reference of the BAM the model's, or -1
     std::shared_ptr<Resident> res;          // acquire_reads: the reads on every slot and where they came from
     std::string how_decoded = "resident";
     RangeView ranges() const { return RangeView{call.at.n, rid.data(), loc.data(), call.at.width, call.at.strand}; }
@@ -879,6 +881,12 @@ int judge_call(const FileCall &c, Stage &s)
         if (!to.junctions) return fail(BSIG_ERR_ARG, "result is NULL");
         if (const int rk = junctions_rule(to.arg)) return rk;
     }
+    if (to.shape == Shape::genes) {
+        if (const int rk = gene_counts_rule(to.model, to.arg, to.gene_counts, to.gene_summary)) return rk;
+        if (at.n_levels != to.model->host.n_ref)
+            return fail(BSIG_ERR_ARG, "the gene model has %d references, %d sequence names were given", (int)to.model->host.n_ref, (int)at.n_levels);
+        if (at.n_levels > 0 && !at.levels) return fail(BSIG_ERR_ARG, "sequence names missing");
+    }
     if (c.spliced) {
         // what bsig_plan_create would refuse on spliced reads, before any I/O: only the coverage of the blocks as they lie
         if (c.prm.mode != BSIG_MODE_COVERAGE && c.prm.mode != BSIG_MODE_COVERAGE_EX)
@@ -1020,6 +1028,20 @@ int resolve_ranges(Stage &s)
     return BSIG_OK;
 }
 
+// ... of a gene count: the model's references are the names in `levels`; every one must be a reference of the BAM
+int resolve_gene_references(Stage &s)
+{
+    const RangeArgs &at = s.call.at;
+    s.ref_map.assign((size_t)bsig_bam_n_ref(s.ob->bam), -1);
+    for (int32_t c = 0; c < at.n_levels; ++c) {
+        const int32_t rid = at.levels[c] ? bsig_bam_name2id(s.ob->bam, at.levels[c]) : -1;
+        if (rid < 0 || (size_t)rid >= s.ref_map.size())
+            return fail(BSIG_ERR_CHROM, "chromosome %s not present in the bam file", at.levels[c] ? at.levels[c] : "(null)");
+        s.ref_map[(size_t)rid] = c;
+    }
+    return BSIG_OK;
+}
+
 // Stage 4: the GPUs of this call.  Every device list seen keeps its own contexts, scratch and resident BAMs (a session
 // that alternates between two device= arguments keeps both copies; the LRU budget bounds them).
 int slots_for(const std::vector<int> &devs, Stage &s)
@@ -1066,6 +1088,7 @@ Wanted what_to_decode(const Stage &s)
     w.whole = wanted * 3 > genome;
     if (force && !strcmp(force, "all")) w.whole = true;
     if (force && !strcmp(force, "regions")) w.whole = false;
+    if (s.call.whole_file) w.whole = true;
     if (!w.whole) {
         w.qbeg.resize((size_t)at.n); w.qend.resize((size_t)at.n);
         for (int64_t i = 0; i < at.n; ++i) {
@@ -1286,6 +1309,19 @@ int junctions_on_first(const Stage &s, std::string &route)
     return rc;
 }
 
+// The reads per gene (bsig_gene_counts): the query of genecounts.hip on the first slot's spliced set -- the read table is the
+// same on every slot, and only the two int64 vectors come back
+int gene_counts_on_first(const Stage &s, std::string &route)
+{
+    const FileCall &c = s.call;
+    const bsig_reads *R = s.res->reads[0];
+    if ((size_t)R->n_ref != s.ref_map.size()) return fail(BSIG_ERR_ARG, "the resident reads have %d references, the BAM %zu", (int)R->n_ref, s.ref_map.size());
+    const int rc = gene_counts_query(R, c.to.model, s.ref_map.data(), c.prm.mapqual, c.prm.requiredF, c.prm.filteredF, c.to.arg,
+                                     c.to.gene_counts, c.to.gene_summary);
+    route = "gene counts of " + std::to_string(c.to.model->host.n_genes) + " gene(s), counted on the first GPU";
+    return rc;
+}
+
 // one GPU, the per-range result: plan (ranges -> tiles in HBM), kernels, download -- timed apart
 int run_on_one(const Stage &s, double t_run)
 {
@@ -1310,12 +1346,14 @@ int run_result(const Stage &s, std::string &result)
     for (int attempt = 0; attempt < 2 && rc == BSIG_ERR_NOMEM; ++attempt) {
         if (attempt) drop_spare_device_memory(s.slots.get());
         if (to.shape == FileDest::Shape::junctions) rc = junctions_on_first(s, result);
+        else if (to.shape == FileDest::Shape::genes) rc = gene_counts_on_first(s, result);
         else if (to.shape == FileDest::Shape::reduced) rc = reduced_on_slots(s, result);
         else if (to.runs) rc = encoded_on_slots(s, result);
         else if (!s.many) rc = run_on_one(s, t_run);
         else rc = run_on_slots(s, result);
     }
-    if (!s.many && to.shape != FileDest::Shape::reduced && to.shape != FileDest::Shape::junctions && !to.runs) result = "download";
+    if (!s.many && to.shape != FileDest::Shape::reduced && to.shape != FileDest::Shape::junctions && to.shape != FileDest::Shape::genes && !to.runs)
+        result = "download";
     return rc;
 }
 
@@ -1372,6 +1410,7 @@ int file_level(const FileCall &call)
     if (rc) return rc;
     T[0] = now_s() - t_begin;
     rc = resolve_ranges(s);
+    if (rc == BSIG_OK && call.to.shape == FileDest::Shape::genes) rc = resolve_gene_references(s);
     if (rc == BSIG_OK) rc = slots_for(pick_devices(call.device), s);
     if (rc == BSIG_OK) rc = acquire_reads(s);
     if (rc) return rc;

@@ -35,10 +35,10 @@ inline Encoder views_encoder(int32_t lower, int32_t upper) { return Encoder{Enco
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
 // layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, an encoder's columns, or the columns of
-// a junction query (junctions.hip)
+// a junction query (junctions.hip), or the two int64 vectors of a gene count (genecounts.hip)
 enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled, vplot, capped };
 struct FileDest {
-    enum class Shape { flat, into, reduced, encoded, junctions } shape = Shape::flat;
+    enum class Shape { flat, into, reduced, encoded, junctions, genes } shape = Shape::flat;
     int32_t *out = nullptr;
     const int64_t *off = nullptr;
     int32_t *const *dst = nullptr;
@@ -47,11 +47,13 @@ struct FileDest {
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
     const char *name = "out";       // ... as the entry point calls that argument
     int32_t arg = 0;                // xcorr: max_lag; frag, vplot: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins;
-                                    // capped: keep_dup; junctions: min_anchor
+                                    // capped: keep_dup; junctions: min_anchor; genes: strandedness
     const int32_t *thresholds = nullptr;    // summary: arg of them
     EncodedColumns *runs = nullptr;         // the per-range result as runs or views (enc says which), in the caller's range order
     Encoder enc = runs_encoder();
     EncodedColumns *junctions = nullptr;    // the ranges' distinct junctions with their counts: start, end, count, max_anchor
+    const bsig_gene_model *model = nullptr; // a gene count: the model, counts[n_genes] and summary[5]
+    int64_t *gene_counts = nullptr, *gene_summary = nullptr;
     static FileDest flat(int32_t *out, const int64_t *off)
     {
         FileDest to;
@@ -90,6 +92,12 @@ struct FileDest {
         to.shape = Shape::junctions; to.junctions = cols; to.arg = min_anchor;
         return to;
     }
+    static FileDest gene_table(const bsig_gene_model *model, int32_t strandedness, int64_t *counts, int64_t *summary)
+    {
+        FileDest to;
+        to.shape = Shape::genes; to.model = model; to.arg = strandedness; to.gene_counts = counts; to.gene_summary = summary;
+        return to;
+    }
 };
 
 // the GRanges slots as the shim flattens them: the eight arguments every file-level entry point begins with
@@ -115,7 +123,9 @@ struct FileCall {
     bool overlap = false;           // bamOverlaps: its type as given, and whether a tlen_filter was promised but not passed
     int32_t overlap_type = 0;
     bool filter_missing = false;
-    bool spliced = false;           // coverage that skips N gaps, or the junctions: the call runs on the file's spliced reads (splice.hip)
+    bool spliced = false;           // coverage that skips N gaps, the junctions, the gene counts: the call runs on the file's spliced
+                                    // reads (splice.hip)
+    bool whole_file = false;        // the call speaks of every read of the file (the gene counts): never an index-driven decode
 };
 int file_level(const FileCall &call);
 

@@ -919,6 +919,20 @@ int bsig_reads_clone(const bsig_reads *src, bsig_ctx *dst_ctx, bsig_reads **out)
         D.n = S.n;
     }
     R->junc.h_ref_off = src->junc.h_ref_off;
+    if (src->rtab.n > 0) {      // a spliced set's read table (splice.hip, genecounts.hip)
+        const bsig_reads::ReadTable &S = src->rtab;
+        bsig_reads::ReadTable &D = R->rtab;
+        const size_t reads = (size_t)S.n, blocks = (size_t)std::max<int64_t>(S.n_blocks, 1);
+        void *p;
+        copy(S.blk_off, (reads + 1) * sizeof(uint32_t), &p); D.blk_off = (const uint32_t *)p;
+        copy(S.fm, reads * sizeof(uint32_t), &p); D.fm = (const uint32_t *)p;
+        copy(S.bstart, blocks * sizeof(int32_t), &p); D.bstart = (const int32_t *)p;
+        copy(S.bend, blocks * sizeof(int32_t), &p); D.bend = (const int32_t *)p;
+        copy(S.ref_off, ((size_t)src->n_ref + 1) * sizeof(int64_t), &p); D.ref_off = (const int64_t *)p;
+        D.n = S.n;
+        D.n_blocks = S.n_blocks;
+    }
+    R->rtab.h_ref_off = src->rtab.h_ref_off;
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         delete R;

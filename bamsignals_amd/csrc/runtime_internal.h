@@ -192,6 +192,18 @@ struct bsig_reads {
         const int64_t *ref_off = nullptr;                // device: the first row of every reference, n_ref + 1 entries
         std::vector<int64_t> h_ref_off;                  // ... on the host
     } junc;
+    // a spliced set's read table (splice.hip keeps it, genecounts.hip reads it): the reads in BAM order with their blocks as
+    // k_block_emit wrote them, before the sort forgets which read a block came from; the columns live in `pool`.  Read i
+    // owns blocks blk_off[i] .. blk_off[i + 1] (ascending, disjoint).  An empty spliced set has an empty table (n = 0, the
+    // offsets all 0), a plain set has none
+    struct ReadTable {
+        int64_t n = 0, n_blocks = 0;                     // reads, blocks
+        const uint32_t *blk_off = nullptr;               // n + 1 entries
+        const uint32_t *fm = nullptr;                    // flag | mapq << 16
+        const int32_t *bstart = nullptr, *bend = nullptr;    // first and last base of every block
+        const int64_t *ref_off = nullptr;                // device: the first read of every reference, n_ref + 1 entries
+        std::vector<int64_t> h_ref_off;                  // ... on the host
+    } rtab;
 };
 namespace bsig { uint64_t next_layout_gen(); }
 

@@ -12,6 +12,8 @@
 //   gather      k_block_gather: the five columns of the sorted rows; ref_off' follows from the scan (the rows of one
 //               reference stay contiguous), and layout_from_device does the rest.
 // The gap table is not thrown away behind the split: junctions.hip keeps it with the set, sorted, as its junction table.
+// Nor are the rows in read order: k_block_emit writes them into the set's own pool with every read's slice of them and its
+// flag | mapq << 16 -- the READ TABLE (runtime_internal.h), which genecounts.hip walks one read at a time.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -152,14 +154,17 @@ __device__ __forceinline__ int32_t ref_of(const int64_t *__restrict__ ref_off, i
 }
 
 // the block rows in read order: key, start, end and the read they come from; ref_row[r] = the row of reference r's first
-// read (written by that read; a reference without reads keeps -1)
+// read (written by that read; a reference without reads keeps -1).  read_first[i] = read i's first row (read_first[n] = m)
+// and read_fm[i] = its flag | mapq << 16: with bpos and bend the set's read table
 __global__ __launch_bounds__(kSpliceThreads) void k_block_emit(int64_t n, int32_t n_ref, const int64_t *__restrict__ ref_off,
                                                                const int32_t *__restrict__ pos, const int32_t *__restrict__ end,
                                                                const GapRow *__restrict__ rows, int64_t n_rows,
                                                                const uint32_t *__restrict__ read_blocks, const int64_t *__restrict__ group_base,
                                                                int64_t m, uint64_t *__restrict__ key, uint32_t *__restrict__ row_id,
                                                                int32_t *__restrict__ bpos, int32_t *__restrict__ bend,
-                                                               uint32_t *__restrict__ bread, long long *__restrict__ ref_row)
+                                                               uint32_t *__restrict__ bread, long long *__restrict__ ref_row,
+                                                               const uint16_t *__restrict__ flag, const uint8_t *__restrict__ mapq,
+                                                               uint32_t *__restrict__ read_first, uint32_t *__restrict__ read_fm)
 {
     __shared__ uint32_t scratch[kSpliceThreads];
     const int64_t i = (int64_t)blockIdx.x * kSpliceThreads + threadIdx.x;
@@ -170,6 +175,9 @@ __global__ __launch_bounds__(kSpliceThreads) void k_block_emit(int64_t n, int32_
     const int64_t at = group_base[blockIdx.x] + before;
     const int32_t rid = ref_of(ref_off, n_ref, i);
     if (ref_off[rid] == i) ref_row[rid] = at;
+    read_first[i] = (uint32_t)at;
+    read_fm[i] = (uint32_t)flag[i] | ((uint32_t)mapq[i] << 16);
+    if (i == n - 1) read_first[n] = (uint32_t)(at + c);
     if (!c) return;
     const int32_t p = pos[i], e = end[i];
     const uint64_t hi = (uint64_t)(uint32_t)rid << 32;
@@ -262,6 +270,8 @@ int spliced_layout(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_ref, const
     hipStream_t st = ctx->stream;
     HIP_TRY(hipSetDevice(ctx->device));
     R->spliced = true;
+    R->rtab = bsig_reads::ReadTable{};
+    R->rtab.h_ref_off.assign((size_t)std::max(n_ref, 0) + 1, 0);       // (an empty set: an empty table)
     if (n <= 0 || n_ref <= 0) {
         if (const int rc = junctions_build(ctx, R, 0, n_ref, nullptr, nullptr, nullptr, nullptr, nullptr, GapTable{})) return rc;
         return layout_from_device(ctx, R, 0, n_ref, ref_len, ref_off, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -296,15 +306,24 @@ int spliced_layout(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_ref, const
     uint64_t *d_key, *d_key_sorted;
     uint32_t *d_row, *d_order, *d_bread;
     int32_t *d_bpos, *d_bend;
+    uint32_t *d_read_first, *d_read_fm;
+    int64_t *d_read_ref_off;
     HIP_TRY(tmp.alloc(&d_key, cap));
     HIP_TRY(tmp.alloc(&d_key_sorted, cap));
     HIP_TRY(tmp.alloc(&d_row, cap));
     HIP_TRY(tmp.alloc(&d_order, cap));
     HIP_TRY(tmp.alloc(&d_bread, cap));
-    HIP_TRY(tmp.alloc(&d_bpos, cap));
-    HIP_TRY(tmp.alloc(&d_bend, cap));
+    // the read table stays with the set: its columns come from the set's own pool, so that hbm_bytes and the cache's budget
+    // count them
+    HIP_TRY(R->pool.alloc(&d_bpos, cap));
+    HIP_TRY(R->pool.alloc(&d_bend, cap));
+    HIP_TRY(R->pool.alloc(&d_read_first, (size_t)n + 1));
+    HIP_TRY(R->pool.alloc(&d_read_fm, (size_t)n));
+    HIP_TRY(R->pool.alloc(&d_read_ref_off, (size_t)n_ref + 1));
+    HIP_TRY(hipMemcpyAsync(d_read_ref_off, d_ref_off, ((size_t)n_ref + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_block_emit, dim3((unsigned)n_groups), dim3(kSpliceThreads), 0, st, n, n_ref, d_ref_off, d_pos, d_end, gaps.rows,
-                       gaps.n, d_read_blocks, d_group_base, m, d_key, d_row, d_bpos, d_bend, d_bread, d_ref_row);
+                       gaps.n, d_read_blocks, d_group_base, m, d_key, d_row, d_bpos, d_bend, d_bread, d_ref_row, d_flag, d_mapq, d_read_first,
+                       d_read_fm);
     HIP_TRY(hipGetLastError());
     std::vector<long long> ref_row((size_t)n_ref + 1, -1);
     HIP_TRY(hipMemcpyAsync(ref_row.data(), d_ref_row, ref_row.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -335,6 +354,10 @@ int spliced_layout(bsig_ctx *ctx, bsig_reads *R, int64_t n, int32_t n_ref, const
     for (int32_t r = n_ref - 1; r >= 0; --r)
         row_off[(size_t)r] = ref_off[r] < ref_off[r + 1] && ref_row[(size_t)r] >= 0 ? (int64_t)ref_row[(size_t)r] : row_off[(size_t)r + 1];
     row_off[0] = 0;
+    bsig_reads::ReadTable &T = R->rtab;
+    T.n = n; T.n_blocks = m;
+    T.blk_off = d_read_first; T.fm = d_read_fm; T.bstart = d_bpos; T.bend = d_bend; T.ref_off = d_read_ref_off;
+    T.h_ref_off.assign(ref_off, ref_off + n_ref + 1);
     // layout_from_device synchronises the stream before it returns: tmp may be released then
     return layout_from_device(ctx, R, m, n_ref, ref_len, row_off.data(), o_pos, o_end, o_flag, o_mapq, o_tlen);
 }

@@ -239,6 +239,27 @@ class Reads:
                                                   int(requiredF), int(filteredF), int(min_anchor), int(bool(ss)), C.byref(h)))
         return take_junctions(self._lib, h, ss)
 
+    @property
+    def n_source_reads(self):
+        """Reads a spliced set was made from, the rows of its read table (``info()["n_reads"]`` counts blocks); 0 for a
+        plain set."""
+        return int(self._lib.bsig_reads_n_source_reads(self._h))
+
+    def gene_counts(self, model, mapqual=0, requiredF=0, filteredF=-1, strand="unstranded"):
+        """Reads per gene (csrc/genecounts.hip): every read of the set's read table classified against ``model`` (a
+        ``genecounts.GeneModel`` whose ``n_ref`` is the set's), on the GPU: ``(counts, summary)`` -- int64, one count per
+        gene and the five of ``genecounts.SUMMARY_FIELDS`` (assigned, ambiguous, no_feature, filtered, unmapped), which add
+        up to ``n_source_reads``.  ``strand``: "unstranded", "forward" or "reverse".  Only a spliced set has a read table."""
+        from .genecounts import GeneModel, strand_code
+        if not isinstance(model, GeneModel):
+            raise TypeError("model must be a GeneModel")
+        mode = strand_code(strand)
+        counts = np.zeros(max(model.n_genes, 1), dtype=np.int64)
+        summary = np.zeros(5, dtype=np.int64)
+        _lib.check(self._lib.bsig_reads_gene_counts(self._h, model._h, int(mapqual), int(requiredF), int(filteredF), mode,
+                                                    _ptr(counts), _ptr(summary)))
+        return counts[:model.n_genes], summary
+
     @staticmethod
     def device_decode_timing():
         """Stage seconds of this thread's last ``from_bam`` (all 0 when it took the CPU decode)."""

@@ -996,6 +996,51 @@ int64_t bsig_junctions_result_n_junctions(const bsig_junctions_result *result);
 int bsig_junctions_result_copy(const bsig_junctions_result *result, int64_t *seg_off, int32_t *start, int32_t *end,
                                uint32_t *count, int32_t *max_anchor);
 void bsig_junctions_result_free(bsig_junctions_result *result);
+/* ------------------------------------------------------------------------------------------
+ * Reads per gene over exon models (HTSeq's union mode = featureCounts' default = summarizeOverlaps mode "Union"), counted
+ * on the GPU (csrc/genecounts.hip).
+ * A GENE MODEL is n features (reference rid in 0 .. n_ref - 1, 0-based loc, len, strand -1 / 0 / +1) with gene[i] in
+ * 0 .. n_genes - 1 saying which gene feature i belongs to.  Features may overlap, repeat, nest and come in any order; a
+ * feature of width 0 takes part in nothing; a gene may have no feature.  bsig_gene_model_create flattens them on the host
+ * (csrc/genemodel.h; no GPU is needed for any bsig_gene_model_* call) into three tables of disjoint segments sorted by
+ * (reference, start): table 0 from all features, 1 from those with strand +1 or 0, 2 from those with strand -1 or 0.  A
+ * segment's value is the one gene active there, or -1 where two or more genes overlap; touching segments of equal value are
+ * one.  Refused with BSIG_ERR_ARG, naming the first offending feature: a negative width, a reference outside 0 .. n_ref - 1,
+ * a gene outside 0 .. n_genes - 1, a strand outside -1 .. 1, loc + len beyond 2^31 - 1.
+ * bsig_gene_model_copy_segments: ref_off has n_ref + 1 entries; start / end are a segment's first and last base.
+ * A spliced bsig_reads keeps a READ TABLE: its source reads in BAM order, each with its aligned blocks (what
+ * bsig_coverage_*_spliced cover) and its flag and mapq, in the object's own device memory (hbm_bytes counts it,
+ * bsig_reads_clone copies it).  bsig_reads_n_source_reads is their number (bsig_reads_info.n_reads of a spliced object counts
+ * blocks); 0 for NULL and for a plain object.
+ * bsig_reads_gene_counts classifies every source read, in this order: flag & 0x4 -> unmapped; failing mapqual / requiredF /
+ * filteredF as in every other call -> filtered; else with s = -1 if flag & 0x10 else +1, flipped if (flag & 0x81) == 0x81 (a
+ * second mate), a feature of strand f MATCHES under strandedness 0 (unstranded) always, 1 (forward) iff f == 0 or f == s,
+ * 2 (reverse) iff f == 0 or f == -s; H = the genes with a matching feature on the read's reference that shares a base with a
+ * block of the read; |H| = 0 -> no_feature, 1 -> assigned (counts[that gene] += 1), >= 2 -> ambiguous.  counts has n_genes
+ * entries, summary five: assigned, ambiguous, no_feature, filtered, unmapped; they sum to the number of source reads.  The
+ * model's n_ref must be the object's; a plain object is BSIG_ERR_ARG.  All integer work: the result does not depend on the
+ * order in which the GPU runs it.  The model's tables are copied to a GPU at its first query there and stay until
+ * bsig_gene_model_free.
+ * bsig_gene_counts is the file-level call: the model's reference r is the sequence named seq_levels[r] (n_seq_levels must be
+ * the model's n_ref; a name the BAM lacks is BSIG_ERR_CHROM), the reads are the WHOLE file's spliced reads (the resident set
+ * bsig_coverage_*_spliced and bsig_junctions use when they decode the whole file); its parameters are judged before the BAM
+ * is opened; bsig_last_call_route() says "gene counts".  With several GPUs the first one answers.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct bsig_gene_model bsig_gene_model;
+int bsig_gene_model_create(int64_t n_features, const int32_t *rid, const int32_t *loc, const int32_t *len, const int32_t *strand,
+                           const int32_t *gene, int32_t n_genes, int32_t n_ref, bsig_gene_model **model);
+void bsig_gene_model_free(bsig_gene_model *model);
+int32_t bsig_gene_model_n_genes(const bsig_gene_model *model);
+int32_t bsig_gene_model_n_ref(const bsig_gene_model *model);
+int64_t bsig_gene_model_n_segments(const bsig_gene_model *model, int32_t table);    /* -1 for a table that is none of 0, 1, 2 */
+int bsig_gene_model_copy_segments(const bsig_gene_model *model, int32_t table, int64_t *ref_off, int32_t *start, int32_t *end,
+                                  int32_t *value);
+int64_t bsig_reads_n_source_reads(const bsig_reads *reads);
+int bsig_reads_gene_counts(const bsig_reads *reads, const bsig_gene_model *model, int32_t mapqual, int32_t requiredF,
+                           int32_t filteredF, int32_t strandedness, int64_t *counts, int64_t *summary);
+int bsig_gene_counts(const char *bampath, const bsig_gene_model *model, int32_t n_seq_levels, const char *const *seq_levels,
+                     int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t strandedness, int32_t device,
+                     int64_t *counts, int64_t *summary);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
