@@ -868,6 +868,9 @@ int bsig_reads_clone(const bsig_reads *src, bsig_ctx *dst_ctx, bsig_reads **out)
     }
     bsig_reads *R = new bsig_reads;
     R->ctx = dst_ctx;
+    // a layout of its own: with the 0 a new set starts with, a plan's second run on the clone took its windows for looked
+    // up already (resolved_gen 0 == layout_gen 0, run_main) and read a table nothing had written
+    R->layout_gen = bsig::next_layout_gen();
     R->info = src->info;
     R->spliced = src->spliced;
     R->n_ref = src->n_ref;

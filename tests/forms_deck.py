@@ -141,10 +141,14 @@ def _permuted(rng, counts):
 
 
 @functools.lru_cache(maxsize=None)
-def reads():
+def reads(placement=None):
     """dict(ref_len, ref_off, pos, end, flag, mapq, tlen, short_refs, long_refs, c0_refs, pair_refs, short_m, long_m, c0_m,
     pair_m): the columns, and the islands' reference ids with their read counts (in reference order, a seeded
-    permutation of the counts)."""
+    permutation of the counts).  placement (a far_deck.Placement; here and in every function below): the deck moved
+    to far coordinates -- the same code on the placed columns and ranges, cached per placement."""
+    if placement is not None:
+        import far_deck
+        return far_deck.place_columns(reads(), placement)
     rng = np.random.default_rng(20_250)
     parts, ref_len = [], list(BULK_REFS)
     for L in BULK_REFS:
@@ -207,14 +211,32 @@ def island_windows(packed, cls_id, refs):
     return before[lo], before[hi] - before[lo]
 
 
-def oracle_reads(mask=None):
+def oracle_reads(mask=None, placement=None):
     from oracle import oracle_c
-    c = reads()
+    c = _reads(placement)
     if mask is None:
         return oracle_c.OracleReads(c["ref_off"], c["pos"], c["end"], c["flag"], c["mapq"], c["tlen"])
     rid = np.repeat(np.arange(len(c["ref_len"])), np.diff(c["ref_off"]))
     off = np.concatenate([[0], np.cumsum(np.bincount(rid[mask], minlength=len(c["ref_len"])))]).astype(np.int64)
     return oracle_c.OracleReads(off, c["pos"][mask], c["end"][mask], c["flag"][mask], c["mapq"][mask], c["tlen"][mask])
+
+
+def _reads(placement):
+    return reads() if placement is None else reads(placement)       # (one cache key for the deck where it is)
+
+
+def _ranges(placement):
+    return ranges() if placement is None else ranges(placement)
+
+
+def _sum_ranges(placement):
+    return sum_ranges() if placement is None else sum_ranges(placement)
+
+
+def named_placement(name):
+    """far_deck's placement `name` of this deck: `top` is computed from its reads and both range tables"""
+    import far_deck
+    return far_deck.placement(name, reads(), ranges(), sum_ranges())
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -233,8 +255,11 @@ def _island_ranges(refs):
 
 
 @functools.lru_cache(maxsize=None)
-def ranges():
+def ranges(placement=None):
     """The deck: len(WIDTHS) * COPIES ranges on the bulk references, then the islands' (island_refs' order)."""
+    if placement is not None:
+        import far_deck
+        return far_deck.place_ranges(ranges(), placement)
     for seed in range(5, 200):
         rng = np.random.default_rng(seed)
         width = rng.permutation(np.repeat(np.asarray(WIDTHS, np.int64), COPIES))
@@ -293,8 +318,11 @@ def cut_expected(name, k):
 
 
 @functools.lru_cache(maxsize=None)
-def sum_ranges():
+def sum_ranges(placement=None):
     """Ranges of one width for the sums: the islands' and 60 on the bulk references, strands mixed."""
+    if placement is not None:
+        import far_deck
+        return far_deck.place_ranges(sum_ranges(), placement)
     rng = np.random.default_rng(77)
     n = 60
     rid = rng.integers(0, len(BULK_REFS), n)
@@ -313,14 +341,14 @@ def _binned(v, b):
     return np.add.reduceat(v, np.arange(0, len(v), b)) if len(v) else np.zeros(0, np.int64)
 
 
-def _coverage(rg, binsize, ss):
+def _coverage(rg, binsize, ss, placement=None):
     """per-base oracle coverage (all reads, or forward and reverse reads apart: the sense row counts the reads on the
     range's strand, '*' = '+'), summed over bins, in the plan's flat layout; returns (flat int64, offsets)"""
     from oracle import oracle_c
-    c = reads()
+    c = _reads(placement)
 
     def per_base(mask):
-        out, off = oracle_c.coverage_core(oracle_reads(mask), rg)
+        out, off = oracle_c.coverage_core(oracle_reads(mask, placement), rg)
         return [out[off[i]:off[i + 1]].astype(np.int64) for i in range(len(off) - 1)]
     if not ss:
         parts = [_binned(v, binsize) for v in per_base(None)]
@@ -334,12 +362,12 @@ def _coverage(rg, binsize, ss):
     return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), off
 
 
-def _expected(entry, args, rg):
+def _expected(entry, args, rg, placement=None):
     from oracle import oracle_c
     if entry == "pileup":
-        out, off = oracle_c.pileup_core(oracle_reads(), rg, **args)
+        out, off = oracle_c.pileup_core(oracle_reads(None, placement), rg, **args)
     else:
-        out, off = _coverage(rg, args["binsize"], args["ss"])
+        out, off = _coverage(rg, args["binsize"], args["ss"], placement)
         assert out.max(initial=0) < 2 ** 31
         out = out.astype(np.int32)
     out.setflags(write=False)
@@ -347,17 +375,17 @@ def _expected(entry, args, rg):
 
 
 @functools.lru_cache(maxsize=None)
-def expected(name):
+def expected(name, placement=None):
     """(flat int32 result, offsets per range) of PARAM_SETS[name] on the whole deck; a cut's is its prefix"""
-    return _expected(*PARAM_SETS[name], ranges())
+    return _expected(*PARAM_SETS[name], _ranges(placement), placement)
 
 
 @functools.lru_cache(maxsize=None)
-def expected_sum(name):
+def expected_sum(name, placement=None):
     """the int64 sum over SUM_RANGES of what the oracle gives per range (cell 2 * bin + antisense with strands)"""
     entry, args = SUM_SETS[name]
-    rg = sum_ranges()
-    out, _ = _expected(entry, args, rg)
+    rg = _sum_ranges(placement)
+    out, _ = _expected(entry, args, rg, placement)
     s = out.astype(np.int64).reshape(len(rg["len"]), -1).sum(axis=0)
     s.setflags(write=False)
     return s
@@ -393,36 +421,36 @@ def _frozen(a):
 
 
 @functools.lru_cache(maxsize=None)
-def _xcorr_full(mapqual):
+def _xcorr_full(mapqual, placement=None):
     import crosscorr_expected as xe
-    cross, mom = xe.expected(oracle_reads(), ranges(), XCORR_MAX_LAG, mapqual=mapqual)
+    cross, mom = xe.expected(oracle_reads(None, placement), _ranges(placement), XCORR_MAX_LAG, mapqual=mapqual)
     return _frozen(cross), _frozen(mom)
 
 
-def expected_xcorr(max_lag, mapqual=0):
+def expected_xcorr(max_lag, mapqual=0, placement=None):
     """cross[0 .. max_lag], then the five moments: lag d's sum does not depend on the largest lag asked for, so the
     result for XCORR_MAX_LAG, computed once, holds every smaller one as a prefix"""
-    cross, mom = _xcorr_full(mapqual)
+    cross, mom = _xcorr_full(mapqual) if placement is None else _xcorr_full(mapqual, placement)
     assert 0 <= max_lag <= XCORR_MAX_LAG
     return np.concatenate([cross[:max_lag + 1], mom])
 
 
-def _some_ranges(which):
-    rg = ranges()
+def _some_ranges(which, placement=None):
+    rg = _ranges(placement)
     if which == "all":
         return rg
-    c = reads()
+    c = _reads(placement)
     keep = np.isin(rg["rid"], c[{"c0": "c0_refs", "paired": "pair_refs"}[which]])
     return {k: v[keep] for k, v in rg.items()}
 
 
 @functools.lru_cache(maxsize=None)
-def expected_frag(tlen_filter, len_bin, midpoint, which="all"):
+def expected_frag(tlen_filter, len_bin, midpoint, which="all", placement=None):
     """the fragment-length histogram of the deck's ranges (which: all, or the class-0 / the paired islands' alone).  No
     template of the deck is longer than 600, which one oracle bamCount over all longer lengths confirms: the rows above
     600 are zero without an oracle call each."""
     import fragsizes_expected as fe
-    orc, rg = oracle_reads(), _some_ranges(which)
+    orc, rg = oracle_reads(None, placement), _some_ranges(which, placement)
     lo, hi = tlen_filter
     if hi <= 600 * len_bin:
         return _frozen(fe.expected(orc, rg, (lo, hi), len_bin, midpoint))
@@ -433,28 +461,32 @@ def expected_frag(tlen_filter, len_bin, midpoint, which="all"):
 
 
 @functools.lru_cache(maxsize=None)
-def reduction_cells(signal, ss, mapqual=0):
+def reduction_cells(signal, ss, mapqual=0, placement=None):
     """all per-base cells of the deck's ranges in the oracle's order: "coverage", or "ends" (5' ends, shift 0)"""
     import depthhist_expected as de
-    return _frozen(de.cells(oracle_reads(), ranges(), signal, ss, mapqual=mapqual))
+    return _frozen(de.cells(oracle_reads(None, placement), _ranges(placement), signal, ss, mapqual=mapqual))
+
+
+def _cells(signal, ss, mapqual, placement):
+    return reduction_cells(signal, ss, mapqual) if placement is None else reduction_cells(signal, ss, mapqual, placement)
 
 
 @functools.lru_cache(maxsize=None)
-def expected_hist(signal, ss, max_value, mapqual=0):
+def expected_hist(signal, ss, max_value, mapqual=0, placement=None):
     import depthhist_expected as de
-    return _frozen(de.from_cells(reduction_cells(signal, ss, mapqual), max_value))
+    return _frozen(de.from_cells(_cells(signal, ss, mapqual, placement), max_value))
 
 
 @functools.lru_cache(maxsize=None)
-def expected_summary(signal, ss, thresholds, mapqual=0):
+def expected_summary(signal, ss, thresholds, mapqual=0, placement=None):
     import summary_expected as se
-    return _frozen(se.from_cells(reduction_cells(signal, ss, mapqual), ranges(), ss, thresholds))
+    return _frozen(se.from_cells(_cells(signal, ss, mapqual, placement), _ranges(placement), ss, thresholds))
 
 
 @functools.lru_cache(maxsize=None)
-def expected_scaled(signal, ss, n_bins, mapqual=0):
+def expected_scaled(signal, ss, n_bins, mapqual=0, placement=None):
     import scaled_expected as sc
-    return _frozen(sc.from_cells(reduction_cells(signal, ss, mapqual), ranges(), ss, n_bins))
+    return _frozen(sc.from_cells(_cells(signal, ss, mapqual, placement), _ranges(placement), ss, n_bins))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -469,26 +501,27 @@ VPLOT_CELLS = {"small": 86 * 41, "budget": 20 * 2048, "below": 19 * 2048, "above
 
 
 @functools.lru_cache(maxsize=None)
-def capped_cells(shift=0, mapqual=0):
+def capped_cells(shift=0, mapqual=0, placement=None):
     """per range of the deck the (2, w) int64 matrix of its per-base 5'-end cells, rows sense and antisense, uncapped"""
     import capped_expected as ce
-    return tuple(_frozen(c) for c in ce.stranded_cells(oracle_reads(), ranges(), shift=shift, mapqual=mapqual))
+    return tuple(_frozen(c) for c in ce.stranded_cells(oracle_reads(None, placement), _ranges(placement), shift=shift, mapqual=mapqual))
 
 
 @functools.lru_cache(maxsize=None)
-def expected_capped(k, binsize, ss, shift=0, mapqual=0):
+def expected_capped(k, binsize, ss, shift=0, mapqual=0, placement=None):
     """(flat int64 cells, offsets) of keepDup = k over ranges(): capped first, binned second (binsize -1: bamCount), the
     strands added last"""
     import capped_expected as ce
-    flat, off = ce.ends_from_cells(capped_cells(shift, mapqual), k, binsize, ss)
+    cells = capped_cells(shift, mapqual) if placement is None else capped_cells(shift, mapqual, placement)
+    flat, off = ce.ends_from_cells(cells, k, binsize, ss)
     return _frozen(flat), _frozen(off)
 
 
 @functools.lru_cache(maxsize=None)
-def expected_capped_cover(k, L, binsize, ss, mapqual=0):
+def expected_capped_cover(k, L, binsize, ss, mapqual=0, placement=None):
     """(flat int64 cells, offsets) over ranges() of the coverage of the kept reads resized to L bases"""
     import capped_expected as ce
-    flat, off = ce.coverage(oracle_reads(), ranges(), k, L, binsize, ss, mapqual=mapqual)
+    flat, off = ce.coverage(oracle_reads(None, placement), _ranges(placement), k, L, binsize, ss, mapqual=mapqual)
     return _frozen(flat), _frozen(off)
 
 
@@ -501,39 +534,40 @@ def capped_cover_rows(L):
     return np.where(w > 0, np.maximum(loc - lo + w + L - 1, 0), 0)
 
 
-def _some_sum_ranges(which):
-    rg = sum_ranges()
+def _some_sum_ranges(which, placement=None):
+    rg = _sum_ranges(placement)
     if which == "all":
         return rg
-    c = reads()
+    c = _reads(placement)
     keep = np.isin(rg["rid"], c[{"c0": "c0_refs", "paired": "pair_refs"}[which]])
     return {k: v[keep] for k, v in rg.items()}
 
 
 @functools.lru_cache(maxsize=None)
-def expected_vplot(tlen_filter, len_bin, binsize, midpoint, mapqual=0, which="all"):
+def expected_vplot(tlen_filter, len_bin, binsize, midpoint, mapqual=0, which="all", placement=None):
     """the (rows, cols) int64 V-plot of sum_ranges() (which: all, or the class-0 / the paired islands' ranges alone): one
     oracle bamProfile per non-empty row band, summed over the ranges"""
     import vplot_expected as ve
     assert tlen_filter[1] <= 600
-    return _frozen(ve.expected(oracle_reads(), _some_sum_ranges(which), tlen_filter, len_bin, binsize, midpoint, mapqual=mapqual))
+    return _frozen(ve.expected(oracle_reads(None, placement), _some_sum_ranges(which, placement), tlen_filter, len_bin, binsize, midpoint, mapqual=mapqual))
 
 
 @functools.lru_cache(maxsize=None)
-def resized_columns(L):
+def resized_columns(L, placement=None):
     """the deck's read columns with every read resized to L bases from its 5' end (tests/resized_expected.py)"""
     import resized_expected as rx
-    return rx.resize_columns(reads(), L)
+    return rx.resize_columns(_reads(placement), L)
 
 
 @functools.lru_cache(maxsize=None)
-def expected_resized(L, pset):
+def expected_resized(L, pset, placement=None):
     """(flat int32 result, offsets) of the coverage parameter set PARAM_SETS[pset] on the whole deck with the reads
     resized to L bases: the oracle's coverage of the resized columns"""
     import resized_expected as rx
     entry, args = PARAM_SETS[pset]
     assert entry == "coverage"
-    out, off = rx.coverage(resized_columns(L), ranges(), args["binsize"], args["ss"])
+    cols = resized_columns(L) if placement is None else resized_columns(L, placement)
+    out, off = rx.coverage(cols, _ranges(placement), args["binsize"], args["ss"])
     assert out.max(initial=0) < 2 ** 31
     out = out.astype(np.int32)
     out.setflags(write=False)
@@ -541,10 +575,10 @@ def expected_resized(L, pset):
 
 
 @functools.lru_cache(maxsize=None)
-def expected_resized_sum(L, ss):
+def expected_resized_sum(L, ss, placement=None):
     """the int64 sum over sum_ranges() of the per-base coverage of the reads resized to L bases (cell 2 * base + antisense
     with strands)"""
     import resized_expected as rx
-    rg = sum_ranges()
-    per_range, _ = rx.coverage(resized_columns(L), rg, 1, ss)
+    rg = _sum_ranges(placement)
+    per_range, _ = rx.coverage(resized_columns(L) if placement is None else resized_columns(L, placement), rg, 1, ss)
     return _frozen(per_range.reshape(len(rg["len"]), -1).sum(axis=0).astype(np.int64))
