@@ -8,7 +8,10 @@ strategies (default, filtered, Huffman only, RLE, fixed codes), in blocks of 1 .
 workgroup.   usage: fuzz_inflate.py [first seed] [seeds] [blocks per seed] [damage]
 With `damage`: one to four bytes of the DEFLATE data of seven blocks in ten are then overwritten at random (headers and
 trailers stay: the block table is as before) and the file goes through the kernel again -- a launch over damaged blocks must
-come back, with a status that says so, whatever the damage made of the code tables, the distances and the lengths."""
+come back, with a status that says so, whatever the damage made of the code tables, the distances and the lengths.
+Every stream here is zlib's: what its compressor never writes (matches beyond 32,506 bytes, 3-byte matches beyond 4,096, one
+distance code or none, chosen code lengths and code-length headers) comes from tests/deflate_writer.py and goes through the
+kernel in tests/test_inflate_foreign_gpu.py."""
 import ctypes
 import os
 import struct

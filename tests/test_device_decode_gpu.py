@@ -523,7 +523,10 @@ def test_inflate_kernel_on_every_kind_of_content(ctx, tmp_path, monkeypatch):
     """k_inflate by itself on what BAM records never hold (scripts/fuzz_inflate.py's generator, two seeds here; DESIGN.md
     section 4 has the long campaign): runs, periods of 1-40 bytes, copies at chosen distances (1, 7, 8, 9, 15, 16, 17, ... 32,768)
     and lengths (3 ... 258), skewed alphabets, random bytes, zeros, in blocks of 1 ... 65,280 bytes at zlib levels 0 / 1 / 6 / 9
-    under all five strategies; every block's CRC32 and length checked on the device."""
+    under all five strategies; every block's CRC32 and length checked on the device.  (The data holds such copies; what zlib makes
+    of them is zlib's choice: it writes no match further back than 32,506 bytes, no 3-byte match beyond 4,096, never fewer
+    than two distance codes.  The streams no zlib writes -- distance 32,768 itself, one distance code or none, 15-bit codes with
+    the largest extra bits, every legal form of the code-length header -- are tests/test_inflate_foreign_gpu.py's.)"""
     import ctypes
     import importlib.util
     from bamsignals_amd import _lib

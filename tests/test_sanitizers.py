@@ -182,3 +182,19 @@ def test_inflate_lane_on_damaged_streams(driver, tmp_path):
                 rc, _ = driver("inflate", str(f), str(int(len(d) * rng.choice([1, 1, 0.5, 2]))))
                 bad += rc == 3
     assert ok == 36 and bad > 30
+
+
+def test_inflate_lane_on_streams_zlib_never_writes(driver, tmp_path):
+    """every valid and invalid case of tests/deflate_writer.py (15-bit codes, distance 32,768, one distance code and none,
+    ISIZE 65,536, code sets that are over-subscribed or incomplete, ...) with exactly-sized heap buffers: the expected
+    bytes (their sum) or a clean error, never a report"""
+    import deflate_writer as dw
+    f = tmp_path / "d.raw"
+    for name, (raw, data) in dw.corpus().items():
+        f.write_bytes(raw)
+        rc, out = driver("inflate", str(f), str(len(data)))
+        assert rc == 0 and int(out.split()[2]) == sum(data), name
+    for name, (raw, n) in dw.invalid().items():
+        f.write_bytes(raw)
+        rc, _ = driver("inflate", str(f), str(n))
+        assert rc == (0 if name in dw.LANE_ACCEPTS else 3), name
