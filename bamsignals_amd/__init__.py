@@ -14,7 +14,9 @@ bamVPlot, fragment length by position summed over ranges of one width (the V-plo
 TSSs, motif sites or dyads), made in one pass over the reads; bamJunctions, the splice junctions of every range with the reads
 that support them and their largest anchor (summarizeJunctions, STAR's SJ.out.tab), counted on the GPU from the gap table of
 the file's spliced reads; bamGeneCounts, the reads of every gene over its exons with the ambiguous, featureless, filtered and
-unmapped reads beside them (htseq-count's union mode, featureCounts), each read decided on the GPU from the same spliced reads.
+unmapped reads beside them (htseq-count's union mode, featureCounts), each read decided on the GPU from the same spliced reads;
+bamNucleotides, the A / C / G / T / N / deletion counts of every base of a range (Rsamtools::pileup, bam-readcount), counted
+on the GPU from the bases and qualities the file's reads with bases keep.
 Handle-level API for resident data and benchmarking: ``bamsignals_amd.device``.
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
 include/bamsignals_abi.h; there is no CPU fallback.
@@ -27,6 +29,7 @@ from .fragsizes import FragSizes, bamFragSizes  # noqa: F401
 from .genecounts import GeneCounts, GeneModel, bamGeneCounts  # noqa: F401
 from .granges import GRanges  # noqa: F401
 from .junctions import Junctions, bamJunctions  # noqa: F401
+from .nucleotides import NucleotideCounts, bamNucleotides  # noqa: F401
 from .overlaps import bamOverlaps  # noqa: F401
 from .runsignals import RunSignals  # noqa: F401
 from .scaled import ScaledSignals, bamScaled  # noqa: F401
@@ -38,6 +41,6 @@ from .wrappers import bamCount, bamCoverage, bamProfile, coverage_core, pileup_c
 __all__ = ["bamCount", "bamProfile", "bamCoverage", "bamCrossCorr", "CrossCorr", "bamFragSizes",
            "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "bamScaled", "ScaledSignals",
            "bamOverlaps", "bamViews", "SignalViews", "bamVPlot", "VPlot", "bamJunctions", "Junctions",
-           "bamGeneCounts", "GeneCounts", "GeneModel",
+           "bamGeneCounts", "GeneCounts", "GeneModel", "bamNucleotides", "NucleotideCounts",
            "CountSignals", "RunSignals", "GRanges", "BamFile",
            "writeSamAsBamAndIndex", "write_columns_as_bam", "pileup_core", "coverage_core"]

@@ -49,6 +49,11 @@ class Columns(C.Structure):
                 ("cigar_off", C.c_void_p), ("cigar", C.c_void_p)]
 
 
+class BaseColumns(C.Structure):
+    # bsig_base_columns: seq_off counts bases; base g is nibble g of seq (the high half of byte g / 2 where g is even), byte g of qual
+    _fields_ = [("seq_off", C.c_void_p), ("seq", C.c_void_p), ("qual", C.c_void_p)]
+
+
 class ReadsInfo(C.Structure):
     # classes 0..3 by span, 4 = the packed class (include/bamsignals_abi.h: BSIG_N_CLASSES)
     _fields_ = [("n_reads", C.c_int64), ("hbm_bytes", C.c_int64), ("n_classes", C.c_int32), ("n_codes", C.c_int32),
@@ -302,6 +307,21 @@ def load():
         lib.bsig_reads_n_source_reads.restype = C.c_int64
         lib.bsig_reads_gene_counts.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 2
         lib.bsig_gene_counts.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)] + [C.c_int32] * 5 + [C.c_void_p] * 2
+    # reads with bases and the nucleotide counts (BSIG_LIB_PATH may name a build from before them)
+    if hasattr(lib, "bsig_reads_nucleotides"):
+        lib.bsig_reads_upload_bases.argtypes = [C.c_void_p, C.POINTER(Columns), C.POINTER(BaseColumns), C.POINTER(C.c_void_p)]
+        lib.bsig_reads_has_bases.argtypes = [C.c_void_p]
+        lib.bsig_reads_has_bases.restype = C.c_int32
+        lib.bsig_reads_base_table_bytes.argtypes = [C.c_void_p]
+        lib.bsig_reads_base_table_bytes.restype = C.c_int64
+        lib.bsig_bam_decode_bases.argtypes = lib.bsig_bam_decode.argtypes + [C.POINTER(BaseColumns)]
+        lib.bsig_reads_from_bam_bases.argtypes = lib.bsig_reads_from_bam.argtypes
+        lib.bsig_reads_from_bam_regions_bases.argtypes = lib.bsig_reads_from_bam_regions.argtypes
+        lib.bsig_nucleotides_cells.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.bsig_nucleotides_cells.restype = C.c_int64
+        lib.bsig_reads_nucleotides.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
+        lib.bsig_reads_nucleotides_host.argtypes = lib.bsig_reads_nucleotides.argtypes
+        lib.bsig_nucleotides.argtypes = core_head[:8] + [C.c_int32] * 6 + [C.c_void_p]
     lib.bsig_views_result_n_seg.argtypes = [C.c_void_p]
     lib.bsig_views_result_n_seg.restype = C.c_int64
     lib.bsig_views_result_n_views.argtypes = [C.c_void_p]

@@ -456,6 +456,12 @@ bool parse_block(const MappedFile &f, uint64_t off, Block &b)
 class BamParser {
 public:
     BamParser(BamHeader &h, HostColumns &c, bool want_header) : hdr_(h), cols_(c), in_header_(want_header) {}
+    // every placed record's bases and qualities go to `b` as well (its seq_off starts at 0)
+    void set_bases(HostBases *b)
+    {
+        bases_ = b;
+        if (b && b->seq_off.empty()) b->seq_off.push_back(0);
+    }
 
     // stop parsing at this absolute stream position (records starting at or after it are left alone)
     void set_limit(uint64_t lim) { limit_ = lim; }
@@ -583,6 +589,9 @@ private:
             return fail(BSIG_ERR_FORMAT, "malformed BAM record (fields exceed block_size)");
         if (rid < 0) { ++cols_.n_unplaced; return 0; }
         if (rid >= (int)hdr_.names.size()) return fail(BSIG_ERR_FORMAT, "BAM record with refID %d out of range", rid);
+        const size_t seq_at = 36 + (size_t)l_name + 4 * (size_t)n_cig;      // the record's bases, then its qualities
+        if (bases_ && (l_seq < 0 || seq_at + ((size_t)l_seq + 1) / 2 + (size_t)l_seq > len))
+            return fail(BSIG_ERR_FORMAT, "malformed BAM record (l_seq %d exceeds block_size)", l_seq);
         if (rid < last_rid_ || (rid == last_rid_ && pos < last_pos_))
             return fail(BSIG_ERR_FORMAT, "BAM file is not sorted by coordinate");
         while ((int)cols_.ref_off.size() <= rid) cols_.ref_off.push_back(cols_.size());
@@ -623,11 +632,19 @@ private:
         cols_.flag.push_back(flag);
         cols_.mapq.push_back(mapq);
         cols_.tlen.push_back(tlen);
+        if (bases_) {
+            const int64_t g = bases_->n_bases();
+            bases_->seq.resize((size_t)((g + l_seq + 1) / 2));
+            append_nibbles(bases_->seq.data(), g, r + seq_at, l_seq);
+            bases_->qual.insert(bases_->qual.end(), r + seq_at + ((size_t)l_seq + 1) / 2, r + seq_at + ((size_t)l_seq + 1) / 2 + (size_t)l_seq);
+            bases_->seq_off.push_back(g + l_seq);
+        }
         return 0;
     }
 
     BamHeader &hdr_;
     HostColumns &cols_;
+    HostBases *bases_ = nullptr;
     bool in_header_;
     bool done_ = false;
     size_t header_need_ = 12;
@@ -1598,8 +1615,9 @@ std::vector<BaiChunk> bai_region_chunks(const BaiIndex &idx, const std::vector<R
     return merged;
 }
 
-int bam_decode_regions(const std::string &path, const BaiIndex &idx, const std::vector<Region> &regions,
-                       int threads, BamHeader &hdr, HostColumns &cols)
+// (bases != nullptr: every record's bases and qualities as well, concatenated like the columns)
+static int decode_regions_impl(const std::string &path, const BaiIndex &idx, const std::vector<Region> &regions,
+                               int threads, BamHeader &hdr, HostColumns &cols, HostBases *bases)
 {
     MappedFile f;
     if (f.open(path) != 0) return fail(BSIG_ERR_IO, "Fail to open BAM file %s", path.c_str());
@@ -1620,6 +1638,7 @@ int bam_decode_regions(const std::string &path, const BaiIndex &idx, const std::
     // are concatenated in file order afterwards.
     struct Job {
         HostColumns c;
+        HostBases b;
         int err = 0;
         std::string msg;
     };
@@ -1632,6 +1651,7 @@ int bam_decode_regions(const std::string &path, const BaiIndex &idx, const std::
         const uint64_t cb = c.beg >> 16, ub = c.beg & 0xFFFF, ce = c.end >> 16, ue = c.end & 0xFFFF;
         BamHeader h = H;                       // the parser only reads names.size()
         BamParser parser(h, J.c, false);
+        if (bases) parser.set_bases(&J.b);
         std::vector<uint8_t> buf;
         uint64_t off = cb, upos = 0;           // upos: stream position (relative to block cb) of buf's start
         bool first = true;
@@ -1695,6 +1715,78 @@ int bam_decode_regions(const std::string &path, const BaiIndex &idx, const std::
     });
     const int n_ref = (int)hdr.names.size();
     while ((int)cols.ref_off.size() < n_ref + 1) cols.ref_off.push_back(cols.size());
+    if (bases) {
+        // the jobs' nibble strings one behind the other (serial: two jobs may share a byte)
+        *bases = HostBases();
+        int64_t total = 0;
+        for (const Job &J : jobs) total += J.b.n_bases();
+        bases->seq_off.resize(m + 1);
+        bases->seq.resize((size_t)((total + 1) / 2));
+        bases->qual.resize((size_t)total);
+        bases->seq_off[0] = 0;
+        int64_t g = 0;
+        for (size_t k = 0; k < jobs.size(); ++k) {
+            const HostBases &b = jobs[k].b;
+            const size_t n = (size_t)jobs[k].c.size(), r0 = (size_t)rec0[k];
+            for (size_t i = 0; i < n; ++i) bases->seq_off[r0 + i + 1] = g + b.seq_off[i + 1];
+            append_nibbles(bases->seq.data(), g, b.seq.data(), b.n_bases());
+            if (b.n_bases()) memcpy(bases->qual.data() + g, b.qual.data(), (size_t)b.n_bases());
+            g += b.n_bases();
+        }
+    }
+    return 0;
+}
+
+int bam_decode_regions(const std::string &path, const BaiIndex &idx, const std::vector<Region> &regions,
+                       int threads, BamHeader &hdr, HostColumns &cols)
+{
+    return decode_regions_impl(path, idx, regions, threads, hdr, cols, nullptr);
+}
+
+void append_nibbles(uint8_t *dst, int64_t g, const uint8_t *src, int64_t l)
+{
+    if (l <= 0) return;
+    if (!(g & 1)) {
+        memcpy(dst + g / 2, src, (size_t)((l + 1) / 2));
+        if (l & 1) dst[(g + l - 1) / 2] &= 0xF0;
+        return;
+    }
+    uint8_t *d = dst + g / 2;
+    d[0] = (uint8_t)((d[0] & 0xF0) | (src[0] >> 4));
+    const int64_t pairs = (l - 1) / 2;          // nibbles 2b + 1, 2b + 2 of src make byte 1 + b
+    for (int64_t b = 0; b < pairs; ++b) d[1 + b] = (uint8_t)((src[b] << 4) | (src[b + 1] >> 4));
+    if (!(l & 1)) d[1 + pairs] = (uint8_t)(src[pairs] << 4);
+}
+
+// The bases' decode on the host: what bsig_reads_from_bam_bases falls back to where the device decode (devdecode.hip:
+// chunk_bases) declines a file, and what bsig_bam_decode_bases hands out.  The whole file is inflated in batches by the pool and
+// walked record by record on this thread: one walk, where the columns' own decode walks segments in parallel
+int bam_decode_bases(const std::string &path, const BaiIndex *idx, const std::vector<Region> &regions, int threads,
+                     BamHeader &hdr, HostColumns &cols, HostBases &bases)
+{
+    if (idx) return decode_regions_impl(path, *idx, regions, threads, hdr, cols, &bases);
+    MappedFile f;
+    if (f.open(path) != 0) return fail(BSIG_ERR_IO, "Fail to open BAM file %s", path.c_str());
+    threads = n_threads(threads);
+    std::vector<Block> blocks;
+    int rc = scan_blocks(f, path, blocks);
+    if (rc) return rc;
+    cols = HostColumns();
+    bases = HostBases();
+    if (blocks.empty()) return fail(BSIG_ERR_FORMAT, "truncated BAM header in %s", path.c_str());
+    BamParser parser(hdr, cols, true);
+    parser.set_bases(&bases);
+    std::vector<uint8_t> buf;
+    const size_t batch = 1024;
+    for (size_t b0 = 0; b0 < blocks.size(); b0 += batch) {
+        rc = inflate_batch(f, blocks, b0, std::min(b0 + batch, blocks.size()), threads, buf);
+        if (rc) return rc;
+        rc = parser.feed(buf.data(), buf.size());
+        if (rc) return rc;
+    }
+    if (parser.in_header()) return fail(BSIG_ERR_FORMAT, "truncated BAM header in %s", path.c_str());
+    if (parser.pending()) return fail(BSIG_ERR_FORMAT, "truncated BAM record at the end of %s", path.c_str());
+    parser.finish_refs();
     return 0;
 }
 

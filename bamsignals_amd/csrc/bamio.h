@@ -62,6 +62,18 @@ struct HostColumns {
     int64_t size() const { return (int64_t)pos.size(); }
 };
 
+// what the records say at their bases, beside HostColumns and in its order: read i owns bases seq_off[i] .. seq_off[i + 1].
+// Base g of the whole is nibble g of `seq` (BAM's 4-bit codes, tightly packed: byte g / 2, the high half where g is even)
+// and byte g of `qual` (0xFF: missing)
+struct HostBases {
+    ColVec<int64_t> seq_off;          // n + 1, counted in bases
+    ColVec<uint8_t> seq, qual;
+    int64_t n_bases() const { return seq_off.empty() ? 0 : seq_off.back(); }
+};
+// l nibbles from the start of src (high half first, as a BAM record holds them) to nibbles g .. g + l - 1 of dst.  Where g is
+// odd, byte g / 2 of dst holds its high half already; a low half left over behind the last nibble is zero
+void append_nibbles(uint8_t *dst, int64_t g, const uint8_t *src, int64_t l);
+
 struct BaiChunk { uint64_t beg, end; };
 struct BaiRef {
     std::vector<std::pair<uint32_t, std::vector<BaiChunk>>> bins;   // sorted by bin number
@@ -147,6 +159,10 @@ int bam_decode_all(const std::string &path, int threads, BamHeader &hdr, HostCol
 // each record at most once, file order kept).
 int bam_decode_regions(const std::string &path, const BaiIndex &idx, const std::vector<Region> &regions,
                        int threads, BamHeader &hdr, HostColumns &cols);
+// ... with the bases and qualities of every placed record (a serial record walk behind a parallel inflate; a record whose
+// l_seq runs past its block_size is BSIG_ERR_FORMAT).  idx == nullptr: the whole file
+int bam_decode_bases(const std::string &path, const BaiIndex *idx, const std::vector<Region> &regions, int threads,
+                     BamHeader &hdr, HostColumns &cols, HostBases &bases);
 int bam_read_header(const std::string &path, BamHeader &hdr);
 // seconds of the last bam_decode_all on this thread: block scan, inflate wait, boundary scan,
 // column extraction, total

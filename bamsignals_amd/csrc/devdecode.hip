@@ -43,6 +43,7 @@
 #include "bamio.h"
 #include "collect.h"
 #include "inflate_lane.h"
+#include "nucleotides.h"
 #include "runtime_internal.h"
 #include "splice.h"
 
@@ -361,6 +362,122 @@ __global__ __launch_bounds__(kExtractThreads) void k_bam_gap_emit(
                             });
         }
         at += total;
+    }
+}
+
+// ---- decodes with bases: the operations, bases and qualities of a chunk's records, while its stream is still resident ----
+// k_bam_extract's segments and launch shape: per record its number of operations (record_cigar: the CG tag's where the record
+// holds the placeholder) and its l_seq, per segment their sums.  An l_seq that is negative or runs past its record counts as 0
+// and raises *bad: the host decode then takes the file and names what is wrong
+__global__ __launch_bounds__(kExtractThreads) void k_bam_base_count(
+    const uint8_t *__restrict__ stream, const uint64_t *__restrict__ seg_start, const uint16_t *__restrict__ off16,
+    const uint32_t *__restrict__ seg_n, const int64_t *__restrict__ seg_base, uint32_t *__restrict__ read_ops,
+    uint32_t *__restrict__ read_seq, uint32_t *__restrict__ seg_ops, uint32_t *__restrict__ seg_seq, int *__restrict__ bad)
+{
+    __shared__ uint32_t scratch[kExtractThreads];
+    const int64_t s = blockIdx.x;
+    const uint32_t n = seg_n[s];
+    uint32_t my_ops = 0, my_seq = 0;
+    if (n) {
+        const uint8_t *seg = stream + seg_start[s];
+        const uint16_t *offs = off16 + s * kMaxRecPerSeg;
+        const int64_t base = seg_base[s];
+        for (uint32_t k = threadIdx.x; k < n; k += kExtractThreads) {
+            const uint8_t *r = seg + offs[k];
+            const uint8_t *c;
+            const uint32_t n_ops = record_cigar(r, &c);
+            const uint32_t l_name = ld32(r + 12) & 0xFFu, n_cig = ld32(r + 16) & 0xFFFFu;
+            const int64_t l_seq = (int32_t)ld32(r + 20), rec_len = 4ll + (int32_t)ld32(r);
+            uint32_t l = (uint32_t)l_seq;
+            if (l_seq < 0 || 36ll + l_name + 4ll * n_cig + (l_seq + 1) / 2 + l_seq > rec_len) { l = 0; *bad = 1; }
+            read_ops[base + k] = n_ops;
+            read_seq[base + k] = l;
+            my_ops += n_ops;
+            my_seq += l;
+        }
+    }
+    uint32_t total;
+    bsig::block_exclusive_scan<kExtractThreads>(my_ops, scratch, &total);
+    if (threadIdx.x == 0) seg_ops[s] = total;
+    bsig::block_exclusive_scan<kExtractThreads>(my_seq, scratch, &total);
+    if (threadIdx.x == 0) seg_seq[s] = total;
+}
+
+// ... and the piece.  The segment's records in rounds of one per thread: a scan gives every record of the round where its
+// operations and bases begin in the chunk (written out as the piece's offsets), then a record goes to a GROUP OF 16 LANES --
+// a record of 100 - 150 bases is one or a few operation words, 50 - 75 bytes of nibbles and 100 - 150 quality bytes, so
+// sixteen lanes copy it in 4 + 7 .. 5 + 10 passes of consecutive bytes, where a wave would idle three lanes in four on the
+// nibbles and a thread would copy 150-odd bytes one at a time.  The nibbles are packed tightly over the whole chunk: a record
+// that begins on an odd nibble is shifted by four bits as it is copied, and the two half bytes it shares with its neighbours
+// are OR-ed into the zeroed piece with integer atomics on their dword (whole bytes are plain stores): OR commutes, the piece
+// is the same on every run
+constexpr int kBaseLanes = 16;
+__device__ __forceinline__ void or_byte(uint8_t *dst, int64_t at, uint32_t v)
+{
+    atomicOr(reinterpret_cast<uint32_t *>(dst + (at & ~(int64_t)3)), v << (8 * (uint32_t)(at & 3)));
+}
+__global__ __launch_bounds__(kExtractThreads) void k_bam_base_emit(
+    const uint8_t *__restrict__ stream, const uint64_t *__restrict__ seg_start, const uint16_t *__restrict__ off16,
+    const uint32_t *__restrict__ seg_n, const int64_t *__restrict__ seg_base, const uint32_t *__restrict__ read_ops,
+    const uint32_t *__restrict__ read_seq, const int64_t *__restrict__ seg_ops_base, const int64_t *__restrict__ seg_seq_base,
+    int64_t *__restrict__ cig_off, int64_t *__restrict__ seq_off, uint32_t *__restrict__ ops_out, uint8_t *__restrict__ seq_out,
+    uint8_t *__restrict__ qual_out, int64_t n_ops_total, int64_t n_bases_total)
+{
+    __shared__ uint32_t scratch[kExtractThreads];
+    __shared__ int64_t s_op[kExtractThreads], s_sq[kExtractThreads];
+    __shared__ uint32_t s_no[kExtractThreads], s_nq[kExtractThreads];
+    const int64_t s = blockIdx.x;
+    const uint32_t n = seg_n[s];
+    if (n == 0) return;                                   // (the whole workgroup)
+    const uint8_t *seg = stream + seg_start[s];
+    const uint16_t *offs = off16 + s * kMaxRecPerSeg;
+    const int64_t base = seg_base[s];
+    int64_t at_ops = seg_ops_base[s], at_seq = seg_seq_base[s];
+    const uint32_t group = threadIdx.x / kBaseLanes, gl = threadIdx.x % kBaseLanes;
+    for (uint32_t k0 = 0; k0 < n; k0 += kExtractThreads) {
+        const uint32_t k = k0 + threadIdx.x;
+        const uint32_t o = k < n ? read_ops[base + k] : 0u, q = k < n ? read_seq[base + k] : 0u;
+        uint32_t tot_o, tot_q;
+        const uint32_t before_o = bsig::block_exclusive_scan<kExtractThreads>(o, scratch, &tot_o);
+        const uint32_t before_q = bsig::block_exclusive_scan<kExtractThreads>(q, scratch, &tot_q);
+        s_op[threadIdx.x] = at_ops + before_o;
+        s_sq[threadIdx.x] = at_seq + before_q;
+        s_no[threadIdx.x] = o;
+        s_nq[threadIdx.x] = q;
+        if (k < n) {
+            cig_off[base + k] = at_ops + before_o;
+            seq_off[base + k] = at_seq + before_q;
+        }
+        __syncthreads();
+        const uint32_t here = n - k0 < (uint32_t)kExtractThreads ? n - k0 : (uint32_t)kExtractThreads;
+        for (uint32_t j = group; j < here; j += kExtractThreads / kBaseLanes) {
+            const uint8_t *r = seg + offs[k0 + j];
+            const uint8_t *c;
+            const uint32_t n_ops = record_cigar(r, &c);
+            const uint32_t l_name = ld32(r + 12) & 0xFFu, n_cig = ld32(r + 16) & 0xFFFFu;
+            const int64_t to_op = s_op[j], g = s_sq[j];
+            const uint32_t l = s_nq[j];
+            for (uint32_t t = gl; t < n_ops && t < s_no[j]; t += kBaseLanes)
+                if (to_op + t < n_ops_total) ops_out[to_op + t] = ld32(c + 4 * t);
+            if (l == 0 || g + l > n_bases_total) continue;
+            const uint8_t *sq = r + 36 + l_name + 4 * n_cig, *ql = sq + (l + 1) / 2;
+            for (uint32_t t = gl; t < l; t += kBaseLanes) qual_out[g + t] = ql[t];
+            if (!(g & 1)) {
+                // on its own byte: l / 2 whole bytes, then a high half that the next record's first base shares
+                for (uint32_t b = gl; b < l / 2; b += kBaseLanes) seq_out[g / 2 + b] = sq[b];
+                if ((l & 1) && gl == 0) or_byte(seq_out, (g + l - 1) / 2, (uint32_t)sq[l / 2] & 0xF0u);
+            } else {
+                // in the low half of a byte: base 0 there, bases 2b + 1, 2b + 2 make byte 1 + b, a last base alone a high half
+                uint8_t *d = seq_out + g / 2;
+                const uint32_t pairs = (l - 1) / 2;
+                if (gl == 0) or_byte(seq_out, g / 2, (uint32_t)sq[0] >> 4);
+                for (uint32_t b = gl; b < pairs; b += kBaseLanes) d[1 + b] = (uint8_t)(((uint32_t)sq[b] << 4) | ((uint32_t)sq[b + 1] >> 4));
+                if (!(l & 1) && gl == 0) or_byte(seq_out, g / 2 + 1 + pairs, ((uint32_t)sq[pairs] << 4) & 0xF0u);
+            }
+        }
+        at_ops += tot_o;
+        at_seq += tot_q;
+        __syncthreads();
     }
 }
 
@@ -1269,7 +1386,7 @@ struct Reservation {
 // in *out or an error; t_gpu_join receives the time before the layout, t_layout the layout's.
 int finish_reads(bsig_ctx *ctx, hipStream_t st, ScratchPool &tmp, std::vector<std::unique_ptr<Piece>> &pieces, int64_t n_reads,
                  const BamHeader &hdr, const long long *d_ref_first, double &t_gpu_join, double &t_layout, bsig_reads **out,
-                 Reservation *reserved, const std::vector<GapTable> *gaps = nullptr)
+                 Reservation *reserved, const std::vector<GapTable> *gaps = nullptr, const std::vector<BasePiece> *bases = nullptr)
 {
     const double t_join = now_s();
     const int32_t n_ref = (int32_t)hdr.names.size();
@@ -1282,6 +1399,7 @@ int finish_reads(bsig_ctx *ctx, hipStream_t st, ScratchPool &tmp, std::vector<st
         R->spliced = gaps != nullptr;
         const int rc = layout_from_device(ctx, R, 0, n_ref, hdr.lens.data(), ref_off.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
         if (rc) return bail(rc);
+        if (bases) R->btab.present = true;          // (an empty set with bases: an empty table)
         *out = R;
         return BSIG_OK;
     }
@@ -1348,6 +1466,9 @@ int finish_reads(bsig_ctx *ctx, hipStream_t st, ScratchPool &tmp, std::vector<st
     } else {
         rc = layout_from_device(ctx, R, n_reads, n_ref, hdr.lens.data(), ref_off.data(), cols->pos, cols->end, cols->flag,
                                 cols->mapq, cols->tlen);
+        // a decode with bases: the plain layout above, and the chunks' base pieces as the set's base table (nucleotides.hip)
+        if (rc == BSIG_OK && bases)
+            rc = bases_from_device(ctx, R, n_reads, n_ref, ref_off.data(), cols->pos, cols->end, cols->flag, cols->mapq, *bases);
     }
     if (rc) return bail(rc);
     t_layout = now_s() - t_lay;
@@ -1386,6 +1507,10 @@ struct ShareOut {
     // each, the reads numbered share-locally
     bool want_gaps = false;
     std::vector<GapTable> gaps;
+    // a decode with bases (set by the caller): every chunk also leaves its records' operations, bases and qualities, one
+    // piece of the base table each, numbered within the chunk (nucleotides.h); bases_bad: a record's l_seq ran past it
+    bool want_bases = false, bases_bad = false;
+    std::vector<BasePiece> bases;
 };
 constexpr size_t kOverlapBlocks = 4;
 
@@ -1424,6 +1549,65 @@ hipError_t chunk_gaps(ScratchPool &tmp, hipStream_t st, const uint8_t *d_stream,
     tmp.give_back(d_read_gaps);
     tmp.give_back(d_seg_gaps);
     tmp.give_back(d_seg_gap_base);
+    return e;
+}
+
+// The base piece of one chunk, launched right behind its k_bam_extract with the same segment arguments while the chunk's
+// stream is still resident: operations and l_seq per record and segment, two scans on the device, ONE host read (the two
+// totals and the verdict on the l_seqs) to size the piece, the zeroed nibbles, emit.
+hipError_t chunk_bases(ScratchPool &tmp, hipStream_t st, const uint8_t *d_stream, const uint64_t *d_seg_start, const uint16_t *d_off16,
+                       const uint32_t *d_seg_n, const int64_t *d_seg_base, int64_t n_seg, int64_t n_chunk, ShareOut &R)
+{
+    uint32_t *d_read_ops = nullptr, *d_read_seq = nullptr, *d_seg_ops = nullptr, *d_seg_seq = nullptr;
+    int64_t *d_seg_ops_base = nullptr, *d_seg_seq_base = nullptr, *d_totals = nullptr;
+    hipError_t e = tmp.alloc(&d_read_ops, (size_t)n_chunk);
+    if (e == hipSuccess) e = tmp.alloc(&d_read_seq, (size_t)n_chunk);
+    if (e == hipSuccess) e = tmp.alloc(&d_seg_ops, (size_t)n_seg);
+    if (e == hipSuccess) e = tmp.alloc(&d_seg_seq, (size_t)n_seg);
+    if (e == hipSuccess) e = tmp.alloc(&d_seg_ops_base, (size_t)n_seg);
+    if (e == hipSuccess) e = tmp.alloc(&d_seg_seq_base, (size_t)n_seg);
+    if (e == hipSuccess) e = tmp.alloc(&d_totals, 3);              // operations, bases, the verdict (an int in the third)
+    if (e != hipSuccess) return e;
+    int *d_bad = reinterpret_cast<int *>(d_totals + 2);
+    e = hipMemsetAsync(d_totals, 0, 3 * sizeof(int64_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bam_base_count, dim3((unsigned)n_seg), dim3(kExtractThreads), 0, st, d_stream, d_seg_start, d_off16, d_seg_n,
+                       d_seg_base, d_read_ops, d_read_seq, d_seg_ops, d_seg_seq, d_bad);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = launch_gap_scan(n_seg, d_seg_ops, d_seg_ops_base, d_totals, st);
+    if (e == hipSuccess) e = launch_gap_scan(n_seg, d_seg_seq, d_seg_seq_base, d_totals + 1, st);
+    int64_t totals[3] = {0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && totals[2] != 0) R.bases_bad = true;
+    if (e == hipSuccess && !R.bases_bad) {
+        BasePiece piece;
+        piece.n = n_chunk; piece.n_ops = totals[0]; piece.n_bases = totals[1];
+        int64_t *d_cig_off = nullptr, *d_seq_off = nullptr;
+        uint32_t *d_ops = nullptr;
+        uint8_t *d_seq = nullptr, *d_qual = nullptr;
+        const size_t seq_bytes = (size_t)((piece.n_bases + 1) / 2) + 4;     // (whole dwords for the half bytes' atomics)
+        e = tmp.alloc(&d_cig_off, (size_t)n_chunk);
+        if (e == hipSuccess) e = tmp.alloc(&d_seq_off, (size_t)n_chunk);
+        if (e == hipSuccess) e = tmp.alloc(&d_ops, (size_t)std::max<int64_t>(piece.n_ops, 1));
+        if (e == hipSuccess) e = tmp.alloc(&d_seq, seq_bytes);
+        if (e == hipSuccess) e = tmp.alloc(&d_qual, (size_t)std::max<int64_t>(piece.n_bases, 1));
+        if (e == hipSuccess) e = hipMemsetAsync(d_seq, 0, seq_bytes, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_bam_base_emit, dim3((unsigned)n_seg), dim3(kExtractThreads), 0, st, d_stream, d_seg_start, d_off16, d_seg_n,
+                           d_seg_base, d_read_ops, d_read_seq, d_seg_ops_base, d_seg_seq_base, d_cig_off, d_seq_off, d_ops, d_seq, d_qual,
+                           piece.n_ops, piece.n_bases);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);      // (the counts go back below)
+        piece.cig_off = d_cig_off; piece.seq_off = d_seq_off; piece.cigar = d_ops; piece.seq = d_seq; piece.qual = d_qual;
+        R.bases.push_back(piece);
+    }
+    tmp.give_back(d_read_ops);
+    tmp.give_back(d_read_seq);
+    tmp.give_back(d_seg_ops);
+    tmp.give_back(d_seg_seq);
+    tmp.give_back(d_seg_ops_base);
+    tmp.give_back(d_seg_seq_base);
     return e;
 }
 
@@ -1891,6 +2075,7 @@ int decode_share(bsig_ctx *ctx, const BgzfFile &f, const BamHeader &hdr, const s
                                d_seg_n, d_seg_base, d_seg_prev, pc.pos, pc.flag, pc.mapq, pc.tlen, pc.end, R.d_ref_first, R.n_reads);
             DD_TRY(hipGetLastError());
             if (R.want_gaps) DD_TRY(chunk_gaps(tmp, st, d_stream, d_seg_start, d_off16, d_seg_n, d_seg_base, n_seg, n_chunk, R.n_reads, R));
+            if (R.want_bases) DD_TRY(chunk_bases(tmp, st, d_stream, d_seg_start, d_off16, d_seg_n, d_seg_base, n_seg, n_chunk, R));
             R.n_reads += n_chunk;
         }
         // the cut-off record moves in front of the next chunk (source and destination do not overlap:
@@ -2236,14 +2421,17 @@ int reads_from_bam_streamed(bsig_ctx *ctx, const std::string &path, int threads,
 // GPUs: the chains must meet, the reads must stay in order.
 // spliced: the reads split at their N gaps (splice.hip).  Such a decode takes neither the streamed form nor the two-step
 // scan nor the reservation: one share, chunk by chunk, every chunk leaving its gap piece.
-int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, bsig_reads **out, bool spliced = false)
+// bases: a plain set with its base table (nucleotides.hip); the same simplifications as a spliced decode, every chunk leaving
+// its base piece.  A record whose l_seq runs past it sends the file to the host decode, which names it.
+int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, bsig_reads **out, bool spliced = false, bool bases = false)
 {
+    const bool plain = !spliced && !bases;
     double *T = g_dev_decode_timing;
     for (int k = 0; k < 6; ++k) T[k] = 0;
     const double t_begin = now_s();
     *out = nullptr;
     diag_mark(nullptr);
-    if (!spliced) {
+    if (plain) {
         // large files: the file streamed into HBM once, decoded round by round behind the stream
         bool taken = false;
         const int rs = reads_from_bam_streamed(ctx, path, threads, out, taken, T);
@@ -2265,6 +2453,7 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
     T[0] = now_s() - t_begin;
     ShareOut S, S2;
     S.want_gaps = spliced;
+    S.want_bases = bases;
     bool two = false;
     // the resident columns are reserved while the file is still being inflated (Reservation above): the first pass
     // says how many reads a byte of stream holds; 8 bytes per read (a packed word and the template length) plus the
@@ -2294,7 +2483,7 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
         const double est_blocks = (double)hb.size() * (double)F.f.size() / (double)std::max<uint64_t>(seen, 1);
         double min_blocks = 150000.0;
         if (const char *e = getenv("BAMSIGNALS_TWO_STEP_MIN_BLOCKS")) min_blocks = atof(e);
-        if (!spliced && F.gpu_inflate && hb.size() > 4 * kOverlapBlocks && est_blocks >= min_blocks) {
+        if (plain && F.gpu_inflate && hb.size() > 4 * kOverlapBlocks && est_blocks >= min_blocks) {
             // the head share ends kOverlapBlocks before the end of what is tabulated: its last record may run on
             // ... and holds whole rounds of inflate lanes (the blocks behind them go with the rest)
             size_t Bh = F.f.blocks().size() - kOverlapBlocks;
@@ -2323,8 +2512,9 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
         }
     }
     if (!two) {
-        rc = decode_share(ctx, F.f, F.hdr, F.uoff, 0, F.f.blocks().size(), threads, F.gpu_inflate, S, false, false, spliced ? nullptr : &reserve);
+        rc = decode_share(ctx, F.f, F.hdr, F.uoff, 0, F.f.blocks().size(), threads, F.gpu_inflate, S, false, false, plain ? &reserve : nullptr);
         if (rc) return rc;
+        if (S.bases_bad) return kNeedsCpuPath;
     }
     diag_mark("decode_share (all passes)");
     T[1] = S.t_inflate + S2.t_inflate;
@@ -2350,7 +2540,7 @@ int reads_from_bam_device(bsig_ctx *ctx, const std::string &path, int threads, b
         rc = finish_reads(ctx, ctx->stream, *S2.tmp, pieces, S.n_reads + S2.n_reads, F.hdr, S2.d_ref_first, t_join, t_layout, out, &reserved);
     } else {
         rc = finish_reads(ctx, ctx->stream, *S.tmp, S.pieces, S.n_reads, F.hdr, S.d_ref_first, t_join, t_layout, out, &reserved,
-                          spliced ? &S.gaps : nullptr);
+                          spliced ? &S.gaps : nullptr, bases ? &S.bases : nullptr);
     }
     g_reserve_wait = reserved.t_wait;
     if (rc) return rc;
@@ -2883,6 +3073,7 @@ int decode_islands(bsig_ctx *ctx, const BgzfFile &f, const BamHeader &hdr, const
                                d_seg_n, d_seg_base, d_seg_prev, pc.pos, pc.flag, pc.mapq, pc.tlen, pc.end, d_ref_first, n_reads);
             DR_TRY(hipGetLastError());
             if (R.want_gaps) DR_TRY(chunk_gaps(tmp, st, d_view, d_seg_start, d_off16, d_seg_n, d_seg_base, n_seg, n_chunk, n_reads, R));
+            if (R.want_bases) DR_TRY(chunk_bases(tmp, st, d_view, d_seg_start, d_off16, d_seg_n, d_seg_base, n_seg, n_chunk, R));
             n_reads += n_chunk;
         }
         DR_TRY(hipStreamSynchronize(st));
@@ -2914,7 +3105,7 @@ bool islands_gpu_inflate(const std::vector<Island> &isl, int threads)
 // for.  A superset of the overlapping records, each at most once, in file order -- exactly what the CPU
 // region decode (bamio.cpp: bam_decode_regions) returns.
 int reads_from_regions_device(bsig_ctx *ctx, const std::string &path, const BaiIndex &idx,
-                              const std::vector<Region> &regions, int threads, bsig_reads **out, bool spliced = false)
+                              const std::vector<Region> &regions, int threads, bsig_reads **out, bool spliced = false, bool bases = false)
 {
     double *T = g_dev_decode_timing;
     for (int k = 0; k < 6; ++k) T[k] = 0;
@@ -2931,8 +3122,10 @@ int reads_from_regions_device(bsig_ctx *ctx, const std::string &path, const BaiI
     T[0] = now_s() - t_begin;
     ShareOut S;
     S.want_gaps = spliced;
+    S.want_bases = bases;
     rc = decode_islands(ctx, f, hdr, isl, 0, isl.size(), threads, islands_gpu_inflate(isl, threads), S);
     if (rc) return rc;
+    if (S.bases_bad) return kNeedsCpuPath;
     T[1] = S.t_inflate;
     T[2] = S.t_wait;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2940,7 +3133,7 @@ int reads_from_regions_device(bsig_ctx *ctx, const std::string &path, const BaiI
     // ---- join the pieces, first read of every reference, resident layout ---------------------------
     double t_join = 0, t_layout = 0;
     rc = finish_reads(ctx, ctx->stream, *S.tmp, S.pieces, S.n_reads, hdr, S.d_ref_first, t_join, t_layout, out, nullptr,
-                      spliced ? &S.gaps : nullptr);
+                      spliced ? &S.gaps : nullptr, bases ? &S.bases : nullptr);
     if (rc) return rc;
     T[3] = S.t_gpu + t_join;
     T[5] = t_layout;
@@ -3031,20 +3224,23 @@ hipError_t warm_decode_module(hipStream_t st)
 
 extern "C" {
 
-static int reads_from_bam_impl(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads, bool spliced)
+static int reads_from_bam_impl(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads, bool spliced, bool bases = false)
 {
     *reads = nullptr;
     const char *path = bsig_bam_path(bam);
     const char *mode = getenv("BAMSIGNALS_DEVICE_DECODE");        // "0": always the CPU decode
     int rc = bsig::kNeedsCpuPath;
-    if (!(mode && !strcmp(mode, "0"))) rc = bsig::reads_from_bam_device(ctx, path, threads, reads, spliced);
+    if (!(mode && !strcmp(mode, "0"))) rc = bsig::reads_from_bam_device(ctx, path, threads, reads, spliced, bases);
     if (rc != bsig::kNeedsCpuPath) return rc;
     if (mode && !strcmp(mode, "require"))                          // testing: no silent change of path
         return fail(BSIG_ERR_FORMAT, "%s needs the CPU decode path (BAMSIGNALS_DEVICE_DECODE=require)", path);
     bsig_columns cols;
-    rc = bsig_bam_decode(bam, -1, nullptr, nullptr, nullptr, threads, &cols);
+    bsig_base_columns bcols;
+    rc = bases ? bsig_bam_decode_bases(bam, -1, nullptr, nullptr, nullptr, threads, &cols, &bcols)
+               : bsig_bam_decode(bam, -1, nullptr, nullptr, nullptr, threads, &cols);
     if (rc) return rc;
     for (int k = 0; k < 6; ++k) g_dev_decode_timing[k] = 0;
+    if (bases) return bsig_reads_upload_bases(ctx, &cols, &bcols, reads);
     // (the CPU decode's columns hold the CIGARs: the gap table comes from them)
     return spliced ? bsig_reads_upload_spliced(ctx, &cols, reads) : bsig_reads_upload(ctx, &cols, reads);
 }
@@ -3059,6 +3255,12 @@ int bsig_reads_from_bam_spliced(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, b
 {
     if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_spliced");
     return reads_from_bam_impl(ctx, bam, threads, reads, true);
+}
+
+int bsig_reads_from_bam_bases(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads)
+{
+    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_bases");
+    return reads_from_bam_impl(ctx, bam, threads, reads, false, true);
 }
 
 int bsig_reads_from_bam_multi(bsig_ctx *const *ctxs, int32_t n, bsig_bam *bam, int32_t threads, bsig_reads **reads,
@@ -3095,9 +3297,10 @@ int bsig_reads_from_bam_multi(bsig_ctx *const *ctxs, int32_t n, bsig_bam *bam, i
 }
 
 static int reads_from_regions_impl(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
-                                   const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads, bool spliced)
+                                   const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads, bool spliced,
+                                   bool bases = false)
 {
-    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_regions%s", spliced ? "_spliced" : "");
+    if (!ctx || !bam || !reads) return fail(BSIG_ERR_ARG, "NULL argument to bsig_reads_from_bam_regions%s", spliced ? "_spliced" : bases ? "_bases" : "");
     if (n_regions < 0 || (n_regions > 0 && (!rid || !beg || !end))) return fail(BSIG_ERR_ARG, "region arrays missing");
     *reads = nullptr;
     const char *mode = getenv("BAMSIGNALS_DEVICE_DECODE");
@@ -3105,15 +3308,18 @@ static int reads_from_regions_impl(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regio
     if (!(mode && !strcmp(mode, "0"))) {
         std::vector<bsig::Region> rg((size_t)n_regions);
         for (int64_t i = 0; i < n_regions; ++i) rg[(size_t)i] = bsig::Region{rid[i], beg[i], end[i]};
-        rc = bsig::reads_from_regions_device(ctx, bsig_bam_path(bam), *bsig_bam_index(bam), rg, threads, reads, spliced);
+        rc = bsig::reads_from_regions_device(ctx, bsig_bam_path(bam), *bsig_bam_index(bam), rg, threads, reads, spliced, bases);
     }
     if (rc != bsig::kNeedsCpuPath) return rc;
     if (mode && !strcmp(mode, "require"))
         return fail(BSIG_ERR_FORMAT, "%s needs the CPU decode path (BAMSIGNALS_DEVICE_DECODE=require)", bsig_bam_path(bam));
     bsig_columns cols;
-    rc = bsig_bam_decode(bam, n_regions, rid, beg, end, threads, &cols);
+    bsig_base_columns bcols;
+    rc = bases ? bsig_bam_decode_bases(bam, n_regions, rid, beg, end, threads, &cols, &bcols)
+               : bsig_bam_decode(bam, n_regions, rid, beg, end, threads, &cols);
     if (rc) return rc;
     for (int k = 0; k < 6; ++k) g_dev_decode_timing[k] = 0;
+    if (bases) return bsig_reads_upload_bases(ctx, &cols, &bcols, reads);
     return spliced ? bsig_reads_upload_spliced(ctx, &cols, reads) : bsig_reads_upload(ctx, &cols, reads);
 }
 
@@ -3127,6 +3333,12 @@ int bsig_reads_from_bam_regions_spliced(bsig_ctx *ctx, bsig_bam *bam, int64_t n_
                                         const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads)
 {
     return reads_from_regions_impl(ctx, bam, n_regions, rid, beg, end, threads, reads, true);
+}
+
+int bsig_reads_from_bam_regions_bases(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
+                                      const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads)
+{
+    return reads_from_regions_impl(ctx, bam, n_regions, rid, beg, end, threads, reads, false, true);
 }
 
 // (debug, host only -- no GPU is touched: the block table as RawStream's header walk builds it, the file fed in chunks

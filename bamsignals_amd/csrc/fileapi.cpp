@@ -21,6 +21,7 @@
 #include "genecounts.h"
 #include "host_util.h"
 #include "junctions.h"
+#include "nucleotides.h"
 #include "runtime_internal.h"
 
 using bsig::EncodedColumns;
@@ -32,6 +33,7 @@ struct bsig_bam {
     bsig::BaiIndex idx;
     bool from_csi = false;      // the index was read from a .csi file (htslib's bam_index_load accepts both, ref: :207)
     bsig::HostColumns cols;
+    bsig::HostBases bases;      // ... of bsig_bam_decode_bases
     std::string idx_err;
     // file-level handles: the index is parsed by a helper thread.  LAST member: its destructor waits for that
     // thread, which writes idx and idx_err above
@@ -185,6 +187,25 @@ int bsig_bam_decode(bsig_bam *b, int64_t n_regions, const int32_t *rid, const in
     }
     if (rc) return rc;
     fill_columns(b, cols);
+    return BSIG_OK;
+}
+
+int bsig_bam_decode_bases(bsig_bam *b, int64_t n_regions, const int32_t *rid, const int64_t *beg, const int64_t *end,
+                          int32_t threads, bsig_columns *cols, bsig_base_columns *bases)
+{
+    if (!b || !cols || !bases) return fail(BSIG_ERR_ARG, "NULL argument to bsig_bam_decode_bases");
+    if (n_regions > 0 && (!rid || !beg || !end)) return fail(BSIG_ERR_ARG, "region arrays missing");
+    std::vector<bsig::Region> rg((size_t)std::max<int64_t>(n_regions, 0));
+    for (int64_t i = 0; i < n_regions; ++i) rg[(size_t)i] = bsig::Region{rid[i], beg[i], end[i]};
+    if (n_regions >= 0)
+        if (const int rc = bam_index_wait(b)) return rc;
+    bsig::BamHeader h;
+    const int rc = bsig::bam_decode_bases(b->path, n_regions < 0 ? nullptr : &b->idx, rg, threads, h, b->cols, b->bases);
+    if (rc) return rc;
+    fill_columns(b, cols);
+    bases->seq_off = b->bases.seq_off.data();
+    bases->seq = b->bases.seq.data();
+    bases->qual = b->bases.qual.data();
     return BSIG_OK;
 }
 
@@ -672,6 +693,20 @@ int bsig_junctions(const char *bampath, int64_t n, const int32_t *seq_code, int3
                                            FileDest::junction_table(res.get(), min_anchor), true));
     if (rc == BSIG_OK) *result = res.release();
     return rc;
+}
+
+// bamNucleotides: A / C / G / T / N / deletion counts per base from the file's reads with bases.  The call carries a coverage
+// call's parameters (the range rule is theirs: widths that are not negative); min_base_qual is judged before the BAM is opened.
+int bsig_nucleotides(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+                     const char *const *levels, const int32_t *start, const int32_t *width, const int32_t *strand,
+                     int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual, int32_t ss, int32_t device,
+                     int32_t *out)
+{
+    bsig_params p = coverage_params(nullptr, 0, mapqual, requiredF, filteredF, 0, true, 1, ss != 0);
+    FileCall c{{bampath, n, seq_code, n_levels, levels, start, width, strand}, p, device, FileDest::nucleotide_cells(out, min_base_qual)};
+    c.bases = true;
+    c.rule_first = true;
+    return file_level(c);
 }
 
 // bamGeneCounts: every read of the file's spliced reads against a gene model.  A spliced call without ranges (the model's

@@ -23,6 +23,7 @@
 #include "genecounts.h"
 #include "host_util.h"
 #include "junctions.h"
+#include "nucleotides.h"
 #include "rangemath.h"
 
 namespace bsig {
@@ -881,6 +882,8 @@ int judge_call(const FileCall &c, Stage &s)
         if (!to.junctions) return fail(BSIG_ERR_ARG, "result is NULL");
         if (const int rk = junctions_rule(to.arg)) return rk;
     }
+    if (to.shape == Shape::nucleotides)
+        if (const int rk = nucleotides_rule(to.arg)) return rk;
     if (to.shape == Shape::genes) {
         if (const int rk = gene_counts_rule(to.model, to.arg, to.gene_counts, to.gene_summary)) return rk;
         if (at.n_levels != to.model->host.n_ref)
@@ -1049,6 +1052,7 @@ int slots_for(const std::vector<int> &devs, Stage &s)
     s.rkey = s.bkey + "@";
     for (int d : devs) s.rkey += std::to_string(d) + ",";
     if (s.call.spliced) s.rkey += "|spliced";      // (a file's plain and spliced reads are two resident sets)
+    if (s.call.bases) s.rkey += "|bases";          // (... and its reads with bases a third, kept only once a nucleotide call asked)
     s.many = devs.size() > 1 || env_is("BAMSIGNALS_FORCE_SHARDED", "1");     // (=1: the multi-GPU route on one GPU, testing)
     std::lock_guard<std::mutex> lock(g_cache.mu);
     for (auto &sp : g_cache.slot_sets)
@@ -1114,6 +1118,7 @@ bool lookup_reads(Stage &s, const Wanted &w)
         s.how_decoded = s.call.spliced ? "spliced, resident (index-driven decode of an earlier call)"
                                        : "resident (index-driven decode of an earlier call)";
     }
+    if (s.call.bases) s.how_decoded = "with bases, " + s.how_decoded;
     if (s.res) s.T[5] = 1;
     return s.res != nullptr;
 }
@@ -1138,7 +1143,8 @@ int decode_to_slots(Stage &s, double *t6, const char **transport, Sharded sharde
         bsig_device_decode_timing(t6);
         if (rc == BSIG_OK)
             rc = for_each_slot(R.reads.size(), [&](size_t k) -> int {
-                return k == 0 ? (int)BSIG_OK : bsig_reads_clone(R.reads[0], s.slots->ctx[k], &R.reads[k]);
+                // (a set with bases is asked on the first slot alone -- nucleotides_on_first --: its table is not copied round)
+                return k == 0 || s.call.bases ? (int)BSIG_OK : bsig_reads_clone(R.reads[0], s.slots->ctx[k], &R.reads[k]);
             });
     }
     return rc;
@@ -1156,8 +1162,8 @@ int decode_whole(Stage &s, Sidecar &side, double *t6)
     const char *bampath = s.call.at.bampath;
     Resident &R = *s.res;
     const std::vector<bsig_ctx *> &ctx = s.slots->ctx;
-    // (spliced reads have no reads file: none is loaded, none is written)
-    const std::string path = s.key.empty() || s.call.spliced ? std::string() : sidecar_path(bampath);
+    // (spliced reads and reads with bases have no reads file: none is loaded, none is written)
+    const std::string path = s.key.empty() || s.call.spliced || s.call.bases ? std::string() : sidecar_path(bampath);
     // (the reads file is tied to the CONTENT it was made from -- size and mtime of the BAM and of its
     // index files -- not to the spelling of the path it was reached by)
     side.stamp = file_stamp(bampath) + "#" + index_stamps(bampath);
@@ -1171,17 +1177,19 @@ int decode_whole(Stage &s, Sidecar &side, double *t6)
         R.free_reads();
     }
     const char *transport = nullptr;
-    const bool spliced = s.call.spliced;
-    // (a spliced set is decoded on the first GPU and cloned: the sharded route declines it)
+    const bool spliced = s.call.spliced, bases = s.call.bases;
+    // (a spliced set is decoded on the first GPU and cloned, one with bases stays there: the sharded route declines both)
     const int rc = decode_to_slots(s, t6, &transport,
-                                   [&](const char **over) { return spliced ? (int)kNeedsCpuPath : reads_from_bam_sharded(ctx, bampath, 0, R.reads, over); },
+                                   [&](const char **over) { return spliced || bases ? (int)kNeedsCpuPath : reads_from_bam_sharded(ctx, bampath, 0, R.reads, over); },
                                    [&] {
-                                       return spliced ? bsig_reads_from_bam_spliced(ctx[0], s.ob->bam, 0, &R.reads[0])
-                                                      : bsig_reads_from_bam(ctx[0], s.ob->bam, 0, &R.reads[0]);
+                                       return bases     ? bsig_reads_from_bam_bases(ctx[0], s.ob->bam, 0, &R.reads[0])
+                                              : spliced ? bsig_reads_from_bam_spliced(ctx[0], s.ob->bam, 0, &R.reads[0])
+                                                        : bsig_reads_from_bam(ctx[0], s.ob->bam, 0, &R.reads[0]);
                                    });
     s.how_decoded = transport ? std::string("sharded decode, columns over ") + transport
                               : ctx.size() > 1 ? "decode on the first GPU + clones" : "decode";
     if (spliced) s.how_decoded = "spliced " + s.how_decoded;
+    if (bases) s.how_decoded = "with bases, " + s.how_decoded;
     if (rc == BSIG_OK) side.to_write = path;          // written after the decode lock is released (best effort)
     return rc;
 }
@@ -1196,14 +1204,17 @@ int decode_regions(Stage &s, const Wanted &w, double *t6)
     int rc = bam_index_wait(bam);                 // (parsed in the background since the open)
     if (rc) return rc;
     const char *transport = nullptr;
-    const bool spliced = s.call.spliced;
+    const bool spliced = s.call.spliced, bases = s.call.bases;
     rc = decode_to_slots(s, t6, &transport,
                          [&](const char **over) {
-                             if (spliced) return (int)kNeedsCpuPath;
+                             if (spliced || bases) return (int)kNeedsCpuPath;
                              return reads_from_regions_sharded(s.slots->ctx, s.call.at.bampath, *bsig_bam_index(bam), n, s.rid.data(),
                                                                w.qbeg.data(), w.qend.data(), 0, R.reads, over);
                          },
                          [&] {
+                             if (bases)
+                                 return bsig_reads_from_bam_regions_bases(s.slots->ctx[0], bam, n, s.rid.data(), w.qbeg.data(), w.qend.data(), 0,
+                                                                          &R.reads[0]);
                              return spliced ? bsig_reads_from_bam_regions_spliced(s.slots->ctx[0], bam, n, s.rid.data(), w.qbeg.data(),
                                                                                  w.qend.data(), 0, &R.reads[0])
                                             : bsig_reads_from_bam_regions(s.slots->ctx[0], bam, n, s.rid.data(), w.qbeg.data(), w.qend.data(), 0,
@@ -1211,6 +1222,7 @@ int decode_regions(Stage &s, const Wanted &w, double *t6)
                          });
     s.how_decoded = transport ? std::string("index-driven decode, sharded, columns over ") + transport : "index-driven decode";
     if (spliced) s.how_decoded = "spliced " + s.how_decoded;
+    if (bases) s.how_decoded = "with bases, " + s.how_decoded;
     if (rc == BSIG_OK) set_coverage(R.cov, n, s.rid.data(), w.qbeg.data(), w.qend.data());
     return rc;
 }
@@ -1309,6 +1321,18 @@ int junctions_on_first(const Stage &s, std::string &route)
     return rc;
 }
 
+// The nucleotide counts of the ranges (bsig_nucleotides): the query of nucleotides.hip on the first slot's set with bases -- the
+// table is the same on every slot --, downloaded into the caller's cells
+int nucleotides_on_first(const Stage &s, std::string &route)
+{
+    const FileCall &c = s.call;
+    const RangeView g = s.ranges();
+    const int rc = nucleotides_query(s.res->reads[0], g.n, g.rid, g.loc, g.width, g.strand, c.prm.mapqual, c.prm.requiredF, c.prm.filteredF,
+                                     c.to.arg, c.prm.ss, nullptr, c.to.out);
+    route = "nucleotides of " + std::to_string(g.n) + " range(s), counted on the first GPU";
+    return rc;
+}
+
 // The reads per gene (bsig_gene_counts): the query of genecounts.hip on the first slot's spliced set -- the read table is the
 // same on every slot, and only the two int64 vectors come back
 int gene_counts_on_first(const Stage &s, std::string &route)
@@ -1347,12 +1371,14 @@ int run_result(const Stage &s, std::string &result)
         if (attempt) drop_spare_device_memory(s.slots.get());
         if (to.shape == FileDest::Shape::junctions) rc = junctions_on_first(s, result);
         else if (to.shape == FileDest::Shape::genes) rc = gene_counts_on_first(s, result);
+        else if (to.shape == FileDest::Shape::nucleotides) rc = nucleotides_on_first(s, result);
         else if (to.shape == FileDest::Shape::reduced) rc = reduced_on_slots(s, result);
         else if (to.runs) rc = encoded_on_slots(s, result);
         else if (!s.many) rc = run_on_one(s, t_run);
         else rc = run_on_slots(s, result);
     }
-    if (!s.many && to.shape != FileDest::Shape::reduced && to.shape != FileDest::Shape::junctions && to.shape != FileDest::Shape::genes && !to.runs)
+    if (!s.many && to.shape != FileDest::Shape::reduced && to.shape != FileDest::Shape::junctions && to.shape != FileDest::Shape::genes &&
+        to.shape != FileDest::Shape::nucleotides && !to.runs)
         result = "download";
     return rc;
 }

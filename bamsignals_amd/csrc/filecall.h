@@ -35,10 +35,11 @@ inline Encoder views_encoder(int32_t lower, int32_t upper) { return Encoder{Enco
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
 // layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, an encoder's columns, or the columns of
-// a junction query (junctions.hip), or the two int64 vectors of a gene count (genecounts.hip)
+// a junction query (junctions.hip), the two int64 vectors of a gene count (genecounts.hip), or the int32 cells of a nucleotide
+// count (nucleotides.hip: bsig_nucleotides_cells' layout, not bsig_layout's)
 enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled, vplot, capped };
 struct FileDest {
-    enum class Shape { flat, into, reduced, encoded, junctions, genes } shape = Shape::flat;
+    enum class Shape { flat, into, reduced, encoded, junctions, genes, nucleotides } shape = Shape::flat;
     int32_t *out = nullptr;
     const int64_t *off = nullptr;
     int32_t *const *dst = nullptr;
@@ -47,7 +48,7 @@ struct FileDest {
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
     const char *name = "out";       // ... as the entry point calls that argument
     int32_t arg = 0;                // xcorr: max_lag; frag, vplot: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins;
-                                    // capped: keep_dup; junctions: min_anchor; genes: strandedness
+                                    // capped: keep_dup; junctions: min_anchor; genes: strandedness; nucleotides: min_base_qual
     const int32_t *thresholds = nullptr;    // summary: arg of them
     EncodedColumns *runs = nullptr;         // the per-range result as runs or views (enc says which), in the caller's range order
     Encoder enc = runs_encoder();
@@ -92,6 +93,12 @@ struct FileDest {
         to.shape = Shape::junctions; to.junctions = cols; to.arg = min_anchor;
         return to;
     }
+    static FileDest nucleotide_cells(int32_t *out, int32_t min_base_qual)
+    {
+        FileDest to;
+        to.shape = Shape::nucleotides; to.out = out; to.arg = min_base_qual;
+        return to;
+    }
     static FileDest gene_table(const bsig_gene_model *model, int32_t strandedness, int64_t *counts, int64_t *summary)
     {
         FileDest to;
@@ -125,6 +132,8 @@ struct FileCall {
     bool filter_missing = false;
     bool spliced = false;           // coverage that skips N gaps, the junctions, the gene counts: the call runs on the file's spliced
                                     // reads (splice.hip)
+    bool bases = false;             // the nucleotide counts: the call runs on the file's reads with bases (nucleotides.hip), a
+                                    // resident set of its own
     bool whole_file = false;        // the call speaks of every read of the file (the gene counts): never an index-driven decode
 };
 int file_level(const FileCall &call);

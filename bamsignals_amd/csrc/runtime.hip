@@ -936,6 +936,23 @@ int bsig_reads_clone(const bsig_reads *src, bsig_ctx *dst_ctx, bsig_reads **out)
         D.n_blocks = S.n_blocks;
     }
     R->rtab.h_ref_off = src->rtab.h_ref_off;
+    if (src->btab.present && src->btab.n > 0) {     // a set with bases: its base table (nucleotides.hip)
+        const bsig_reads::BaseTable &S = src->btab;
+        bsig_reads::BaseTable &D = R->btab;
+        const size_t reads = (size_t)S.n;
+        void *p;
+        copy(S.pos, reads * sizeof(int32_t), &p); D.pos = (const int32_t *)p;
+        copy(S.endmax, reads * sizeof(int32_t), &p); D.endmax = (const int32_t *)p;
+        copy(S.fm, reads * sizeof(uint32_t), &p); D.fm = (const uint32_t *)p;
+        copy(S.cig_off, (reads + 1) * sizeof(int64_t), &p); D.cig_off = (const int64_t *)p;
+        copy(S.seq_off, (reads + 1) * sizeof(int64_t), &p); D.seq_off = (const int64_t *)p;
+        copy(S.cigar, (size_t)std::max<int64_t>(S.n_ops, 1) * sizeof(uint32_t), &p); D.cigar = (const uint32_t *)p;
+        copy(S.seq, (size_t)std::max<int64_t>((S.n_bases + 1) / 2, 1), &p); D.seq = (const uint8_t *)p;
+        copy(S.qual, (size_t)std::max<int64_t>(S.n_bases, 1), &p); D.qual = (const uint8_t *)p;
+        copy(S.ref_off, ((size_t)src->n_ref + 1) * sizeof(int64_t), &p); D.ref_off = (const int64_t *)p;
+        D.n = S.n; D.n_ops = S.n_ops; D.n_bases = S.n_bases;
+    }
+    R->btab.present = src->btab.present;
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         delete R;
@@ -1254,6 +1271,9 @@ int bsig_reads_save(const bsig_reads *reads, const char *path, const char *stamp
     if (reads->spliced)
         return fail(BSIG_ERR_ARG, "spliced reads have no reads file: the format has no mark for rows that are aligned blocks, and a "
                                   "loader would take them for reads");
+    if (reads->btab.present)
+        return fail(BSIG_ERR_ARG, "reads with bases have no reads file: the format holds no base table, and a loader would "
+                                  "give back a set without one");
     HIP_TRY(hipSetDevice(reads->ctx->device));
     SidecarHeader H;
     memset(&H, 0, sizeof H);

@@ -204,6 +204,22 @@ struct bsig_reads {
         const int64_t *ref_off = nullptr;                // device: the first read of every reference, n_ref + 1 entries
         std::vector<int64_t> h_ref_off;                  // ... on the host
     } rtab;
+    // a set with bases (nucleotides.hip): an ordinary plain set that also keeps, in `pool`, its reads in BAM order with
+    // their CIGARs, bases and qualities -- the BASE TABLE the nucleotide counts walk.  Read k owns operations cig_off[k] ..
+    // cig_off[k + 1] and bases seq_off[k] .. seq_off[k + 1]; base g is nibble g of seq (byte g / 2, the high half where g is
+    // even) and byte g of qual.  endmax is the running maximum, within the read's reference, of the reads' last bases
+    // (clamped to int32): non-decreasing, so both ends of a tile's read window are binary searches.  An empty set with bases
+    // has an empty table (present, n = 0); a plain or spliced set has none
+    struct BaseTable {
+        bool present = false;
+        int64_t n = 0, n_ops = 0, n_bases = 0;
+        const int32_t *pos = nullptr, *endmax = nullptr;
+        const uint32_t *fm = nullptr;                    // flag | mapq << 16
+        const int64_t *cig_off = nullptr, *seq_off = nullptr;    // n + 1 entries each
+        const uint32_t *cigar = nullptr;
+        const uint8_t *seq = nullptr, *qual = nullptr;
+        const int64_t *ref_off = nullptr;                // device: the first read of every reference, n_ref + 1 entries
+    } btab;
 };
 namespace bsig { uint64_t next_layout_gen(); }
 

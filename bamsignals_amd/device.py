@@ -81,9 +81,15 @@ class Reads:
     ``spliced=True`` (needs ``cigar_off``/``cigar``): the reads are split at their N gaps and the rows are their aligned
     blocks, each with its read's flag, mapq and tlen (csrc/splice.hip); ``info()["n_reads"]`` then counts blocks.  Such
     reads give plain coverage only: every other plan refuses them.
+
+    ``bases=True`` (needs ``cigar_off``/``cigar`` and ``seq_off``, ``seq``, ``qual``): an ordinary plain set that also keeps
+    what the reads say -- read i owns bases ``seq_off[i] .. seq_off[i + 1]``; base g of the whole is nibble g of ``seq``
+    (BAM's 4-bit codes, the high half of byte ``g // 2`` where g is even) and byte g of ``qual`` (0xFF: missing) -- as a
+    base table beside the reads (csrc/nucleotides.hip).  Every plan works on it as on a plain set; ``nucleotides`` needs it.
     """
 
-    def __init__(self, ctx, ref_len, ref_off, pos, flag, mapq, tlen, end=None, cigar_off=None, cigar=None, *, spliced=False):
+    def __init__(self, ctx, ref_len, ref_off, pos, flag, mapq, tlen, end=None, cigar_off=None, cigar=None, *, spliced=False,
+                 bases=False, seq_off=None, seq=None, qual=None):
         self._lib = _lib.load()
         self.ctx = ctx
         ref_len = _i32(ref_len)
@@ -104,13 +110,17 @@ class Reads:
         keep = [ref_len, ref_off, pos, flag, mapq, tlen]
         if spliced and (cigar_off is None or cigar is None):
             raise ValueError("spliced reads need cigar_off + cigar: an end column does not say where the N gaps lie")
-        if end is not None and not spliced:
+        if bases and spliced:
+            raise ValueError("a set is spliced or has bases, not both")
+        if bases and (cigar_off is None or cigar is None or seq_off is None or seq is None or qual is None):
+            raise ValueError("reads with bases need cigar_off + cigar and seq_off, seq, qual")
+        if end is not None and not spliced and not bases:
             end = _i32(end)
             if len(end) != n:
                 raise ValueError("end column differs in length")
             cols.end = _ptr(end).value
             keep.append(end)
-        if end is None or spliced:
+        if end is None or spliced or bases:
             if cigar_off is None or cigar is None:
                 raise ValueError("need either end or cigar_off + cigar")
             cigar_off = np.ascontiguousarray(cigar_off, dtype=np.int64)
@@ -121,22 +131,40 @@ class Reads:
             cols.cigar = _ptr(cigar).value
             keep += [cigar_off, cigar]
         h = C.c_void_p()
-        upload = self._lib.bsig_reads_upload_spliced if spliced else self._lib.bsig_reads_upload
-        _lib.check(upload(ctx._h, C.byref(cols), C.byref(h)))
+        if bases:
+            seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            qual = np.ascontiguousarray(qual, dtype=np.uint8)
+            if len(seq_off) != n + 1:
+                raise ValueError("seq_off must have n_reads + 1 entries")
+            total = int(seq_off[-1])
+            if len(qual) < total or 2 * len(seq) < total:
+                raise ValueError("seq or qual is shorter than seq_off says")
+            bc = _lib.BaseColumns()
+            bc.seq_off, bc.seq, bc.qual = (_ptr(a).value for a in (seq_off, seq, qual))
+            _lib.check(self._lib.bsig_reads_upload_bases(ctx._h, C.byref(cols), C.byref(bc), C.byref(h)))
+        else:
+            upload = self._lib.bsig_reads_upload_spliced if spliced else self._lib.bsig_reads_upload
+            _lib.check(upload(ctx._h, C.byref(cols), C.byref(h)))
         self._h = h
         self.n_reads = n
         self.n_ref = len(ref_len)
 
     @classmethod
-    def from_bam(cls, ctx, bam, threads=0, *, spliced=False):
+    def from_bam(cls, ctx, bam, threads=0, *, spliced=False, bases=False):
         """The whole of an open ``bamio.BamFile`` decoded to HBM: BGZF inflate on the CPU thread pool,
         records -> columns on the GPU (csrc/devdecode.hip; CPU decode where the file needs it).  ``spliced``: the reads
-        split at their N gaps, the gaps found on the GPU while the stream is resident."""
+        split at their N gaps, the gaps found on the GPU while the stream is resident.  ``bases``: a plain set with its base
+        table (bases and qualities are decoded on the host)."""
         self = cls.__new__(cls)
         self._lib = _lib.load()
         self.ctx = ctx
         h = C.c_void_p()
+        if bases and spliced:
+            raise ValueError("a set is spliced or has bases, not both")
         decode = self._lib.bsig_reads_from_bam_spliced if spliced else self._lib.bsig_reads_from_bam
+        if bases:
+            decode = self._lib.bsig_reads_from_bam_bases
         _lib.check(decode(ctx._h, bam._h, int(threads), C.byref(h)))
         self._h = h
         self.n_ref = len(bam.ref_len)
@@ -165,7 +193,7 @@ class Reads:
         return out, bool(sharded.value)
 
     @classmethod
-    def from_bam_regions(cls, ctx, bam, rid, beg, end, threads=0, *, spliced=False):
+    def from_bam_regions(cls, ctx, bam, rid, beg, end, threads=0, *, spliced=False, bases=False):
         """The records the BAI lists for the regions [beg, end) (0-based) decoded to HBM -- a superset
         of the overlapping records, each once, in file order (what ``BamFile.decode(rid, beg, end)``
         returns on the host)."""
@@ -178,7 +206,11 @@ class Reads:
         if not (len(rid) == len(beg) == len(end)):
             raise ValueError("region arrays differ in length")
         h = C.c_void_p()
+        if bases and spliced:
+            raise ValueError("a set is spliced or has bases, not both")
         decode = self._lib.bsig_reads_from_bam_regions_spliced if spliced else self._lib.bsig_reads_from_bam_regions
+        if bases:
+            decode = self._lib.bsig_reads_from_bam_regions_bases
         _lib.check(decode(ctx._h, bam._h, len(rid), _ptr(rid), _ptr(beg), _ptr(end), int(threads), C.byref(h)))
         self._h = h
         self.n_ref = len(bam.ref_len)
@@ -240,6 +272,34 @@ class Reads:
         return take_junctions(self._lib, h, ss)
 
     @property
+    def has_bases(self):
+        """Does the set keep a base table (``bases=True``)?"""
+        return bool(self._lib.bsig_reads_has_bases(self._h))
+
+    @property
+    def base_table_bytes(self):
+        """Bytes of the base table's arrays: 28 a read (and 16 for the closing offsets), 4 an operation, 1.5 a base,
+        8 * (n_ref + 1); 0 without a table or with an empty one."""
+        return int(self._lib.bsig_reads_base_table_bytes(self._h))
+
+    def nucleotides(self, rid, loc, length, strand, mapqual=0, requiredF=0, filteredF=-1, min_base_qual=0, ss=False):
+        """A / C / G / T / N / deletion counts per base of every range (csrc/nucleotides.hip), counted on the GPU from the
+        set's base table: a list with one int32 array per range, ``(6, width)`` or with ``ss`` ``(2, 6, width)`` (sense,
+        antisense) -- views of one buffer.  include/bamsignals_abi.h says what counts.  Only a set with bases has a table."""
+        rid, loc, length, strand = (_i32(a) for a in (rid, loc, length, strand))
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        off = np.zeros(n + 1, dtype=np.int64)
+        cells = int(self._lib.bsig_nucleotides_cells(n, _ptr(length), int(bool(ss)), _ptr(off)))
+        if cells < 0:
+            raise ValueError("a range has a negative width")
+        out = np.zeros(max(cells, 1), dtype=np.int32)
+        _lib.check(self._lib.bsig_reads_nucleotides_host(self._h, n, _ptr(rid), _ptr(loc), _ptr(length), _ptr(strand), int(mapqual),
+                                                         int(requiredF), int(filteredF), int(min_base_qual), int(bool(ss)), _ptr(out)))
+        return split_nucleotides(out, off, length, ss)
+
+    @property
     def n_source_reads(self):
         """Reads a spliced set was made from, the rows of its read table (``info()["n_reads"]`` counts blocks); 0 for a
         plain set."""
@@ -283,6 +343,13 @@ class Reads:
 
     def __del__(self):
         self.close()
+
+
+def split_nucleotides(out, off, width, ss):
+    """the flat cells of a nucleotide count -> one read-only (6, width) / (2, 6, width) view per range"""
+    out.setflags(write=False)
+    shape = (2, 6) if ss else (6,)
+    return [out[int(a):int(b)].reshape(shape + (int(w),)) for a, b, w in zip(off[:-1], off[1:], width)]
 
 
 def take_junctions(lib, handle, ss):

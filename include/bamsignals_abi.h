@@ -1041,6 +1041,85 @@ int bsig_reads_gene_counts(const bsig_reads *reads, const bsig_gene_model *model
 int bsig_gene_counts(const char *bampath, const bsig_gene_model *model, int32_t n_seq_levels, const char *const *seq_levels,
                      int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t strandedness, int32_t device,
                      int64_t *counts, int64_t *summary);
+/* ------------------------------------------------------------------------------------------
+ * A / C / G / T / N / deletion counts per base (Rsamtools::pileup, bam-readcount, deepSNV::bam2R, the count columns of
+ * samtools mpileup), counted on the GPU (csrc/nucleotides.hip).
+ * A read TAKES PART iff flag 0x4 is clear and it passes mapqual / requiredF / filteredF exactly as a read passes them in every
+ * other call (mapq >= mapqual, every requiredF bit set, not every filteredF bit set: for a mask of one bit that is
+ * (flag & filteredF) == 0, and -1 filters nothing).  Its CIGAR -- the record's own, or the CG:B,I tag behind the
+ * <l_seq>S<n>N placeholder -- is walked with a reference cursor r = pos and a query cursor q = 0:
+ *
+ *   operation                     what is counted                                                     cursors
+ *   M, =, X (0, 7, 8), length L   for i in 0 .. L - 1: query base q + i at reference base r + i,      r += L, q += L
+ *                                 if its quality passes
+ *   I, S (1, 4)                   nothing                                                             q += L
+ *   D (2)                         one count in the deletion channel at each of r .. r + L - 1         r += L
+ *                                 (no quality: it always counts)
+ *   N (3)                         nothing                                                             r += L
+ *   H, P (5, 6), any op > 8       nothing                                                             none
+ *
+ * Operations of length 0 do nothing; positions are 64-bit inside the walk; a cell outside every range is not asked for.
+ * The CHANNELS, in this order: A (4-bit code 1), C (2), G (4), T (8), N (every other code: '=', the IUPAC ambiguity codes
+ * and 15), '-' (deletion).  A query base at an index >= l_seq (SEQ '*', or a CIGAR longer than the sequence) counts in N and
+ * its quality is missing; nothing beyond a read's own bytes is read.  A base PASSES iff qual >= min_base_qual; a missing
+ * quality (byte 0xFF, or an index >= l_seq) passes every threshold; min_base_qual is 0 .. 93, else BSIG_ERR_ARG.
+ * Range i (0-based loc, len, strand) owns 6 * len int32 cells [channel][position], with ss 2 * 6 * len cells
+ * [sense | antisense][channel][position]: a read is sense iff its 0x10 bit agrees with the range's strand, '*' counted as
+ * '+' (no mate-aware strand).  A '-' range reads 5' -> 3' on its own strand: positions reversed, channels complemented
+ * (A <-> T, C <-> G; N and '-' stay).  Ranges are independent (overlapping ranges each get their counts); a range of width
+ * 0 owns nothing; a range on a reference without reads, or past its end, is all zeros.  bsig_nucleotides_cells gives the
+ * total and (off: n + 1 entries, or NULL) every range's first cell.  Counters are 32-bit: a cell past 2^31 - 1 is out of
+ * scope.  All integer work: the result does not depend on the order in which the GPU runs it.  With min_base_qual == 0 the
+ * six channels of a base add up to bsig_coverage_*_spliced there (D covered, N not) for reads that have a
+ * reference-consuming operation.
+ * A bsig_reads WITH BASES (bsig_reads_upload_bases, bsig_reads_from_bam_bases / _regions_bases) is an ordinary plain
+ * object -- every plan works on it unchanged -- that carries a BASE TABLE in BAM order in its own device memory (hbm_bytes
+ * counts it, bsig_reads_clone copies it, bsig_reads_base_table_bytes states its size: 28 bytes a read and 8 + 8 for the two
+ * closing offsets, 4 an operation, 1.5 a base, 8 * (n_ref + 1)): per read pos, the running maximum of end within its
+ * reference, flag | mapq << 16 and where its operations and its bases begin; then the operations, the bases as BAM's own
+ * nibbles tightly packed, one quality byte a base.  bsig_base_columns describes them to bsig_reads_upload_bases, which needs
+ * cigar_off + cigar (cols->end is not read): seq_off has n + 1 entries counted in bases from 0; base g of the whole is
+ * nibble g of seq (byte g / 2, the high half where g is even) and byte g of qual.  bsig_bam_decode_bases is bsig_bam_decode
+ * that fills them as well (host memory owned by the handle, valid until its next decode or close); the _from_bam_ forms
+ * are bsig_reads_from_bam / _regions that also copy every record's operations, bases and qualities out of a chunk's inflated
+ * stream on the GPU, right behind the record extraction (one host read per chunk sizes the chunk's piece; one share, chunk by
+ * chunk, as a spliced decode); where the file takes the CPU decode -- a record whose l_seq runs past it among the reasons --
+ * bsig_bam_decode_bases' columns go through bsig_reads_upload_bases: same result.  BAMSIGNALS_DEVICE_DECODE as above.  bsig_reads_save of such an object is
+ * BSIG_ERR_ARG; an object without bases (plain or spliced) answers bsig_reads_nucleotides with BSIG_ERR_ARG.
+ * bsig_reads_nucleotides writes device memory, _host host memory (the cells of bsig_nucleotides_cells).
+ * bsig_nucleotides is the file-level call: the eight range arguments of every file-level call, on the file's reads with
+ * bases (a resident set of its own, kept only once a nucleotide call asked for it; whole-file or index-driven as the ranges
+ * ask); its parameters are judged before the BAM is opened; bsig_last_call_route() says "nucleotides".  With several GPUs
+ * the first one answers.
+ * ------------------------------------------------------------------------------------------ */
+#define BSIG_NUC_CHANNELS 6
+#define BSIG_NUC_MAX_BASE_QUAL 93
+typedef struct {
+    const int64_t *seq_off;    /* n_reads+1 : read i owns bases [seq_off[i], seq_off[i+1])              */
+    const uint8_t *seq;        /* 4-bit codes, two a byte, the first of a byte in its high half         */
+    const uint8_t *qual;       /* one byte a base, 0xFF = missing                                       */
+} bsig_base_columns;
+int bsig_reads_upload_bases(bsig_ctx *ctx, const bsig_columns *cols, const bsig_base_columns *bases, bsig_reads **reads);
+int32_t bsig_reads_has_bases(const bsig_reads *reads);           /* 1 / 0; 0 for NULL                            */
+int64_t bsig_reads_base_table_bytes(const bsig_reads *reads);    /* 0 for NULL and for an object without bases   */
+int bsig_bam_decode_bases(bsig_bam *bam, int64_t n_regions, const int32_t *rid, const int64_t *beg, const int64_t *end,
+                          int32_t threads, bsig_columns *cols, bsig_base_columns *bases);
+int bsig_reads_from_bam_bases(bsig_ctx *ctx, bsig_bam *bam, int32_t threads, bsig_reads **reads);
+int bsig_reads_from_bam_regions_bases(bsig_ctx *ctx, bsig_bam *bam, int64_t n_regions, const int32_t *rid,
+                                      const int64_t *beg, const int64_t *end, int32_t threads, bsig_reads **reads);
+int64_t bsig_nucleotides_cells(int64_t n_ranges, const int32_t *len, int32_t ss, int64_t *off);      /* -1: a negative width */
+int bsig_reads_nucleotides(const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc, const int32_t *len,
+                           const int32_t *strand, int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual,
+                           int32_t ss, int32_t *out_dev);
+int bsig_reads_nucleotides_host(const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc,
+                                const int32_t *len, const int32_t *strand, int32_t mapqual, int32_t requiredF, int32_t filteredF,
+                                int32_t min_base_qual, int32_t ss, int32_t *out_host);
+int bsig_nucleotides(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual, int32_t ss,
+    int32_t device, int32_t *out);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
