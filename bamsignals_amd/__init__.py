@@ -16,7 +16,9 @@ that support them and their largest anchor (summarizeJunctions, STAR's SJ.out.ta
 the file's spliced reads; bamGeneCounts, the reads of every gene over its exons with the ambiguous, featureless, filtered and
 unmapped reads beside them (htseq-count's union mode, featureCounts), each read decided on the GPU from the same spliced reads;
 bamNucleotides, the A / C / G / T / N / deletion counts of every base of a range (Rsamtools::pileup, bam-readcount), counted
-on the GPU from the bases and qualities the file's reads with bases keep.
+on the GPU from the bases and qualities the file's reads with bases keep; bamSites, the bases at which the reads disagree with
+a reference or with each other (the candidate stage of VarScan and bcftools mpileup | call), judged on the GPU in the same
+tiles so that only the sites come back.
 Handle-level API for resident data and benchmarking: ``bamsignals_amd.device``.
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
 include/bamsignals_abi.h; there is no CPU fallback.
@@ -33,6 +35,7 @@ from .nucleotides import NucleotideCounts, bamNucleotides  # noqa: F401
 from .overlaps import bamOverlaps  # noqa: F401
 from .runsignals import RunSignals  # noqa: F401
 from .scaled import ScaledSignals, bamScaled  # noqa: F401
+from .sites import AlleleSites, bamSites  # noqa: F401
 from .summary import RangeSummary, bamSummary  # noqa: F401
 from .views import SignalViews, bamViews  # noqa: F401
 from .vplot import VPlot, bamVPlot  # noqa: F401
@@ -41,6 +44,6 @@ from .wrappers import bamCount, bamCoverage, bamProfile, coverage_core, pileup_c
 __all__ = ["bamCount", "bamProfile", "bamCoverage", "bamCrossCorr", "CrossCorr", "bamFragSizes",
            "FragSizes", "bamDepthHist", "DepthHist", "bamSummary", "RangeSummary", "bamScaled", "ScaledSignals",
            "bamOverlaps", "bamViews", "SignalViews", "bamVPlot", "VPlot", "bamJunctions", "Junctions",
-           "bamGeneCounts", "GeneCounts", "GeneModel", "bamNucleotides", "NucleotideCounts",
+           "bamGeneCounts", "GeneCounts", "GeneModel", "bamNucleotides", "NucleotideCounts", "bamSites", "AlleleSites",
            "CountSignals", "RunSignals", "GRanges", "BamFile",
            "writeSamAsBamAndIndex", "write_columns_as_bam", "pileup_core", "coverage_core"]

@@ -322,6 +322,21 @@ def load():
         lib.bsig_reads_nucleotides.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
         lib.bsig_reads_nucleotides_host.argtypes = lib.bsig_reads_nucleotides.argtypes
         lib.bsig_nucleotides.argtypes = core_head[:8] + [C.c_int32] * 6 + [C.c_void_p]
+    # the sites among the nucleotide cells: the query at handle level and at file level, the result handle (BSIG_LIB_PATH may
+    # name a build from before them -- the yardstick of scripts/sites_times.py)
+    if hasattr(lib, "bsig_reads_sites"):
+        lib.bsig_reads_sites.argtypes = ([C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5
+                                         + [C.POINTER(C.c_void_p)])
+        lib.bsig_sites.argtypes = core_head[:8] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_void_p)]
+        lib.bsig_sites_result_n_ranges.argtypes = [C.c_void_p]
+        lib.bsig_sites_result_n_ranges.restype = C.c_int64
+        lib.bsig_sites_result_n_sites.argtypes = [C.c_void_p]
+        lib.bsig_sites_result_n_sites.restype = C.c_int64
+        lib.bsig_sites_result_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        lib.bsig_sites_result_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.bsig_sites_result_timing.restype = None
+        lib.bsig_sites_result_free.argtypes = [C.c_void_p]
+        lib.bsig_sites_result_free.restype = None
     lib.bsig_views_result_n_seg.argtypes = [C.c_void_p]
     lib.bsig_views_result_n_seg.restype = C.c_int64
     lib.bsig_views_result_n_views.argtypes = [C.c_void_p]

@@ -22,6 +22,7 @@
 #include "host_util.h"
 #include "junctions.h"
 #include "nucleotides.h"
+#include "sites.h"
 #include "runtime_internal.h"
 
 using bsig::EncodedColumns;
@@ -707,6 +708,28 @@ int bsig_nucleotides(const char *bampath, int64_t n, const int32_t *seq_code, in
     c.bases = true;
     c.rule_first = true;
     return file_level(c);
+}
+
+// bamSites: the variant and mixed-allele sites among the nucleotide cells of the ranges.  bsig_nucleotides' call -- the same
+// parameters, the same resident set -- with a destination of its own; the site rule and the reference codes are judged with the
+// rest before the BAM is opened
+int bsig_sites(const char *bampath, int64_t n, const int32_t *seq_code, int32_t n_levels,
+               const char *const *levels, const int32_t *start, const int32_t *width, const int32_t *strand,
+               int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual, int32_t ss, const uint8_t *ref,
+               int32_t min_depth, int32_t min_alt, int32_t frac_num, int32_t frac_den, int32_t alt_mask, int32_t device,
+               bsig_sites_result **result)
+{
+    if (!result) return fail(BSIG_ERR_ARG, "result is NULL");
+    *result = nullptr;
+    std::unique_ptr<bsig_sites_result> res(new bsig_sites_result);
+    bsig_params p = coverage_params(nullptr, 0, mapqual, requiredF, filteredF, 0, true, 1, ss != 0);
+    FileCall c{{bampath, n, seq_code, n_levels, levels, start, width, strand}, p, device,
+               FileDest::site_table(res.get(), min_base_qual, ref, min_depth, min_alt, frac_num, frac_den, alt_mask)};
+    c.bases = true;
+    c.rule_first = true;
+    const int rc = file_level(c);
+    if (rc == BSIG_OK) *result = res.release();
+    return rc;
 }
 
 // bamGeneCounts: every read of the file's spliced reads against a gene model.  A spliced call without ranges (the model's

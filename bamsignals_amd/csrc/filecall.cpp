@@ -24,6 +24,7 @@
 #include "host_util.h"
 #include "junctions.h"
 #include "nucleotides.h"
+#include "sites.h"
 #include "rangemath.h"
 
 namespace bsig {
@@ -884,6 +885,11 @@ int judge_call(const FileCall &c, Stage &s)
     }
     if (to.shape == Shape::nucleotides)
         if (const int rk = nucleotides_rule(to.arg)) return rk;
+    if (to.shape == Shape::sites) {
+        if (!to.sites) return fail(BSIG_ERR_ARG, "result is NULL");
+        if (const int rk = sites_rule(to.arg, to.site_rule[0], to.site_rule[1], to.site_rule[2], to.site_rule[3], to.site_rule[4])) return rk;
+        if (const int rk = sites_ref_rule(at.n > 0 && at.width ? at.n : 0, at.width, to.site_ref)) return rk;
+    }
     if (to.shape == Shape::genes) {
         if (const int rk = gene_counts_rule(to.model, to.arg, to.gene_counts, to.gene_summary)) return rk;
         if (at.n_levels != to.model->host.n_ref)
@@ -1333,6 +1339,20 @@ int nucleotides_on_first(const Stage &s, std::string &route)
     return rc;
 }
 
+// The sites of the ranges (bsig_sites): the query of sites.hip on the first slot's set with bases, as nucleotides_on_first; only
+// the sites come back
+int sites_on_first(const Stage &s, std::string &route)
+{
+    const FileCall &c = s.call;
+    const RangeView g = s.ranges();
+    const int32_t *r = c.to.site_rule;
+    const SiteParams prm{r[0], r[1], r[2], r[3], (uint32_t)r[4]};
+    const int rc = sites_query(s.res->reads[0], g.n, g.rid, g.loc, g.width, g.strand, c.prm.mapqual, c.prm.requiredF, c.prm.filteredF, c.to.arg,
+                               c.prm.ss, c.to.site_ref, prm, c.to.sites);
+    route = "sites of " + std::to_string(g.n) + " range(s), found on the first GPU";
+    return rc;
+}
+
 // The reads per gene (bsig_gene_counts): the query of genecounts.hip on the first slot's spliced set -- the read table is the
 // same on every slot, and only the two int64 vectors come back
 int gene_counts_on_first(const Stage &s, std::string &route)
@@ -1372,13 +1392,14 @@ int run_result(const Stage &s, std::string &result)
         if (to.shape == FileDest::Shape::junctions) rc = junctions_on_first(s, result);
         else if (to.shape == FileDest::Shape::genes) rc = gene_counts_on_first(s, result);
         else if (to.shape == FileDest::Shape::nucleotides) rc = nucleotides_on_first(s, result);
+        else if (to.shape == FileDest::Shape::sites) rc = sites_on_first(s, result);
         else if (to.shape == FileDest::Shape::reduced) rc = reduced_on_slots(s, result);
         else if (to.runs) rc = encoded_on_slots(s, result);
         else if (!s.many) rc = run_on_one(s, t_run);
         else rc = run_on_slots(s, result);
     }
     if (!s.many && to.shape != FileDest::Shape::reduced && to.shape != FileDest::Shape::junctions && to.shape != FileDest::Shape::genes &&
-        to.shape != FileDest::Shape::nucleotides && !to.runs)
+        to.shape != FileDest::Shape::nucleotides && to.shape != FileDest::Shape::sites && !to.runs)
         result = "download";
     return rc;
 }

@@ -35,11 +35,11 @@ inline Encoder views_encoder(int32_t lower, int32_t upper) { return Encoder{Enco
 
 // Where a file-level call's result goes: one flat buffer (out, at off: bsig_layout), one vector per range (dst; bamCount's
 // layout is one vector, dst[0]), one int64 vector for a reduction over the ranges, an encoder's columns, or the columns of
-// a junction query (junctions.hip), the two int64 vectors of a gene count (genecounts.hip), or the int32 cells of a nucleotide
-// count (nucleotides.hip: bsig_nucleotides_cells' layout, not bsig_layout's)
+// a junction query (junctions.hip), the two int64 vectors of a gene count (genecounts.hip), the int32 cells of a nucleotide
+// count (nucleotides.hip: bsig_nucleotides_cells' layout, not bsig_layout's), or the sites among those cells (sites.hip)
 enum class Reduce { none, sum, xcorr, frag, hist, summary, scaled, vplot, capped };
 struct FileDest {
-    enum class Shape { flat, into, reduced, encoded, junctions, genes, nucleotides } shape = Shape::flat;
+    enum class Shape { flat, into, reduced, encoded, junctions, genes, nucleotides, sites } shape = Shape::flat;
     int32_t *out = nullptr;
     const int64_t *off = nullptr;
     int32_t *const *dst = nullptr;
@@ -48,13 +48,16 @@ struct FileDest {
                                     // rows, max_value + 1 + BSIG_HIST_MOMENTS
     const char *name = "out";       // ... as the entry point calls that argument
     int32_t arg = 0;                // xcorr: max_lag; frag, vplot: len_bin; hist: max_value; summary: the number of thresholds; scaled: n_bins;
-                                    // capped: keep_dup; junctions: min_anchor; genes: strandedness; nucleotides: min_base_qual
+                                    // capped: keep_dup; junctions: min_anchor; genes: strandedness; nucleotides, sites: min_base_qual
     const int32_t *thresholds = nullptr;    // summary: arg of them
     EncodedColumns *runs = nullptr;         // the per-range result as runs or views (enc says which), in the caller's range order
     Encoder enc = runs_encoder();
     EncodedColumns *junctions = nullptr;    // the ranges' distinct junctions with their counts: start, end, count, max_anchor
     const bsig_gene_model *model = nullptr; // a gene count: the model, counts[n_genes] and summary[5]
     int64_t *gene_counts = nullptr, *gene_summary = nullptr;
+    bsig_sites_result *sites = nullptr;     // the sites of the ranges' nucleotide cells: the rule's five numbers (min_depth, min_alt,
+    int32_t site_rule[5] = {0, 0, 0, 0, 0}; // frac_num, frac_den, alt_mask) and the reference codes (sum(width) bytes, or NULL)
+    const uint8_t *site_ref = nullptr;
     static FileDest flat(int32_t *out, const int64_t *off)
     {
         FileDest to;
@@ -99,6 +102,14 @@ struct FileDest {
         to.shape = Shape::nucleotides; to.out = out; to.arg = min_base_qual;
         return to;
     }
+    static FileDest site_table(bsig_sites_result *res, int32_t min_base_qual, const uint8_t *ref, int32_t min_depth, int32_t min_alt,
+                               int32_t frac_num, int32_t frac_den, int32_t alt_mask)
+    {
+        FileDest to;
+        to.shape = Shape::sites; to.sites = res; to.arg = min_base_qual; to.site_ref = ref;
+        to.site_rule[0] = min_depth; to.site_rule[1] = min_alt; to.site_rule[2] = frac_num; to.site_rule[3] = frac_den; to.site_rule[4] = alt_mask;
+        return to;
+    }
     static FileDest gene_table(const bsig_gene_model *model, int32_t strandedness, int64_t *counts, int64_t *summary)
     {
         FileDest to;
@@ -132,7 +143,7 @@ struct FileCall {
     bool filter_missing = false;
     bool spliced = false;           // coverage that skips N gaps, the junctions, the gene counts: the call runs on the file's spliced
                                     // reads (splice.hip)
-    bool bases = false;             // the nucleotide counts: the call runs on the file's reads with bases (nucleotides.hip), a
+    bool bases = false;             // the nucleotide counts and the sites: the call runs on the file's reads with bases (nucleotides.hip), a
                                     // resident set of its own
     bool whole_file = false;        // the call speaks of every read of the file (the gene counts): never an index-driven decode
 };
@@ -145,6 +156,7 @@ int scatter_segments_to(int64_t n, const int32_t *src, const int64_t *src_off, c
 }  // namespace bsig
 struct bsig_runs_result : bsig::EncodedColumns {};
 struct bsig_views_result : bsig::EncodedColumns {};
+struct bsig_sites_result;       // (sites.h)
 
 // a BAM handle as the file-level calls open it (fileapi.cpp): the header now, the index parsed by a helper thread;
 // bam_index_wait joins that parse and reports what it found, bsig_bam_index joins and hands out the index

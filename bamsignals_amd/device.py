@@ -299,6 +299,34 @@ class Reads:
                                                          int(requiredF), int(filteredF), int(min_base_qual), int(bool(ss)), _ptr(out)))
         return split_nucleotides(out, off, length, ss)
 
+    def sites(self, rid, loc, length, strand, ref=None, min_depth=10, min_alt=2, frac=(1, 5), alt_mask=0x2F, mapqual=0, requiredF=0,
+              filteredF=-1, min_base_qual=0, ss=False, timing=None):
+        """The variant and mixed-allele sites of every range (csrc/sites.hip): the cells ``nucleotides`` would count, judged on
+        the GPU where they are counted; only the sites come back: ``(seg_off, pos, alleles, counts)`` -- range i owns entries
+        ``seg_off[i] .. seg_off[i + 1]``, ``pos`` is the cell's index in the range as the range reads, ``alleles`` is
+        ``base | alt << 8``, ``counts`` int32 ``(n, 6)`` or with ``ss`` ``(n, 2, 6)``.  ``ref``: uint8 channel codes 0 .. 4,
+        ``sum(length)`` of them, range after range in the range's reading direction, or None (the base channel is then the
+        first of the largest counts).  ``frac``: ``(num, den)``.  include/bamsignals_abi.h says what a site is.  ``timing``: a
+        list that receives the seconds of count + scan, fill and download.  Only a set with bases has a table."""
+        from .sites import take_sites
+        rid, loc, length, strand = (_i32(a) for a in (rid, loc, length, strand))
+        n = len(rid)
+        if not (len(loc) == len(length) == len(strand) == n):
+            raise ValueError("range arrays differ in length")
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, dtype=np.uint8)
+            if ref.ndim != 1 or len(ref) != int(np.maximum(length, 0).astype(np.int64).sum()):
+                raise ValueError("ref must hold one code per base of the ranges")
+        h = C.c_void_p()
+        _lib.check(self._lib.bsig_reads_sites(self._h, n, _ptr(rid), _ptr(loc), _ptr(length), _ptr(strand), int(mapqual), int(requiredF),
+                                              int(filteredF), int(min_base_qual), int(bool(ss)), None if ref is None else _ptr(ref),
+                                              int(min_depth), int(min_alt), int(frac[0]), int(frac[1]), int(alt_mask), C.byref(h)))
+        if timing is not None:
+            t = (C.c_double * 3)()
+            self._lib.bsig_sites_result_timing(h, t)
+            timing[:] = list(t)
+        return take_sites(self._lib, h, bool(ss))
+
     @property
     def n_source_reads(self):
         """Reads a spliced set was made from, the rows of its read table (``info()["n_reads"]`` counts blocks); 0 for a

@@ -1120,6 +1120,52 @@ int bsig_nucleotides(
     const int32_t *width, const int32_t *strand,
     int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual, int32_t ss,
     int32_t device, int32_t *out);
+/* ------------------------------------------------------------------------------------------
+ * Variant and mixed-allele SITES: the bases at which the reads disagree with a reference, or with each other (the candidate
+ * stage of VarScan, of bcftools mpileup | call and of deepSNV; the filter over Rsamtools::pileup), found on the GPU
+ * (csrc/sites.hip; the decision itself is csrc/sitemath.h: site_classify, the same function on host and device).
+ * A site is decided from the cells of a range EXACTLY as bsig_reads_nucleotides defines them -- after a '-' range's reversal
+ * and complement, with the same read and base filters --: sites == f(nucleotide counts) by definition, and only the sites
+ * leave the device.  For cell p of range i let c[0 .. 5] be the six channels A C G T N '-', the two planes SUMMED when ss is
+ * set (ss changes only what is reported), and D their sum.
+ *   The BASE channel b: with ref, b = ref[cell]: ref is a host array of sum(len) bytes holding channel codes 0 .. 4, range
+ *   after range in the range's own reading direction (for a '-' range the reverse complement, as getSeq(genome, gr) gives
+ *   it); a cell whose ref is 4 (N) is never a site; a code above 4 is BSIG_ERR_ARG, judged on the host before anything runs.
+ *   Without ref (NULL), b is the first channel of all six that holds the largest count.
+ *   The ALT channel a: the first channel with the largest count among those in alt_mask (bits 0 .. 5, nonzero), b excluded; a
+ *   mask that names no channel but b leaves the cell without an alt: no site.
+ *   The cell is a site iff D >= min_depth and c[a] >= min_alt and c[a] * frac_den >= frac_num * D (64-bit integers).
+ * min_depth >= 1, min_alt >= 1, 0 <= frac_num <= frac_den, 1 <= frac_den <= 2^20, alt_mask in 1 .. 0x3F and min_base_qual as
+ * for the nucleotide counts: anything else is BSIG_ERR_ARG with a sentence of its own.
+ * The result, a structure of arrays in the caller's range order: seg_off (int64, n_ranges + 1: range i owns sites seg_off[i]
+ * .. seg_off[i + 1]), pos (int32 a site: the cell's index in the range, 0-based, in the range's reading direction, ascending
+ * within a range), alleles (int32 a site: b | a << 8), counts (int32 [site][channel], with ss [site][plane][channel]: sense,
+ * antisense).  Ranges are independent (duplicated ranges give duplicated sites); the order is fixed and does not depend on how
+ * the GPU schedules the work; the arrays have their exact size; with no site at all the value pointers of
+ * bsig_sites_result_copy may be NULL.  bsig_sites_result_timing: the seconds of count + scan, of the fill and of the download
+ * of the query that made the result (0 where a stage did not run).
+ * An object without bases answers bsig_reads_sites as it answers bsig_reads_nucleotides; the limit of 2^31 - 1 tiles and the
+ * empty set's behaviour (no site) are that call's as well.  bsig_sites is the file-level call: the eight range arguments of
+ * every file-level call on the file's reads with bases (bsig_nucleotides' resident set); its parameters and the ref codes
+ * are judged before the BAM is opened; bsig_last_call_route() says "sites".  With several GPUs the first one answers.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct bsig_sites_result bsig_sites_result;
+int bsig_reads_sites(const bsig_reads *reads, int64_t n_ranges, const int32_t *rid, const int32_t *loc, const int32_t *len,
+                     const int32_t *strand, int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual,
+                     int32_t ss, const uint8_t *ref, int32_t min_depth, int32_t min_alt, int32_t frac_num, int32_t frac_den,
+                     int32_t alt_mask, bsig_sites_result **result);
+int bsig_sites(
+    const char *bampath, int64_t n_ranges, const int32_t *seq_code,
+    int32_t n_seq_levels, const char *const *seq_levels, const int32_t *start,
+    const int32_t *width, const int32_t *strand,
+    int32_t mapqual, int32_t requiredF, int32_t filteredF, int32_t min_base_qual, int32_t ss,
+    const uint8_t *ref, int32_t min_depth, int32_t min_alt, int32_t frac_num, int32_t frac_den, int32_t alt_mask,
+    int32_t device, bsig_sites_result **result);
+int64_t bsig_sites_result_n_ranges(const bsig_sites_result *result);
+int64_t bsig_sites_result_n_sites(const bsig_sites_result *result);
+int bsig_sites_result_copy(const bsig_sites_result *result, int64_t *seg_off, int32_t *pos, int32_t *alleles, int32_t *counts);
+void bsig_sites_result_timing(const bsig_sites_result *result, double *t3);
+void bsig_sites_result_free(bsig_sites_result *result);
 /* replaces bamsignals_writeSamAsBamAndIndex (ref: src/bamsignals.cpp:496-534): text SAM ->
  * BAM + <bampath>.bai                                                                          */
 int bsig_write_sam_as_bam_and_index(const char *sampath, const char *bampath);
